@@ -24,6 +24,9 @@ Prints ONE JSON line (rank 0).  `value` is whole-job throughput of the FULL
 step; the per-phase split, the roofline of the HBM-bound fused cell kernel
 (112 algorithmic bytes per cell) and the CPU baseline (the
 oracle, oracle/liboracle.so, on the host cores) ride along in the same line.
+`--dump-outputs DIR` writes the planes the last timed step left as .npy files, so
+that two builds run with the same arguments can be compared output for output; in
+such a run every step starts from the same primed state (see --dump-outputs).
 """
 import argparse
 import ctypes as C
@@ -38,6 +41,19 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 CELL_BYTES = 112               # fused floor, SURVEY.md §8d / DESIGN.md §Roofline
 CELL_BYTES_LAZY = 84           # ... without the 28 B/cell re-zero of the flux planes (lazy chain of steps)
+# --dump-outputs: the planes a caller of the step carries on with; 9 floats a cell over all six, so a
+# sample of 2^20 cells is 36 MiB, inside the 64 MB a dump may take
+DUMP_PLANES = ("layers", "height", "waterHeight", "velocity", "debris", "debrisVelocity")
+DUMP_CELLS = 1 << 20
+# the planes a step reads that the step before it wrote.  A --dump-outputs run takes one step from the seeded
+# terrain (water and momentum on it), keeps these planes as they are then, and starts every later step from
+# them, at the same particle-stream offset.  A chain of steps does not reproduce: the particle launches add
+# their fp32 deposits in whatever order the hardware runs them, so two runs' planes differ in the last bits
+# (3e-7 of the plane's largest value after one step, at 8192^2), and from the third step on a walk whose
+# first direction hangs on such a bit takes another turn and carries its whole deposit elsewhere: 2e-3 to
+# 4e-3 of waterHeight's largest value, bounded, step after step.  The step from the primed state (the
+# chain's second) reproduces to rounding.
+STEP_INPUTS = ("layers", "waterHeight", "velocity", "debrisVelocity")
 
 
 def script_param(soil):
@@ -267,7 +283,19 @@ def parse_args():
                          "64-row halo, walkers handed over at its far end as 64-byte records")
     ap.add_argument("--particle-mode", type=int, default=0,
                     help="0 auto, 1 direct (reference launch shape), 2 staged — ablation")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the planes the last timed step left (%s) as float32 "
+                         "DIR/<name>.npy: whole on grids of at most %d cells, else at the same seeded sample of "
+                         "that many cells (sorted flat indices, np.random.default_rng(0).choice without replacement).  "
+                         "So that two runs with the same arguments compute from the same inputs, such a run first "
+                         "takes one untimed step from the seeded terrain, and every warmup and timed step after it "
+                         "starts from the state that step left (%s restored, and the particle streams re-seeded at "
+                         "the same offset, outside the timed interval) instead of from the step before it: a chain's "
+                         "walks take other turns from run to run (see STEP_INPUTS).  One GPU, c4 and c2 only"
+                         % (", ".join(DUMP_PLANES), DUMP_CELLS, ", ".join(STEP_INPUTS)))
     args = ap.parse_args()
+    if args.dump_outputs and (args.config in ("c1", "c3") or args.gpus > 1 or os.environ.get("SOIL_BENCH_FORCE_SLAB") == "1"):
+        ap.error("--dump-outputs covers the erosion step on one GPU (--config c4 or c2, --gpus 1)")
     args.steps_given, args.warmup_given, args.size_given = args.steps is not None, args.warmup is not None, args.size is not None
     dflt = {"c4": (10, 2, 8192), "c2": (10000, 10, 1024), "c1": (200, 5, 256), "c3": (512, 8, 4096)}[args.config]
     if args.steps is None:
@@ -276,6 +304,8 @@ def parse_args():
         args.warmup = dflt[1]
     if args.size is None:
         args.size = dflt[2]
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     return args
 
 
@@ -329,18 +359,28 @@ class _Single:
         pass
 
 
-def timed_steps(runner, ev, steps, warmup, world):
+def timed_steps(runner, ev, steps, warmup, world, restore=None):
     """W untimed steps, then exactly K steps between barrier + device synchronise on both sides;
-    the elapsed wall time is the maximum over the ranks."""
+    the elapsed wall time is the maximum over the ranks.  `restore`: called before every step, its
+    work synchronised and left out of the elapsed time."""
     from soillib_amd import soil
     for _ in range(warmup):
+        if restore:
+            restore()
         runner.step()
     runner.barrier()
     runner.sync()
     soil.particle_steps(reset=True)
     phase = [0.0, 0.0, 0.0, 0.0, 0.0]
+    elapsed = 0.0
     t0 = time.perf_counter()
     for _ in range(steps):
+        if restore:
+            runner.sync()
+            elapsed += time.perf_counter() - t0
+            restore()
+            runner.sync()
+            t0 = time.perf_counter()
         runner.step(ev)
         # events are read back after the step's work is queued; elapsed_ms
         # synchronises on the last event, so this also paces the host
@@ -352,7 +392,7 @@ def timed_steps(runner, ev, steps, warmup, world):
             phase[4] += ev.ms(5, 3)
     runner.sync()
     runner.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed += time.perf_counter() - t0
     if world > 1:
         elapsed = runner.max_over_ranks(elapsed)
     return elapsed, phase, soil.particle_steps(reset=True)
@@ -377,6 +417,21 @@ def halo_report(runner):
             "ghost_rows_walked_vs_bound": hr["window"] / max(hr["window_full"], 1),
             "reach_rows_last_steps": runner.reach_hist, "repeated_launches": runner.fallbacks,
             "trimmed_by_measured_reach": bool(runner.trim)}
+
+
+def dump_outputs(out_dir, plane, H, W):
+    """Writes DUMP_PLANES as float32 .npy (see --dump-outputs); `plane(name)` returns the plane of the
+    H x W grid as a numpy array."""
+    import numpy as np
+    cells = None
+    if H * W > DUMP_CELLS:
+        cells = np.sort(np.random.default_rng(0).choice(H * W, DUMP_CELLS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in DUMP_PLANES:
+        a = plane(name)
+        if cells is not None:
+            a = a.reshape((-1,) + a.shape[2:])[cells]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
 
 def main():
@@ -458,7 +513,19 @@ def _main():
         runner = _Single(H_global, W, param, args.particles_div, serial)
 
     ev = Events(_abi, 6)
-    elapsed, phase, psteps_rank = timed_steps(runner, ev, args.steps, args.warmup, world)
+    restore = None
+    if args.dump_outputs:
+        runner.step()
+        primed_index = runner.model.step_index
+        primed = {k: silt.clone(getattr(runner.model, k)) for k in STEP_INPUTS}
+
+        def restore():
+            for k, v in primed.items():
+                silt.set(getattr(runner.model, k), v)
+            runner.model.step_index = primed_index
+    elapsed, phase, psteps_rank = timed_steps(runner, ev, args.steps, args.warmup, world, restore)
+    if args.dump_outputs:   # before the side blocks below step the same model on
+        dump_outputs(args.dump_outputs, lambda k: getattr(runner.model, k).cpu().numpy(), H_global, W)
     other_block, other = None, ("fast" if args.particle_arith == "exact" else "exact")
     if world == 1 and not slabbed and os.environ.get("SOIL_BENCH_NO_OTHER_ARITH", os.environ.get("SOIL_BENCH_NO_EXACT")) != "1":
         # the same model a few steps on in the other arithmetic, same harness — a side block, never `value`
@@ -579,11 +646,16 @@ def _main():
                                    "as the fast intrinsics the source names" if args.particle_arith == "exact" else
                                    "approximate reciprocal; reference is IEEE"),
             "debris_walkers": DEBRIS_NOTE[retire_mode],
+            "step_inputs": ("every step from the state one step from the seeded terrain left (--dump-outputs: %s "
+                            "restored and the streams re-seeded before each step, outside the timed interval)"
+                            % ", ".join(STEP_INPUTS)) if restore else
+                           "the previous step's outputs (a chain of steps)",
         },
         "final_state": final,
         "halo": halo,
         "nccl_ranks": nccl_ranks,
         "particle_steps_per_step": psteps_rank * world // K,
+        "particle_steps_timed": psteps_rank * world,
         "gparticle_steps_per_s": psteps_rank * world / elapsed / 1e9,
         "phases_ms": ({"particles_fluvial": phase[0] / K, "particles_debris": phase[1] / K}
                       if serial else {"particles_fluvial+debris_overlapped": (phase[0] + phase[1]) / K}) | {

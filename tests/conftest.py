@@ -60,7 +60,7 @@ _ORDER = ["test_gpu_parity", "test_debris_retire", "test_golden", "test_oracle_k
           "test_fma_tolerance", "test_gpu_window_shapes", "test_gpu_fullsize", "test_gpu_api_surface",
           "test_abi_symbols", "test_io_tiff", "test_knobs", "test_parallel_gloo", "test_cpp_api", "test_bench_configs",
           "test_bench_spawn", "test_gpu_parallel"]
-_LAST_WITHIN = ("rccl", "eight_processes")   # within a file: the RCCL wire and the 8-process job at the very end
+_LAST_WITHIN = ("rccl", "four_processes")   # within a file: the RCCL wire and the 4-process job at the very end
 
 
 def pytest_collection_modifyitems(session, config, items):
@@ -71,8 +71,8 @@ def pytest_collection_modifyitems(session, config, items):
         return (2 * len(_ORDER) if late else rank)
     items.sort(key=key)   # stable: the order inside a file is kept
     # and no single test may sit on the session: pytest-timeout (in the image) fails a test after 300 s
-    # (the 8-process 16384^2 job: 600 s) and the session goes on
+    # (the 4-process 16384^2 job: 600 s) and the session goes on
     if config.pluginmanager.hasplugin("timeout"):
         for item in items:
             if item.get_closest_marker("timeout") is None:
-                item.add_marker(pytest.mark.timeout(600 if "eight_processes" in item.name else 300))
+                item.add_marker(pytest.mark.timeout(600 if "four_processes" in item.name else 300))

@@ -23,7 +23,7 @@ def main():
         r.step()
     r.sync()
     planes = {k: r.plane(k, owned=True) for k in ("layers", "waterHeight", "velocity", "debris")}
-    if sample is not None:   # (a 2048 x 16384 slab: a few rows per rank travel back, not 800 MB)
+    if sample is not None:   # (a 4096 x 16384 slab: a few rows per rank travel back, not 1.6 GB)
         planes = {k: np.ascontiguousarray(v[sample]) for k, v in planes.items()}
         planes["halo_rows"] = np.array([r.halo_rows["flux"], r.halo_rows["field"], r.halo_rows["full"]], np.int64)
         planes["fallbacks"] = np.array([r.fallbacks], np.int64)

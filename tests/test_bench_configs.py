@@ -51,3 +51,56 @@ def test_config_lines_on_gpu(hip):
     assert r["bound"] == "hbm" and r["avg_launch_ms"] > 0 and r["algorithmic_bytes_per_cell"] > 0
     assert c3["config"]["mean_upstream_area_min_max"][0] >= 1.0        # every cell drains at least itself
     assert c3["cpu_baseline"]["cores"] == 1
+
+
+def test_dump_outputs_takes_one_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: a grid above DUMP_CELLS is written at the same seeded cells every time,
+    within 64 MB; a grid of at most DUMP_CELLS cells is written whole."""
+    import numpy as np
+    import bench
+    H, W = 1536, 1024
+    full = {k: np.random.default_rng(7).random((H, W, 2) if k in ("layers", "velocity", "debrisVelocity") else (H, W),
+                                                 np.float32) for k in bench.DUMP_PLANES}
+    one, again = str(tmp_path / "one"), str(tmp_path / "again")
+    bench.dump_outputs(one, lambda k: full[k], H, W)
+    bench.dump_outputs(again, lambda k: full[k], H, W)
+    cells = np.sort(np.random.default_rng(0).choice(H * W, bench.DUMP_CELLS, replace=False))
+    total = 0
+    for k in bench.DUMP_PLANES:
+        a = np.load(os.path.join(one, k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (bench.DUMP_CELLS,) + full[k].shape[2:], (k, a.shape)
+        assert np.array_equal(a, np.load(os.path.join(again, k + ".npy"))), k
+        assert np.array_equal(a, full[k].reshape((H * W,) + full[k].shape[2:])[cells]), k
+        total += os.path.getsize(os.path.join(one, k + ".npy"))
+    assert total <= 64 * 2**20
+    small = str(tmp_path / "small")
+    bench.dump_outputs(small, lambda k: full[k][:512], 512, W)
+    for k in bench.DUMP_PLANES:
+        assert np.array_equal(np.load(os.path.join(small, k + ".npy")), full[k][:512]), k
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_agree(hip, tmp_path):
+    """The default line with --dump-outputs, with 2 and with 4 timed steps.  Every step of such a run computes
+    from the same primed state, so the loop really ran --steps steps when the particle steps it counted are in
+    the ratio 1:2, and the planes of the last step (float32, whole at 1024^2) are the same in both runs but for
+    the order of the fp32 deposits."""
+    import numpy as np
+    runs, walked = [], []
+    for k in (2, 4):
+        d = str(tmp_path / str(k))
+        out = _line("--size", "1024", "--steps", str(k), "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", d)
+        assert out["steps"] == k and out["ms_per_step"] > 0 and out["config"]["grid"] == [1024, 1024]
+        assert out["config"]["step_inputs"].startswith("every step from the state one step")
+        walked.append(out["particle_steps_timed"])
+        runs.append({p: np.load(os.path.join(d, p + ".npy")) for p in
+                     ("layers", "height", "waterHeight", "velocity", "debris", "debrisVelocity")})
+    assert walked[0] > 0 and walked[1] == 2 * walked[0], walked
+    a, b = runs
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape[:2] == (1024, 1024), (k, a[k].shape)
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6 * np.nanmax(np.abs(a[k])), err_msg=k)
+    # the terrain stays finite; the flow planes may not (the reference's NaN walkers, DESIGN.md 3.2)
+    assert np.isfinite(a["layers"]).all() and np.isfinite(a["height"]).all()
+    assert np.abs(a["waterHeight"][np.isfinite(a["waterHeight"])]).max() > 0
+    assert np.abs(a["velocity"][np.isfinite(a["velocity"])]).max() > 0
