@@ -243,6 +243,34 @@ def particles_debris(massFlux, velocityFlux, albedoFlux, rng, layers, velocity, 
     return steps.value
 
 
+def particles_debris_retire(massFlux, velocityFlux, albedoFlux, rng, layers, velocity, albedoSource,
+                            scale, param, dom=None, threads=1, remote0=None):
+    """particles_debris (the same planes, the full walk) with the rule of the product's spent-walker retirement
+    (soil_oracle.c: orc_debris_spent).  Returns a dict: `steps` of the full walk, `rule_steps` walked when
+    every spent walker ends its walk, `violations` — deposits of spent walkers that are not exact zeros — and
+    `lapses` — spent walkers that stop meeting the rule later on — and `gate`, whether the launch allows the rule
+    at all (rule_steps == steps when it does not)."""
+    dom = dom or domain(*layers.shape[:2])
+    steps, rule_steps, violations, lapses = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    f = lib().orc_particles_debris_retire
+    f.restype = C.c_int
+    gate = f(
+        _f(_chk(massFlux)), _f(_chk(velocityFlux)), _f(_chk(albedoFlux)),
+        C.c_void_p(rng.ctypes.data), C.c_int64(len(rng)), _f(_chk(layers)), _f(_chk(velocity)),
+        _f(_chk(albedoSource)), C.byref(dom), _scale(scale, 3), C.byref(param),
+        C.c_int(threads), C.byref(steps), _f(_chk(remote0)), C.byref(rule_steps), C.byref(violations),
+        C.byref(lapses))
+    return dict(steps=steps.value, rule_steps=rule_steps.value, violations=violations.value, lapses=lapses.value,
+                gate=bool(gate))
+
+
+def debris_retire_gate(layers, velocity, scale, param, dom=None):
+    """Whether the launch allows spent walkers to retire (orc_debris_retire_gate)."""
+    dom = dom or domain(*layers.shape[:2])
+    return bool(lib().orc_debris_retire_gate(_f(_chk(layers)), _f(_chk(velocity)), C.byref(dom),
+                                             _scale(scale, 3), C.byref(param)))
+
+
 def normalize_debris(massFlux, velocityFlux, albedoFlux, layers, mass, velocity, albedoSource,
                      scale, param, dom=None):
     dom = dom or domain(*layers.shape[:2])

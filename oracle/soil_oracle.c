@@ -465,18 +465,74 @@ void orc_normalize_fluvial(const float* waterFlux, const float* massFlux,
 
 /* -------------------------------------------------- debris particles (A5) */
 
-/* __transport_debris, erosion.cu:245-351 */
-void orc_particles_debris(float* massFlux, float* velocityFlux, float* albedoFlux, orc_rng* rng,
-                          int64_t N, const float* layers, const float* velocity,
-                          const float* albedoSource, const orc_domain* d, const float scale[3],
-                          const orc_param* param, int threads, int64_t* steps_out,
-                          float* remote0) {
+/* Spent debris walkers (the product's retirement of them: csrc/erosion_particles_tiled.hip, "spent debris
+ * walkers"), restated from the argument's text, not from the kernel.  Every deposit of a walker is
+ * att_d * source_d and att_v * source_v (:310-318).  A walker that at the bottom of an iteration (after :347) has
+ *     att_v == 0,  att_d * source_d == 0,  att_d >= 0,
+ *     position, speed, source_d, source_v and att_d finite
+ * is SPENT — provided the launch allows it (orc_debris_retire_gate): the argument says that nothing it adds
+ * afterwards is anything but an exact zero.  The oracle does not take that on trust: it walks every walker to the
+ * end as the reference does and counts the deposits of spent walkers that are not exact zeros. */
+/* The speed's magnitude bound of the argument: a spent walker's speed update (:335) is a convex combination of its
+ * speed and the cell's -(g grad) + nu vel over D = nu + tau / eps, so with both under ORC_SPENT_SPEED (and maxage
+ * <= 2^24 for the rounding) the speed stays far below the 1e19 at which v_norm (:321) overflows. */
+#define ORC_SPENT_SPEED 1.0e17f
+static int orc_debris_spent(float px, float py, float spx, float spy, float att_d, float att_v,
+                            float source_d, float source_vx, float source_vy) {
+  if (!(att_v == 0.0f && att_d * source_d == 0.0f)) return 0;
+  const float v[9] = {px, py, spx, spy, source_d, source_vx, source_vy, att_d, att_v};
+  for (int i = 0; i < 9; ++i)
+    if (!isfinite(v[i])) return 0;
+  return att_d >= 0.0f && fabsf(spx) <= ORC_SPENT_SPEED && fabsf(spy) <= ORC_SPENT_SPEED;
+}
+
+/* The launch-level gate of the argument: launch constants in range (maxage <= 2^24 included), and on every cell a
+ * walker of this slab can stand on (the rows orc_slab_escape lets it trace) a finite record (-(g grad) + nu vel,
+ * excessSlope; :332, :339), a finite excessStress < 0 at debrisHeight = eps (:340) and |-(g grad) + nu vel| <=
+ * ORC_SPENT_SPEED * (nu + tau / eps) (:333-335). */
+int orc_debris_retire_gate(const float* layers, const float* velocity, const orc_domain* d,
+                           const float scale[3], const orc_param* param) {
+  const float nu = param->viscosityDebris, tau = param->bedShearDebris, kdd = param->depositionRateDebris;
+  const float g = param->gravity, tau_y = param->yieldStress, theta = param->critSlopeBedrock;
+  if (!(nu >= 0.0f && nu <= 1.0e30f && tau >= 0.0f && tau <= 1.0e25f && kdd >= 0.0f && kdd <= 1.0e30f &&
+        isfinite(g) && isfinite(tau_y) && param->maxage <= (1ull << 24)))
+    return 0;
+  const float eps = 1E-12f;
+  const float D = nu + tau / eps;
+  const int64_t lo = (d->x0 == 0) ? 0 : 1;
+  const int64_t hi = (d->x0 + d->rows == d->H) ? d->rows - 1 : d->rows - 2;
+  for (int64_t lx = lo; lx <= hi; ++lx)
+    for (int64_t y = 0; y < d->W; ++y) {
+      const int64_t l = lx * d->W + y;
+      float grad[2];
+      orc_glocal(layers, d, scale, d->x0 + lx, y, param->exitSlope, grad);
+      const float ax = -(g * grad[0]) + nu * velocity[2 * l];
+      const float ay = -(g * grad[1]) + nu * velocity[2 * l + 1];
+      const float excessSlope = orc_length2(grad[0], grad[1]) - theta;
+      const float excessStress = g * (excessSlope - tau_y / eps);
+      if (!(isfinite(ax) && isfinite(ay) && isfinite(excessSlope) && isfinite(excessStress) &&
+            excessStress < 0.0f && fabsf(ax) <= ORC_SPENT_SPEED * D && fabsf(ay) <= ORC_SPENT_SPEED * D))
+        return 0;
+    }
+  return 1;
+}
+
+/* __transport_debris, erosion.cu:245-351.  rule != 0: also the steps each walker walks until it is spent
+ * (that iteration's step counted, orc_debris_spent) into *rule_steps_out, the deposits of spent walkers that
+ * are not exact zeros into *violations_out and the spent walkers that stop meeting the rule at the bottom of a
+ * later iteration into *lapses_out; the walk and the planes are the reference's either way. */
+static void orc_debris_walk(float* massFlux, float* velocityFlux, float* albedoFlux, orc_rng* rng,
+                            int64_t N, const float* layers, const float* velocity,
+                            const float* albedoSource, const orc_domain* d, const float scale[3],
+                            const orc_param* param, int threads, int64_t* steps_out, float* remote0,
+                            int rule, int64_t* rule_steps_out, int64_t* violations_out,
+                            int64_t* lapses_out) {
   const int64_t W = d->W;
   const int64_t base = d->x0 * W;
-  int64_t steps_total = 0;
+  int64_t steps_total = 0, rule_total = 0, violations = 0, lapses = 0;
   const int nthreads = threads > 1 ? threads : 1;
 
-#pragma omp parallel for schedule(dynamic, 32) num_threads(nthreads) reduction(+ : steps_total)
+#pragma omp parallel for schedule(dynamic, 32) num_threads(nthreads) reduction(+ : steps_total, rule_total, violations, lapses)
   for (int64_t n = 0; n < N; ++n) {
     const float A = scale[0] * scale[1];               /* :263 */
     const float Lx = scale[0], Ly = scale[1];          /* :264 */
@@ -525,18 +581,26 @@ void orc_particles_debris(float* massFlux, float* velocityFlux, float* albedoFlu
 
     float att_d = 1.0f, att_v = 1.0f; /* :301-302 */
     int64_t iter = 0;
+    int spent = 0, lapsed = 0;
+    /* a deposit of a spent walker that is not an exact zero (a NaN one included) */
+#define ORC_DEBRIS_NONZERO(a, b, c) ((a) != 0.0f || (b) != 0.0f || (c) != 0.0f)
     while (!orc_oob(d, px, py) && (uint64_t)(++iter) < param->maxage) { /* :306 */
       if (orc_slab_escape(d, orc_cell(px))) {
         if (px != px && remote0 && ind != 0) { /* NaN walker, see orc_particles_fluvial */
           orc_atomic_add(&remote0[4], att_d * source_d, threads);
           orc_atomic_add(&remote0[5], att_v * source_vx, threads);
           orc_atomic_add(&remote0[6], att_v * source_vy, threads);
+          if (spent && ORC_DEBRIS_NONZERO(att_d * source_d, att_v * source_vx, att_v * source_vy)) ++violations;
         }
         break;
       }
       ++steps_total;
+      if (!spent) ++rule_total;
       const int64_t nind = orc_cell(px) * W + orc_cell(py); /* :309 */
       if (nind != ind) {                                  /* :310-318 */
+        if (spent && (ORC_DEBRIS_NONZERO(att_d * source_d, att_v * source_vx, att_v * source_vy) ||
+                      ORC_DEBRIS_NONZERO(att_d * source_a[0], att_d * source_a[1], att_d * source_a[2])))
+          ++violations;
         ind = nind;
         const int64_t l = ind - base;
         orc_atomic_add(&massFlux[l], att_d * source_d, threads);
@@ -572,9 +636,45 @@ void orc_particles_debris(float* massFlux, float* velocityFlux, float* albedoFlu
       att_v = att_v * orc_expf(-dL * decay_v);                               /* :346 */
       px += v_step * ux;                                                     /* :347 */
       py += v_step * uy;
+      if (rule && !spent) {
+        spent = orc_debris_spent(px, py, spx, spy, att_d, att_v, source_d, source_vx, source_vy);
+      } else if (spent && !lapsed &&
+                 !orc_debris_spent(px, py, spx, spy, att_d, att_v, source_d, source_vx, source_vy)) {
+        lapsed = 1; /* the argument says this cannot happen */
+        ++lapses;
+      }
     }
+#undef ORC_DEBRIS_NONZERO
   }
   if (steps_out) *steps_out = steps_total;
+  if (rule_steps_out) *rule_steps_out = rule_total;
+  if (violations_out) *violations_out = violations;
+  if (lapses_out) *lapses_out = lapses;
+}
+
+void orc_particles_debris(float* massFlux, float* velocityFlux, float* albedoFlux, orc_rng* rng,
+                          int64_t N, const float* layers, const float* velocity,
+                          const float* albedoSource, const orc_domain* d, const float scale[3],
+                          const orc_param* param, int threads, int64_t* steps_out,
+                          float* remote0) {
+  orc_debris_walk(massFlux, velocityFlux, albedoFlux, rng, N, layers, velocity, albedoSource, d, scale,
+                  param, threads, steps_out, remote0, 0, NULL, NULL, NULL);
+}
+
+/* orc_particles_debris with the spent-walker rule applied where the gate (orc_debris_retire_gate) is open:
+ * the planes and *steps_out of the full walk, *rule_steps_out the steps walked under the rule (the full count
+ * when the gate is shut), *violations_out the non-zero deposits of spent walkers, *lapses_out the spent walkers
+ * that stop meeting the rule later on; returns the gate. */
+int orc_particles_debris_retire(float* massFlux, float* velocityFlux, float* albedoFlux, orc_rng* rng,
+                                int64_t N, const float* layers, const float* velocity,
+                                const float* albedoSource, const orc_domain* d, const float scale[3],
+                                const orc_param* param, int threads, int64_t* steps_out,
+                                float* remote0, int64_t* rule_steps_out, int64_t* violations_out,
+                                int64_t* lapses_out) {
+  const int gate = orc_debris_retire_gate(layers, velocity, d, scale, param);
+  orc_debris_walk(massFlux, velocityFlux, albedoFlux, rng, N, layers, velocity, albedoSource, d, scale,
+                  param, threads, steps_out, remote0, gate, rule_steps_out, violations_out, lapses_out);
+  return gate;
 }
 
 /* __normalize_debris, erosion.cu:353-393 */

@@ -85,6 +85,15 @@ void orc_particles_debris(float* massFlux, float* velocityFlux, float* albedoFlu
                           const float* albedoSource, const orc_domain* dom,
                           const float scale[3], const orc_param* param, int threads,
                           int64_t* steps_out, float* remote0);
+/* the same walk with the spent-walker rule of the product's retirement (soil_oracle.c: orc_debris_spent) */
+int orc_debris_retire_gate(const float* layers, const float* velocity, const orc_domain* dom,
+                           const float scale[3], const orc_param* param);
+int orc_particles_debris_retire(float* massFlux, float* velocityFlux, float* albedoFlux, orc_rng* rng,
+                                int64_t N, const float* layers, const float* velocity,
+                                const float* albedoSource, const orc_domain* dom,
+                                const float scale[3], const orc_param* param, int threads,
+                                int64_t* steps_out, float* remote0, int64_t* rule_steps_out,
+                                int64_t* violations_out, int64_t* lapses_out);
 void orc_normalize_debris(const float* massFlux, const float* velocityFlux, float* albedoFlux,
                           const float* layers, float* mass, float* velocity,
                           const float* albedoSource, const orc_domain* dom,

@@ -123,7 +123,11 @@ __device__ __forceinline__ float length2(float x, float y) {  // erosion_map.cu:
 // division is monotonic and sign-symmetric, so for dx > 0 the maximum IS the second
 // quotient and for dx < 0 the first, bit for bit (signed zeros included; a NaN px or
 // dx gives NaN either way): one division per axis instead of two.  A zero dx divides
-// to infinities whose maximum depends on both numerators: that case keeps both.
+// to infinities whose maximum depends on both numerators: that case keeps both — and so
+// does a NaN in either component, whose product with the other one is NaN, not zero: a
+// direction (NaN, 0) (a speed that has overflowed to (inf, finite), v_norm = inf) must
+// keep the reference's fmaxf(-inf, +inf) = +inf on the zero axis, not take -inf from the
+// single quotient (v_step = -inf and NaN attenuations, where the reference clamps to sqrt2).
 __device__ __forceinline__ float stepsize_both(float neg, float pos, float d) {
   return fmaxf(neg / d, pos / d);
 }
@@ -134,7 +138,8 @@ __device__ __forceinline__ float stepsize(float px, float py, float dx, float dy
   const float x_pos = 1.0f + x_neg;
   const float y_pos = 1.0f + y_neg;
   float tx, ty;
-  if (dx * dy == 0.0f) {  // a zero (or underflowing) direction component: as written
+  const float p = dx * dy;
+  if (!(p < 0.0f || p > 0.0f)) {  // a zero (or underflowing) or NaN direction component: as written
     tx = stepsize_both(x_neg - px, x_pos - px, dx);
     ty = stepsize_both(y_neg - py, y_pos - py, dy);
   } else {

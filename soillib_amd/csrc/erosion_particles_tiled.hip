@@ -302,21 +302,32 @@ extern "C" int soil_retire_dbg_read(float* out) {
 #else
 #define RETIRE_DBG(r, k)
 #endif
+//
+// The speed needs a magnitude bound, not only finiteness (round-6 advice; a plateau of 1e14-sized cells above a
+// cliff with g grad = 1e30 and nu + tau / eps = 1e-9 carried spent walkers to an infinite speed and on as NaN
+// walkers).  A spent walker's update (:335) is  s' = w s + (w dL) a  with  w dL = (1 - w) / D,  D = nu + tau / eps:
+// a convex combination of s and a / D, so |s| never exceeds max(|s| when spent, max over the cells of |a| / D) — up
+// to a rounding of a few ulps per step, at most a factor e^4 over 2^24 steps.  With both bounded by kSpentSpeed and
+// maxage <= 2^24 every speed stays below 1e19 and v_norm = sqrt(spx^2 + spy^2) (:321) stays finite: no inf / inf.
+// So: every cell's record |a| <= kSpentSpeed * D (debris_cell_bad), the spent walker's |spx|, |spy| <= kSpentSpeed
+// (debris_spent), maxage <= 2^24 (debris_params_allow_retire).  The example's parameters: D = 2.4e10, |a| ~ 1e2.
+constexpr float kSpentSpeed = 1.0e17f;
 __device__ __forceinline__ bool debris_cell_bad(const float4 qd, const Param& param) {
   const float es = param.gravity * (qd.z - param.yieldStress / 1E-12f);  // :340 with debrisHeight = eps
   const float t = (qd.x - qd.x) + (qd.y - qd.y) + (es - es);             // 0 iff all three are finite
-  return !(es < 0.0f) || !(t == 0.0f);
+  const float D = param.viscosityDebris + param.bedShearDebris / 1E-12f;  // :333 / :343 with debrisHeight = eps
+  return !(es < 0.0f) || !(t == 0.0f) || !(fmaxf(fabsf(qd.x), fabsf(qd.y)) <= kSpentSpeed * D);
 }
 __device__ __forceinline__ bool debris_spent(const PRec& r) {
   if (!(r.a1 == 0.0f && r.a0 * r.s0 == 0.0f)) return false;
   const float t = ((r.px - r.px) + (r.py - r.py)) + ((r.spx - r.spx) + (r.spy - r.spy)) +
                   ((r.svx - r.svx) + (r.svy - r.svy)) + ((r.s0 - r.s0) + (r.a0 - r.a0));
-  return t == 0.0f && r.a0 >= 0.0f;
+  return t == 0.0f && r.a0 >= 0.0f && fmaxf(fabsf(r.spx), fabsf(r.spy)) <= kSpentSpeed;
 }
 static bool debris_params_allow_retire(const Param& p) {
   auto ok = [](float v, float hi) { return v >= 0.0f && v <= hi; };
   return ok(p.viscosityDebris, 1.0e30f) && ok(p.bedShearDebris, 1.0e25f) && ok(p.depositionRateDebris, 1.0e30f) &&
-         (p.gravity - p.gravity) == 0.0f && (p.yieldStress - p.yieldStress) == 0.0f;
+         (p.gravity - p.gravity) == 0.0f && (p.yieldStress - p.yieldStress) == 0.0f && p.maxage <= (1ull << 24);
 }
 
 // The body of one loop iteration AFTER the bookkeeping at its top (oob, ++iter,

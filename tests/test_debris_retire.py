@@ -8,7 +8,7 @@ the-end mode and the oracle, and the guards that switch the retirement off."""
 import numpy as np
 import pytest
 
-from util import product_param, rng_to_gpu, script_param, terrain, to_gpu, to_np
+from util import product_param, retired_steps_close, rng_to_gpu, script_param, terrain, to_gpu, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -64,7 +64,9 @@ def test_retired_walks_leave_the_planes_of_the_full_walks(hip, oracle, retire, H
     layers = terrain(oracle, H, W, sediment=0.01)
     vel0 = (np.random.default_rng(5).standard_normal((H, W, 2)) * 0.5).astype(np.float32)
     mf, vf = np.zeros((H, W), np.float32), np.zeros((H, W, 2), np.float32)
-    want_steps = oracle.particles_debris(mf, vf, None, oracle.rng_seed(N, 6, 0), layers, vel0, None, scale, op)
+    rule = oracle.particles_debris_retire(mf, vf, None, oracle.rng_seed(N, 6, 0), layers, vel0, None, scale, op)
+    want_steps = rule["steps"]
+    assert rule["gate"] and rule["violations"] == 0
     assert hip.soil_set_particle_mode(3) == 0   # the tiled shape whatever N
     out = {}
     for mode in ("off", "watch", "on"):
@@ -72,7 +74,7 @@ def test_retired_walks_leave_the_planes_of_the_full_walks(hip, oracle, retire, H
         out[mode] = _debris_launch(soil, layers, vel0, N, scale, pp)
     assert soil.debris_retire_violations(reset=True) == 0
     assert out["off"][0] == want_steps and out["watch"][0] == want_steps      # the reference's walks, step for step
-    assert out["on"][0] <= want_steps
+    assert retired_steps_close(out["on"][0], rule, N), (out["on"][0], rule)   # where the oracle's rule says
     if which == "script":
         assert out["on"][0] < want_steps // 3, "the example's parameters: walkers are spent within a few steps"
     for mode in ("off", "on"):
@@ -109,7 +111,10 @@ def test_random_parameter_sets_watched(hip, oracle, retire, seed):
     assert soil.debris_retire_violations(reset=True) == 0
     retire("on")
     steps_on, mf_on, vf_on = _debris_launch(soil, layers, vel0, N, scale, pp)
-    assert steps_on <= steps_w
+    rule = oracle.particles_debris_retire(np.zeros((H, W), np.float32), np.zeros((H, W, 2), np.float32), None,
+                                          oracle.rng_seed(N, 6, 0), layers, vel0, None, scale, op)
+    assert rule["violations"] == 0 and steps_w == rule["steps"]
+    assert steps_on <= steps_w and retired_steps_close(steps_on, rule, N), (steps_on, rule)
     _same_planes(mf_on, mf_w, "mass flux")
     _same_planes(vf_on, vf_w, "velocity flux")
 
@@ -139,10 +144,13 @@ def test_guards_switch_the_retirement_off(hip, oracle, retire, case):
     pp = product_param(op)
     vel0 = np.zeros((H, W, 2), np.float32)
     mf, vf = np.zeros((H, W), np.float32), np.zeros((H, W, 2), np.float32)
-    want = oracle.particles_debris(mf, vf, None, oracle.rng_seed(N, 6, 0), layers, vel0, None, scale, op)
+    rule = oracle.particles_debris_retire(mf, vf, None, oracle.rng_seed(N, 6, 0), layers, vel0, None, scale, op)
+    want = rule["steps"]
+    assert rule["gate"] == (case == "nan cell"), case
     assert hip.soil_set_particle_mode(3) == 0
     retire("on")
     steps, got_mf, got_vf = _debris_launch(soil, layers, vel0, N, scale, pp)
+    assert retired_steps_close(steps, rule, N), (case, steps, rule)
     if case == "nan cell":
         # (a NaN height is the reference's sentinel for "outside the grid", erosion_map.cu:122-125: the slopes
         # next to it are the exit slope, every record stays finite and the argument holds — same planes below)
@@ -261,14 +269,15 @@ def test_first_steps_that_leave_the_grid(hip, oracle, retire):
     layers[..., 0] = -0.01 * x - 0.003 * np.arange(W, dtype=np.float32)[None, :]      # downhill towards the far corner
     vel0 = np.zeros((H, W, 2), np.float32)
     mf, vf = np.zeros((H, W), np.float32), np.zeros((H, W, 2), np.float32)
-    want = oracle.particles_debris(mf, vf, None, oracle.rng_seed(N, 6, 0), layers, vel0, None, scale, op)
+    rule = oracle.particles_debris_retire(mf, vf, None, oracle.rng_seed(N, 6, 0), layers, vel0, None, scale, op)
+    want = rule["steps"]
     assert hip.soil_set_particle_mode(3) == 0
     retire("off")
     steps_off, mf_off, vf_off = _debris_launch(soil, layers, vel0, N, scale, pp)
     assert steps_off == want
     retire("on")
     steps_on, mf_on, vf_on = _debris_launch(soil, layers, vel0, N, scale, pp)
-    assert steps_on <= want
+    assert steps_on <= want and retired_steps_close(steps_on, rule, N) and rule["rule_steps"] < want, (steps_on, rule)
     for got, ref, what in ((mf_on, mf, "mass flux"), (vf_on, vf, "velocity flux"), (mf_off, mf, "mass flux, off"),
                            (vf_off, vf, "velocity flux, off")):
         _same_planes(got, ref, what, rtol=1e-4)

@@ -33,8 +33,8 @@ def _oracle_step(oracle, st, step, N, scale, op, threads):
     wf, mf, vf, df, dvf = z1(), z1(), z2(), z1(), z2()
     sf = oracle.particles_fluvial(wf, mf, vf, None, rng, st["layers"], rain, st["wh"], st["v"], None,
                                   scale, op, threads=threads)
-    sd = oracle.particles_debris(df, dvf, None, rng, st["layers"], st["dv"], None, scale, op,
-                                 threads=threads)
+    sd = oracle.particles_debris_retire(df, dvf, None, rng, st["layers"], st["dv"], None, scale, op,
+                                        threads=threads)
     res = oracle.erode_cells(st["layers"], uplift, rain, wf, mf, vf, df, dvf, scale, op)
     new = dict(layers=res["layers_next"], wh=res["waterHeight"], m=res["mass"], v=res["velocity"],
                d=res["debris"], dv=res["debrisVelocity"])
@@ -95,8 +95,8 @@ def _run(hip, oracle, H, W, steps, warm_steps=0):
             forced.swap_layers()
             free.step()                                  # soil_erode_step: the library's own driver
             st, o = _oracle_step(oracle, st, step, N, scale, op, threads)
-            from util import debris_steps_match
-            assert gsf == o["steps_f"] and debris_steps_match(gsd, o["steps_d"]), "step %d: particle steps" % step
+            from util import debris_steps_agree
+            assert gsf == o["steps_f"] and debris_steps_agree(gsd, o["steps_d"], N), ("step %d: particle steps" % step, gsd, o["steps_d"])
             assert gsf > 20 * N                          # the walks are long ones
             for k in ("wf", "mf", "vf", "df", "dvf"):
                 _flux_close(flux[k], o[k], "step %d flux %s" % (step, k))
