@@ -274,8 +274,9 @@ typedef struct soil_erosion_planes {
  *   + layers_next = layers + delta (silt.add, example/dem_process.py:47)
  *   + __layer_merge (:733-745) + re-zero of the five flux planes,
  * bit-identical to running those reference steps one after another (same
- * operation order per cell).  Physics planes only (no albedo).  This is the
- * HBM-roofline kernel: 112 algorithmic bytes per cell. */
+ * operation order per cell).  Physics planes only (no albedo; the coloured step
+ * has soil_erode_cells_fused_colour below).  This is the HBM-roofline kernel:
+ * 112 algorithmic bytes per cell. */
 int soil_erode_cells_fused(const soil_erosion_planes* planes, const soil_domain* dom,
                            const float scale[3], const soil_param* param, void* stream);
 /* The same with flags.  SOIL_CELLS_KEEP_FLUX: the five flux planes are read and left as they are
@@ -362,6 +363,58 @@ int soil_erode_step_ex(const soil_erosion_planes* planes, soil_rng* rng, int64_t
                        uint64_t step_index, int64_t H, int64_t W, const float scale[3],
                        const soil_param* param, int flags, void* stream);
 
+/* ------------------------------------------ erosion: the coloured step */
+
+/* The colour planes of one erosion model: (rows,W,3) float32, a vec3 per cell (AoS), the
+ * albedo arguments the reference's live binding passes through erosion (model.cpp:237-328).
+ * The reference has no composite step with colour; this build defines one:
+ * the step of soil_erode_step with those arguments filled in —
+ *   1. seed(rng, seed, step * N)
+ *   2. albedo_fluvial = albedo_debris = 0
+ *   3. transport_fluvial(..., albedo_bedrock, albedo_fluvial, albedo_surface, ...)
+ *   4. transport_debris(..., albedo_bedrock, albedo_debris, albedo_surface, ...)
+ *   5. delta = 0
+ *   6. mass_transfer(..., albedo_bedrock, albedo_fluvial, albedo_debris, albedo_surface, ...)
+ *   7. mass_creep   8. layers += delta   9. layer_merge
+ *  10. the physics flux planes zeroed (or left dirty: SOIL_STEP_FLUX_*).
+ * Step 2 keeps a step's colour flux from being added onto the previous step's colours. */
+typedef struct soil_colour_planes {
+  const float* albedo_bedrock; /* in     __transfer's colour where the cell has no sediment (erosion.cu:558-559) */
+  float* albedo_surface;       /* inout  the particles' colour source at their spawn cells (:91, :299);
+                                         mixed in place by __transfer (:558-572)                          */
+  float* albedo_fluvial;       /* inout  stale on entry; this step's fluvial colour flux, normalised in
+                                         place into the transport colour (:181-185), which it holds on exit */
+  float* albedo_debris;        /* inout  the same for the debris launch (:387-391)                        */
+} soil_colour_planes;
+
+/* The fused cell phase of the coloured step: soil_erode_cells_fused_ex, plus per cell the colour
+ * branches of both normalises (reading massFlux / debrisFlux for m; 3-component norm, SURVEY.md
+ * Appendix A4), __transfer's colour mix and the in-place writes of albedo_fluvial, albedo_debris
+ * and albedo_surface — bit-identical to normalize_fluvial, normalize_debris, mass_transfer,
+ * mass_creep, add, layer_merge with the colour planes, one after another.  Flags and the row range
+ * of `dom` as soil_erode_cells_fused_ex.  168 algorithmic bytes per cell with SOIL_CELLS_KEEP_FLUX
+ * (84 physics + 48 colour read + 36 colour written; albedo_bedrock's read and albedo_surface's
+ * write counted in full).  Every colour plane is required. */
+int soil_erode_cells_fused_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                  const soil_domain* dom, const float scale[3], const soil_param* param,
+                                  int flags, void* stream);
+/* Both particle launches of the coloured step, overlapped as soil_particles_pair_slab_ex (whole
+ * (H, W) grid only): the fluvial launch adds its colour flux to albedo_fluvial, the debris launch to
+ * albedo_debris, both reading the spawn cell's colour from albedo_surface.  The two colour planes are
+ * cleared first and hold exactly this call's colour deposits on return; `flags` (SOIL_FLUX_OVERWRITE)
+ * concerns the physics flux planes.  Spent debris walkers are retired as soil_set_debris_retire says,
+ * a walker whose colour deposit can still be anything but zero excepted (debris_spent). */
+int soil_particles_pair_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                               soil_rng* rng_fluvial, soil_rng* rng_debris, int64_t N, int64_t H, int64_t W,
+                               const float scale[3], const soil_param* param, int flags, void* stream);
+/* One whole coloured step on one device: soil_erode_step_ex with the colour planes (the contract
+ * above): re-seed, soil_particles_pair_colour, soil_erode_cells_fused_colour.  Flags as
+ * soil_erode_step_ex. */
+int soil_erode_step_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                           soil_rng* rng, int64_t N, uint64_t seed, uint64_t step_index, int64_t H,
+                           int64_t W, const float scale[3], const soil_param* param, int flags,
+                           void* stream);
+
 /* The containers of the legacy API (example/erosion_gpu.py:44-71): model_t, the `data` and the
  * `track` buffers.  All float32 device planes of H*W cells ((H,W,2) for the momenta). */
 typedef struct soil_erode_model {
@@ -421,7 +474,10 @@ int soil_get_particle_arith(void);
  *   0 = walked to the end, as the reference does.
  *   2 = watched: marked, walked on, and every deposit of a marked walker that is not an exact zero (and every
  *       marked walker that stops qualifying) counted — soil_debris_retire_violations; the tests want 0.
- * Off in the slab runner's migrate mode (the walker's later cells lie on other ranks) and with colour planes.
+ * Off in the slab runner's migrate mode (the walker's later cells lie on other ranks) and in the launches with
+ * colour planes of soil_transport_debris / soil_particles_debris_slab (walked to the end); on in the coloured
+ * step's launches (soil_particles_pair_colour, soil_erode_step_colour), where a spent walker's colour deposit
+ * att_d * source_d * albedo must be an exact zero too.
  * SOIL_DEBRIS_RETIRE in the environment sets the default of the process. */
 int soil_set_debris_retire(int mode);
 int soil_get_debris_retire(void);

@@ -60,6 +60,14 @@ class ErosionPlanes(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _PLANES]
 
 
+COLOUR_PLANES = ("albedo_bedrock", "albedo_surface", "albedo_fluvial", "albedo_debris")
+
+
+class ColourPlanes(C.Structure):
+    """soil_colour_planes: the four (rows, W, 3) colour planes of the coloured step."""
+    _fields_ = [(n, C.c_void_p) for n in COLOUR_PLANES]
+
+
 _ERODE_MODEL = ("height", "sediment", "uplift", "rainfall", "discharge", "mass", "momentum", "debris",
                 "debris_momentum", "discharge_track", "mass_track", "momentum_track", "debris_track",
                 "debris_momentum_track")
@@ -124,6 +132,12 @@ SIGNATURES = {
                                   C.POINTER(Param), cint, vp]),
     "soil_erode_step": (cint, [C.POINTER(ErosionPlanes), vp, i64, u64, u64, i64, i64, F3,
                                C.POINTER(Param), vp]),
+    "soil_erode_cells_fused_colour": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes),
+                                             C.POINTER(Domain), F3, C.POINTER(Param), cint, vp]),
+    "soil_particles_pair_colour": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), vp, vp, i64,
+                                          i64, i64, F3, C.POINTER(Param), cint, vp]),
+    "soil_erode_step_colour": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), vp, i64, u64, u64,
+                                      i64, i64, F3, C.POINTER(Param), cint, vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),

@@ -54,19 +54,21 @@ __device__ __forceinline__ DebrisOut normalize_debris_cell(float2 grad, float ma
 
 // albedo tail of both normalise kernels, erosion.cu:181-185 / :387-391
 // (3-component norm: SURVEY.md Appendix A4)
+// The colour of one cell in registers: a = the colour flux on entry, the transport colour on return.
+__device__ __forceinline__ void normalize_albedo(float a[3], const float source[3], float m) {
+  if (m > 0.0f && sqrtf(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) > 0.0f) {
+    for (int c = 0; c < 3; ++c) a[c] = a[c] / m;
+  } else {
+    for (int c = 0; c < 3; ++c) a[c] = source[c];
+  }
+}
 __device__ __forceinline__ void normalize_albedo_cell(float* __restrict__ albedoFlux,
                                                       const float* __restrict__ albedoSource,
                                                       int64_t n, float m) {
-  const float a0 = albedoFlux[3 * n], a1 = albedoFlux[3 * n + 1], a2 = albedoFlux[3 * n + 2];
-  if (m > 0.0f && sqrtf(a0 * a0 + a1 * a1 + a2 * a2) > 0.0f) {
-    albedoFlux[3 * n] = a0 / m;
-    albedoFlux[3 * n + 1] = a1 / m;
-    albedoFlux[3 * n + 2] = a2 / m;
-  } else {
-    albedoFlux[3 * n] = albedoSource[3 * n];
-    albedoFlux[3 * n + 1] = albedoSource[3 * n + 1];
-    albedoFlux[3 * n + 2] = albedoSource[3 * n + 2];
-  }
+  float a[3] = {albedoFlux[3 * n], albedoFlux[3 * n + 1], albedoFlux[3 * n + 2]};
+  const float src[3] = {albedoSource[3 * n], albedoSource[3 * n + 1], albedoSource[3 * n + 2]};
+  normalize_albedo(a, src, m);
+  for (int c = 0; c < 3; ++c) albedoFlux[3 * n + c] = a[c];
 }
 
 // Physics half of __transfer, erosion.cu:476-547.  Updates `delta` in place and
@@ -112,6 +114,31 @@ __device__ __forceinline__ float transfer_cell(float2& delta, float2 layer, floa
     delta.x += transfer / s.z;
   }
   return transfer;
+}
+
+// Colour half of __transfer, erosion.cu:553-572: `surface` (albedo_surface of the cell) is mixed in place
+// with the transport colours `fluvial` / `debris` (both normalised), or replaced by `bedrock` where the cell
+// has no sediment.  `transfer` is what transfer_cell returned.
+__device__ __forceinline__ void transfer_albedo(float surface[3], const float bedrock[3],
+                                                const float fluvial[3], const float debris[3],
+                                                float2 layer, float massHeight, float debrisHeight,
+                                                float transfer, Scale3 s) {
+  const float eps = 1E-12f;
+  const float totalHeight = massHeight + debrisHeight;
+  const float mixDepth = 1.0f;
+  if (layer.y == 0.0f) {
+    for (int c = 0; c < 3; ++c) surface[c] = bedrock[c];
+  } else if (totalHeight > 0.0f && transfer > eps) {
+    const float wMass = fminf(massHeight / totalHeight, 1.0f);
+    const float wSurf = fminf(mixDepth, layer.y * s.z);
+    const float wTrsp = fmaxf(eps, transfer);
+    const float w = fminf(wTrsp / (wTrsp + wSurf), 1.0f);
+    for (int c = 0; c < 3; ++c) {
+      const float colorTransport = fminf(wMass * fluvial[c] + (1.0f - wMass) * debris[c], 1.0f);
+      const float colorSurface = fminf(surface[c], 1.0f);
+      surface[c] = w * colorTransport + (1.0f - w) * colorSurface;
+    }
+  }
 }
 
 // the lambda at erosion.cu:675-680

@@ -108,23 +108,15 @@ __global__ void __launch_bounds__(kBlock)
   deltas[n] = delta;  // :547
 
   if (albedo_surface) {  // :553-572
-    const float eps = 1E-12f;
-    const float totalHeight = massHeight + debrisHeight;
-    const float mixDepth = 1.0f;
-    if (layer.y == 0.0f) {
-      for (int c = 0; c < 3; ++c) albedo_surface[3 * n + c] = albedo_bedrock[3 * n + c];
-    } else if (totalHeight > 0.0f && transfer > eps) {
-      const float wMass = fminf(massHeight / totalHeight, 1.0f);
-      const float wSurf = fminf(mixDepth, layer.y * s.z);
-      const float wTrsp = fmaxf(eps, transfer);
-      const float w = fminf(wTrsp / (wTrsp + wSurf), 1.0f);
-      for (int c = 0; c < 3; ++c) {
-        const float colorTransport = fminf(
-            wMass * albedoFluvial[3 * n + c] + (1.0f - wMass) * albedoDebris[3 * n + c], 1.0f);
-        const float colorSurface = fminf(albedo_surface[3 * n + c], 1.0f);
-        albedo_surface[3 * n + c] = w * colorTransport + (1.0f - w) * colorSurface;
-      }
+    float surface[3], bedrock[3], fluvial[3], debris_c[3];
+    for (int c = 0; c < 3; ++c) {
+      surface[c] = albedo_surface[3 * n + c];
+      bedrock[c] = albedo_bedrock[3 * n + c];
+      fluvial[c] = albedoFluvial[3 * n + c];
+      debris_c[c] = albedoDebris[3 * n + c];
     }
+    transfer_albedo(surface, bedrock, fluvial, debris_c, layer, massHeight, debrisHeight, transfer, s);
+    for (int c = 0; c < 3; ++c) albedo_surface[3 * n + c] = surface[c];
   }
 }
 
@@ -234,6 +226,11 @@ struct Planes {  // soil_erosion_planes by value, typed
   float* debrisFlux;
   float2* debrisVelocity;
   float2* debrisVelocityFlux;
+  // soil_colour_planes (vec3 AoS; null in the physics-only launches)
+  const float* albedoBedrock;
+  float* albedoSurface;
+  float* albedoFluvial;
+  float* albedoDebris;
 };
 
 struct Row4 {  // four consecutive float2
@@ -291,6 +288,7 @@ struct CellResult {
   float height;
   FluvialOut fl;
   DebrisOut db;
+  float transfer;  // what __transfer's colour block reads (:558-572)
 };
 __device__ __forceinline__ CellResult fused_cell(const Nbhd& nb, float uplift, float rainfall,
                                                  float waterFlux, float massFlux, float2 velFlux,
@@ -301,11 +299,24 @@ __device__ __forceinline__ CellResult fused_cell(const Nbhd& nb, float uplift, f
   r.fl = normalize_fluvial_cell(grad, waterFlux, massFlux, velFlux, rainfall, s, p);
   r.db = normalize_debris_cell(grad, debrisFlux, debrisVelFlux, s, p);
   float2 delta = make_float2(0.0f, 0.0f);  // silt.set(delta, 0)
-  (void)transfer_cell(delta, nb.l00, grad, uplift, r.fl.mass, r.fl.velocity, r.db.mass, s, p);
+  r.transfer = transfer_cell(delta, nb.l00, grad, uplift, r.fl.mass, r.fl.velocity, r.db.mass, s, p);
   delta.y += creep_cell(nb.l00, nb.ln0, nb.lp0, nb.l0n, nb.l0p, s, p.critSlopeSediment);
   r.layers_next = make_float2(nb.l00.x + delta.x, nb.l00.y + delta.y);  // silt.add(layers, delta)
   r.height = r.layers_next.x + r.layers_next.y;                         // __layer_merge
   return r;
+}
+
+// The colour of one cell of the coloured step, after fused_cell: the colour branches of __normalize_fluvial
+// (:181-185) and __normalize_debris (:387-391) on the raw mass fluxes, then __transfer's mix (:553-572).  On
+// entry `fluvial` / `debris` hold the colour fluxes and `surface` albedo_surface; on return the two transport
+// colours and the mixed surface colour.  The normalises read the surface colour as it was on entry, as the
+// reference's order of launches has it.
+__device__ __forceinline__ void colour_cell(float fluvial[3], float debris[3], float surface[3],
+                                            const float bedrock[3], float massFlux, float debrisFlux,
+                                            float2 layer, const CellResult& r, Scale3 s) {
+  normalize_albedo(fluvial, surface, massFlux);
+  normalize_albedo(debris, surface, debrisFlux);
+  transfer_albedo(surface, bedrock, fluvial, debris, layer, r.fl.mass, r.db.mass, r.transfer, s);
 }
 
 // DIRECT: every lane stores its own 32 bytes of a two-channel plane (round 1's stores) instead of
@@ -313,7 +324,10 @@ __device__ __forceinline__ CellResult fused_cell(const Nbhd& nb, float uplift, f
 // (SOIL_CELLS_VARIANT=4)
 // REZERO = false: the five flux planes are left as they are (SOIL_CELLS_KEEP_FLUX: the next particle
 // launch overwrites them, soil_erode_step's lazy mode) — 84 instead of 112 bytes per cell.
-template <bool XCD_REMAP, bool NT, int BLOCK = kBlock, bool DIRECT = false, bool REZERO = true>
+// ALB: the coloured step (soil_erode_cells_fused_colour) — the four vec3 planes of Planes too: a lane's
+// four cells are 48 contiguous, 16-byte aligned bytes of each (three 16-byte accesses), 168 bytes per cell
+// with REZERO = false.
+template <bool XCD_REMAP, bool NT, int BLOCK = kBlock, bool DIRECT = false, bool REZERO = true, bool ALB = false>
 __global__ void __launch_bounds__(BLOCK)
     k_erode_cells_fused(Planes P, Dom d, Scale3 s, Param p, int64_t groups_per_row,
                         int64_t total_groups) {
@@ -348,6 +362,17 @@ __global__ void __launch_bounds__(BLOCK)
   load4<NT>(P.debrisFlux + n0, dflux);
   const Row4 vflux = load_row4<NT>(P.velocityFlux + n0);
   const Row4 dvflux = load_row4<NT>(P.debrisVelocityFlux + n0);
+  // colour: 4 cells x 3 channels of each plane, [3 * k + c] = channel c of cell k
+  float a_bed[ALB ? 3 * kVec : 1], a_surf[ALB ? 3 * kVec : 1], a_fl[ALB ? 3 * kVec : 1], a_db[ALB ? 3 * kVec : 1];
+  if constexpr (ALB) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      load4<NT>(P.albedoBedrock + 3 * n0 + 4 * j, a_bed + 4 * j);
+      load4<NT>(P.albedoSurface + 3 * n0 + 4 * j, a_surf + 4 * j);
+      load4<NT>(P.albedoFluvial + 3 * n0 + 4 * j, a_fl + 4 * j);
+      load4<NT>(P.albedoDebris + 3 * n0 + 4 * j, a_db + 4 * j);
+    }
+  }
   const bool has_left = y0 - 1 >= 0, has_right = y0 + kVec < d.W;
   // lanes at a wave edge, or whose shuffle partner sits on another row, reload
   const bool left_ok = lane != 0 && (gsafe % groups_per_row) != 0;
@@ -388,6 +413,8 @@ __global__ void __launch_bounds__(BLOCK)
     o_vel.v[k] = r.fl.velocity;
     o_d[k] = r.db.mass;
     o_dvel.v[k] = r.db.velocity;
+    if constexpr (ALB)
+      colour_cell(a_fl + 3 * k, a_db + 3 * k, a_surf + 3 * k, a_bed + 3 * k, mflux[k], dflux[k], c.v[k], r, s);
   }
 
   if constexpr (DIRECT) {
@@ -439,6 +466,14 @@ __global__ void __launch_bounds__(BLOCK)
   store4<NT>(P.waterHeight + n0, o_wh);
   store4<NT>(P.mass + n0, o_m);
   store4<NT>(P.debris + n0, o_d);
+  if constexpr (ALB) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      store4<NT>(P.albedoFluvial + 3 * n0 + 4 * j, a_fl + 4 * j);
+      store4<NT>(P.albedoDebris + 3 * n0 + 4 * j, a_db + 4 * j);
+      store4<NT>(P.albedoSurface + 3 * n0 + 4 * j, a_surf + 4 * j);
+    }
+  }
   if (REZERO) {  // re-zero the scalar flux planes for the next step's atomics
     const float z[kVec] = {0.0f, 0.0f, 0.0f, 0.0f};
     store4<NT>(P.waterFlux + n0, z);
@@ -481,6 +516,21 @@ __global__ void __launch_bounds__(kBlock)
   P.velocity[n] = r.fl.velocity;
   P.debris[n] = r.db.mass;
   P.debrisVelocity[n] = r.db.velocity;
+  if (P.albedoSurface) {  // the coloured step
+    float fl[3], db[3], surf[3], bed[3];
+    for (int c = 0; c < 3; ++c) {
+      fl[c] = P.albedoFluvial[3 * n + c];
+      db[c] = P.albedoDebris[3 * n + c];
+      surf[c] = P.albedoSurface[3 * n + c];
+      bed[c] = P.albedoBedrock[3 * n + c];
+    }
+    colour_cell(fl, db, surf, bed, P.massFlux[n], P.debrisFlux[n], nb.l00, r, s);
+    for (int c = 0; c < 3; ++c) {
+      P.albedoFluvial[3 * n + c] = fl[c];
+      P.albedoDebris[3 * n + c] = db[c];
+      P.albedoSurface[3 * n + c] = surf[c];
+    }
+  }
   if (!rezero) return;
   P.waterFlux[n] = 0.0f;
   P.massFlux[n] = 0.0f;
@@ -645,9 +695,14 @@ int soil_erode_cells_fused(const soil_erosion_planes* pl, const soil_domain* dom
   return soil_erode_cells_fused_ex(pl, dom, scale, param, 0, stream);
 }
 
-int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* dom,
-                              const float scale[3], const soil_param* param, int flags, void* stream) {
-  SOIL_DEVICE();
+}  // extern "C"
+
+namespace soil {
+
+// soil_erode_cells_fused_ex (colour == nullptr) and soil_erode_cells_fused_colour
+static int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* colour,
+                             const soil_domain* dom, const float scale[3], const soil_param* param,
+                             int flags, void* stream) {
   SOIL_REQUIRE(pl && dom && scale && param, "erode_cells_fused: null argument");
   SOIL_REQUIRE(pl->layers && pl->layers_next && pl->uplift && pl->rainfall && pl->waterHeight &&
                    pl->waterFlux && pl->mass && pl->massFlux && pl->velocity &&
@@ -662,7 +717,7 @@ int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* 
   const int64_t cells = (d.r1 - d.r0) * d.W;
   if (cells <= 0) return SOIL_OK;
 
-  Planes P;
+  Planes P{};
   P.layers = reinterpret_cast<const float2*>(pl->layers);
   P.layers_next = reinterpret_cast<float2*>(pl->layers_next);
   P.height = pl->height;
@@ -678,6 +733,12 @@ int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* 
   P.debrisFlux = pl->debrisFlux;
   P.debrisVelocity = reinterpret_cast<float2*>(pl->debrisVelocity);
   P.debrisVelocityFlux = reinterpret_cast<float2*>(pl->debrisVelocityFlux);
+  if (colour) {
+    P.albedoBedrock = colour->albedo_bedrock;
+    P.albedoSurface = colour->albedo_surface;
+    P.albedoFluvial = colour->albedo_fluvial;
+    P.albedoDebris = colour->albedo_debris;
+  }
 
   const bool vec_ok = (d.W % kVec == 0) && aligned16(pl->layers) && aligned16(pl->layers_next) &&
                       (!pl->height || aligned16(pl->height)) && aligned16(pl->uplift) &&
@@ -685,9 +746,22 @@ int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* 
                       aligned16(pl->waterFlux) && aligned16(pl->mass) && aligned16(pl->massFlux) &&
                       aligned16(pl->velocity) && aligned16(pl->velocityFlux) &&
                       aligned16(pl->debris) && aligned16(pl->debrisFlux) &&
-                      aligned16(pl->debrisVelocity) && aligned16(pl->debrisVelocityFlux);
+                      aligned16(pl->debrisVelocity) && aligned16(pl->debrisVelocityFlux) &&
+                      (!colour || (aligned16(colour->albedo_bedrock) && aligned16(colour->albedo_surface) &&
+                                   aligned16(colour->albedo_fluvial) && aligned16(colour->albedo_debris)));
   hipStream_t st = as_stream(stream);
-  if (vec_ok) {
+  if (vec_ok && colour) {
+    // the coloured step: the 168-byte kernel, and the flux planes' re-zero as a pass of its own unless
+    // SOIL_CELLS_KEEP_FLUX (the physics path's default split)
+    const int64_t groups_per_row = d.W / kVec;
+    const int64_t total = (d.r1 - d.r0) * groups_per_row;
+    const unsigned nblk = blocks_for(total, kBlock);
+    if (nblk % 8 == 0 && nblk >= 64)
+      k_erode_cells_fused<true, false, kBlock, false, false, true><<<nblk, kBlock, 0, st>>>(P, d, s3(scale), *param, groups_per_row, total);
+    else
+      k_erode_cells_fused<false, false, kBlock, false, false, true><<<nblk, kBlock, 0, st>>>(P, d, s3(scale), *param, groups_per_row, total);
+    if ((flags & SOIL_CELLS_KEEP_FLUX) == 0) k_zero_flux<<<nblk, kBlock, 0, st>>>(P, d.r0 * d.W, total);
+  } else if (vec_ok) {
     const int64_t groups_per_row = d.W / kVec;
     const int64_t total = (d.r1 - d.r0) * groups_per_row;
     const unsigned nblk = blocks_for(total, kBlock);
@@ -727,6 +801,26 @@ int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* 
   }
   SOIL_LAUNCH_CHECK();
   return SOIL_OK;
+}
+
+}  // namespace soil
+
+extern "C" {
+
+int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* dom,
+                              const float scale[3], const soil_param* param, int flags, void* stream) {
+  SOIL_DEVICE();
+  return erode_cells_fused(pl, nullptr, dom, scale, param, flags, stream);
+}
+
+int soil_erode_cells_fused_colour(const soil_erosion_planes* pl, const soil_colour_planes* colour,
+                                  const soil_domain* dom, const float scale[3], const soil_param* param,
+                                  int flags, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(colour && colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial &&
+                   colour->albedo_debris,
+               "erode_cells_fused_colour: every colour plane is required");
+  return erode_cells_fused(pl, colour, dom, scale, param, flags, stream);
 }
 
 }  // extern "C"

@@ -763,6 +763,45 @@ int soil_particles_pair_slab_ex(const soil_erosion_planes* planes, soil_rng* rng
                                  P.debrisVelocity, nullptr, remote0, d, s, *param, st);
 }
 
+int soil_particles_pair_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                               soil_rng* rng_fluvial, soil_rng* rng_debris, int64_t N, int64_t H, int64_t W,
+                               const float scale[3], const soil_param* param, int flags, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && colour && scale && param, "particles_pair_colour: null argument");
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
+                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
+               "particles_pair_colour: null plane");
+  SOIL_REQUIRE(colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial && colour->albedo_debris,
+               "particles_pair_colour: every colour plane is required");
+  SOIL_REQUIRE(H > 0 && W > 0, "particles_pair_colour: empty grid");
+  SOIL_REQUIRE(N >= 0 && (N == 0 || (rng_fluvial && rng_debris && rng_fluvial != rng_debris)),
+               "particles_pair_colour: needs two distinct rng tensors");
+  const Dom d = full_domain(H, W);
+  hipStream_t st = as_stream(stream);
+  const Scale3 s = s3p(scale);
+  const bool overwrite = (flags & SOIL_FLUX_OVERWRITE) != 0;
+  if (N > 0 && use_tiled(N, d))
+    return launch_pair_tiled(P, streams_of(rng_fluvial), streams_of(rng_debris), N, nullptr, d, s, *param, st,
+                             overwrite, MigrateBox{}, MigrateBox{}, nullptr, 0, nullptr, 0, colour);
+  // the small-N shapes: one launch after the other, every walker walked to the end
+  const size_t b = sizeof(float) * static_cast<size_t>(H) * static_cast<size_t>(W);
+  if (overwrite) {
+    for (float* t : {P.waterFlux, P.massFlux, P.debrisFlux}) SOIL_HIP(hipMemsetAsync(t, 0, b, st));
+    for (float* t : {P.velocityFlux, P.debrisVelocityFlux}) SOIL_HIP(hipMemsetAsync(t, 0, 2 * b, st));
+  }
+  SOIL_HIP(hipMemsetAsync(colour->albedo_fluvial, 0, 3 * b, st));
+  SOIL_HIP(hipMemsetAsync(colour->albedo_debris, 0, 3 * b, st));
+  if (N <= 0) return SOIL_OK;
+  if (int rc = launch_particles_fluvial(P.waterFlux, P.massFlux, P.velocityFlux, colour->albedo_fluvial, rng_fluvial,
+                                        N, P.layers, P.rainfall, P.waterHeight, P.velocity, colour->albedo_surface,
+                                        nullptr, d, s, *param, st);
+      rc != SOIL_OK)
+    return rc;
+  return launch_particles_debris(P.debrisFlux, P.debrisVelocityFlux, colour->albedo_debris, rng_debris, N, P.layers,
+                                 P.debrisVelocity, colour->albedo_surface, nullptr, d, s, *param, st);
+}
+
 int soil_particle_steps(uint64_t* total, int reset, void* stream) {
   SOIL_REQUIRE(total != nullptr, "soil_particle_steps: null output");
   unsigned long long* counter = nullptr;

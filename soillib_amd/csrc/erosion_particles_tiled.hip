@@ -312,14 +312,25 @@ extern "C" int soil_retire_dbg_read(float* out) {
 // So: every cell's record |a| <= kSpentSpeed * D (debris_cell_bad), the spent walker's |spx|, |spy| <= kSpentSpeed
 // (debris_spent), maxage <= 2^24 (debris_params_allow_retire).  The example's parameters: D = 2.4e10, |a| ~ 1e2.
 constexpr float kSpentSpeed = 1.0e17f;
+//
+// With colour planes (the coloured step's launches only: TiledRun::retire_colour) a walker also deposits
+// att_d * sa_c, c = 0, 1, 2 (PRec::sa0..sa2 = source_d * albedoSource at the spawn cell, :299, :315-317), so a
+// spent walker also needs att_d * sa_c == 0 for each c.  That stays so: att_d only ever takes factors
+// exp(decay_d) in [0, 1] (decay_d <= 0 or -0, above), so |att_d| never grows, |att_d * sa_c| is not larger than
+// it was, and rounding is monotonic — a product that rounded to zero keeps rounding to zero; sa_c is constant.
+// A non-finite spawn colour never qualifies: att_d * inf or att_d * NaN is NaN or inf (0 * inf is NaN).
+__device__ __forceinline__ bool debris_colour_spent(const PRec& r) {
+  return r.a0 * r.sa0 == 0.0f && r.a0 * r.sa1 == 0.0f && r.a0 * r.sa2 == 0.0f;
+}
 __device__ __forceinline__ bool debris_cell_bad(const float4 qd, const Param& param) {
   const float es = param.gravity * (qd.z - param.yieldStress / 1E-12f);  // :340 with debrisHeight = eps
   const float t = (qd.x - qd.x) + (qd.y - qd.y) + (es - es);             // 0 iff all three are finite
   const float D = param.viscosityDebris + param.bedShearDebris / 1E-12f;  // :333 / :343 with debrisHeight = eps
   return !(es < 0.0f) || !(t == 0.0f) || !(fmaxf(fabsf(qd.x), fabsf(qd.y)) <= kSpentSpeed * D);
 }
-__device__ __forceinline__ bool debris_spent(const PRec& r) {
+__device__ __forceinline__ bool debris_spent(const PRec& r, bool colour = false) {
   if (!(r.a1 == 0.0f && r.a0 * r.s0 == 0.0f)) return false;
+  if (colour && !debris_colour_spent(r)) return false;
   const float t = ((r.px - r.px) + (r.py - r.py)) + ((r.spx - r.spx) + (r.spy - r.spy)) +
                   ((r.svx - r.svx) + (r.svy - r.svy)) + ((r.s0 - r.s0) + (r.a0 - r.a0));
   return t == 0.0f && r.a0 >= 0.0f && fmaxf(fabsf(r.spx), fabsf(r.spy)) <= kSpentSpeed;
@@ -845,7 +856,7 @@ __global__ void __launch_bounds__(256)
         r.iter = 1;
         head_steps = 1;
         walks_on = fast ? advance<DEBRIS, true>(r, q, k) : advance<DEBRIS, false>(r, q, k);  // false: v_norm < eps, :326-327
-        walks_on = walks_on && !debris_spent(r);
+        walks_on = walks_on && !debris_spent(r, albedoSource != nullptr);
         // ... and where the step took it: off the grid the walk is over (:306), off the slab's rows it is another
         // rank's (a finite walker leaves nothing behind: park_remote), as the round kernel sorts a stop out
         const int ix = floor_cell(r.px), iy = floor_cell(r.py);
@@ -1967,7 +1978,9 @@ __global__ void __launch_bounds__(NT, SPARSE ? 2 : round_waves_per_simd(KIND, TR
           float v[kFluxPlanes + 3];
           float* pp[kFluxPlanes + 3];
           deposit_terms(c, v, pp);
-          if (KIND == DEBRIS && retire == 2u && r.a2 != 0.0f && !(v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f)) {
+          if (KIND == DEBRIS && retire == 2u && r.a2 != 0.0f &&
+              !(v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f &&
+                (!ALB || (v[kFluxPlanes] == 0.0f && v[kFluxPlanes + 1] == 0.0f && v[kFluxPlanes + 2] == 0.0f)))) {
             atomicAdd(&soil_retire_violations_dev, 1ull);  // a marked walker added something: must not happen
             RETIRE_DBG(r, 3.0f);
           }
@@ -2026,7 +2039,7 @@ __global__ void __launch_bounds__(NT, SPARSE ? 2 : round_waves_per_simd(KIND, TR
           const bool walks_on = !(v_norm < k.eps);
           const bool maybe = walks_on && r.a1 == 0.0f && r.a0 * r.s0 == 0.0f;
           if (any_lane(maybe)) {
-            const bool spent = maybe && debris_spent(r);
+            const bool spent = maybe && debris_spent(r, ALB);
             if (retire == 1u) {
               if (spent) {
                 ended |= 1u;
@@ -2513,7 +2526,8 @@ __global__ void __launch_bounds__(256)
         atomicAdd(&fluxV[2 * l], r.a2 * r.svx);
         atomicAdd(&fluxV[2 * l + 1], r.a2 * r.svy);
       } else {
-        if (retire == 2u && r.a2 != 0.0f && !(r.a0 * r.s0 == 0.0f && r.a1 * r.svx == 0.0f && r.a1 * r.svy == 0.0f))
+        if (retire == 2u && r.a2 != 0.0f &&
+            !(r.a0 * r.s0 == 0.0f && r.a1 * r.svx == 0.0f && r.a1 * r.svy == 0.0f && (!fluxA || debris_colour_spent(r))))
           atomicAdd(&soil_retire_violations_dev, 1ull);
         atomicAdd(&flux0[l], r.a0 * r.s0);
         atomicAdd(&fluxV[2 * l], r.a1 * r.svx);
@@ -2528,7 +2542,7 @@ __global__ void __launch_bounds__(256)
     }
     if (!advance<KIND, FAST>(r, q, k)) break;
     if (KIND == DEBRIS && retire != 0u) {  // (the round kernel's rule)
-      const bool spent = debris_spent(r);
+      const bool spent = debris_spent(r, fluxA != nullptr);
       if (retire == 1u) {
         if (spent) break;
       } else {
@@ -2717,6 +2731,7 @@ struct TiledRun {
   int agg_min = 48, agg_groups = 4, retries = 2;
   uint32_t* retire_bad = nullptr;  // debris: set by the pack pass when a cell rules retirement out (debris_cell_bad)
   uint32_t retire_mode = 0;        // debris: soil_set_debris_retire, if the launch constants allow it
+  bool retire_colour = false;      // debris with colour planes: retire all the same (the coloured step's launches)
   bool fast = false;  // the step in fast arithmetic (soil_set_particle_arith; not with colour planes or native adds)
   MigrateBox box{};                 // where walkers that leave the launch's rows go (null count: dropped, as ever)
   const PRec* inbox = nullptr;      // the launch starts from these records instead of the streams' spawns
@@ -2898,8 +2913,10 @@ struct TiledRun {
     static_assert(64 + sizeof(TiledCtl) <= 224, "the pack pass's word stands behind the block begin() clears");
     retire_bad = reinterpret_cast<uint32_t*>(w + 224);
     // spent debris walkers end their walks (debris_spent).  Not in migrate mode: the walker's later cells lie on
-    // other ranks, whose pack passes this rank's word knows nothing about.  Not with colour planes (never measured).
-    retire_mode = (KIND == DEBRIS && !box.count && !fluxA && debris_params_allow_retire(p))
+    // other ranks, whose pack passes this rank's word knows nothing about.  With colour planes only where the
+    // caller asks for it (retire_colour: the coloured step); soil_transport_debris and soil_particles_debris_slab
+    // with colour walk every walker to the end, as they always did.
+    retire_mode = (KIND == DEBRIS && !box.count && (!fluxA || retire_colour) && debris_params_allow_retire(p))
                       ? static_cast<uint32_t>(debris_retire_mode()) : 0u;
     rc = step_counter(&steps_global);
     if (rc != SOIL_OK) return rc;
@@ -3230,7 +3247,7 @@ static int run_tiled(float* flux0, float* flux1, float* fluxV, float* fluxA,
 int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams rng_debris, int64_t N,
                       float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st, bool overwrite,
                       MigrateBox box_fluvial, MigrateBox box_debris, const void* inbox_fluvial, uint32_t n_fluvial,
-                      const void* inbox_debris, uint32_t n_debris) {
+                      const void* inbox_debris, uint32_t n_debris, const soil_colour_planes* colour) {
   // forked streams and their events, one set per (thread, device)
   struct Fork {
     hipStream_t sA = nullptr, sB = nullptr;
@@ -3293,6 +3310,14 @@ int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams
   // still be in flight on the workspace the next call reuses.
   A.overwrite = B.overwrite = overwrite;
   A.box = box_fluvial, B.box = box_debris;
+  if (colour) {  // the coloured step: colour flux planes cleared here, spent debris walkers retired
+    A.fluxA = colour->albedo_fluvial, A.albedoSource = colour->albedo_surface;
+    B.fluxA = colour->albedo_debris, B.albedoSource = colour->albedo_surface;
+    B.retire_colour = true;
+    const size_t b3 = 3 * sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
+    SOIL_HIP(hipMemsetAsync(colour->albedo_fluvial, 0, b3, st));  // ahead of the fork
+    SOIL_HIP(hipMemsetAsync(colour->albedo_debris, 0, b3, st));
+  }
   const bool immigrants = inbox_fluvial != nullptr || inbox_debris != nullptr;
   if (immigrants) {  // both kinds' handed-over walkers, walked on side by side: the step's pack pass stands
     A.inbox = static_cast<const PRec*>(inbox_fluvial), A.n_in = n_fluvial;

@@ -123,6 +123,37 @@ int soil_erode_step_ex(const soil_erosion_planes* planes, soil_rng* rng, int64_t
   return soil_erode_cells_fused_ex(planes, &dom, scale, param, cell_flags, stream);
 }
 
+int soil_erode_step_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour, soil_rng* rng,
+                           int64_t N, uint64_t seed, uint64_t step_index, int64_t H, int64_t W,
+                           const float scale[3], const soil_param* param, int flags, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && colour && rng && scale && param, "erode_step_colour: null argument");
+  SOIL_REQUIRE(H > 0 && W > 0 && N > 0, "erode_step_colour: empty grid or no particles");
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux &&
+                   P.mass && P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux &&
+                   P.debrisVelocity && P.debrisVelocityFlux,
+               "erode_step_colour: every plane but `height` is required");
+  SOIL_REQUIRE(colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial && colour->albedo_debris,
+               "erode_step_colour: every colour plane is required");
+  const soil_domain dom{H, W, 0, H, 0, H};
+  const uint64_t offset = step_index * static_cast<uint64_t>(N);
+  const bool in_dirty = (flags & SOIL_STEP_FLUX_IN_DIRTY) != 0, out_dirty = (flags & SOIL_STEP_FLUX_OUT_DIRTY) != 0;
+  // both launches overlapped as in soil_erode_step_ex: the fluvial one draws from the workspace's
+  // tensor, the debris one from `rng` seeded two draws on
+  void* scratch = nullptr;
+  if (int rc = workspace_get(7, sizeof(soil_rng) * static_cast<size_t>(N), &scratch); rc != SOIL_OK) return rc;
+  soil_rng* rng_fluvial = static_cast<soil_rng*>(scratch);
+  if (int rc = soil_rng_seed(rng_fluvial, N, seed, offset, stream); rc != SOIL_OK) return rc;
+  if (int rc = soil_rng_seed(rng, N, seed, offset + 2, stream); rc != SOIL_OK) return rc;
+  if (int rc = soil_particles_pair_colour(planes, colour, rng_fluvial, rng, N, H, W, scale, param,
+                                          in_dirty ? SOIL_FLUX_OVERWRITE : 0, stream);
+      rc != SOIL_OK)
+    return rc;
+  return soil_erode_cells_fused_colour(planes, colour, &dom, scale, param, out_dirty ? SOIL_CELLS_KEEP_FLUX : 0,
+                                       stream);
+}
+
 int soil_erode(const soil_erode_model* model, int64_t H, int64_t W, int64_t N, uint64_t seed,
                uint64_t first_step, int steps, const float scale[3], const soil_param* param,
                void* stream) {

@@ -113,7 +113,9 @@ int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams
                       int64_t N, float* remote0, const Dom& d, Scale3 s, const Param& p,
                       hipStream_t st, bool overwrite, MigrateBox box_fluvial = MigrateBox{},
                       MigrateBox box_debris = MigrateBox{}, const void* inbox_fluvial = nullptr,
-                      uint32_t n_fluvial = 0, const void* inbox_debris = nullptr, uint32_t n_debris = 0);
+                      uint32_t n_fluvial = 0, const void* inbox_debris = nullptr, uint32_t n_debris = 0,
+                      const soil_colour_planes* colour = nullptr);
+// (`colour`: the coloured step's planes — soil_particles_pair_colour; the colour flux planes are cleared first)
 // (inboxes: both launches start from handed-over records instead of the streams' spawns — the immigrants of
 // both kinds walked on side by side, slab runner's migrate mode; the pack pass of the step's spawn launches
 // stands)

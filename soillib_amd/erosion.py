@@ -14,6 +14,11 @@ ONE fused cell kernel (soil_erode_cells_fused) that also re-zeroes the flux
 planes; `step_unfused()` runs the same step through the individual reference
 ops (one launch each) and exists so that tests can show both are bit-identical.
 The model may be a row slab of a larger grid (see soillib_amd.parallel).
+
+`ErosionModel(..., colour=True)` carries the four colour planes of the coloured
+step (include/soil_hip.h, soil_colour_planes) through every phase:
+`step()` is soil_erode_step_colour, `step_unfused()` the same step through the
+reference ops with their albedo arguments.  Whole grids on one GPU only.
 """
 import ctypes as C
 import os
@@ -31,8 +36,10 @@ class ErosionModel:
     PLANES_1 = ("height", "uplift", "rainfall", "waterHeight", "waterFlux", "mass", "massFlux",
                 "debris", "debrisFlux")
     PLANES_2 = ("velocity", "velocityFlux", "debrisVelocity", "debrisVelocityFlux")
+    # soil_colour_planes, in its order: (rows, W, 3) each
+    PLANES_3 = ("albedoBedrock", "albedoSurface", "albedoFluvial", "albedoDebris")
 
-    def __init__(self, H, W, scale, param, n_particles, seed=0, dom=None, alloc=None):
+    def __init__(self, H, W, scale, param, n_particles, seed=0, dom=None, alloc=None, colour=False):
         self.H, self.W = int(H), int(W)
         self.scale = [float(v) for v in scale]
         self.param = param
@@ -40,6 +47,9 @@ class ErosionModel:
         self.seed = int(seed)
         self.dom = dom if dom is not None else _abi.Domain(self.H, self.W, 0, self.H, 0, self.H)
         self.rows = int(self.dom.rows)
+        self.colour = bool(colour)
+        if self.colour and self.rows != self.H:
+            raise ValueError("a coloured model needs the whole grid on one GPU (no slabs)")
         self.step_index = 0
         alloc = alloc or (lambda dtype, shape: silt.tensor(dtype, silt.shape(*shape), silt.gpu))
         self._alloc = alloc
@@ -52,7 +62,9 @@ class ErosionModel:
             setattr(self, name, alloc(silt.float32, (r, w, 2)))
         self.rng = alloc(silt.rng, (self.N,))
         self.rng_debris = alloc(silt.rng, (self.N,))   # the fluvial launch's state two draws on
-        for name in ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2:
+        for name in self.PLANES_3 if self.colour else ():
+            setattr(self, name, alloc(silt.float32, (r, w, 3)))
+        for name in ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2 + (self.PLANES_3 if self.colour else ()):
             silt.set(getattr(self, name), 0.0)
         silt.seed(self.rng, self.seed, 0)
 
@@ -62,6 +74,12 @@ class ErosionModel:
         for name in _abi._PLANES:
             setattr(p, name, getattr(self, name).ptr)
         return p
+
+    def _colour(self):
+        c = _abi.ColourPlanes()
+        for field, name in zip(_abi.COLOUR_PLANES, self.PLANES_3):
+            setattr(c, field, getattr(self, name).ptr)
+        return c
 
     def _scale(self):
         return _abi.vec(self.scale, 3)
@@ -82,24 +100,43 @@ class ErosionModel:
         (SOIL_FLUX_OVERWRITE: the launches' first rounds store instead of adding)."""
         silt.seed(self.rng_debris, self.seed, self.step_index * self.N + 2)
         planes = self._planes()
+        if self.colour:   # soil_particles_pair_colour: the two colour flux planes cleared first
+            colour = self._colour()
+            _abi.check(_abi.lib().soil_particles_pair_colour(
+                C.byref(planes), C.byref(colour), self.rng.c_ptr, self.rng_debris.c_ptr, self.N, self.H,
+                self.W, self._scale(), self.param._ref(), _abi.SOIL_FLUX_OVERWRITE if overwrite else 0,
+                _abi.stream()))
+            return
         _abi.check(_abi.lib().soil_particles_pair_slab_ex(
             C.byref(planes), self.rng.c_ptr, self.rng_debris.c_ptr, self.N, None,
             C.byref(self.dom), self._scale(), self.param._ref(),
             _abi.SOIL_FLUX_OVERWRITE if overwrite else 0, _abi.stream()))
 
     def particles_fluvial(self):
+        """The fluvial launch; a coloured model clears albedoFluvial first and adds this launch's
+        colour flux to it (spawn colours from albedoSurface)."""
         L = _abi.lib()
+        flux_a = src_a = None
+        if self.colour:
+            silt.set(self.albedoFluvial, 0.0)
+            flux_a, src_a = self.albedoFluvial.c_ptr, self.albedoSurface.c_ptr
         _abi.check(L.soil_particles_fluvial_slab(
-            self.waterFlux.c_ptr, self.massFlux.c_ptr, self.velocityFlux.c_ptr, None,
+            self.waterFlux.c_ptr, self.massFlux.c_ptr, self.velocityFlux.c_ptr, flux_a,
             self.rng.c_ptr, self.N, self.layers.c_ptr, self.rainfall.c_ptr,
-            self.waterHeight.c_ptr, self.velocity.c_ptr, None, None, C.byref(self.dom),
+            self.waterHeight.c_ptr, self.velocity.c_ptr, src_a, None, C.byref(self.dom),
             self._scale(), self.param._ref(), _abi.stream()))
 
     def particles_debris(self):
+        """The debris launch; with colour as particles_fluvial, into albedoDebris (every walker
+        walked to the end, as soil_particles_debris_slab with colour planes does)."""
         L = _abi.lib()
+        flux_a = src_a = None
+        if self.colour:
+            silt.set(self.albedoDebris, 0.0)
+            flux_a, src_a = self.albedoDebris.c_ptr, self.albedoSurface.c_ptr
         _abi.check(L.soil_particles_debris_slab(
-            self.debrisFlux.c_ptr, self.debrisVelocityFlux.c_ptr, None, self.rng.c_ptr, self.N,
-            self.layers.c_ptr, self.debrisVelocity.c_ptr, None, None, C.byref(self.dom),
+            self.debrisFlux.c_ptr, self.debrisVelocityFlux.c_ptr, flux_a, self.rng.c_ptr, self.N,
+            self.layers.c_ptr, self.debrisVelocity.c_ptr, src_a, None, C.byref(self.dom),
             self._scale(), self.param._ref(), _abi.stream()))
 
     def cells_fused(self, r0=None, r1=None, keep_flux=False):
@@ -110,9 +147,15 @@ class ErosionModel:
         dom = _abi.Domain(d.H, d.W, d.x0, d.rows, d.r0 if r0 is None else r0,
                           d.r1 if r1 is None else r1)
         planes = self._planes()
+        flags = _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0
+        if self.colour:
+            colour = self._colour()
+            _abi.check(_abi.lib().soil_erode_cells_fused_colour(
+                C.byref(planes), C.byref(colour), C.byref(dom), self._scale(), self.param._ref(), flags,
+                _abi.stream()))
+            return
         _abi.check(_abi.lib().soil_erode_cells_fused_ex(
-            C.byref(planes), C.byref(dom), self._scale(), self.param._ref(),
-            _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0, _abi.stream()))
+            C.byref(planes), C.byref(dom), self._scale(), self.param._ref(), flags, _abi.stream()))
 
     def swap_layers(self):
         self.layers, self.layers_next = self.layers_next, self.layers
@@ -122,7 +165,16 @@ class ErosionModel:
         """One erosion step: 2 particle launches + 1 fused cell launch.  With the whole grid on
         this device it is the library's own step driver (soil_erode_step, csrc/erosion_step.hip:
         seed, both particle launches overlapped on two streams, fused cell phase;
-        SOIL_STEP_PAIR=0 in the environment makes it run them one after the other)."""
+        SOIL_STEP_PAIR=0 in the environment makes it run them one after the other).  A coloured
+        model runs soil_erode_step_colour."""
+        if self.colour:
+            planes, colour = self._planes(), self._colour()
+            _abi.check(_abi.lib().soil_erode_step_colour(
+                C.byref(planes), C.byref(colour), self.rng.c_ptr, self.N, self.seed, self.step_index, self.H,
+                self.W, self._scale(), self.param._ref(), 0, _abi.stream()))
+            self.swap_layers()
+            self.step_index += 1
+            return
         if self.rows == self.H:
             planes = self._planes()
             _abi.check(_abi.lib().soil_erode_step(
@@ -142,21 +194,27 @@ class ErosionModel:
         self.step_index += 1
 
     def step_unfused(self):
-        """The same step through the stand-alone reference ops (single GPU only)."""
+        """The same step through the stand-alone reference ops (single GPU only); with colour the
+        contract of soil_colour_planes (include/soil_hip.h), colour flux planes zeroed first."""
         from . import soil
         if self.rows != self.H:
             raise ValueError("step_unfused needs the whole grid on one GPU")
         self.seed_step()
+        bed = surf = fl = db = None
+        if self.colour:
+            bed, surf, fl, db = self.albedoBedrock, self.albedoSurface, self.albedoFluvial, self.albedoDebris
+            silt.set(fl, 0.0)
+            silt.set(db, 0.0)
         soil.transport_fluvial(self.layers, self.rainfall, self.waterHeight, self.waterFlux,
-                               self.mass, self.massFlux, self.velocity, self.velocityFlux, None,
-                               None, None, self.rng, self.scale, self.param)
+                               self.mass, self.massFlux, self.velocity, self.velocityFlux, bed,
+                               fl, surf, self.rng, self.scale, self.param)
         soil.transport_debris(self.layers, self.debrisVelocity, self.debrisVelocityFlux,
-                              self.debris, self.debrisFlux, None, None, None, self.rng, self.scale,
+                              self.debris, self.debrisFlux, bed, db, surf, self.rng, self.scale,
                               self.param)
         delta = self.layers_next  # reuse the spare layer buffer as the delta plane
         silt.set(delta, 0.0)
         soil.mass_transfer(delta, self.layers, self.uplift, self.waterHeight, self.mass,
-                           self.velocity, self.debris, self.debrisVelocity, None, None, None, None,
+                           self.velocity, self.debris, self.debrisVelocity, bed, fl, db, surf,
                            self.scale, self.param)
         soil.mass_creep(delta, self.layers, self.scale, self.param)
         silt.add(self.layers, delta)
