@@ -407,6 +407,16 @@ int soil_erode_cells_fused_colour(const soil_erosion_planes* planes, const soil_
 int soil_particles_pair_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
                                soil_rng* rng_fluvial, soil_rng* rng_debris, int64_t N, int64_t H, int64_t W,
                                const float scale[3], const soil_param* param, int flags, void* stream);
+/* soil_particles_pair_colour on a row slab (the sharded coloured step, soil_slab.h): spawns, tracing and
+ * ownership as soil_particles_pair_slab_ex, `flags` as there.  Before the launches the two colour flux planes
+ * are cleared over local rows [0, dom->rows); spent debris walkers are retired as in soil_particles_pair_colour.
+ * albedo_bedrock is not read (it may be NULL).  `remote0` (device float[16], may be NULL): [0..7] as
+ * soil_particles_pair_slab's, [8..10] the fluvial and [11..13] the debris colour deposits (att * spawn colour)
+ * of NaN walkers for GLOBAL cell (0,0) when this slab does not hold it; [14..15] unused. */
+int soil_particles_pair_colour_slab(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                    soil_rng* rng_fluvial, soil_rng* rng_debris, int64_t N, float* remote0,
+                                    const soil_domain* dom, const float scale[3], const soil_param* param, int flags,
+                                    void* stream);
 /* One whole coloured step on one device: soil_erode_step_ex with the colour planes (the contract
  * above): re-seed, soil_particles_pair_colour, soil_erode_cells_fused_colour.  Flags as
  * soil_erode_step_ex. */

@@ -140,6 +140,36 @@ typedef struct soil_slab_ops {
                         void* out_down, uint32_t* out_count, int64_t cap);
 } soil_slab_ops;
 
+/* The colour entries of a back-end (soil_slab_create_colour): the launches and the cell phase of the
+ * coloured step (soil_hip.h, soil_colour_planes; DESIGN.md 3.4 and 5, "Colour on slabs") on a slab.  `colour` holds the
+ * four (rows, W, 3) colour planes from the same local row as `planes`.  The particle launches clear
+ * the colour flux plane(s) they add to (albedo_fluvial: fluvial, albedo_debris: debris) over local
+ * rows [0, dom->rows) first, read the spawn colour from albedo_surface, and take a float[16] `remote0`:
+ * [0..7] as soil_slab_ops', [8..10] / [11..13] the fluvial / debris colour deposits of NaN walkers for
+ * global cell (0,0) (soil_particles_pair_colour_slab). */
+typedef struct soil_slab_colour_ops {
+  void* ctx;
+  int (*particles_fluvial)(void* ctx, const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                           soil_rng* rng, int64_t N, float* remote0, const soil_domain* dom, const float scale[3],
+                           const soil_param* param);
+  int (*particles_debris)(void* ctx, const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                          soil_rng* rng, int64_t N, float* remote0, const soil_domain* dom, const float scale[3],
+                          const soil_param* param);
+  /* NULL: the back-end has none (as soil_slab_ops::particles_pair) */
+  int (*particles_pair)(void* ctx, const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                        soil_rng* rng_fluvial, soil_rng* rng_debris, int64_t N, float* remote0,
+                        const soil_domain* dom, const float scale[3], const soil_param* param);
+  /* soil_erode_cells_fused_colour on the local rows [dom->r0, dom->r1) */
+  int (*cells)(void* ctx, const soil_erosion_planes* planes, const soil_colour_planes* colour,
+               const soil_domain* dom, const float scale[3], const soil_param* param);
+  /* soil_slab_ops::particles_pass with colour: the records keep their spawn colour, the immigrants' launches add
+   * colour flux and do not clear.  NULL: SOIL_SLAB_MIGRATE with colour is refused (the HIP table has none). */
+  int (*particles_pass)(void* ctx, int32_t kind, const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                        soil_rng* rng, soil_rng* rng_debris, int64_t N, float* remote0, const soil_domain* dom,
+                        const float scale[3], const soil_param* param, const void* inbox, int64_t n_in,
+                        void* out_up, void* out_down, uint32_t* out_count, int64_t cap);
+} soil_slab_colour_ops;
+
 /* ------------------------------------------------------------ the slab runner */
 
 typedef struct soil_slab soil_slab; /* opaque */
@@ -203,12 +233,24 @@ typedef void (*soil_slab_mark_fn)(void* ctx, int32_t mark);
 /* `comm` and `ops` (if given) must outlive the runner; `ops` == NULL: HIP on the current device. */
 int soil_slab_create(soil_slab** out, const soil_slab_config* cfg, const soil_param* param,
                      const soil_comm* comm, const soil_slab_ops* ops);
+/* A coloured runner: soil_slab_create, and every step carries the four colour planes of soil_colour_planes
+ * (albedo_bedrock, albedo_surface, albedo_fluvial, albedo_debris; 3 floats per cell) through the particle
+ * launches and the cell phase, so that after a step the owned rows hold what soil_erode_step_colour leaves on
+ * the whole grid (fp32 summation order of the flux aside).  `ops` and `colour_ops` both NULL: HIP on the
+ * current device; a back-end of one's own gives both (`colour_ops` must outlive the runner).  The colour planes
+ * start at zero; the caller fills them through soil_slab_plane (with `init` too).  SOIL_SLAB_MIGRATE needs
+ * colour_ops->particles_pass.  DESIGN.md 5, "Colour on slabs". */
+int soil_slab_create_colour(soil_slab** out, const soil_slab_config* cfg, const soil_param* param,
+                            const soil_comm* comm, const soil_slab_ops* ops, const soil_slab_colour_ops* colour_ops);
 int soil_slab_step(soil_slab* slab, soil_slab_mark_fn mark, void* mark_ctx);
 /* A plane of the slab by the names of soil_erosion_planes ("layers" is the current one): local
  * rows incl. ghost rows, `channels` floats per cell.  The five flux planes are scratch of a step:
  * with the HIP back-end they are not re-zeroed behind the cell phase (the next step's launches
  * overwrite them; SOIL_SLAB_LAZY=0 restores the zeros), so between two steps their OWNED rows hold
- * the flux the last one consumed; their ghost rows have no stated content. */
+ * the flux the last one consumed; their ghost rows have no stated content.  A coloured runner
+ * (soil_slab_create_colour) also serves "albedo_bedrock", "albedo_surface", "albedo_fluvial" and
+ * "albedo_debris" (3 channels; the owned rows of the last two hold the transport colours after a
+ * step); a physics runner refuses those names. */
 int soil_slab_plane(soil_slab* slab, const char* name, float** data, int64_t* rows,
                     int64_t* channels);
 int soil_slab_get_info(const soil_slab* slab, soil_slab_info* info);
@@ -220,6 +262,10 @@ int soil_slab_destroy(soil_slab* slab);
 /* the HIP back-end by itself (what `ops` == NULL uses), for callers that wrap it */
 int soil_slab_ops_hip_create(soil_slab_ops** out);
 int soil_slab_ops_hip_destroy(soil_slab_ops* ops);
+/* the colour entries of the HIP back-end `ops` (made by soil_slab_ops_hip_create: the table shares its
+ * streams and state); destroy it before `ops` */
+int soil_slab_colour_ops_hip_create(soil_slab_colour_ops** out, const soil_slab_ops* ops);
+int soil_slab_colour_ops_hip_destroy(soil_slab_colour_ops* ops);
 /* rows a rank holds: (x0, rows, r0, r1) of rank `rank` */
 void soil_slab_layout(int32_t rank, int32_t world, int64_t S, int64_t G, int64_t out[4]);
 

@@ -138,6 +138,8 @@ SIGNATURES = {
                                           i64, i64, F3, C.POINTER(Param), cint, vp]),
     "soil_erode_step_colour": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), vp, i64, u64, u64,
                                       i64, i64, F3, C.POINTER(Param), cint, vp]),
+    "soil_particles_pair_colour_slab": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), vp, vp, i64, vp,
+                                               C.POINTER(Domain), F3, C.POINTER(Param), cint, vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),
@@ -232,6 +234,26 @@ class SlabOps(C.Structure):
     _fields_ = [("ctx", C.c_void_p)] + OPS_FIELDS
 
 
+_CP = C.POINTER(ColourPlanes)
+COLOUR_OPS_FIELDS = [
+    ("particles_fluvial", C.CFUNCTYPE(C.c_int, C.c_void_p, _PP, _CP, C.c_void_p, C.c_int64, C.c_void_p, _DP, _F3P,
+                                      _PARP)),
+    ("particles_debris", C.CFUNCTYPE(C.c_int, C.c_void_p, _PP, _CP, C.c_void_p, C.c_int64, C.c_void_p, _DP, _F3P,
+                                     _PARP)),
+    ("particles_pair", C.CFUNCTYPE(C.c_int, C.c_void_p, _PP, _CP, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, _DP,
+                                   _F3P, _PARP)),
+    ("cells", C.CFUNCTYPE(C.c_int, C.c_void_p, _PP, _CP, _DP, _F3P, _PARP)),
+    ("particles_pass", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, _PP, _CP, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_void_p, _DP, _F3P, _PARP, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int64)),
+]
+
+
+class SlabColourOps(C.Structure):
+    """soil_slab_colour_ops: the colour entries of a slab runner's back-end (soil_slab_create_colour)."""
+    _fields_ = [("ctx", C.c_void_p)] + COLOUR_OPS_FIELDS
+
+
 class SlabConfig(C.Structure):
     _fields_ = [("rows_per_rank", C.c_int64), ("W", C.c_int64), ("particles_div", C.c_int64),
                 ("seed", C.c_uint64), ("scale", C.c_float * 3), ("noise_seed", C.c_float),
@@ -272,6 +294,10 @@ SLAB_SIGNATURES = {
     "soil_slab_destroy": (cint, [vp]),
     "soil_slab_ops_hip_create": (cint, [C.POINTER(C.POINTER(SlabOps))]),
     "soil_slab_ops_hip_destroy": (cint, [C.POINTER(SlabOps)]),
+    "soil_slab_create_colour": (cint, [C.POINTER(vp), C.POINTER(SlabConfig), C.POINTER(Param), C.POINTER(Comm),
+                                       C.POINTER(SlabOps), C.POINTER(SlabColourOps)]),
+    "soil_slab_colour_ops_hip_create": (cint, [C.POINTER(C.POINTER(SlabColourOps)), C.POINTER(SlabOps)]),
+    "soil_slab_colour_ops_hip_destroy": (cint, [C.POINTER(SlabColourOps)]),
     "soil_slab_layout": (None, [C.c_int32, C.c_int32, i64, i64, C.POINTER(i64)]),
 }
 

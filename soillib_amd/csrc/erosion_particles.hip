@@ -90,6 +90,7 @@ struct FluvialPlanes {
   const float* __restrict__ albedoSource;
   float* __restrict__ remote0;
   unsigned long long* __restrict__ steps;  // step_counter() of the device
+  float* __restrict__ remoteA = nullptr;   // float[6]: the NaN walkers' colour for (0,0), fluvial | debris (Remote0)
 };
 
 // __transport_fluvial, erosion.cu:49-139, from the spawn position on
@@ -153,6 +154,8 @@ __device__ __forceinline__ void trace_fluvial(const Fields& F, const FluvialPlan
         atomicAdd(&P.remote0[2], att_v * source_vx);
         atomicAdd(&P.remote0[3], att_v * source_vy);
       }
+      if (px != px && P.remoteA && ind != 0)
+        for (int c = 0; c < 3; ++c) atomicAdd(&P.remoteA[c], att_m * source_a[c]);
       break;
     }
     ++nsteps;
@@ -203,6 +206,7 @@ struct DebrisPlanes {
   const float* __restrict__ albedoSource;
   float* __restrict__ remote0;
   unsigned long long* __restrict__ steps;  // step_counter() of the device
+  float* __restrict__ remoteA = nullptr;   // as FluvialPlanes::remoteA
 };
 
 // __transport_debris, erosion.cu:262-349, from the spawn position on
@@ -260,6 +264,8 @@ __device__ __forceinline__ void trace_debris(const Fields& F, const DebrisPlanes
         atomicAdd(&P.remote0[5], att_v * source_vx);
         atomicAdd(&P.remote0[6], att_v * source_vy);
       }
+      if (px != px && P.remoteA && ind != 0)
+        for (int c = 0; c < 3; ++c) atomicAdd(&P.remoteA[3 + c], att_d * source_a[c]);
       break;
     }
     ++nsteps;
@@ -546,16 +552,18 @@ static int launch_particles_fluvial(float* waterFlux, float* massFlux, float* ve
                                     const float* layers, const float* waterSource,
                                     const float* waterHeight, const float* velocity,
                                     const float* albedoSource, float* remote0, const Dom& d,
-                                    Scale3 s, const Param& p, hipStream_t st) {
+                                    Scale3 s, const Param& p, hipStream_t st,
+                                    float* remoteA = nullptr) {
   if (N <= 0) return SOIL_OK;
+  if (!albedoFlux) remoteA = nullptr;
   if (use_tiled(N, d))
     return launch_fluvial_tiled(waterFlux, massFlux, velocityFlux, albedoFlux, streams_of(rng), N, layers,
                                 waterSource, waterHeight, velocity, albedoSource, remote0, d, s, p,
-                                st);
+                                st, remoteA);
   unsigned long long* steps = nullptr;
   if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
   const FluvialPlanes P{waterFlux,   massFlux,    velocityFlux, albedoFlux, waterSource,
-                        waterHeight, albedoSource, remote0,      steps};
+                        waterHeight, albedoSource, remote0,      steps,      remoteA};
   if (use_staged(N)) {
     Staged sg;
     int rc = stage(&sg, rng, N, layers, velocity, d, s, p, st);
@@ -575,14 +583,15 @@ static int launch_particles_debris(float* massFlux, float* velocityFlux, float* 
                                    soil_rng* rng, int64_t N, const float* layers,
                                    const float* velocity, const float* albedoSource,
                                    float* remote0, const Dom& d, Scale3 s, const Param& p,
-                                   hipStream_t st) {
+                                   hipStream_t st, float* remoteA = nullptr) {
   if (N <= 0) return SOIL_OK;
+  if (!albedoFlux) remoteA = nullptr;
   if (use_tiled(N, d))
     return launch_debris_tiled(massFlux, velocityFlux, albedoFlux, streams_of(rng), N, layers, velocity,
-                               albedoSource, remote0, d, s, p, st);
+                               albedoSource, remote0, d, s, p, st, remoteA);
   unsigned long long* steps = nullptr;
   if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
-  const DebrisPlanes P{massFlux, velocityFlux, albedoFlux, albedoSource, remote0, steps};
+  const DebrisPlanes P{massFlux, velocityFlux, albedoFlux, albedoSource, remote0, steps, remoteA};
   if (use_staged(N)) {
     Staged sg;
     int rc = stage(&sg, rng, N, layers, velocity, d, s, p, st);
@@ -596,6 +605,55 @@ static int launch_particles_debris(float* massFlux, float* velocityFlux, float* 
   }
   SOIL_LAUNCH_CHECK();
   return SOIL_OK;
+}
+
+// The launches with colour on a slab (soil_particles_pair_colour_slab; the slab runner's coloured HIP
+// back-end).  Each clears the colour flux plane(s) it deposits into over local rows [0, d.rows) first;
+// `remote0` (may be null) is float[16]: [0..7] as the physics slab launches, [8..10] / [11..13] the
+// fluvial / debris colour deposits of NaN walkers for global (0, 0) (Remote0::colour = remote0 + 8).
+static size_t colour_plane_bytes(const Dom& d) {
+  return 3 * sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
+}
+int particles_fluvial_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rng, int64_t N,
+                                     float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st) {
+  SOIL_HIP(hipMemsetAsync(C.albedo_fluvial, 0, colour_plane_bytes(d), st));
+  if (N <= 0) return SOIL_OK;
+  float* const rc0 = remote0 ? remote0 + 8 : nullptr;
+  if (use_tiled(N, d))
+    return launch_fluvial_tiled(P.waterFlux, P.massFlux, P.velocityFlux, C.albedo_fluvial, rng, N, P.layers, P.rainfall,
+                                P.waterHeight, P.velocity, C.albedo_surface, remote0, d, s, p, st, rc0);
+  if (int rc = materialise(rng, N, st); rc != SOIL_OK) return rc;
+  return launch_particles_fluvial(P.waterFlux, P.massFlux, P.velocityFlux, C.albedo_fluvial, rng.rng, N, P.layers,
+                                  P.rainfall, P.waterHeight, P.velocity, C.albedo_surface, remote0, d, s, p, st, rc0);
+}
+// (walked to the end, as soil_particles_debris_slab with colour planes: retirement makes no difference to the
+// planes, and only the overlapped pair retires with colour)
+int particles_debris_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rng, int64_t N,
+                                    float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st) {
+  SOIL_HIP(hipMemsetAsync(C.albedo_debris, 0, colour_plane_bytes(d), st));
+  if (N <= 0) return SOIL_OK;
+  float* const rc0 = remote0 ? remote0 + 8 : nullptr;
+  if (use_tiled(N, d))
+    return launch_debris_tiled(P.debrisFlux, P.debrisVelocityFlux, C.albedo_debris, rng, N, P.layers, P.debrisVelocity,
+                               C.albedo_surface, remote0, d, s, p, st, rc0);
+  if (int rc = materialise(rng, N, st); rc != SOIL_OK) return rc;
+  return launch_particles_debris(P.debrisFlux, P.debrisVelocityFlux, C.albedo_debris, rng.rng, N, P.layers,
+                                 P.debrisVelocity, C.albedo_surface, remote0, d, s, p, st, rc0);
+}
+int particles_pair_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rf, Streams rd,
+                                  int64_t N, float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st,
+                                  bool overwrite) {
+  if (N > 0 && use_tiled(N, d))  // (clears the colour flux planes itself, ahead of its fork)
+    return launch_pair_tiled(P, rf, rd, N, remote0, d, s, p, st, overwrite, MigrateBox{}, MigrateBox{}, nullptr, 0,
+                             nullptr, 0, &C, remote0 ? remote0 + 8 : nullptr);
+  // the small-N shapes: one launch after the other, every walker walked to the end
+  if (overwrite) {
+    const size_t b = sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
+    for (float* t : {P.waterFlux, P.massFlux, P.debrisFlux}) SOIL_HIP(hipMemsetAsync(t, 0, b, st));
+    for (float* t : {P.velocityFlux, P.debrisVelocityFlux}) SOIL_HIP(hipMemsetAsync(t, 0, 2 * b, st));
+  }
+  if (int rc = particles_fluvial_colour_streams(P, C, rf, N, remote0, d, s, p, st); rc != SOIL_OK) return rc;
+  return particles_debris_colour_streams(P, C, rd, N, remote0, d, s, p, st);
 }
 
 }  // namespace soil
@@ -800,6 +858,26 @@ int soil_particles_pair_colour(const soil_erosion_planes* planes, const soil_col
     return rc;
   return launch_particles_debris(P.debrisFlux, P.debrisVelocityFlux, colour->albedo_debris, rng_debris, N, P.layers,
                                  P.debrisVelocity, colour->albedo_surface, nullptr, d, s, *param, st);
+}
+
+int soil_particles_pair_colour_slab(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                    soil_rng* rng_fluvial, soil_rng* rng_debris, int64_t N, float* remote0,
+                                    const soil_domain* dom, const float scale[3], const soil_param* param, int flags,
+                                    void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && colour && dom && scale && param, "particles_pair_colour_slab: null argument");
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
+                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
+               "particles_pair_colour_slab: null plane");
+  SOIL_REQUIRE(colour->albedo_surface && colour->albedo_fluvial && colour->albedo_debris,
+               "particles_pair_colour_slab: albedo_surface, albedo_fluvial and albedo_debris are required");
+  SOIL_REQUIRE(N >= 0 && (N == 0 || (rng_fluvial && rng_debris && rng_fluvial != rng_debris)),
+               "particles_pair_colour_slab: needs two distinct rng tensors");
+  const Dom d = to_dom(dom);
+  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
+  return particles_pair_colour_streams(P, *colour, streams_of(rng_fluvial), streams_of(rng_debris), N, remote0, d,
+                                       s3p(scale), *param, as_stream(stream), (flags & SOIL_FLUX_OVERWRITE) != 0);
 }
 
 int soil_particle_steps(uint64_t* total, int reset, void* stream) {

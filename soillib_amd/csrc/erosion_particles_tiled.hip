@@ -549,17 +549,26 @@ __device__ __forceinline__ bool advance(PRec& r, const float4 q, const StepConst
 
 // a NaN walker's deposit for global cell (0,0) held by another rank (soil_hip.h)
 template <int KIND>
-__device__ __forceinline__ void park_remote(const PRec& r, float* __restrict__ remote0) {
-  if (!(r.px != r.px) || !remote0 || r.ind == 0) return;
-  if (KIND == FLUVIAL) {
-    atomicAdd(&remote0[0], r.a0 * r.s0);
-    atomicAdd(&remote0[1], r.a1 * r.s1);
-    atomicAdd(&remote0[2], r.a2 * r.svx);
-    atomicAdd(&remote0[3], r.a2 * r.svy);
-  } else {
-    atomicAdd(&remote0[4], r.a0 * r.s0);
-    atomicAdd(&remote0[5], r.a1 * r.svx);
-    atomicAdd(&remote0[6], r.a1 * r.svy);
+__device__ __forceinline__ void park_remote(const PRec& r, Remote0 remote0) {
+  if (!(r.px != r.px) || r.ind == 0) return;
+  if (float* const q = remote0.phys) {
+    if (KIND == FLUVIAL) {
+      atomicAdd(&q[0], r.a0 * r.s0);
+      atomicAdd(&q[1], r.a1 * r.s1);
+      atomicAdd(&q[2], r.a2 * r.svx);
+      atomicAdd(&q[3], r.a2 * r.svy);
+    } else {
+      atomicAdd(&q[4], r.a0 * r.s0);
+      atomicAdd(&q[5], r.a1 * r.svx);
+      atomicAdd(&q[6], r.a1 * r.svy);
+    }
+  }
+  if (float* const q = remote0.colour) {  // the colour deposit rides on the mass attenuation, as in the rounds
+    const float att = (KIND == FLUVIAL) ? r.a1 : r.a0;
+    float* const c = q + (KIND == FLUVIAL ? 0 : 3);
+    atomicAdd(&c[0], att * r.sa0);
+    atomicAdd(&c[1], att * r.sa1);
+    atomicAdd(&c[2], att * r.sa2);
   }
 }
 
@@ -1642,7 +1651,7 @@ __global__ void __launch_bounds__(NT, SPARSE ? 2 : round_waves_per_simd(KIND, TR
                   float* __restrict__ flux0,
                   float* __restrict__ flux1, float2* __restrict__ fluxV,
                   float* __restrict__ fluxA, const float4* __restrict__ p4,
-                  float* __restrict__ remote0, unsigned long long* __restrict__ steps, Dom d,
+                  Remote0 remote0, unsigned long long* __restrict__ steps, Dom d,
                   Scale3 s, Param param, int tiles_w, int off_r, int off_c, int steps_per_round,
                   TileShape ts_next,
                   int tiles_w_next, int agg_min, int agg_groups, int retries, int store_all,
@@ -2477,7 +2486,7 @@ __global__ void __launch_bounds__(256)
     k_tiled_finish(MigrateBox box, const PRec* __restrict__ recs, const uint32_t* __restrict__ dest,
                    const TiledCtl* __restrict__ ctl, float* __restrict__ flux0,
                    float* __restrict__ flux1, float* __restrict__ fluxV, float* __restrict__ fluxA,
-                   const float4* __restrict__ p4, float* __restrict__ remote0,
+                   const float4* __restrict__ p4, Remote0 remote0,
                    unsigned long long* __restrict__ steps, Dom d, Scale3 s, Param param) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (ctl->mode != 1 || i >= static_cast<int64_t>(ctl->slots)) return;
@@ -2675,7 +2684,7 @@ struct TiledRun {
   Streams rng;
   int64_t N;
   const float *layers, *waterSource, *waterHeight, *velocity;
-  float* remote0;
+  Remote0 remote0;
   Dom d;
   Scale3 s;
   Param p;
@@ -3220,12 +3229,13 @@ static TiledRun<KIND> make_run(float* flux0, float* flux1, float* fluxV, float* 
                                const float* albedoSource, Streams rng, int64_t N,
                                const float* layers, const float* waterSource,
                                const float* waterHeight, const float* velocity, float* remote0,
-                               const Dom& d, Scale3 s, const Param& p, hipStream_t st) {
+                               const Dom& d, Scale3 s, const Param& p, hipStream_t st,
+                               float* remote_colour = nullptr) {
   TiledRun<KIND> r;
   r.flux0 = flux0, r.flux1 = flux1, r.fluxV = fluxV, r.rng = rng, r.N = N;
   r.fluxA = fluxA, r.albedoSource = fluxA ? albedoSource : nullptr;
   r.layers = layers, r.waterSource = waterSource, r.waterHeight = waterHeight, r.velocity = velocity;
-  r.remote0 = remote0, r.d = d, r.s = s, r.p = p, r.st = st;
+  r.remote0 = Remote0{remote0, fluxA ? remote_colour : nullptr}, r.d = d, r.s = s, r.p = p, r.st = st;
   return r;
 }
 
@@ -3233,9 +3243,9 @@ template <int KIND>
 static int run_tiled(float* flux0, float* flux1, float* fluxV, float* fluxA,
                      const float* albedoSource, Streams rng, int64_t N, const float* layers, const float* waterSource, const float* waterHeight,
                      const float* velocity, float* remote0, const Dom& d, Scale3 s, const Param& p,
-                     hipStream_t st) {
+                     hipStream_t st, float* remote_colour) {
   TiledRun<KIND> r = make_run<KIND>(flux0, flux1, fluxV, fluxA, albedoSource, rng, N, layers,
-                                    waterSource, waterHeight, velocity, remote0, d, s, p, st);
+                                    waterSource, waterHeight, velocity, remote0, d, s, p, st, remote_colour);
   if (int rc = r.begin(); rc != SOIL_OK) return rc;
   while (!r.done)
     if (int rc = r.advance(); rc != SOIL_OK) return rc;
@@ -3247,7 +3257,8 @@ static int run_tiled(float* flux0, float* flux1, float* fluxV, float* fluxA,
 int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams rng_debris, int64_t N,
                       float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st, bool overwrite,
                       MigrateBox box_fluvial, MigrateBox box_debris, const void* inbox_fluvial, uint32_t n_fluvial,
-                      const void* inbox_debris, uint32_t n_debris, const soil_colour_planes* colour) {
+                      const void* inbox_debris, uint32_t n_debris, const soil_colour_planes* colour,
+                      float* remote_colour) {
   // forked streams and their events, one set per (thread, device)
   struct Fork {
     hipStream_t sA = nullptr, sB = nullptr;
@@ -3314,6 +3325,7 @@ int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams
     A.fluxA = colour->albedo_fluvial, A.albedoSource = colour->albedo_surface;
     B.fluxA = colour->albedo_debris, B.albedoSource = colour->albedo_surface;
     B.retire_colour = true;
+    A.remote0.colour = B.remote0.colour = remote_colour;  // (slab launches: the NaN walkers' colour for (0, 0))
     const size_t b3 = 3 * sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
     SOIL_HIP(hipMemsetAsync(colour->albedo_fluvial, 0, b3, st));  // ahead of the fork
     SOIL_HIP(hipMemsetAsync(colour->albedo_debris, 0, b3, st));
@@ -3394,17 +3406,17 @@ int launch_fluvial_tiled(float* waterFlux, float* massFlux, float* velocityFlux,
                          Streams rng, int64_t N, const float* layers, const float* waterSource,
                          const float* waterHeight, const float* velocity,
                          const float* albedoSource, float* remote0, const Dom& d, Scale3 s,
-                         const Param& p, hipStream_t st) {
+                         const Param& p, hipStream_t st, float* remote_colour) {
   return run_tiled<FLUVIAL>(waterFlux, massFlux, velocityFlux, albedoFlux, albedoSource, rng, N,
-                            layers, waterSource, waterHeight, velocity, remote0, d, s, p, st);
+                            layers, waterSource, waterHeight, velocity, remote0, d, s, p, st, remote_colour);
 }
 
 int launch_debris_tiled(float* massFlux, float* velocityFlux, float* albedoFlux, Streams rng,
                         int64_t N, const float* layers, const float* velocity,
                         const float* albedoSource, float* remote0, const Dom& d, Scale3 s,
-                        const Param& p, hipStream_t st) {
+                        const Param& p, hipStream_t st, float* remote_colour) {
   return run_tiled<DEBRIS>(massFlux, nullptr, velocityFlux, albedoFlux, albedoSource, rng, N, layers,
-                           nullptr, nullptr, velocity, remote0, d, s, p, st);
+                           nullptr, nullptr, velocity, remote0, d, s, p, st, remote_colour);
 }
 
 // One launch of one kind for the slab runner's migrate mode: spawns (inbox null) or handed-over records,

@@ -69,6 +69,14 @@ __device__ __forceinline__ float2 spawn_position(const Streams& st, int64_t n, c
     y = 0.5f + rng_uniform_at(st.seed, static_cast<uint64_t>(n), st.offset + 1) * static_cast<float>(d.W - 1);
   return make_float2(x, y);
 }
+// Where a NaN walker's deposits for GLOBAL cell (0, 0) go when that cell lies on another rank (soil_hip.h:
+// soil_particles_*_slab's remote0): `phys` float[8] (fluvial water, mass, velocity.x/.y | debris mass,
+// velocity.x/.y), `colour` float[6] (fluvial | debris colour; the slab launches with colour planes only).
+// Either may be null.
+struct Remote0 {
+  float* phys;
+  float* colour;
+};
 // Walkers handed over at the slab's edge (SURVEY.md 8e option B; the slab runner's `migrate` mode,
 // round 5): a walker that steps off the rows this launch may walk on, inside the grid and with life
 // left, is written — state untouched, at the top of an iteration, as at a tile edge — into the box of
@@ -102,11 +110,11 @@ int launch_fluvial_tiled(float* waterFlux, float* massFlux, float* velocityFlux,
                          Streams rng, int64_t N, const float* layers, const float* waterSource,
                          const float* waterHeight, const float* velocity,
                          const float* albedoSource, float* remote0, const Dom& d, Scale3 s,
-                         const Param& p, hipStream_t st);
+                         const Param& p, hipStream_t st, float* remote_colour = nullptr);
 int launch_debris_tiled(float* massFlux, float* velocityFlux, float* albedoFlux, Streams rng,
                         int64_t N, const float* layers, const float* velocity,
                         const float* albedoSource, float* remote0, const Dom& d, Scale3 s,
-                        const Param& p, hipStream_t st);
+                        const Param& p, hipStream_t st, float* remote_colour = nullptr);
 // both launches of a step overlapped on two internal streams forked from / joined into `st`
 // (`overwrite`: the flux planes hold stale values — SOIL_FLUX_OVERWRITE, soil_hip.h)
 int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams rng_debris,
@@ -114,8 +122,9 @@ int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams
                       hipStream_t st, bool overwrite, MigrateBox box_fluvial = MigrateBox{},
                       MigrateBox box_debris = MigrateBox{}, const void* inbox_fluvial = nullptr,
                       uint32_t n_fluvial = 0, const void* inbox_debris = nullptr, uint32_t n_debris = 0,
-                      const soil_colour_planes* colour = nullptr);
-// (`colour`: the coloured step's planes — soil_particles_pair_colour; the colour flux planes are cleared first)
+                      const soil_colour_planes* colour = nullptr, float* remote_colour = nullptr);
+// (`colour`: the coloured step's planes — soil_particles_pair_colour; the colour flux planes are cleared first.
+// `remote_colour`: float[6], the NaN walkers' colour deposits for global (0, 0) on a slab — Remote0::colour)
 // (inboxes: both launches start from handed-over records instead of the streams' spawns — the immigrants of
 // both kinds walked on side by side, slab runner's migrate mode; the pack pass of the step's spawn launches
 // stands)
@@ -126,5 +135,14 @@ int particles_debris_streams(const soil_erosion_planes& P, Streams rng, int64_t 
                              const Dom& d, Scale3 s, const Param& p, hipStream_t st);
 int particles_pair_streams(const soil_erosion_planes& P, Streams rng_fluvial, Streams rng_debris, int64_t N,
                            float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st, bool overwrite = false);
+// ... with colour (soil_particles_pair_colour_slab): each clears the colour flux plane(s) it adds to over local
+// rows [0, d.rows); `remote0` float[16] (or null), [8..13] the NaN walkers' colour for global (0, 0)
+int particles_fluvial_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rng, int64_t N,
+                                     float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st);
+int particles_debris_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rng, int64_t N,
+                                    float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st);
+int particles_pair_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rf, Streams rd,
+                                  int64_t N, float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st,
+                                  bool overwrite = false);
 
 }  // namespace soil

@@ -55,16 +55,21 @@ Layout slab_layout(int rank, int world, int64_t S, int64_t G) {
 
 enum Plane {
   kLayers, kLayersNext, kHeight, kUplift, kRainfall, kWaterHeight, kWaterFlux, kMass, kMassFlux,
-  kVelocity, kVelocityFlux, kDebris, kDebrisFlux, kDebrisVelocity, kDebrisVelocityFlux, kPlanes
+  kVelocity, kVelocityFlux, kDebris, kDebrisFlux, kDebrisVelocity, kDebrisVelocityFlux,
+  // the colour planes of a coloured runner (soil_colour_planes), allocated by it only
+  kAlbedoBedrock, kAlbedoSurface, kAlbedoFluvial, kAlbedoDebris, kPlanes
 };
+constexpr int kPhysPlanes = kAlbedoBedrock;
 const char* const kPlaneName[kPlanes] = {
     "layers", "layers_next", "height", "uplift", "rainfall", "waterHeight", "waterFlux", "mass",
     "massFlux", "velocity", "velocityFlux", "debris", "debrisFlux", "debrisVelocity",
-    "debrisVelocityFlux"};
-const int kPlaneCh[kPlanes] = {2, 2, 1, 1, 1, 1, 1, 1, 1, 2, 2, 1, 1, 2, 2};
+    "debrisVelocityFlux", "albedo_bedrock", "albedo_surface", "albedo_fluvial", "albedo_debris"};
+const int kPlaneCh[kPlanes] = {2, 2, 1, 1, 1, 1, 1, 1, 1, 2, 2, 1, 1, 2, 2, 3, 3, 3, 3};
 const Plane kField[4] = {kLayers, kVelocity, kWaterHeight, kDebrisVelocity};  // what particles read
-const Plane kFluxFluvial[3] = {kWaterFlux, kMassFlux, kVelocityFlux};         // final after the fluvial launch
-const Plane kFluxDebris[2] = {kDebrisFlux, kDebrisVelocityFlux};              // final after the debris launch
+// final after the fluvial launch / after the debris launch; a coloured runner's lists carry the kind's
+// colour flux plane too (the flux halo, the reach scan and the fallback's clearing go by these lists)
+const Plane kFluxFluvial[4] = {kWaterFlux, kMassFlux, kVelocityFlux, kAlbedoFluvial};
+const Plane kFluxDebris[3] = {kDebrisFlux, kDebrisVelocityFlux, kAlbedoDebris};
 
 }  // namespace
 
@@ -74,13 +79,20 @@ using soil::fail;
 
 // what soillib_amd/_abi.py mirrors with ctypes
 static_assert(sizeof(soil_xfer) == 24 && sizeof(soil_comm) == 56 && sizeof(soil_slab_ops) == 20 * 8 &&
-                  sizeof(soil_slab_config) == 80 && sizeof(soil_slab_info) == 192,
+                  sizeof(soil_slab_colour_ops) == 6 * 8 && sizeof(soil_slab_config) == 80 &&
+                  sizeof(soil_slab_info) == 192,
               "soil_slab.h struct layout changed: update soillib_amd/_abi.py");
 
 struct soil_slab {
   const soil_comm* comm = nullptr;
   const soil_slab_ops* ops = nullptr;
   soil_slab_ops* own_ops = nullptr;  // HIP back-end made by soil_slab_create
+  // a coloured runner (soil_slab_create_colour): the colour entries of the back-end, the lengths of the flux
+  // lists (kFluxFluvial / kFluxDebris: 3 / 2 physics planes, 4 / 3 with colour) and of remote0 (8 / 16 floats)
+  const soil_slab_colour_ops* cops = nullptr;
+  soil_slab_colour_ops* own_cops = nullptr;
+  bool colour = false;
+  int nff = 3, nfd = 2, nremote = 8;
   soil_param param{};
   int rank = 0, world = 1;
   int64_t S = 0, W = 0, H = 0, G = 0, N = 0;
@@ -144,6 +156,41 @@ struct soil_slab {
     q.debrisVelocityFlux = at(soil::kDebrisVelocityFlux);
     return q;
   }
+  // the colour planes from local row `first` on (a coloured runner)
+  soil_colour_planes colour_planes(int64_t first = 0) const {
+    return soil_colour_planes{rowp(soil::kAlbedoBedrock, first), rowp(soil::kAlbedoSurface, first),
+                              rowp(soil::kAlbedoFluvial, first), rowp(soil::kAlbedoDebris, first)};
+  }
+  // the back-end's launches and cell phase, with colour on a coloured runner
+  int launch_pair(const soil_erosion_planes& pl, const soil_domain& dom, int64_t first) {
+    if (!colour) return ops->particles_pair(ops->ctx, &pl, rng, rng_debris, N, remote0, &dom, scale, &param);
+    const soil_colour_planes c = colour_planes(first);
+    return cops->particles_pair(cops->ctx, &pl, &c, rng, rng_debris, N, remote0, &dom, scale, &param);
+  }
+  int launch_fluvial(const soil_erosion_planes& pl, const soil_domain& dom, int64_t first) {
+    if (!colour) return ops->particles_fluvial(ops->ctx, &pl, rng, N, remote0, &dom, scale, &param);
+    const soil_colour_planes c = colour_planes(first);
+    return cops->particles_fluvial(cops->ctx, &pl, &c, rng, N, remote0, &dom, scale, &param);
+  }
+  int launch_debris(const soil_erosion_planes& pl, const soil_domain& dom, int64_t first) {
+    if (!colour) return ops->particles_debris(ops->ctx, &pl, rng, N, remote0, &dom, scale, &param);
+    const soil_colour_planes c = colour_planes(first);
+    return cops->particles_debris(cops->ctx, &pl, &c, rng, N, remote0, &dom, scale, &param);
+  }
+  int launch_pass(int32_t kind, const soil_erosion_planes& pl, soil_rng* rd, const soil_domain& dom, const void* in,
+                  int64_t n_in, void* up_box, void* down_box, uint32_t* count, int64_t cap) {
+    if (!colour)
+      return ops->particles_pass(ops->ctx, kind, &pl, rng, rd, N, remote0, &dom, scale, &param, in, n_in, up_box,
+                                 down_box, count, cap);
+    const soil_colour_planes c = colour_planes();  // (migrate mode: the launches get all the local rows)
+    return cops->particles_pass(cops->ctx, kind, &pl, &c, rng, rd, N, remote0, &dom, scale, &param, in, n_in, up_box,
+                                down_box, count, cap);
+  }
+  int cells(const soil_erosion_planes& pl, const soil_domain& dom) {
+    if (!colour) return ops->cells(ops->ctx, &pl, &dom, scale, &param);
+    const soil_colour_planes c = colour_planes();
+    return cops->cells(cops->ctx, &pl, &c, &dom, scale, &param);
+  }
   // the launch window of this step, from the ghost rows that hold fresh fields right now
   void set_window() {
     w0 = 0, w1 = lay.rows;
@@ -175,7 +222,7 @@ struct soil_slab {
   }
   // every rank's k small non-negative ints, as out[rank * k + i]: one all-reduce of a zero-padded
   // vector (any wire that can sum will do); blocks until the host has them
-  // `with_remote0`: the 8 sums of remote0 (the NaN walkers' deposits for global cell (0,0)) ride behind
+  // `with_remote0`: the 8 (colour: 16) sums of remote0 (the NaN walkers' deposits for global cell (0,0)) ride behind
   // the ints in the same all-reduce and stay on the device, at remote_sum()
   float* remote_sum() const { return ints + static_cast<int64_t>(world) * 4; }
   int all_ints(const int* mine, int k, std::vector<int>& out, bool with_remote0 = false) {
@@ -185,9 +232,9 @@ struct soil_slab {
     SLAB_TRY(ops->from_host(ops->ctx, ints, h.data(), n * 4));
     int64_t total = n;
     if (with_remote0) {  // (k == 4: the ints fill the block in front of remote_sum())
-      SLAB_TRY(ops->fill_f32(ops->ctx, remote_sum(), 0.0f, 8, 0));
-      SLAB_TRY(ops->add_f32(ops->ctx, remote_sum(), remote0, 8, 0));
-      total = static_cast<int64_t>(world) * 4 + 8;
+      SLAB_TRY(ops->fill_f32(ops->ctx, remote_sum(), 0.0f, nremote, 0));
+      SLAB_TRY(ops->add_f32(ops->ctx, remote_sum(), remote0, nremote, 0));
+      total = static_cast<int64_t>(world) * 4 + nremote;
     }
     if (host_ordered) SLAB_TRY(ops->sync(ops->ctx));
     SLAB_TRY(comm->all_reduce_sum_f32(comm->ctx, ints, total, stream(0)));
@@ -276,9 +323,9 @@ struct soil_slab {
   // (above, below), debris (above, below)
   int reach_pair(std::vector<int>& rf, std::vector<int>& rd) {
     int32_t df[2] = {0, 0}, dd[2] = {0, 0};
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < nff; ++i)
       SLAB_TRY(ops->ghost_extent(ops->ctx, rowp(soil::kFluxFluvial[i], w0), w1 - w0, row_floats(soil::kFluxFluvial[i]), lay.r0 - w0, lay.r1 - w0, df));
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < nfd; ++i)
       SLAB_TRY(ops->ghost_extent(ops->ctx, rowp(soil::kFluxDebris[i], w0), w1 - w0, row_floats(soil::kFluxDebris[i]), lay.r0 - w0, lay.r1 - w0, dd));
     const int mine[4] = {df[0], df[1], dd[0], dd[1]};
     std::vector<int> all;
@@ -428,7 +475,7 @@ struct soil_slab {
           SLAB_TRY(ops->sync(ops->ctx));
           t0 = std::chrono::steady_clock::now();
         }
-        SLAB_TRY(ops->particles_pass(ops->ctx, kind, &pl, rng, nullptr, N, remote0, &dom, scale, &param, inbox, n_in,
+        SLAB_TRY(launch_pass(kind, pl, nullptr, dom, inbox, n_in,
                                      out_box[0], out_box[1], out_count, cap));
         ++passes;
         if (verbose) {
@@ -492,15 +539,15 @@ struct soil_slab {
         t0 = std::chrono::steady_clock::now();
       }
       if (n_f > 0 && n_d > 0) {
-        SLAB_TRY(ops->particles_pass(ops->ctx, 2, &pl, rng, rng_debris, N, remote0, &dom, scale, &param, inbox, n_f | (n_d << 32),
+        SLAB_TRY(launch_pass(2, pl, rng_debris, dom, inbox, n_f | (n_d << 32),
                                      out_box[0], out_box[1], out_count, 2 * half));
         passes += 2;
       } else if (n_f > 0) {
-        SLAB_TRY(ops->particles_pass(ops->ctx, 0, &pl, rng, nullptr, N, remote0, &dom, scale, &param, inbox, n_f, out_box[0],
+        SLAB_TRY(launch_pass(0, pl, nullptr, dom, inbox, n_f, out_box[0],
                                      out_box[1], out_count, half));
         ++passes;
       } else if (n_d > 0) {
-        SLAB_TRY(ops->particles_pass(ops->ctx, 1, &pl, rng, nullptr, N, remote0, &dom, scale, &param, inbox, n_d, up_d, down_d,
+        SLAB_TRY(launch_pass(1, pl, nullptr, dom, inbox, n_d, up_d, down_d,
                                      out_count + 2, half));
         ++passes;
       }
@@ -522,7 +569,7 @@ struct soil_slab {
     SLAB_TRY(ops->fill_f32(ops->ctx, reinterpret_cast<float*>(out_count), 0.0f, 4, 0));
     if (paired) {
       SLAB_TRY(ops->rng_seed(ops->ctx, rng_debris, N, seed, off + 2));
-      SLAB_TRY(ops->particles_pass(ops->ctx, 2, &pl, rng, rng_debris, N, remote0, &dom, scale, &param, nullptr, 0,
+      SLAB_TRY(launch_pass(2, pl, rng_debris, dom, nullptr, 0,
                                    out_box[0], out_box[1], out_count, box_cap));
       passes += 2;
       SLAB_TRY(ops->to_host(ops->ctx, c, out_count, 16));
@@ -541,7 +588,7 @@ struct soil_slab {
     }
     for (int kind = 0; kind < 2; ++kind) {
       SLAB_TRY(ops->fill_f32(ops->ctx, reinterpret_cast<float*>(out_count), 0.0f, 4, 0));
-      SLAB_TRY(ops->particles_pass(ops->ctx, kind, &pl, rng, nullptr, N, remote0, &dom, scale, &param, nullptr, 0, out_box[0],
+      SLAB_TRY(launch_pass(kind, pl, nullptr, dom, nullptr, 0, out_box[0],
                                    out_box[1], out_count, box_cap));
       ++passes;
       SLAB_TRY(ops->to_host(ops->ctx, c, out_count, 8));
@@ -575,20 +622,24 @@ struct soil_slab {
     };
     const uint64_t off = step_index * static_cast<uint64_t>(N);
     SLAB_TRY(ops->rng_seed(ops->ctx, rng, N, seed, off));
-    SLAB_TRY(ops->fill_f32(ops->ctx, remote0, 0.0f, 8, 0));
+    SLAB_TRY(ops->fill_f32(ops->ctx, remote0, 0.0f, nremote, 0));
     bool early = false;  // the fluvial planes' halo went out before the debris launch ended
     bool remote_summed = false;  // the NaN walkers' sums rode with the reach exchange (remote_sum())
     Counts cf{}, cd{};
     std::vector<int> rf, rd;
     mk(0);
-    const bool paired = pair && ops->particles_pair && rng_debris;
+    const bool paired = pair && (colour ? cops->particles_pair != nullptr : ops->particles_pair != nullptr) && rng_debris;
     if (mode == SOIL_SLAB_MIGRATE) {
+      if (colour) {  // (the launches of migrate mode add to the colour flux planes, spawn and immigrants alike)
+        SLAB_TRY(ops->fill_f32(ops->ctx, P[soil::kAlbedoFluvial], 0.0f, lay.rows * row_floats(soil::kAlbedoFluvial), 0));
+        SLAB_TRY(ops->fill_f32(ops->ctx, P[soil::kAlbedoDebris], 0.0f, lay.rows * row_floats(soil::kAlbedoDebris), 0));
+      }
       SLAB_TRY(migrate_particles(pl, dom, off, paired, mark, mctx));
     } else if (paired) {
       // the debris launch draws from a tensor of its own, seeded where the fluvial launch leaves
       // the shared one in the sequential order
       SLAB_TRY(ops->rng_seed(ops->ctx, rng_debris, N, seed, off + 2));
-      SLAB_TRY(ops->particles_pair(ops->ctx, &plw, rng, rng_debris, N, remote0, &domw, scale, &param));
+      SLAB_TRY(launch_pair(plw, domw, w0));
       if (trim) {
         SLAB_TRY(reach_pair(rf, rd));
         remote_summed = true;
@@ -596,12 +647,12 @@ struct soil_slab {
         if (too_deep(rf) || too_deep(rd) || too_deep(rd, true)) {  // rare: both launches again, on complete fields
           SLAB_TRY(refresh_all());
           rewindow();
-          SLAB_TRY(zero_planes(soil::kFluxFluvial, 3));
-          SLAB_TRY(zero_planes(soil::kFluxDebris, 2));
-          SLAB_TRY(ops->fill_f32(ops->ctx, remote0, 0.0f, 8, 0));
+          SLAB_TRY(zero_planes(soil::kFluxFluvial, nff));
+          SLAB_TRY(zero_planes(soil::kFluxDebris, nfd));
+          SLAB_TRY(ops->fill_f32(ops->ctx, remote0, 0.0f, nremote, 0));
           SLAB_TRY(ops->rng_seed(ops->ctx, rng, N, seed, off));
           SLAB_TRY(ops->rng_seed(ops->ctx, rng_debris, N, seed, off + 2));
-          SLAB_TRY(ops->particles_pair(ops->ctx, &plw, rng, rng_debris, N, remote0, &domw, scale, &param));
+          SLAB_TRY(launch_pair(plw, domw, w0));
           SLAB_TRY(reach_pair(rf, rd));
         }
         cf = counts_of(rf), cd = counts_of(rd);
@@ -609,17 +660,17 @@ struct soil_slab {
       }
       mk(1);
     } else {
-      SLAB_TRY(ops->particles_fluvial(ops->ctx, &plw, rng, N, remote0, &domw, scale, &param));
+      SLAB_TRY(launch_fluvial(plw, domw, w0));
       if (trim) {
-        SLAB_TRY(reach(soil::kFluxFluvial, 3, rf));
+        SLAB_TRY(reach(soil::kFluxFluvial, nff, rf));
         if (too_deep(rf)) {  // rare: repeat the launch on complete fields
           SLAB_TRY(refresh_all());
           rewindow();
-          SLAB_TRY(zero_planes(soil::kFluxFluvial, 3));
-          SLAB_TRY(ops->fill_f32(ops->ctx, remote0, 0.0f, 8, 0));
+          SLAB_TRY(zero_planes(soil::kFluxFluvial, nff));
+          SLAB_TRY(ops->fill_f32(ops->ctx, remote0, 0.0f, nremote, 0));
           SLAB_TRY(ops->rng_seed(ops->ctx, rng, N, seed, off));
-          SLAB_TRY(ops->particles_fluvial(ops->ctx, &plw, rng, N, remote0, &domw, scale, &param));
-          SLAB_TRY(reach(soil::kFluxFluvial, 3, rf));
+          SLAB_TRY(launch_fluvial(plw, domw, w0));
+          SLAB_TRY(reach(soil::kFluxFluvial, nff, rf));
         }
         cf = counts_of(rf);
       }
@@ -627,22 +678,23 @@ struct soil_slab {
       if (world > 1) {
         // the fluvial flux is final: its halo travels, and is added, while the debris launch runs
         SLAB_TRY(ops->fork(ops->ctx));
-        SLAB_TRY(flux_exchange(soil::kFluxFluvial, 3, trim ? &cf : nullptr, 1));
+        SLAB_TRY(flux_exchange(soil::kFluxFluvial, nff, trim ? &cf : nullptr, 1));
         early = true;
       }
-      SLAB_TRY(ops->particles_debris(ops->ctx, &plw, rng, N, remote0, &domw, scale, &param));
+      SLAB_TRY(launch_debris(plw, domw, w0));
       if (trim) {
-        SLAB_TRY(reach(soil::kFluxDebris, 2, rd));
+        SLAB_TRY(reach(soil::kFluxDebris, nfd, rd));
         if (too_deep(rd) || too_deep(rd, true)) {
           SLAB_TRY(refresh_all());
           rewindow();
-          SLAB_TRY(zero_planes(soil::kFluxDebris, 2));
-          // the NaN walkers' debris deposits are entries 4..6 of remote0; the launch draws where
-          // the fluvial one left the streams (two draws per particle on)
+          SLAB_TRY(zero_planes(soil::kFluxDebris, nfd));
+          // the NaN walkers' debris deposits are entries 4..6 of remote0 (colour: and 11..13); the launch
+          // draws where the fluvial one left the streams (two draws per particle on)
           SLAB_TRY(ops->fill_f32(ops->ctx, remote0 + 4, 0.0f, 4, 0));
+          if (colour) SLAB_TRY(ops->fill_f32(ops->ctx, remote0 + 11, 0.0f, 5, 0));
           SLAB_TRY(ops->rng_seed(ops->ctx, rng, N, seed, off + 2));
-          SLAB_TRY(ops->particles_debris(ops->ctx, &plw, rng, N, remote0, &domw, scale, &param));
-          SLAB_TRY(reach(soil::kFluxDebris, 2, rd));
+          SLAB_TRY(launch_debris(plw, domw, w0));
+          SLAB_TRY(reach(soil::kFluxDebris, nfd, rd));
         }
         cd = counts_of(rd);
         note_reach(rf, rd);
@@ -650,15 +702,15 @@ struct soil_slab {
     }
     mk(2);
     if (world == 1) {
-      SLAB_TRY(ops->cells(ops->ctx, &pl, &dom, scale, &param));
+      SLAB_TRY(cells(pl, dom));
     } else {
-      // NaN walkers of the other ranks -> global cell (0,0) (8 floats, latency only)
+      // NaN walkers of the other ranks -> global cell (0,0) (8 floats, colour: 16; latency only)
       const float* sums = remote0;
       if (remote_summed) {
         sums = remote_sum();
       } else {
         if (host_ordered) SLAB_TRY(ops->sync(ops->ctx));
-        SLAB_TRY(comm->all_reduce_sum_f32(comm->ctx, remote0, 8, stream(0)));
+        SLAB_TRY(comm->all_reduce_sum_f32(comm->ctx, remote0, nremote, stream(0)));
       }
       if (rank == 0) {
         SLAB_TRY(ops->add_f32(ops->ctx, P[soil::kWaterFlux], sums + 0, 1, 0));
@@ -666,27 +718,31 @@ struct soil_slab {
         SLAB_TRY(ops->add_f32(ops->ctx, P[soil::kVelocityFlux], sums + 2, 2, 0));
         SLAB_TRY(ops->add_f32(ops->ctx, P[soil::kDebrisFlux], sums + 4, 1, 0));
         SLAB_TRY(ops->add_f32(ops->ctx, P[soil::kDebrisVelocityFlux], sums + 5, 2, 0));
+        if (colour) {
+          SLAB_TRY(ops->add_f32(ops->ctx, P[soil::kAlbedoFluvial], sums + 8, 3, 0));
+          SLAB_TRY(ops->add_f32(ops->ctx, P[soil::kAlbedoDebris], sums + 11, 3, 0));
+        }
       }
       // rows whose flux is complete without the neighbours' contribution
       const int64_t i0 = std::min(lay.r1, lay.r0 + (up >= 0 ? peer_ghost(up) : 0));
       const int64_t i1 = std::max(i0, lay.r1 - (down >= 0 ? peer_ghost(down) : 0));
       // 1. the rest of the flux halo (exposed: the bands below need it)
       if (early) {
-        SLAB_TRY(flux_exchange(soil::kFluxDebris, 2, trim ? &cd : nullptr, 0));
+        SLAB_TRY(flux_exchange(soil::kFluxDebris, nfd, trim ? &cd : nullptr, 0));
       } else {
-        SLAB_TRY(flux_exchange(soil::kFluxFluvial, 3, trim ? &cf : nullptr, 0));
-        SLAB_TRY(flux_exchange(soil::kFluxDebris, 2, trim ? &cd : nullptr, 0));
+        SLAB_TRY(flux_exchange(soil::kFluxFluvial, nff, trim ? &cf : nullptr, 0));
+        SLAB_TRY(flux_exchange(soil::kFluxDebris, nfd, trim ? &cd : nullptr, 0));
       }
       SLAB_TRY(ops->join(ops->ctx));  // ... and the part that travelled early
       mk(4);                          // 2 -> 4: flux halo not hidden by the debris launch
       // 2. the bands next to the neighbours first: they are what the neighbours' ghost rows get
       if (i0 > lay.r0) {
         const soil_domain b = domain(lay.r0, i0);
-        SLAB_TRY(ops->cells(ops->ctx, &pl, &b, scale, &param));
+        SLAB_TRY(cells(pl, b));
       }
       if (lay.r1 > i1) {
         const soil_domain b = domain(i1, lay.r1);
-        SLAB_TRY(ops->cells(ops->ctx, &pl, &b, scale, &param));
+        SLAB_TRY(cells(pl, b));
       }
       // 3. the field halo travels while the interior rows are computed (they are G rows away from
       //    anything the exchange reads or writes)
@@ -721,7 +777,7 @@ struct soil_slab {
       SLAB_TRY(field_exchange(soil::kLayersNext, fcp, 1, fdp));
       if (i1 > i0) {
         const soil_domain b = domain(i0, i1);
-        SLAB_TRY(ops->cells(ops->ctx, &pl, &b, scale, &param));
+        SLAB_TRY(cells(pl, b));
       }
       mk(5);  // 5 -> 3: field halo not hidden by the interior rows
       SLAB_TRY(ops->join(ops->ctx));
@@ -971,6 +1027,56 @@ int hip_sync(void* c) {
 void* hip_stream(void* c, int32_t lane) {
   HIP_OPS(c);
   return lane ? o.comm : o.main;
+}
+// the colour entries (soil_slab_colour_ops): the same HipOps, its streams and its lazy flux state
+int hipc_fluvial(void* c, const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rng, int64_t N,
+                 float* remote0, const soil_domain* dom, const float scale[3], const soil_param* param) {
+  HIP_OPS(c);
+  const Dom d = to_dom(dom);
+  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
+  if (int rc = o.clear_stale(); rc != SOIL_OK) return rc;
+  o.last_pair = false;
+  const int rc = particles_fluvial_colour_streams(*p, *col, o.streams(rng), N, remote0, d,
+                                                  Scale3{scale[0], scale[1], scale[2]}, *param, o.main);
+  o.drew(rng);
+  return rc;
+}
+int hipc_debris(void* c, const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rng, int64_t N,
+                float* remote0, const soil_domain* dom, const float scale[3], const soil_param* param) {
+  HIP_OPS(c);
+  const Dom d = to_dom(dom);
+  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
+  if (int rc = o.clear_stale(); rc != SOIL_OK) return rc;
+  o.last_pair = false;
+  const int rc = particles_debris_colour_streams(*p, *col, o.streams(rng), N, remote0, d,
+                                                 Scale3{scale[0], scale[1], scale[2]}, *param, o.main);
+  o.drew(rng);
+  return rc;
+}
+int hipc_pair(void* c, const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rf, soil_rng* rd,
+              int64_t N, float* remote0, const soil_domain* dom, const float scale[3], const soil_param* param) {
+  HIP_OPS(c);
+  const Dom d = to_dom(dom);
+  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
+  const int rc = particles_pair_colour_streams(*p, *col, o.streams(rf), o.streams(rd), N, remote0, d,
+                                               Scale3{scale[0], scale[1], scale[2]}, *param, o.main, o.flux_stale);
+  o.flux_stale = false;
+  o.last_pair = true;
+  o.drew(rf);
+  o.drew(rd);
+  return rc;
+}
+int hipc_cells(void* c, const soil_erosion_planes* p, const soil_colour_planes* col, const soil_domain* dom,
+               const float scale[3], const soil_param* param) {
+  HIP_OPS(c);
+  if (dom->r1 <= dom->r0) return SOIL_OK;
+  const bool keep = o.lazy && o.last_pair;
+  if (keep) {
+    o.flux_stale = true;
+    o.stale_planes = *p;
+    o.stale_cells = dom->rows * dom->W;
+  }
+  return soil_erode_cells_fused_colour(p, col, dom, scale, param, keep ? SOIL_CELLS_KEEP_FLUX : 0, o.main);
 }
 
 }  // namespace
@@ -1424,6 +1530,24 @@ int soil_slab_ops_hip_create(soil_slab_ops** out) {
   return SOIL_OK;
 }
 
+int soil_slab_colour_ops_hip_create(soil_slab_colour_ops** out, const soil_slab_ops* ops) {
+  SOIL_REQUIRE(out && ops, "slab_colour_ops_hip_create: null argument");
+  SOIL_REQUIRE(ops->alloc == hip_alloc && ops->ctx,
+               "slab_colour_ops_hip_create: `ops` must be a table made by soil_slab_ops_hip_create");
+  soil_slab_colour_ops* t = new soil_slab_colour_ops{};
+  t->ctx = ops->ctx;
+  t->particles_fluvial = hipc_fluvial, t->particles_debris = hipc_debris, t->particles_pair = hipc_pair;
+  t->cells = hipc_cells;
+  t->particles_pass = nullptr;  // migrate mode with colour: not built (soil_slab_create_colour refuses it)
+  *out = t;
+  return SOIL_OK;
+}
+
+int soil_slab_colour_ops_hip_destroy(soil_slab_colour_ops* ops) {
+  delete ops;
+  return SOIL_OK;
+}
+
 int soil_slab_ops_hip_destroy(soil_slab_ops* ops) {
   if (!ops) return SOIL_OK;
   HipOps* o = static_cast<HipOps*>(ops->ctx);
@@ -1441,9 +1565,30 @@ int soil_slab_ops_hip_destroy(soil_slab_ops* ops) {
   return SOIL_OK;
 }
 
+static int soil_slab_create_colour_impl(soil_slab** out, const soil_slab_config* cfg, const soil_param* param,
+                                        const soil_comm* comm, const soil_slab_ops* ops,
+                                        const soil_slab_colour_ops* colour_ops, bool colour);
+
 int soil_slab_create(soil_slab** out, const soil_slab_config* cfg, const soil_param* param,
                      const soil_comm* comm, const soil_slab_ops* ops) {
+  return soil_slab_create_colour_impl(out, cfg, param, comm, ops, nullptr, false);
+}
+
+int soil_slab_create_colour(soil_slab** out, const soil_slab_config* cfg, const soil_param* param,
+                            const soil_comm* comm, const soil_slab_ops* ops, const soil_slab_colour_ops* colour_ops) {
+  return soil_slab_create_colour_impl(out, cfg, param, comm, ops, colour_ops, true);
+}
+
+static int soil_slab_create_colour_impl(soil_slab** out, const soil_slab_config* cfg, const soil_param* param,
+                                        const soil_comm* comm, const soil_slab_ops* ops,
+                                        const soil_slab_colour_ops* colour_ops, bool colour) {
   SOIL_REQUIRE(out && cfg && param && comm, "slab_create: null argument");
+  if (colour) {
+    SOIL_REQUIRE((ops == nullptr) == (colour_ops == nullptr),
+                 "slab_create_colour: give both `ops` and `colour_ops` (a back-end of one's own) or neither (HIP)");
+    SOIL_REQUIRE(!colour_ops || (colour_ops->particles_fluvial && colour_ops->particles_debris && colour_ops->cells),
+                 "slab_create_colour: incomplete colour table (particles_fluvial, particles_debris and cells are required)");
+  }
   SOIL_REQUIRE(cfg->rows_per_rank > 0 && cfg->W > 0 && cfg->particles_div > 0, "slab_create: empty slab");
   SOIL_REQUIRE(comm->world >= 1 && comm->rank >= 0 && comm->rank < comm->world && comm->exchange &&
                    comm->all_reduce_sum_f32 && comm->barrier,
@@ -1459,8 +1604,16 @@ int soil_slab_create(soil_slab** out, const soil_slab_config* cfg, const soil_pa
       return rc;
     }
     ops = s->own_ops;
+    if (colour) {
+      if (int rc = soil_slab_colour_ops_hip_create(&s->own_cops, ops); rc != SOIL_OK) return bail(rc);
+      colour_ops = s->own_cops;
+    }
   }
   s->comm = comm, s->ops = ops, s->param = *param;
+  if (colour) {
+    s->colour = true, s->cops = colour_ops;
+    s->nff = 4, s->nfd = 3, s->nremote = 16;
+  }
   s->rank = comm->rank, s->world = comm->world;
   s->host_ordered = (comm->flags & SOIL_COMM_HOST_ORDERED) != 0;
   s->S = cfg->rows_per_rank, s->W = cfg->W, s->H = s->world * s->S;
@@ -1473,6 +1626,10 @@ int soil_slab_create(soil_slab** out, const soil_slab_config* cfg, const soil_pa
   if (s->mode == SOIL_SLAB_MIGRATE) {
     if (!ops->particles_pass)
       return bail(fail(SOIL_ERR_INVALID_ARGUMENT, "slab_create: this back-end cannot hand walkers over (no particles_pass): SOIL_SLAB_MIGRATE refused"));
+    if (s->colour && !s->cops->particles_pass)
+      return bail(fail(SOIL_ERR_INVALID_ARGUMENT, "slab_create_colour: the colour table cannot hand walkers over "
+                                                  "(no particles_pass; the HIP table has none): SOIL_SLAB_MIGRATE with colour "
+                                                  "refused, use SOIL_SLAB_DEEP_HALO"));
     // A shallow halo instead of none: with one ghost row a walker that zig-zags along the slab's edge is
     // handed back and forth, a pass of all ranks per crossing (the first version of this mode: 48-step
     // walks on 64-row slabs were still crossing after four passes).  On kMigrateHalo ghost rows it walks
@@ -1512,13 +1669,13 @@ int soil_slab_create(soil_slab** out, const soil_slab_config* cfg, const soil_pa
   s->down = s->rank < s->world - 1 ? s->rank + 1 : -1;
   s->gu = s->lay.r0, s->gd = s->lay.rows - s->lay.r1;
   s->fresh_everything();
-  for (int p = 0; p < kPlanes; ++p) {
+  for (int p = 0; p < (s->colour ? kPlanes : kPhysPlanes); ++p) {
     void* q = nullptr;
     if (int rc = ops->alloc(ops->ctx, &q, s->lay.rows * s->row_floats(p) * 4); rc != SOIL_OK) return bail(rc);
     s->P[p] = static_cast<float*>(q);
   }
   for (const Plane* list : {kFluxFluvial, kFluxDebris})
-    for (int i = 0; i < (list == kFluxFluvial ? 3 : 2); ++i) {
+    for (int i = 0; i < (list == kFluxFluvial ? s->nff : s->nfd); ++i) {
       const int p = list[i];
       for (int side = 0; side < 2; ++side) {
         const int peer = side ? s->down : s->up;
@@ -1531,14 +1688,14 @@ int soil_slab_create(soil_slab** out, const soil_slab_config* cfg, const soil_pa
   void* q = nullptr;
   if (int rc = ops->alloc(ops->ctx, &q, s->N * static_cast<int64_t>(sizeof(soil_rng))); rc != SOIL_OK) return bail(rc);
   s->rng = static_cast<soil_rng*>(q);
-  if (ops->particles_pair) {
+  if (s->colour ? s->cops->particles_pair != nullptr : ops->particles_pair != nullptr) {
     if (int rc = ops->alloc(ops->ctx, &q, s->N * static_cast<int64_t>(sizeof(soil_rng))); rc != SOIL_OK) return bail(rc);
     s->rng_debris = static_cast<soil_rng*>(q);
   }
-  if (int rc = ops->alloc(ops->ctx, &q, 8 * 4); rc != SOIL_OK) return bail(rc);
+  if (int rc = ops->alloc(ops->ctx, &q, s->nremote * 4); rc != SOIL_OK) return bail(rc);
   s->remote0 = static_cast<float*>(q);
-  // (world * 4 small ints, and behind them the 8 sums of the NaN walkers' deposits: one all-reduce carries both)
-  if (int rc = ops->alloc(ops->ctx, &q, (static_cast<int64_t>(s->world) * 4 + 8) * 4); rc != SOIL_OK) return bail(rc);
+  // (world * 4 small ints, and behind them the 8 (16) sums of the NaN walkers' deposits: one all-reduce carries both)
+  if (int rc = ops->alloc(ops->ctx, &q, (static_cast<int64_t>(s->world) * 4 + s->nremote) * 4); rc != SOIL_OK) return bail(rc);
   s->ints = static_cast<float*>(q);
   if (s->mode == SOIL_SLAB_MIGRATE) {
     // (the counts travel as floats in the all-reduce: exact below 2^24)
@@ -1597,6 +1754,9 @@ int soil_slab_plane(soil_slab* slab, const char* name, float** data, int64_t* ro
   SOIL_REQUIRE(slab && name && data, "slab_plane: null argument");
   for (int p = 0; p < kPlanes; ++p)
     if (std::strcmp(name, kPlaneName[p]) == 0) {
+      if (!slab->P[p])
+        return fail(SOIL_ERR_INVALID_ARGUMENT, std::string("slab_plane: ") + name +
+                                                   " is a colour plane and this runner is physics-only (soil_slab_create_colour)");
       *data = slab->P[p];
       if (rows) *rows = slab->lay.rows;
       if (channels) *channels = kPlaneCh[p];
@@ -1649,6 +1809,7 @@ int soil_slab_destroy(soil_slab* s) {
     drop(s->rng), drop(s->rng_debris), drop(s->remote0), drop(s->ints);
     drop(s->out_box[0]), drop(s->out_box[1]), drop(s->inbox), drop(s->out_count);
   }
+  if (s->own_cops) soil_slab_colour_ops_hip_destroy(s->own_cops);
   if (s->own_ops) soil_slab_ops_hip_destroy(s->own_ops);
   delete s;
   return SOIL_OK;

@@ -17,6 +17,10 @@ here is construction:
                   ranks sharing one GPU, or no GPU at all) and the in-process wire of the tests
   CallbackOps     a soil_slab_ops made of Python callables: the CPU tests plug the oracle in
                   here, so that world-size-2/3 gloo runs exercise the library's own host logic
+
+SlabRunner(..., colour=True) is the sharded coloured step (soil_slab_create_colour): the four colour
+planes of ErosionModel(colour=True) ride through every step, their owned rows ending as the
+whole-grid soil_erode_step_colour leaves them ("Colour on slabs").
 """
 import ctypes as C
 import os
@@ -31,7 +35,10 @@ PLANE_CHANNELS = {
     "layers": 2, "layers_next": 2, "height": 1, "uplift": 1, "rainfall": 1, "waterHeight": 1,
     "waterFlux": 1, "mass": 1, "massFlux": 1, "velocity": 2, "velocityFlux": 2, "debris": 1,
     "debrisFlux": 1, "debrisVelocity": 2, "debrisVelocityFlux": 2,
+    "albedo_bedrock": 3, "albedo_surface": 3, "albedo_fluvial": 3, "albedo_debris": 3,
 }
+# the planes a coloured runner adds (soil_colour_planes; soil_slab_plane refuses them on a physics runner)
+COLOUR_PLANES = ("albedo_bedrock", "albedo_surface", "albedo_fluvial", "albedo_debris")
 
 
 def slab_layout(rank, world, S, G):
@@ -339,7 +346,12 @@ def default_comm(device=True):
 
 class CallbackOps:
     """soil_slab_ops whose entries are methods of a Python object (tests/parallel_worker.py: the
-    oracle on host memory).  Methods take raw addresses and the ctypes structs of _abi."""
+    oracle on host memory).  Methods take raw addresses and the ctypes structs of _abi.
+
+    The colour table (soil_slab_colour_ops) is made of the methods colour_particles_fluvial,
+    colour_particles_debris, colour_particles_pair, colour_cells and colour_particles_pass (the
+    soil_slab_colour_ops entries with that prefix); a back-end without colour_cells has none, and a
+    coloured runner refuses it."""
 
     def __init__(self, backend):
         self.backend = backend
@@ -347,8 +359,8 @@ class CallbackOps:
         self._keep = []
         fields = {}
 
-        def wrap(name, proto):
-            fn = getattr(backend, name, None)
+        def wrap(name, proto, attr=None):
+            fn = getattr(backend, attr or name, None)
             if fn is None:
                 return proto()          # NULL entry
             if name == "stream":
@@ -367,9 +379,17 @@ class CallbackOps:
         for name, proto in _abi.OPS_FIELDS:
             fields[name] = wrap(name, proto)
         self._ops = _abi.SlabOps(None, *[fields[n] for n, _ in _abi.OPS_FIELDS])
+        self._cops = None
+        if getattr(backend, "colour_cells", None) is not None:
+            cf = {name: wrap(name, proto, "colour_" + name) for name, proto in _abi.COLOUR_OPS_FIELDS}
+            self._cops = _abi.SlabColourOps(None, *[cf[n] for n, _ in _abi.COLOUR_OPS_FIELDS])
 
     def c_ops(self):
         return C.pointer(self._ops)
+
+    def c_colour_ops(self):
+        """The colour table, or None when the back-end has no colour entries."""
+        return C.pointer(self._cops) if self._cops is not None else None
 
 
 # ---- the runner -----------------------------------------------------------------------------
@@ -380,9 +400,11 @@ class SlabRunner:
 
     def __init__(self, rows_per_rank, W, param, particles_div=8, seed=0, ops=None, scale=None,
                  noise_seed=3.0, init=True, comm=None, noise_rows=None, trim=None, pair=None,
-                 halo_need=0, device=None, mode=None):
+                 halo_need=0, device=None, mode=None, colour=False):
         """comm: SelfComm / RcclComm / CallbackComm (default: default_comm()); ops: CallbackOps or
-        None for the HIP back-end on device `device` (default: SOIL_DEVICE or LOCAL_RANK)."""
+        None for the HIP back-end on device `device` (default: SOIL_DEVICE or LOCAL_RANK).
+        colour: carry the four colour planes (COLOUR_PLANES, zero until set_plane fills them) through
+        every step (soil_slab_create_colour); a CallbackOps back-end must then have a colour table."""
         lib = self.lib = _abi.lib()
         self.cb_ops = ops
         if ops is None:
@@ -406,8 +428,14 @@ class SlabRunner:
         cfg.mode = -1 if mode is None else {"deep": 0, "migrate": 1}[mode]
         self._h = C.c_void_p()
         pref = param._ref() if hasattr(param, "_ref") else C.byref(param)
-        self._check(lib.soil_slab_create(C.byref(self._h), C.byref(cfg), pref, self.comm.c_comm(),
-                                         ops.c_ops() if ops is not None else None))
+        self.colour = bool(colour)
+        if self.colour:
+            self._check(lib.soil_slab_create_colour(C.byref(self._h), C.byref(cfg), pref, self.comm.c_comm(),
+                                                    ops.c_ops() if ops is not None else None,
+                                                    ops.c_colour_ops() if ops is not None else None))
+        else:
+            self._check(lib.soil_slab_create(C.byref(self._h), C.byref(cfg), pref, self.comm.c_comm(),
+                                             ops.c_ops() if ops is not None else None))
         i = self.info()
         self.rank, self.world = i.rank, i.world
         self.S, self.W, self.H, self.G, self.N = i.S, i.W, i.H, i.G, i.N
