@@ -57,6 +57,11 @@ int workspace_release_all();
 // on this device; read and reset through soil_particle_steps().
 int step_counter(unsigned long long** out);
 
+// The fused cell phase behind soil_erode_cells_fused_ex (`colour` null) and soil_erode_cells_fused_colour
+// (erosion_cells.hip); the entries' own checks of `colour` are the caller's.
+int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* colour, const soil_domain* dom,
+                      const float scale[3], const soil_param* param, int flags, void* stream);
+
 // Launch shape of the per-cell kernels: threads along the contiguous axis, and a
 // work-group walks a band of kRowBand consecutive rows (SOIL_ROW_LOOP).  A 64-bit
 // n / W, n % W per cell costs more than most of these kernels' arithmetic, and with

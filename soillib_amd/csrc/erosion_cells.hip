@@ -699,10 +699,9 @@ int soil_erode_cells_fused(const soil_erosion_planes* pl, const soil_domain* dom
 
 namespace soil {
 
-// soil_erode_cells_fused_ex (colour == nullptr) and soil_erode_cells_fused_colour
-static int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* colour,
-                             const soil_domain* dom, const float scale[3], const soil_param* param,
-                             int flags, void* stream) {
+int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* colour,
+                      const soil_domain* dom, const float scale[3], const soil_param* param,
+                      int flags, void* stream) {
   SOIL_REQUIRE(pl && dom && scale && param, "erode_cells_fused: null argument");
   SOIL_REQUIRE(pl->layers && pl->layers_next && pl->uplift && pl->rainfall && pl->waterHeight &&
                    pl->waterFlux && pl->mass && pl->massFlux && pl->velocity &&

@@ -464,44 +464,18 @@ static int materialise(const Streams& st, int64_t N, hipStream_t s) {
   if (!st.rng) return fail(SOIL_ERR_INVALID_ARGUMENT, "uniform streams on a small launch need a tensor to seed");
   return soil_rng_seed(st.rng, N, st.seed, st.offset, s);
 }
-int particles_fluvial_streams(const soil_erosion_planes& P, Streams rng, int64_t N, float* remote0,
-                              const Dom& d, Scale3 s, const Param& p, hipStream_t st) {
-  if (N <= 0) return SOIL_OK;
-  if (use_tiled(N, d))
-    return launch_fluvial_tiled(P.waterFlux, P.massFlux, P.velocityFlux, nullptr, rng, N, P.layers, P.rainfall,
-                                P.waterHeight, P.velocity, nullptr, remote0, d, s, p, st);
-  if (int rc = materialise(rng, N, st); rc != SOIL_OK) return rc;
-  return soil_particles_fluvial_slab(P.waterFlux, P.massFlux, P.velocityFlux, nullptr, rng.rng, N, P.layers,
-                                     P.rainfall, P.waterHeight, P.velocity, nullptr, remote0,
-                                     reinterpret_cast<const soil_domain*>(&d), &s.x, &p, st);
-}
-int particles_debris_streams(const soil_erosion_planes& P, Streams rng, int64_t N, float* remote0,
-                             const Dom& d, Scale3 s, const Param& p, hipStream_t st) {
-  if (N <= 0) return SOIL_OK;
-  if (use_tiled(N, d))
-    return launch_debris_tiled(P.debrisFlux, P.debrisVelocityFlux, nullptr, rng, N, P.layers, P.debrisVelocity,
-                               nullptr, remote0, d, s, p, st);
-  if (int rc = materialise(rng, N, st); rc != SOIL_OK) return rc;
-  return soil_particles_debris_slab(P.debrisFlux, P.debrisVelocityFlux, nullptr, rng.rng, N, P.layers,
-                                    P.debrisVelocity, nullptr, remote0, reinterpret_cast<const soil_domain*>(&d),
-                                    &s.x, &p, st);
-}
-int particles_pair_streams(const soil_erosion_planes& P, Streams rf, Streams rd, int64_t N, float* remote0,
-                           const Dom& d, Scale3 s, const Param& p, hipStream_t st, bool overwrite) {
-  if (N > 0 && use_tiled(N, d)) return launch_pair_tiled(P, rf, rd, N, remote0, d, s, p, st, overwrite);
-  if (overwrite) {  // a launch that cannot store its first round clears the planes it adds to
-    const size_t b = sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
-    SOIL_HIP(hipMemsetAsync(P.waterFlux, 0, b, st));
-    SOIL_HIP(hipMemsetAsync(P.massFlux, 0, b, st));
-    SOIL_HIP(hipMemsetAsync(P.velocityFlux, 0, 2 * b, st));
-    SOIL_HIP(hipMemsetAsync(P.debrisFlux, 0, b, st));
-    SOIL_HIP(hipMemsetAsync(P.debrisVelocityFlux, 0, 2 * b, st));
-  }
-  if (N <= 0) return SOIL_OK;
-  if (int rc = materialise(rf, N, st); rc != SOIL_OK) return rc;
-  if (int rc = materialise(rd, N, st); rc != SOIL_OK) return rc;
-  return soil_particles_pair_slab(&P, rf.rng, rd.rng, N, remote0, reinterpret_cast<const soil_domain*>(&d), &s.x,
-                                  &p, st);
+
+int clear_flux(const soil_erosion_planes* P, const soil_colour_planes* C, int kind, int64_t cells, hipStream_t st) {
+  const size_t b = sizeof(float) * static_cast<size_t>(cells);
+  std::pair<float*, size_t> planes[7] = {};  // (plane, floats per cell)
+  if (P)
+    planes[0] = {P->waterFlux, 1}, planes[1] = {P->massFlux, 1}, planes[2] = {P->velocityFlux, 2},
+    planes[3] = {P->debrisFlux, 1}, planes[4] = {P->debrisVelocityFlux, 2};
+  if (C && kind != DEBRIS) planes[5] = {C->albedo_fluvial, 3};
+  if (C && kind != FLUVIAL) planes[6] = {C->albedo_debris, 3};
+  for (const auto& [plane, n] : planes)
+    if (n) SOIL_HIP(hipMemsetAsync(plane, 0, n * b, st));
+  return SOIL_OK;
 }
 
 // Shared staging: pack the fields, bucket the spawn points.  Returns device
@@ -547,113 +521,76 @@ static int stage(Staged* out, soil_rng* rng, int64_t N, const float* layers,
   return SOIL_OK;
 }
 
-static int launch_particles_fluvial(float* waterFlux, float* massFlux, float* velocityFlux,
-                                    float* albedoFlux, soil_rng* rng, int64_t N,
-                                    const float* layers, const float* waterSource,
-                                    const float* waterHeight, const float* velocity,
-                                    const float* albedoSource, float* remote0, const Dom& d,
-                                    Scale3 s, const Param& p, hipStream_t st,
-                                    float* remoteA = nullptr) {
+// the colour flux plane of `kind` a launch adds to, or null (physics only)
+static float* colour_flux(const Launch& L, int kind) {
+  return L.C ? (kind == FLUVIAL ? L.C->albedo_fluvial : L.C->albedo_debris) : nullptr;
+}
+
+int particles_fluvial(const Launch& L) {
+  const int64_t N = L.N;
   if (N <= 0) return SOIL_OK;
-  if (!albedoFlux) remoteA = nullptr;
-  if (use_tiled(N, d))
-    return launch_fluvial_tiled(waterFlux, massFlux, velocityFlux, albedoFlux, streams_of(rng), N, layers,
-                                waterSource, waterHeight, velocity, albedoSource, remote0, d, s, p,
-                                st, remoteA);
+  if (use_tiled(N, L.d)) return launch_pass_tiled(FLUVIAL, L);
+  if (int rc = materialise(L.fluvial, N, L.st); rc != SOIL_OK) return rc;
   unsigned long long* steps = nullptr;
   if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
-  const FluvialPlanes P{waterFlux,   massFlux,    velocityFlux, albedoFlux, waterSource,
-                        waterHeight, albedoSource, remote0,      steps,      remoteA};
+  const soil_erosion_planes& Q = *L.P;
+  float* const albedoFlux = colour_flux(L, FLUVIAL);
+  const FluvialPlanes P{Q.waterFlux, Q.massFlux, Q.velocityFlux, albedoFlux, Q.rainfall, Q.waterHeight,
+                        albedoFlux ? L.C->albedo_surface : nullptr, L.remote0, steps,
+                        albedoFlux ? L.remote_colour : nullptr};
+  soil_rng* const rng = L.fluvial.rng;
   if (use_staged(N)) {
     Staged sg;
-    int rc = stage(&sg, rng, N, layers, velocity, d, s, p, st);
+    int rc = stage(&sg, rng, N, Q.layers, Q.velocity, L.d, L.s, L.p, L.st);
     if (rc != SOIL_OK) return rc;
-    k_fluvial_sorted<<<blocks_for(N, kPBlock) + 8, kPBlock, 0, st>>>(
-        P, sg.sorted, sg.total, N, PackedFields{sg.p4}, d, s, p);
+    k_fluvial_sorted<<<blocks_for(N, kPBlock) + 8, kPBlock, 0, L.st>>>(
+        P, sg.sorted, sg.total, N, PackedFields{sg.p4}, L.d, L.s, L.p);
   } else {
-    const DirectFields F{reinterpret_cast<const float2*>(layers),
-                         reinterpret_cast<const float2*>(velocity), d, s, p.exitSlope};
-    k_fluvial_direct<<<blocks_for(N, kPBlock), kPBlock, 0, st>>>(P, rng, N, F, p);
+    const DirectFields F{reinterpret_cast<const float2*>(Q.layers),
+                         reinterpret_cast<const float2*>(Q.velocity), L.d, L.s, L.p.exitSlope};
+    k_fluvial_direct<<<blocks_for(N, kPBlock), kPBlock, 0, L.st>>>(P, rng, N, F, L.p);
   }
   SOIL_LAUNCH_CHECK();
   return SOIL_OK;
 }
 
-static int launch_particles_debris(float* massFlux, float* velocityFlux, float* albedoFlux,
-                                   soil_rng* rng, int64_t N, const float* layers,
-                                   const float* velocity, const float* albedoSource,
-                                   float* remote0, const Dom& d, Scale3 s, const Param& p,
-                                   hipStream_t st, float* remoteA = nullptr) {
+// (with colour planes every walker is walked to the end: retirement makes no difference to the planes, and only
+// the overlapped pair retires with colour)
+int particles_debris(const Launch& L) {
+  const int64_t N = L.N;
   if (N <= 0) return SOIL_OK;
-  if (!albedoFlux) remoteA = nullptr;
-  if (use_tiled(N, d))
-    return launch_debris_tiled(massFlux, velocityFlux, albedoFlux, streams_of(rng), N, layers, velocity,
-                               albedoSource, remote0, d, s, p, st, remoteA);
+  if (use_tiled(N, L.d)) return launch_pass_tiled(DEBRIS, L);
+  if (int rc = materialise(L.debris, N, L.st); rc != SOIL_OK) return rc;
   unsigned long long* steps = nullptr;
   if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
-  const DebrisPlanes P{massFlux, velocityFlux, albedoFlux, albedoSource, remote0, steps, remoteA};
+  const soil_erosion_planes& Q = *L.P;
+  float* const albedoFlux = colour_flux(L, DEBRIS);
+  const DebrisPlanes P{Q.debrisFlux, Q.debrisVelocityFlux, albedoFlux, albedoFlux ? L.C->albedo_surface : nullptr,
+                       L.remote0, steps, albedoFlux ? L.remote_colour : nullptr};
+  soil_rng* const rng = L.debris.rng;
   if (use_staged(N)) {
     Staged sg;
-    int rc = stage(&sg, rng, N, layers, velocity, d, s, p, st);
+    int rc = stage(&sg, rng, N, Q.layers, Q.debrisVelocity, L.d, L.s, L.p, L.st);
     if (rc != SOIL_OK) return rc;
-    k_debris_sorted<<<blocks_for(N, kPBlock) + 8, kPBlock, 0, st>>>(
-        P, sg.sorted, sg.total, N, PackedFields{sg.p4}, d, s, p);
+    k_debris_sorted<<<blocks_for(N, kPBlock) + 8, kPBlock, 0, L.st>>>(
+        P, sg.sorted, sg.total, N, PackedFields{sg.p4}, L.d, L.s, L.p);
   } else {
-    const DirectFields F{reinterpret_cast<const float2*>(layers),
-                         reinterpret_cast<const float2*>(velocity), d, s, p.exitSlope};
-    k_debris_direct<<<blocks_for(N, kPBlock), kPBlock, 0, st>>>(P, rng, N, F, p);
+    const DirectFields F{reinterpret_cast<const float2*>(Q.layers),
+                         reinterpret_cast<const float2*>(Q.debrisVelocity), L.d, L.s, L.p.exitSlope};
+    k_debris_direct<<<blocks_for(N, kPBlock), kPBlock, 0, L.st>>>(P, rng, N, F, L.p);
   }
   SOIL_LAUNCH_CHECK();
   return SOIL_OK;
 }
 
-// The launches with colour on a slab (soil_particles_pair_colour_slab; the slab runner's coloured HIP
-// back-end).  Each clears the colour flux plane(s) it deposits into over local rows [0, d.rows) first;
-// `remote0` (may be null) is float[16]: [0..7] as the physics slab launches, [8..10] / [11..13] the
-// fluvial / debris colour deposits of NaN walkers for global (0, 0) (Remote0::colour = remote0 + 8).
-static size_t colour_plane_bytes(const Dom& d) {
-  return 3 * sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
-}
-int particles_fluvial_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rng, int64_t N,
-                                     float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st) {
-  SOIL_HIP(hipMemsetAsync(C.albedo_fluvial, 0, colour_plane_bytes(d), st));
-  if (N <= 0) return SOIL_OK;
-  float* const rc0 = remote0 ? remote0 + 8 : nullptr;
-  if (use_tiled(N, d))
-    return launch_fluvial_tiled(P.waterFlux, P.massFlux, P.velocityFlux, C.albedo_fluvial, rng, N, P.layers, P.rainfall,
-                                P.waterHeight, P.velocity, C.albedo_surface, remote0, d, s, p, st, rc0);
-  if (int rc = materialise(rng, N, st); rc != SOIL_OK) return rc;
-  return launch_particles_fluvial(P.waterFlux, P.massFlux, P.velocityFlux, C.albedo_fluvial, rng.rng, N, P.layers,
-                                  P.rainfall, P.waterHeight, P.velocity, C.albedo_surface, remote0, d, s, p, st, rc0);
-}
-// (walked to the end, as soil_particles_debris_slab with colour planes: retirement makes no difference to the
-// planes, and only the overlapped pair retires with colour)
-int particles_debris_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rng, int64_t N,
-                                    float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st) {
-  SOIL_HIP(hipMemsetAsync(C.albedo_debris, 0, colour_plane_bytes(d), st));
-  if (N <= 0) return SOIL_OK;
-  float* const rc0 = remote0 ? remote0 + 8 : nullptr;
-  if (use_tiled(N, d))
-    return launch_debris_tiled(P.debrisFlux, P.debrisVelocityFlux, C.albedo_debris, rng, N, P.layers, P.debrisVelocity,
-                               C.albedo_surface, remote0, d, s, p, st, rc0);
-  if (int rc = materialise(rng, N, st); rc != SOIL_OK) return rc;
-  return launch_particles_debris(P.debrisFlux, P.debrisVelocityFlux, C.albedo_debris, rng.rng, N, P.layers,
-                                 P.debrisVelocity, C.albedo_surface, remote0, d, s, p, st, rc0);
-}
-int particles_pair_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rf, Streams rd,
-                                  int64_t N, float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st,
-                                  bool overwrite) {
-  if (N > 0 && use_tiled(N, d))  // (clears the colour flux planes itself, ahead of its fork)
-    return launch_pair_tiled(P, rf, rd, N, remote0, d, s, p, st, overwrite, MigrateBox{}, MigrateBox{}, nullptr, 0,
-                             nullptr, 0, &C, remote0 ? remote0 + 8 : nullptr);
-  // the small-N shapes: one launch after the other, every walker walked to the end
-  if (overwrite) {
-    const size_t b = sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
-    for (float* t : {P.waterFlux, P.massFlux, P.debrisFlux}) SOIL_HIP(hipMemsetAsync(t, 0, b, st));
-    for (float* t : {P.velocityFlux, P.debrisVelocityFlux}) SOIL_HIP(hipMemsetAsync(t, 0, 2 * b, st));
-  }
-  if (int rc = particles_fluvial_colour_streams(P, C, rf, N, remote0, d, s, p, st); rc != SOIL_OK) return rc;
-  return particles_debris_colour_streams(P, C, rd, N, remote0, d, s, p, st);
+int particles_pair(const Launch& L) {
+  if (L.N > 0 && use_tiled(L.N, L.d)) return launch_pair_tiled(L);  // (clears the colour flux planes itself)
+  // the small-N shapes: one launch after the other, every walker walked to the end; a launch that cannot store
+  // its first round clears the planes it adds to
+  if (int rc = clear_flux(L.overwrite ? L.P : nullptr, L.C, BOTH_KINDS, L.d.rows * L.d.W, L.st); rc != SOIL_OK)
+    return rc;
+  if (int rc = particles_fluvial(L); rc != SOIL_OK) return rc;
+  return particles_debris(L);
 }
 
 }  // namespace soil
@@ -703,9 +640,10 @@ int soil_transport_fluvial(const float* layers, const float* rainfall, float* wa
   SOIL_REQUIRE(H > 0 && W > 0 && N >= 0 && (N == 0 || rng), "transport_fluvial: bad sizes");
   const Dom d = full_domain(H, W);
   const Scale3 s = s3p(scale);
-  int rc = launch_particles_fluvial(waterFlux, massFlux, velocityFlux, albedoFlux, rng, N, layers,
-                                    rainfall, waterHeight, velocity, albedoSource, nullptr, d, s,
-                                    *param, as_stream(stream));  // erosion.cu:209
+  const soil_domain dom{H, W, 0, H, 0, H};
+  int rc = soil_particles_fluvial_slab(waterFlux, massFlux, velocityFlux, albedoFlux, rng, N, layers, rainfall,
+                                       waterHeight, velocity, albedoSource, nullptr, &dom, scale, param,
+                                       stream);  // erosion.cu:209
   if (rc != SOIL_OK) return rc;
   return launch_normalize_fluvial(waterFlux, massFlux, velocityFlux, albedoFlux, layers, rainfall,
                                   waterHeight, mass, velocity, albedoSource, d, s, *param,
@@ -726,14 +664,16 @@ int soil_transport_debris(const float* layers, float* velocity, float* velocityF
   SOIL_REQUIRE(H > 0 && W > 0 && N >= 0 && (N == 0 || rng), "transport_debris: bad sizes");
   const Dom d = full_domain(H, W);
   const Scale3 s = s3p(scale);
-  int rc = launch_particles_debris(massFlux, velocityFlux, albedoFlux, rng, N, layers, velocity,
-                                   albedoSource, nullptr, d, s, *param,
-                                   as_stream(stream));  // :412
+  const soil_domain dom{H, W, 0, H, 0, H};
+  int rc = soil_particles_debris_slab(massFlux, velocityFlux, albedoFlux, rng, N, layers, velocity, albedoSource,
+                                      nullptr, &dom, scale, param, stream);  // :412
   if (rc != SOIL_OK) return rc;
   return launch_normalize_debris(massFlux, velocityFlux, albedoFlux, layers, mass, velocity,
                                  albedoSource, d, s, *param, as_stream(stream));  // :424
 }
 
+// The per-op slab launches: the colour planes they get hold the colour source (only read) and their kind's
+// flux plane, which they add to without clearing it; no colour reaches remote0.
 int soil_particles_fluvial_slab(float* waterFlux, float* massFlux, float* velocityFlux,
                                 float* albedoFlux, soil_rng* rng, int64_t N, const float* layers,
                                 const float* rainfall, const float* waterHeight,
@@ -750,9 +690,14 @@ int soil_particles_fluvial_slab(float* waterFlux, float* massFlux, float* veloci
   const Dom d = to_dom(dom);
   int rc = check_domain(d);
   if (rc != SOIL_OK) return rc;
-  return launch_particles_fluvial(waterFlux, massFlux, velocityFlux, albedoFlux, rng, N, layers,
-                                  rainfall, waterHeight, velocity, albedoSource, remote0, d,
-                                  s3p(scale), *param, as_stream(stream));
+  soil_erosion_planes P{};
+  P.layers = layers, P.rainfall = rainfall;
+  P.waterHeight = const_cast<float*>(waterHeight), P.velocity = const_cast<float*>(velocity);
+  P.waterFlux = waterFlux, P.massFlux = massFlux, P.velocityFlux = velocityFlux;
+  soil_colour_planes C{};
+  C.albedo_surface = const_cast<float*>(albedoSource), C.albedo_fluvial = albedoFlux;
+  return particles_fluvial(Launch{.P = &P, .C = albedoFlux ? &C : nullptr, .fluvial = streams_of(rng), .N = N,
+                                  .remote0 = remote0, .d = d, .s = s3p(scale), .p = *param, .st = as_stream(stream)});
 }
 
 int soil_particles_debris_slab(float* massFlux, float* velocityFlux, float* albedoFlux,
@@ -769,9 +714,13 @@ int soil_particles_debris_slab(float* massFlux, float* velocityFlux, float* albe
   const Dom d = to_dom(dom);
   int rc = check_domain(d);
   if (rc != SOIL_OK) return rc;
-  return launch_particles_debris(massFlux, velocityFlux, albedoFlux, rng, N, layers, velocity,
-                                 albedoSource, remote0, d, s3p(scale), *param,
-                                 as_stream(stream));
+  soil_erosion_planes P{};
+  P.layers = layers, P.debrisVelocity = const_cast<float*>(velocity);
+  P.debrisFlux = massFlux, P.debrisVelocityFlux = velocityFlux;
+  soil_colour_planes C{};
+  C.albedo_surface = const_cast<float*>(albedoSource), C.albedo_debris = albedoFlux;
+  return particles_debris(Launch{.P = &P, .C = albedoFlux ? &C : nullptr, .debris = streams_of(rng), .N = N,
+                                 .remote0 = remote0, .d = d, .s = s3p(scale), .p = *param, .st = as_stream(stream)});
 }
 
 int soil_particles_pair_slab(const soil_erosion_planes* planes, soil_rng* rng_fluvial,
@@ -794,31 +743,10 @@ int soil_particles_pair_slab_ex(const soil_erosion_planes* planes, soil_rng* rng
   SOIL_REQUIRE(N >= 0 && (N == 0 || (rng_fluvial && rng_debris && rng_fluvial != rng_debris)),
                "particles_pair_slab: needs two distinct rng tensors");
   const Dom d = to_dom(dom);
-  int rc = check_domain(d);
-  if (rc != SOIL_OK) return rc;
-  hipStream_t st = as_stream(stream);
-  const bool overwrite = (flags & SOIL_FLUX_OVERWRITE) != 0;
-  auto clear_flux = [&]() -> int {  // what a launch that cannot store its first round does instead
-    const size_t b = sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
-    SOIL_HIP(hipMemsetAsync(P.waterFlux, 0, b, st));
-    SOIL_HIP(hipMemsetAsync(P.massFlux, 0, b, st));
-    SOIL_HIP(hipMemsetAsync(P.velocityFlux, 0, 2 * b, st));
-    SOIL_HIP(hipMemsetAsync(P.debrisFlux, 0, b, st));
-    SOIL_HIP(hipMemsetAsync(P.debrisVelocityFlux, 0, 2 * b, st));
-    return SOIL_OK;
-  };
-  if (N <= 0) return overwrite ? clear_flux() : SOIL_OK;
-  const Scale3 s = s3p(scale);
-  if (use_tiled(N, d))
-    return launch_pair_tiled(P, streams_of(rng_fluvial), streams_of(rng_debris), N, remote0, d, s, *param, st, overwrite);
-  if (overwrite)
-    if (int rc2 = clear_flux(); rc2 != SOIL_OK) return rc2;
-  rc = launch_particles_fluvial(P.waterFlux, P.massFlux, P.velocityFlux, nullptr, rng_fluvial, N,
-                                P.layers, P.rainfall, P.waterHeight, P.velocity, nullptr, remote0, d,
-                                s, *param, st);
-  if (rc != SOIL_OK) return rc;
-  return launch_particles_debris(P.debrisFlux, P.debrisVelocityFlux, nullptr, rng_debris, N, P.layers,
-                                 P.debrisVelocity, nullptr, remote0, d, s, *param, st);
+  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
+  return particles_pair(Launch{.P = planes, .fluvial = streams_of(rng_fluvial), .debris = streams_of(rng_debris),
+                               .N = N, .remote0 = remote0, .d = d, .s = s3p(scale), .p = *param,
+                               .st = as_stream(stream), .overwrite = (flags & SOIL_FLUX_OVERWRITE) != 0});
 }
 
 int soil_particles_pair_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
@@ -835,31 +763,14 @@ int soil_particles_pair_colour(const soil_erosion_planes* planes, const soil_col
   SOIL_REQUIRE(H > 0 && W > 0, "particles_pair_colour: empty grid");
   SOIL_REQUIRE(N >= 0 && (N == 0 || (rng_fluvial && rng_debris && rng_fluvial != rng_debris)),
                "particles_pair_colour: needs two distinct rng tensors");
-  const Dom d = full_domain(H, W);
-  hipStream_t st = as_stream(stream);
-  const Scale3 s = s3p(scale);
-  const bool overwrite = (flags & SOIL_FLUX_OVERWRITE) != 0;
-  if (N > 0 && use_tiled(N, d))
-    return launch_pair_tiled(P, streams_of(rng_fluvial), streams_of(rng_debris), N, nullptr, d, s, *param, st,
-                             overwrite, MigrateBox{}, MigrateBox{}, nullptr, 0, nullptr, 0, colour);
-  // the small-N shapes: one launch after the other, every walker walked to the end
-  const size_t b = sizeof(float) * static_cast<size_t>(H) * static_cast<size_t>(W);
-  if (overwrite) {
-    for (float* t : {P.waterFlux, P.massFlux, P.debrisFlux}) SOIL_HIP(hipMemsetAsync(t, 0, b, st));
-    for (float* t : {P.velocityFlux, P.debrisVelocityFlux}) SOIL_HIP(hipMemsetAsync(t, 0, 2 * b, st));
-  }
-  SOIL_HIP(hipMemsetAsync(colour->albedo_fluvial, 0, 3 * b, st));
-  SOIL_HIP(hipMemsetAsync(colour->albedo_debris, 0, 3 * b, st));
-  if (N <= 0) return SOIL_OK;
-  if (int rc = launch_particles_fluvial(P.waterFlux, P.massFlux, P.velocityFlux, colour->albedo_fluvial, rng_fluvial,
-                                        N, P.layers, P.rainfall, P.waterHeight, P.velocity, colour->albedo_surface,
-                                        nullptr, d, s, *param, st);
-      rc != SOIL_OK)
-    return rc;
-  return launch_particles_debris(P.debrisFlux, P.debrisVelocityFlux, colour->albedo_debris, rng_debris, N, P.layers,
-                                 P.debrisVelocity, colour->albedo_surface, nullptr, d, s, *param, st);
+  return particles_pair(Launch{.P = planes, .C = colour, .fluvial = streams_of(rng_fluvial),
+                               .debris = streams_of(rng_debris), .N = N, .d = full_domain(H, W), .s = s3p(scale),
+                               .p = *param, .st = as_stream(stream),
+                               .overwrite = (flags & SOIL_FLUX_OVERWRITE) != 0});
 }
 
+// `remote0` (may be null) is float[16]: [0..7] as the physics slab launches, [8..10] / [11..13] the fluvial /
+// debris colour deposits of NaN walkers for global (0, 0) (Remote0::colour = remote0 + 8)
 int soil_particles_pair_colour_slab(const soil_erosion_planes* planes, const soil_colour_planes* colour,
                                     soil_rng* rng_fluvial, soil_rng* rng_debris, int64_t N, float* remote0,
                                     const soil_domain* dom, const float scale[3], const soil_param* param, int flags,
@@ -876,8 +787,11 @@ int soil_particles_pair_colour_slab(const soil_erosion_planes* planes, const soi
                "particles_pair_colour_slab: needs two distinct rng tensors");
   const Dom d = to_dom(dom);
   if (int rc = check_domain(d); rc != SOIL_OK) return rc;
-  return particles_pair_colour_streams(P, *colour, streams_of(rng_fluvial), streams_of(rng_debris), N, remote0, d,
-                                       s3p(scale), *param, as_stream(stream), (flags & SOIL_FLUX_OVERWRITE) != 0);
+  return particles_pair(Launch{.P = planes, .C = colour, .fluvial = streams_of(rng_fluvial),
+                               .debris = streams_of(rng_debris), .N = N, .remote0 = remote0,
+                               .remote_colour = remote0 ? remote0 + 8 : nullptr, .d = d, .s = s3p(scale),
+                               .p = *param, .st = as_stream(stream),
+                               .overwrite = (flags & SOIL_FLUX_OVERWRITE) != 0});
 }
 
 int soil_particle_steps(uint64_t* total, int reset, void* stream) {

@@ -70,8 +70,6 @@ namespace soil {
 struct TileShape { int tr, shift_c, off_r, off_c; };
 constexpr uint32_t kNoTile = 0xffffffffu;     // dest[] of an empty record slot
 
-enum Kind { FLUVIAL = 0, DEBRIS = 1 };
-
 struct alignas(16) PRec {  // parked particle, 64 bytes
   float px, py, spx, spy;
   float a0, a1, a2, s0;  // fluvial: att_w att_m att_v source_w | debris: att_d att_v - source_d
@@ -3224,41 +3222,34 @@ struct TiledRun {
   }
 };
 
+// the run of L's launch of KIND on stream `st`: that kind's planes of P, its colour flux plane of C
 template <int KIND>
-static TiledRun<KIND> make_run(float* flux0, float* flux1, float* fluxV, float* fluxA,
-                               const float* albedoSource, Streams rng, int64_t N,
-                               const float* layers, const float* waterSource,
-                               const float* waterHeight, const float* velocity, float* remote0,
-                               const Dom& d, Scale3 s, const Param& p, hipStream_t st,
-                               float* remote_colour = nullptr) {
+static TiledRun<KIND> make_run(const Launch& L, hipStream_t st) {
+  const soil_erosion_planes& P = *L.P;
   TiledRun<KIND> r;
-  r.flux0 = flux0, r.flux1 = flux1, r.fluxV = fluxV, r.rng = rng, r.N = N;
-  r.fluxA = fluxA, r.albedoSource = fluxA ? albedoSource : nullptr;
-  r.layers = layers, r.waterSource = waterSource, r.waterHeight = waterHeight, r.velocity = velocity;
-  r.remote0 = Remote0{remote0, fluxA ? remote_colour : nullptr}, r.d = d, r.s = s, r.p = p, r.st = st;
+  if (KIND == FLUVIAL) {
+    r.flux0 = P.waterFlux, r.flux1 = P.massFlux, r.fluxV = P.velocityFlux, r.rng = L.fluvial;
+    r.waterSource = P.rainfall, r.waterHeight = P.waterHeight, r.velocity = P.velocity;
+  } else {
+    r.flux0 = P.debrisFlux, r.flux1 = nullptr, r.fluxV = P.debrisVelocityFlux, r.rng = L.debris;
+    r.waterSource = nullptr, r.waterHeight = nullptr, r.velocity = P.debrisVelocity;
+  }
+  if (L.C) r.fluxA = KIND == FLUVIAL ? L.C->albedo_fluvial : L.C->albedo_debris, r.albedoSource = L.C->albedo_surface;
+  r.N = L.N, r.layers = P.layers;
+  r.remote0 = Remote0{L.remote0, L.C ? L.remote_colour : nullptr}, r.d = L.d, r.s = L.s, r.p = L.p, r.st = st;
   return r;
-}
-
-template <int KIND>
-static int run_tiled(float* flux0, float* flux1, float* fluxV, float* fluxA,
-                     const float* albedoSource, Streams rng, int64_t N, const float* layers, const float* waterSource, const float* waterHeight,
-                     const float* velocity, float* remote0, const Dom& d, Scale3 s, const Param& p,
-                     hipStream_t st, float* remote_colour) {
-  TiledRun<KIND> r = make_run<KIND>(flux0, flux1, fluxV, fluxA, albedoSource, rng, N, layers,
-                                    waterSource, waterHeight, velocity, remote0, d, s, p, st, remote_colour);
-  if (int rc = r.begin(); rc != SOIL_OK) return rc;
-  while (!r.done)
-    if (int rc = r.advance(); rc != SOIL_OK) return rc;
-  return SOIL_OK;
 }
 
 // Both launches of a step, overlapped: two internal streams forked from `st` and joined
 // back into it; the host alternates between the two runs' decisions.
-int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams rng_debris, int64_t N,
-                      float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st, bool overwrite,
-                      MigrateBox box_fluvial, MigrateBox box_debris, const void* inbox_fluvial, uint32_t n_fluvial,
-                      const void* inbox_debris, uint32_t n_debris, const soil_colour_planes* colour,
-                      float* remote_colour) {
+int launch_pair_tiled(const Launch& L, MigrateBox box_fluvial, MigrateBox box_debris, const void* inbox_fluvial,
+                      uint32_t n_fluvial, const void* inbox_debris, uint32_t n_debris) {
+  const soil_erosion_planes& P = *L.P;
+  const int64_t N = L.N;
+  const Dom& d = L.d;
+  const Scale3 s = L.s;
+  const Param& p = L.p;
+  const hipStream_t st = L.st;
   // forked streams and their events, one set per (thread, device)
   struct Fork {
     hipStream_t sA = nullptr, sB = nullptr;
@@ -3276,14 +3267,8 @@ int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams
     SOIL_HIP(hipEventCreateWithFlags(&f.joinB, hipEventDisableTiming));
   }
   const hipStream_t sA = f.sA, sB = f.sB;
-  TiledRun<FLUVIAL> A = make_run<FLUVIAL>(P.waterFlux, P.massFlux, P.velocityFlux, nullptr, nullptr,
-                                          rng_fluvial, N,
-                                          P.layers, P.rainfall, P.waterHeight, P.velocity, remote0,
-                                          d, s, p, sA);
-  TiledRun<DEBRIS> B = make_run<DEBRIS>(P.debrisFlux, nullptr, P.debrisVelocityFlux, nullptr, nullptr,
-                                        rng_debris, N,
-                                        P.layers, nullptr, nullptr, P.debrisVelocity, remote0, d, s,
-                                        p, sB);
+  TiledRun<FLUVIAL> A = make_run<FLUVIAL>(L, sA);
+  TiledRun<DEBRIS> B = make_run<DEBRIS>(L, sB);
   // When the second launch starts: from the fluvial launch's round `delay` on.  Measured
   // (tools/ab_pair_sizes.sh; ms per step, sequential | delay 1, 2, 4, 8): 1024^2 3.00 | 2.13 2.03 2.29
   // 2.54; 2048^2 5.70 | 4.99 4.92 4.79 4.94; 4096^2 12.14 | 11.72 11.75 11.98 11.78; 8192^2 37.3 | 37.0
@@ -3319,16 +3304,11 @@ int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams
   const uint64_t delay = delay_env > 0 ? static_cast<uint64_t>(delay_env) : (turns ? 0 : (N <= 300000 ? 1 : 2));
   // Whatever happens in between, `st` is joined with both streams before this returns: rounds may
   // still be in flight on the workspace the next call reuses.
-  A.overwrite = B.overwrite = overwrite;
+  A.overwrite = B.overwrite = L.overwrite;
   A.box = box_fluvial, B.box = box_debris;
-  if (colour) {  // the coloured step: colour flux planes cleared here, spent debris walkers retired
-    A.fluxA = colour->albedo_fluvial, A.albedoSource = colour->albedo_surface;
-    B.fluxA = colour->albedo_debris, B.albedoSource = colour->albedo_surface;
+  if (L.C) {  // the coloured step: colour flux planes cleared here, spent debris walkers retired
     B.retire_colour = true;
-    A.remote0.colour = B.remote0.colour = remote_colour;  // (slab launches: the NaN walkers' colour for (0, 0))
-    const size_t b3 = 3 * sizeof(float) * static_cast<size_t>(d.rows) * static_cast<size_t>(d.W);
-    SOIL_HIP(hipMemsetAsync(colour->albedo_fluvial, 0, b3, st));  // ahead of the fork
-    SOIL_HIP(hipMemsetAsync(colour->albedo_debris, 0, b3, st));
+    if (int rc = clear_flux(nullptr, L.C, BOTH_KINDS, d.rows * d.W, st); rc != SOIL_OK) return rc;  // ahead of the fork
   }
   const bool immigrants = inbox_fluvial != nullptr || inbox_debris != nullptr;
   if (immigrants) {  // both kinds' handed-over walkers, walked on side by side: the step's pack pass stands
@@ -3402,27 +3382,10 @@ int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams
   return SOIL_OK;
 }
 
-int launch_fluvial_tiled(float* waterFlux, float* massFlux, float* velocityFlux, float* albedoFlux,
-                         Streams rng, int64_t N, const float* layers, const float* waterSource,
-                         const float* waterHeight, const float* velocity,
-                         const float* albedoSource, float* remote0, const Dom& d, Scale3 s,
-                         const Param& p, hipStream_t st, float* remote_colour) {
-  return run_tiled<FLUVIAL>(waterFlux, massFlux, velocityFlux, albedoFlux, albedoSource, rng, N,
-                            layers, waterSource, waterHeight, velocity, remote0, d, s, p, st, remote_colour);
-}
-
-int launch_debris_tiled(float* massFlux, float* velocityFlux, float* albedoFlux, Streams rng,
-                        int64_t N, const float* layers, const float* velocity,
-                        const float* albedoSource, float* remote0, const Dom& d, Scale3 s,
-                        const Param& p, hipStream_t st, float* remote_colour) {
-  return run_tiled<DEBRIS>(massFlux, nullptr, velocityFlux, albedoFlux, albedoSource, rng, N, layers,
-                           nullptr, nullptr, velocity, remote0, d, s, p, st, remote_colour);
-}
-
-// One launch of one kind for the slab runner's migrate mode: spawns (inbox null) or handed-over records,
-// leavers into `box`.  Later passes of a step find the kind's cell records where the first one packed them.
-int launch_pass_tiled(int kind, const soil_erosion_planes& P, Streams rng, int64_t N, float* remote0, const Dom& d,
-                      Scale3 s, const Param& p, hipStream_t st, const void* inbox, uint32_t n_in, MigrateBox box) {
+// One launch of one kind: the single-kind launches, and the slab runner's migrate mode — spawns (inbox null) or
+// handed-over records, leavers into `box`.  Later passes of a step find the kind's cell records where the first
+// one packed them.
+int launch_pass_tiled(int kind, const Launch& L, const void* inbox, uint32_t n_in, MigrateBox box) {
   auto run = [&](auto r) -> int {
     r.box = box;
     r.inbox = static_cast<const PRec*>(inbox);
@@ -3433,11 +3396,8 @@ int launch_pass_tiled(int kind, const soil_erosion_planes& P, Streams rng, int64
       if (int rc = r.advance(); rc != SOIL_OK) return rc;
     return SOIL_OK;
   };
-  if (kind == FLUVIAL)
-    return run(make_run<FLUVIAL>(P.waterFlux, P.massFlux, P.velocityFlux, nullptr, nullptr, rng, N, P.layers, P.rainfall,
-                                 P.waterHeight, P.velocity, remote0, d, s, p, st));
-  return run(make_run<DEBRIS>(P.debrisFlux, nullptr, P.debrisVelocityFlux, nullptr, nullptr, rng, N, P.layers, nullptr,
-                              nullptr, P.debrisVelocity, remote0, d, s, p, st));
+  if (kind == FLUVIAL) return run(make_run<FLUVIAL>(L, L.st));
+  return run(make_run<DEBRIS>(L, L.st));
 }
 
 }  // namespace soil

@@ -13,7 +13,7 @@
 // buffer swap from the library (include/soil.hpp, soil::erode), exactly as the Python module does.
 #include <cstdlib>
 
-#include "common.hpp"
+#include "particles_common.hpp"
 
 using namespace soil;
 
@@ -63,6 +63,37 @@ int soil_erode_step(const soil_erosion_planes* planes, soil_rng* rng, int64_t N,
   return soil_erode_step_ex(planes, rng, N, seed, step_index, H, W, scale, param, 0, stream);
 }
 
+}  // extern "C"
+
+namespace soil {
+
+// The common part of soil_erode_step_ex and soil_erode_step_colour (`colour` null: physics only).  The two
+// launches do not depend on each other (they add to different flux planes and read the same fields), so they
+// run overlapped: the sparse late rounds and the finishing launch of one fill with the dense rounds of the
+// other — 3.0 -> 2.0 ms per step at 1024^2, 5.7 -> 4.8 at 2048^2, 12.1 -> 11.7 at 4096^2, 37.3 -> 37.0 at
+// 8192^2.  The fluvial launch draws from a scratch tensor, the debris launch from the caller's, seeded two
+// draws on: results and the state `rng` is left in are those of the sequential order.
+static int erode_step(const soil_erosion_planes* planes, const soil_colour_planes* colour, soil_rng* rng, int64_t N,
+                      uint64_t seed, uint64_t offset, int64_t H, int64_t W, const float scale[3],
+                      const soil_param* param, int flags, void* stream) {
+  void* scratch = nullptr;
+  if (int rc = workspace_get(7, sizeof(soil_rng) * static_cast<size_t>(N), &scratch); rc != SOIL_OK) return rc;
+  soil_rng* rng_fluvial = static_cast<soil_rng*>(scratch);
+  if (int rc = soil_rng_seed(rng_fluvial, N, seed, offset, stream); rc != SOIL_OK) return rc;
+  if (int rc = soil_rng_seed(rng, N, seed, offset + 2, stream); rc != SOIL_OK) return rc;
+  const Launch L{.P = planes, .C = colour, .fluvial = streams_of(rng_fluvial), .debris = streams_of(rng), .N = N,
+                 .d = full_domain(H, W), .s = Scale3{scale[0], scale[1], scale[2]}, .p = *param,
+                 .st = as_stream(stream), .overwrite = (flags & SOIL_STEP_FLUX_IN_DIRTY) != 0};
+  if (int rc = particles_pair(L); rc != SOIL_OK) return rc;
+  const soil_domain dom{H, W, 0, H, 0, H};
+  return erode_cells_fused(planes, colour, &dom, scale, param,
+                           (flags & SOIL_STEP_FLUX_OUT_DIRTY) != 0 ? SOIL_CELLS_KEEP_FLUX : 0, stream);
+}
+
+}  // namespace soil
+
+extern "C" {
+
 int soil_erode_step_ex(const soil_erosion_planes* planes, soil_rng* rng, int64_t N, uint64_t seed,
                        uint64_t step_index, int64_t H, int64_t W, const float scale[3],
                        const soil_param* param, int flags, void* stream) {
@@ -87,11 +118,8 @@ int soil_erode_step_ex(const soil_erosion_planes* planes, soil_rng* rng, int64_t
   const bool in_dirty = (flags & SOIL_STEP_FLUX_IN_DIRTY) != 0, out_dirty = (flags & SOIL_STEP_FLUX_OUT_DIRTY) != 0;
   const int cell_flags = out_dirty ? SOIL_CELLS_KEEP_FLUX : 0;
   if (sequential) {  // one launch after the other on the caller's streams (diagnostics: phase timings)
-    if (in_dirty) {
-      const size_t b = sizeof(float) * static_cast<size_t>(H) * static_cast<size_t>(W);
-      for (float* t : {P.waterFlux, P.massFlux, P.debrisFlux}) SOIL_HIP(hipMemsetAsync(t, 0, b, as_stream(stream)));
-      for (float* t : {P.velocityFlux, P.debrisVelocityFlux}) SOIL_HIP(hipMemsetAsync(t, 0, 2 * b, as_stream(stream)));
-    }
+    if (in_dirty)
+      if (int rc = clear_flux(planes, nullptr, BOTH_KINDS, H * W, as_stream(stream)); rc != SOIL_OK) return rc;
     if (int rc = soil_rng_seed(rng, N, seed, offset, stream); rc != SOIL_OK) return rc;
     if (int rc = soil_particles_fluvial_slab(P.waterFlux, P.massFlux, P.velocityFlux, nullptr, rng, N,
                                              P.layers, P.rainfall, P.waterHeight, P.velocity, nullptr,
@@ -105,22 +133,7 @@ int soil_erode_step_ex(const soil_erosion_planes* planes, soil_rng* rng, int64_t
       return rc;
     return soil_erode_cells_fused_ex(planes, &dom, scale, param, cell_flags, stream);
   }
-  // The two launches do not depend on each other (they add to different flux planes and read the
-  // same fields), so they run overlapped: the sparse late rounds and the finishing launch of
-  // one fill with the dense rounds of the other — 3.0 -> 2.0 ms per step at 1024^2, 5.7 -> 4.8 at
-  // 2048^2, 12.1 -> 11.7 at 4096^2, 37.3 -> 37.0 at 8192^2.  The fluvial launch draws from a scratch
-  // tensor, the debris launch from the caller's, seeded two draws on: results and the state `rng`
-  // is left in are those of the sequential order.
-  void* scratch = nullptr;
-  if (int rc = workspace_get(7, sizeof(soil_rng) * static_cast<size_t>(N), &scratch); rc != SOIL_OK) return rc;
-  soil_rng* rng_fluvial = static_cast<soil_rng*>(scratch);
-  if (int rc = soil_rng_seed(rng_fluvial, N, seed, offset, stream); rc != SOIL_OK) return rc;
-  if (int rc = soil_rng_seed(rng, N, seed, offset + 2, stream); rc != SOIL_OK) return rc;
-  if (int rc = soil_particles_pair_slab_ex(planes, rng_fluvial, rng, N, nullptr, &dom, scale, param,
-                                           in_dirty ? SOIL_FLUX_OVERWRITE : 0, stream);
-      rc != SOIL_OK)
-    return rc;
-  return soil_erode_cells_fused_ex(planes, &dom, scale, param, cell_flags, stream);
+  return erode_step(planes, nullptr, rng, N, seed, offset, H, W, scale, param, flags, stream);
 }
 
 int soil_erode_step_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour, soil_rng* rng,
@@ -136,22 +149,9 @@ int soil_erode_step_colour(const soil_erosion_planes* planes, const soil_colour_
                "erode_step_colour: every plane but `height` is required");
   SOIL_REQUIRE(colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial && colour->albedo_debris,
                "erode_step_colour: every colour plane is required");
-  const soil_domain dom{H, W, 0, H, 0, H};
-  const uint64_t offset = step_index * static_cast<uint64_t>(N);
-  const bool in_dirty = (flags & SOIL_STEP_FLUX_IN_DIRTY) != 0, out_dirty = (flags & SOIL_STEP_FLUX_OUT_DIRTY) != 0;
-  // both launches overlapped as in soil_erode_step_ex: the fluvial one draws from the workspace's
-  // tensor, the debris one from `rng` seeded two draws on
-  void* scratch = nullptr;
-  if (int rc = workspace_get(7, sizeof(soil_rng) * static_cast<size_t>(N), &scratch); rc != SOIL_OK) return rc;
-  soil_rng* rng_fluvial = static_cast<soil_rng*>(scratch);
-  if (int rc = soil_rng_seed(rng_fluvial, N, seed, offset, stream); rc != SOIL_OK) return rc;
-  if (int rc = soil_rng_seed(rng, N, seed, offset + 2, stream); rc != SOIL_OK) return rc;
-  if (int rc = soil_particles_pair_colour(planes, colour, rng_fluvial, rng, N, H, W, scale, param,
-                                          in_dirty ? SOIL_FLUX_OVERWRITE : 0, stream);
-      rc != SOIL_OK)
-    return rc;
-  return soil_erode_cells_fused_colour(planes, colour, &dom, scale, param, out_dirty ? SOIL_CELLS_KEEP_FLUX : 0,
-                                       stream);
+  // the overlapped launches whatever SOIL_STEP_PAIR says
+  return erode_step(planes, colour, rng, N, seed, step_index * static_cast<uint64_t>(N), H, W, scale, param, flags,
+                    stream);
 }
 
 int soil_erode(const soil_erode_model* model, int64_t H, int64_t W, int64_t N, uint64_t seed,

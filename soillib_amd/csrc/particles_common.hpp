@@ -90,10 +90,44 @@ struct MigrateBox {
   uint32_t* count = nullptr;
   uint32_t cap = 0;
 };
-// one launch of `kind` (0 fluvial, 1 debris) in the tiled shape whatever N: from the streams' spawns
-// (`inbox` null) or from `n_in` handed-over records; deposits into P's flux planes of that kind
-int launch_pass_tiled(int kind, const soil_erosion_planes& P, Streams rng, int64_t N, float* remote0, const Dom& d,
-                      Scale3 s, const Param& p, hipStream_t st, const void* inbox, uint32_t n_in, MigrateBox box);
+
+// the two kinds of particle launch
+enum Kind { FLUVIAL = 0, DEBRIS = 1, BOTH_KINDS = 2 };
+
+// One particle launch, or the pair of launches, of a step: what every launch shape and entry point hands on.
+// Each launch takes its kind's planes of P and, with `C`, its kind's colour flux plane and C->albedo_surface;
+// the per-op entries (soil_transport_*, soil_particles_*_slab with albedo planes) pass a C that holds only
+// those two.  `remote0`: the NaN walkers' physics deposits for global (0, 0) (float[8], Remote0::phys),
+// `remote_colour` their colour deposits (float[6], Remote0::colour); either may be null.  `overwrite`: the
+// physics flux planes hold stale values (SOIL_FLUX_OVERWRITE, soil_hip.h): the pair launch leaves them holding
+// its deposits only.
+struct Launch {
+  const soil_erosion_planes* P;
+  const soil_colour_planes* C = nullptr;  // null: physics only
+  Streams fluvial{}, debris{};
+  int64_t N = 0;
+  float* remote0 = nullptr;
+  float* remote_colour = nullptr;
+  Dom d;
+  Scale3 s;
+  Param p;
+  hipStream_t st;
+  bool overwrite = false;
+};
+
+// Zeroes, over `cells` = local rows x W, the flux planes the launches of `kind` (or BOTH_KINDS) add to: the
+// five physics flux planes of P (both kinds; when P is not null) and that kind's colour flux plane(s) of C
+// (when C is not null).
+int clear_flux(const soil_erosion_planes* P, const soil_colour_planes* C, int kind, int64_t cells, hipStream_t st);
+
+// The launches behind the entry points (erosion_particles.hip).  Each picks the launch shape (use_tiled_launch,
+// soil_set_particle_mode); the small-N shapes seed uniform streams into their tensor first.  A single-kind
+// launch walks every debris walker to the end and clears no plane.  The pair clears the colour flux planes
+// first (with C, also when N == 0) and, on `overwrite`, the physics ones where it cannot store its first round;
+// the small-N shapes run the two launches one after the other.
+int particles_fluvial(const Launch& L);
+int particles_debris(const Launch& L);
+int particles_pair(const Launch& L);
 
 // the launch shape a launch of N particles on domain d gets (erosion_particles.hip)
 bool use_tiled_launch(int64_t N, const Dom& d);
@@ -106,43 +140,16 @@ __global__ void __launch_bounds__(1024)
     k_tile_scan(uint32_t* start, const uint32_t* count, int64_t tiles);
 
 // tiled launch shape (erosion_particles_tiled.hip)
-int launch_fluvial_tiled(float* waterFlux, float* massFlux, float* velocityFlux, float* albedoFlux,
-                         Streams rng, int64_t N, const float* layers, const float* waterSource,
-                         const float* waterHeight, const float* velocity,
-                         const float* albedoSource, float* remote0, const Dom& d, Scale3 s,
-                         const Param& p, hipStream_t st, float* remote_colour = nullptr);
-int launch_debris_tiled(float* massFlux, float* velocityFlux, float* albedoFlux, Streams rng,
-                        int64_t N, const float* layers, const float* velocity,
-                        const float* albedoSource, float* remote0, const Dom& d, Scale3 s,
-                        const Param& p, hipStream_t st, float* remote_colour = nullptr);
-// both launches of a step overlapped on two internal streams forked from / joined into `st`
-// (`overwrite`: the flux planes hold stale values — SOIL_FLUX_OVERWRITE, soil_hip.h)
-int launch_pair_tiled(const soil_erosion_planes& P, Streams rng_fluvial, Streams rng_debris,
-                      int64_t N, float* remote0, const Dom& d, Scale3 s, const Param& p,
-                      hipStream_t st, bool overwrite, MigrateBox box_fluvial = MigrateBox{},
-                      MigrateBox box_debris = MigrateBox{}, const void* inbox_fluvial = nullptr,
-                      uint32_t n_fluvial = 0, const void* inbox_debris = nullptr, uint32_t n_debris = 0,
-                      const soil_colour_planes* colour = nullptr, float* remote_colour = nullptr);
-// (`colour`: the coloured step's planes — soil_particles_pair_colour; the colour flux planes are cleared first.
-// `remote_colour`: float[6], the NaN walkers' colour deposits for global (0, 0) on a slab — Remote0::colour)
+// One launch of `kind` (FLUVIAL, DEBRIS) in the tiled shape whatever N: from the streams' spawns (`inbox` null)
+// or from `n_in` handed-over records; leavers into `box` (none: dropped).
+int launch_pass_tiled(int kind, const Launch& L, const void* inbox = nullptr, uint32_t n_in = 0, MigrateBox box = {});
+// Both launches of a step overlapped on two internal streams forked from / joined into L.st.  With L.C: the
+// colour flux planes are cleared first and spent debris walkers are retired (TiledRun::retire_colour).
 // (inboxes: both launches start from handed-over records instead of the streams' spawns — the immigrants of
 // both kinds walked on side by side, slab runner's migrate mode; the pack pass of the step's spawn launches
 // stands)
-// the slab entry points of soil_hip.h on explicit streams (the slab runner's HIP back-end)
-int particles_fluvial_streams(const soil_erosion_planes& P, Streams rng, int64_t N, float* remote0,
-                              const Dom& d, Scale3 s, const Param& p, hipStream_t st);
-int particles_debris_streams(const soil_erosion_planes& P, Streams rng, int64_t N, float* remote0,
-                             const Dom& d, Scale3 s, const Param& p, hipStream_t st);
-int particles_pair_streams(const soil_erosion_planes& P, Streams rng_fluvial, Streams rng_debris, int64_t N,
-                           float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st, bool overwrite = false);
-// ... with colour (soil_particles_pair_colour_slab): each clears the colour flux plane(s) it adds to over local
-// rows [0, d.rows); `remote0` float[16] (or null), [8..13] the NaN walkers' colour for global (0, 0)
-int particles_fluvial_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rng, int64_t N,
-                                     float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st);
-int particles_debris_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rng, int64_t N,
-                                    float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st);
-int particles_pair_colour_streams(const soil_erosion_planes& P, const soil_colour_planes& C, Streams rf, Streams rd,
-                                  int64_t N, float* remote0, const Dom& d, Scale3 s, const Param& p, hipStream_t st,
-                                  bool overwrite = false);
+int launch_pair_tiled(const Launch& L, MigrateBox box_fluvial = {}, MigrateBox box_debris = {},
+                      const void* inbox_fluvial = nullptr, uint32_t n_fluvial = 0, const void* inbox_debris = nullptr,
+                      uint32_t n_debris = 0);
 
 }  // namespace soil

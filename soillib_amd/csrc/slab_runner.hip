@@ -837,14 +837,54 @@ struct HipOps {
   int64_t stale_cells = 0;
   int clear_stale() {
     if (!flux_stale) return SOIL_OK;
-    const size_t b = sizeof(float) * static_cast<size_t>(stale_cells);
-    SOIL_HIP(hipMemsetAsync(stale_planes.waterFlux, 0, b, main));
-    SOIL_HIP(hipMemsetAsync(stale_planes.massFlux, 0, b, main));
-    SOIL_HIP(hipMemsetAsync(stale_planes.velocityFlux, 0, 2 * b, main));
-    SOIL_HIP(hipMemsetAsync(stale_planes.debrisFlux, 0, b, main));
-    SOIL_HIP(hipMemsetAsync(stale_planes.debrisVelocityFlux, 0, 2 * b, main));
+    if (int rc = clear_flux(&stale_planes, nullptr, BOTH_KINDS, stale_cells, main); rc != SOIL_OK) return rc;
     flux_stale = false;
     return SOIL_OK;
+  }
+  // The launches and the cell phase of both tables (soil_slab_ops, soil_slab_colour_ops: `col` null / not null).
+  // `remote0`: float[8], or float[16] with colour ([8..13] the NaN walkers' colour, Remote0::colour).
+  Launch launch(const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rf, soil_rng* rd, int64_t N,
+                float* remote0, const Dom& d, const float scale[3], const soil_param* param) const {
+    return Launch{.P = p, .C = col, .fluvial = streams(rf), .debris = streams(rd), .N = N, .remote0 = remote0,
+                  .remote_colour = col && remote0 ? remote0 + 8 : nullptr, .d = d,
+                  .s = Scale3{scale[0], scale[1], scale[2]}, .p = *param, .st = main};
+  }
+  // one launch of `kind`; with colour it clears its own colour flux plane first
+  int single(int kind, const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rng, int64_t N,
+             float* remote0, const soil_domain* dom, const float scale[3], const soil_param* param) {
+    const Dom d = to_dom(dom);
+    if (int rc = check_domain(d); rc != SOIL_OK) return rc;
+    if (int rc = clear_stale(); rc != SOIL_OK) return rc;
+    last_pair = false;
+    const Launch L = launch(p, col, rng, rng, N, remote0, d, scale, param);
+    int rc = clear_flux(nullptr, col, kind, d.rows * d.W, main);
+    if (rc == SOIL_OK) rc = kind == FLUVIAL ? particles_fluvial(L) : particles_debris(L);
+    drew(rng);
+    return rc;
+  }
+  int pair(const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rf, soil_rng* rd, int64_t N,
+           float* remote0, const soil_domain* dom, const float scale[3], const soil_param* param) {
+    const Dom d = to_dom(dom);
+    if (int rc = check_domain(d); rc != SOIL_OK) return rc;
+    Launch L = launch(p, col, rf, rd, N, remote0, d, scale, param);
+    L.overwrite = flux_stale;
+    const int rc = particles_pair(L);
+    flux_stale = false;
+    last_pair = true;
+    drew(rf);
+    drew(rd);
+    return rc;
+  }
+  int cells(const soil_erosion_planes* p, const soil_colour_planes* col, const soil_domain* dom, const float scale[3],
+            const soil_param* param) {
+    if (dom->r1 <= dom->r0) return SOIL_OK;
+    const bool keep = lazy && last_pair;
+    if (keep) {
+      flux_stale = true;
+      stale_planes = *p;
+      stale_cells = dom->rows * dom->W;
+    }
+    return erode_cells_fused(p, col, dom, scale, param, keep ? SOIL_CELLS_KEEP_FLUX : 0, main);
   }
 };
 
@@ -880,40 +920,15 @@ int hip_seed(void* c, soil_rng* rng, int64_t N, uint64_t seed, uint64_t offset) 
 }
 int hip_fluvial(void* c, const soil_erosion_planes* p, soil_rng* rng, int64_t N, float* remote0,
                 const soil_domain* dom, const float scale[3], const soil_param* param) {
-  HIP_OPS(c);
-  const Dom d = to_dom(dom);
-  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
-  if (int rc = o.clear_stale(); rc != SOIL_OK) return rc;
-  o.last_pair = false;
-  const int rc = particles_fluvial_streams(*p, o.streams(rng), N, remote0, d, Scale3{scale[0], scale[1], scale[2]},
-                                           *param, o.main);
-  o.drew(rng);
-  return rc;
+  return static_cast<HipOps*>(c)->single(FLUVIAL, p, nullptr, rng, N, remote0, dom, scale, param);
 }
 int hip_debris(void* c, const soil_erosion_planes* p, soil_rng* rng, int64_t N, float* remote0,
                const soil_domain* dom, const float scale[3], const soil_param* param) {
-  HIP_OPS(c);
-  const Dom d = to_dom(dom);
-  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
-  if (int rc = o.clear_stale(); rc != SOIL_OK) return rc;
-  o.last_pair = false;
-  const int rc = particles_debris_streams(*p, o.streams(rng), N, remote0, d, Scale3{scale[0], scale[1], scale[2]},
-                                          *param, o.main);
-  o.drew(rng);
-  return rc;
+  return static_cast<HipOps*>(c)->single(DEBRIS, p, nullptr, rng, N, remote0, dom, scale, param);
 }
 int hip_pair(void* c, const soil_erosion_planes* p, soil_rng* rf, soil_rng* rd, int64_t N, float* remote0,
              const soil_domain* dom, const float scale[3], const soil_param* param) {
-  HIP_OPS(c);
-  const Dom d = to_dom(dom);
-  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
-  const int rc = particles_pair_streams(*p, o.streams(rf), o.streams(rd), N, remote0, d,
-                                        Scale3{scale[0], scale[1], scale[2]}, *param, o.main, o.flux_stale);
-  o.flux_stale = false;
-  o.last_pair = true;
-  o.drew(rf);
-  o.drew(rd);
-  return rc;
+  return static_cast<HipOps*>(c)->pair(p, nullptr, rf, rd, N, remote0, dom, scale, param);
 }
 // kind 0 / 1: one launch of that kind (soil_slab.h).  kind 2 with an inbox: both kinds' immigrants walked on
 // side by side (n_in = fluvial | debris << 32, the fluvial records first).  kind 2: both kinds' SPAWN launches overlapped, as
@@ -930,7 +945,7 @@ int hip_pass(void* c, int32_t kind, const soil_erosion_planes* p, soil_rng* rng,
   SOIL_REQUIRE(N > 0 && N <= 0x7fffffffll && d.H * d.W <= 0x7fffffffll && d.H < (1 << 24) && d.W < (1 << 24),
                "particles_pass: the tiled launch shape needs 1 .. 2^31 - 1 particles and cells, rows and columns below 2^24");
   SOIL_REQUIRE(n_in >= 0 && (kind == 2 || n_in <= 0xffffffffll) && cap >= 0 && cap <= 0xffffffffll, "particles_pass: bad record counts");
-  const Scale3 s3{scale[0], scale[1], scale[2]};
+  Launch L = o.launch(p, nullptr, rng, kind == 2 ? rng_debris : rng, N, remote0, d, scale, param);
   if (kind == 2) {
     SOIL_REQUIRE(rng_debris, "particles_pass: the overlapped launches need both kinds' streams");
     const uint32_t half = static_cast<uint32_t>(cap / 2);
@@ -942,11 +957,10 @@ int hip_pass(void* c, int32_t kind, const soil_erosion_planes* p, soil_rng* rng,
       const uint32_t n_f = static_cast<uint32_t>(n_in & 0xffffffffll), n_d = static_cast<uint32_t>(n_in >> 32);
       SOIL_REQUIRE(n_f > 0 && n_d > 0, "particles_pass: the overlapped immigrants' launches want walkers of both kinds");
       if (int rc = o.clear_stale(); rc != SOIL_OK) return rc;
-      return launch_pair_tiled(*p, o.streams(rng), o.streams(rng_debris), N, remote0, d, s3, *param, o.main, false, bf, bd,
-                               inbox, n_f, static_cast<const char*>(inbox) + static_cast<size_t>(n_f) * 64, n_d);
+      return launch_pair_tiled(L, bf, bd, inbox, n_f, static_cast<const char*>(inbox) + static_cast<size_t>(n_f) * 64, n_d);
     }
-    const int rc = launch_pair_tiled(*p, o.streams(rng), o.streams(rng_debris), N, remote0, d, s3, *param, o.main,
-                                     o.flux_stale, bf, bd);
+    L.overwrite = o.flux_stale;
+    const int rc = launch_pair_tiled(L, bf, bd);
     o.flux_stale = false;
     o.last_pair = true;
     o.drew(rng);
@@ -957,22 +971,13 @@ int hip_pass(void* c, int32_t kind, const soil_erosion_planes* p, soil_rng* rng,
   if (!inbox) o.last_pair = false;  // (a launch of immigrants behind the overlapped pair leaves the step a paired one)
   MigrateBox box;
   box.up = out_up, box.down = out_down, box.count = out_count, box.cap = static_cast<uint32_t>(cap);
-  const int rc = launch_pass_tiled(kind, *p, o.streams(rng), N, remote0, d, s3, *param, o.main, inbox,
-                                   static_cast<uint32_t>(n_in), box);
+  const int rc = launch_pass_tiled(kind, L, inbox, static_cast<uint32_t>(n_in), box);
   if (!inbox) o.drew(rng);
   return rc;
 }
 int hip_cells(void* c, const soil_erosion_planes* p, const soil_domain* dom, const float scale[3],
               const soil_param* param) {
-  HIP_OPS(c);
-  if (dom->r1 <= dom->r0) return SOIL_OK;
-  const bool keep = o.lazy && o.last_pair;
-  if (keep) {
-    o.flux_stale = true;
-    o.stale_planes = *p;
-    o.stale_cells = dom->rows * dom->W;
-  }
-  return soil_erode_cells_fused_ex(p, dom, scale, param, keep ? SOIL_CELLS_KEEP_FLUX : 0, o.main);
+  return static_cast<HipOps*>(c)->cells(p, nullptr, dom, scale, param);
 }
 int hip_extent(void* c, const float* plane, int64_t rows, int64_t row_floats, int64_t r0, int64_t r1,
                int32_t depth[2]) {
@@ -1031,52 +1036,19 @@ void* hip_stream(void* c, int32_t lane) {
 // the colour entries (soil_slab_colour_ops): the same HipOps, its streams and its lazy flux state
 int hipc_fluvial(void* c, const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rng, int64_t N,
                  float* remote0, const soil_domain* dom, const float scale[3], const soil_param* param) {
-  HIP_OPS(c);
-  const Dom d = to_dom(dom);
-  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
-  if (int rc = o.clear_stale(); rc != SOIL_OK) return rc;
-  o.last_pair = false;
-  const int rc = particles_fluvial_colour_streams(*p, *col, o.streams(rng), N, remote0, d,
-                                                  Scale3{scale[0], scale[1], scale[2]}, *param, o.main);
-  o.drew(rng);
-  return rc;
+  return static_cast<HipOps*>(c)->single(FLUVIAL, p, col, rng, N, remote0, dom, scale, param);
 }
 int hipc_debris(void* c, const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rng, int64_t N,
                 float* remote0, const soil_domain* dom, const float scale[3], const soil_param* param) {
-  HIP_OPS(c);
-  const Dom d = to_dom(dom);
-  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
-  if (int rc = o.clear_stale(); rc != SOIL_OK) return rc;
-  o.last_pair = false;
-  const int rc = particles_debris_colour_streams(*p, *col, o.streams(rng), N, remote0, d,
-                                                 Scale3{scale[0], scale[1], scale[2]}, *param, o.main);
-  o.drew(rng);
-  return rc;
+  return static_cast<HipOps*>(c)->single(DEBRIS, p, col, rng, N, remote0, dom, scale, param);
 }
 int hipc_pair(void* c, const soil_erosion_planes* p, const soil_colour_planes* col, soil_rng* rf, soil_rng* rd,
               int64_t N, float* remote0, const soil_domain* dom, const float scale[3], const soil_param* param) {
-  HIP_OPS(c);
-  const Dom d = to_dom(dom);
-  if (int rc = check_domain(d); rc != SOIL_OK) return rc;
-  const int rc = particles_pair_colour_streams(*p, *col, o.streams(rf), o.streams(rd), N, remote0, d,
-                                               Scale3{scale[0], scale[1], scale[2]}, *param, o.main, o.flux_stale);
-  o.flux_stale = false;
-  o.last_pair = true;
-  o.drew(rf);
-  o.drew(rd);
-  return rc;
+  return static_cast<HipOps*>(c)->pair(p, col, rf, rd, N, remote0, dom, scale, param);
 }
 int hipc_cells(void* c, const soil_erosion_planes* p, const soil_colour_planes* col, const soil_domain* dom,
                const float scale[3], const soil_param* param) {
-  HIP_OPS(c);
-  if (dom->r1 <= dom->r0) return SOIL_OK;
-  const bool keep = o.lazy && o.last_pair;
-  if (keep) {
-    o.flux_stale = true;
-    o.stale_planes = *p;
-    o.stale_cells = dom->rows * dom->W;
-  }
-  return soil_erode_cells_fused_colour(p, col, dom, scale, param, keep ? SOIL_CELLS_KEEP_FLUX : 0, o.main);
+  return static_cast<HipOps*>(c)->cells(p, col, dom, scale, param);
 }
 
 }  // namespace
