@@ -363,6 +363,43 @@ int soil_erode_step_ex(const soil_erosion_planes* planes, soil_rng* rng, int64_t
                        uint64_t step_index, int64_t H, int64_t W, const float scale[3],
                        const soil_param* param, int flags, void* stream);
 
+/* ------------------------------------------ erosion: batches of models */
+
+/* A batch: B independent whole-grid models of one shape (H, W), N walkers each, one `param`, one `scale`, one
+ * step_index, one seed per model.  Every pointer of `planes` is model 0 of B consecutive models: model b of a
+ * plane of C channels starts at element b * H * W * C (rainfall and uplift too: they are per model).  `seeds`
+ * is a host array of B values, copied before the call returns.  A batch leaves model b holding what the
+ * single-model entry leaves on that model alone with seed = seeds[b] (soil_erode_step; the streams of model b
+ * at (seeds[b], n, step_index * N), the debris launch two draws on): the same trajectories, a NaN walker's
+ * deposits in cell (0, 0) of its own model, nothing of one model in another, particle steps added to
+ * soil_particle_steps' counter; the fp32 sums of a flux cell may be added up in another order.  The
+ * particles are launched in the single model's direct or staged shape (soil_set_particle_mode: staged for
+ * N >= 1024, direct below; an N that gets the tiled shape alone runs staged), exact arithmetic, every walker
+ * walked to the end; each launch covers all B models (grid.y = model, at most 65535 per launch), one after
+ * the other on `stream`.  SOIL_ERR_INVALID_ARGUMENT for B < 1, H or W < 1, N < 0, null seeds with N > 0, a
+ * size whose byte offsets overflow (or N >= 2^31).
+ *
+ * One erosion step of every model: soil_particles_batch, then soil_erode_cells_fused_batch with flags 0.
+ * The flux planes are zero on entry and on exit; reads `layers`, writes `layers_next` (the caller swaps).
+ * Algorithmic bytes: the particle launches' (per walker step one 16-byte packed-field gather and, fluvial,
+ * 4 bytes of waterHeight, plus 16 / 12 bytes of flux atomics per cell entered; the staged shape's pack pass
+ * 28 bytes per cell and kind) and 112 bytes per cell of the cell phase. */
+int soil_erode_step_batch(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W, int64_t N,
+                          const uint64_t* seeds, uint64_t step_index, const float scale[3],
+                          const soil_param* param, void* stream);
+/* Both particle launches of a batch step (fluvial, then debris), adding into the five flux planes of every
+ * model as soil_particles_pair_slab adds into one model's; reads layers, rainfall, waterHeight, velocity and
+ * debrisVelocity; the cell phase's output planes are not touched.  N == 0 launches nothing. */
+int soil_particles_batch(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W, int64_t N,
+                         const uint64_t* seeds, uint64_t step_index, const float scale[3],
+                         const soil_param* param, void* stream);
+/* The fused cell phase of every model of a batch, bit-identical per model to soil_erode_cells_fused_ex on that
+ * model's planes with the same flags (whole grid; every model has the grid's edges, no neighbour read crosses
+ * into another model).  One launch per 65535 models.  112 algorithmic bytes per cell, 84 with
+ * SOIL_CELLS_KEEP_FLUX. */
+int soil_erode_cells_fused_batch(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W,
+                                 const float scale[3], const soil_param* param, int flags, void* stream);
+
 /* ------------------------------------------ erosion: the coloured step */
 
 /* The colour planes of one erosion model: (rows,W,3) float32, a vec3 per cell (AoS), the

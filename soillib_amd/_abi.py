@@ -140,6 +140,12 @@ SIGNATURES = {
                                       i64, i64, F3, C.POINTER(Param), cint, vp]),
     "soil_particles_pair_colour_slab": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), vp, vp, i64, vp,
                                                C.POINTER(Domain), F3, C.POINTER(Param), cint, vp]),
+    "soil_erode_step_batch": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, i64, C.POINTER(u64), u64, F3,
+                                     C.POINTER(Param), vp]),
+    "soil_particles_batch": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, i64, C.POINTER(u64), u64, F3,
+                                    C.POINTER(Param), vp]),
+    "soil_erode_cells_fused_batch": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, F3, C.POINTER(Param), cint,
+                                            vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),

@@ -62,6 +62,13 @@ int step_counter(unsigned long long** out);
 int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* colour, const soil_domain* dom,
                       const float scale[3], const soil_param* param, int flags, void* stream);
 
+// The batch entries' checks of their sizes (soil_hip.h, soil_*_batch): SOIL_ERR_INVALID_ARGUMENT with a message
+// naming `what` for B < 1, an empty grid, N < 0, null seeds with N > 0, byte offsets that overflow
+// (erosion_particles.hip).  The cell phase of a batch (erosion_cells.hip).
+int check_batch(int64_t B, int64_t H, int64_t W, int64_t N, const uint64_t* seeds, const char* what);
+int erode_cells_fused_batch(const soil_erosion_planes* pl, int64_t B, int64_t H, int64_t W, const float scale[3],
+                            const soil_param* param, int flags, hipStream_t st);
+
 // Launch shape of the per-cell kernels: threads along the contiguous axis, and a
 // work-group walks a band of kRowBand consecutive rows (SOIL_ROW_LOOP).  A 64-bit
 // n / W, n % W per cell costs more than most of these kernels' arithmetic, and with

@@ -19,6 +19,10 @@
 //     wave and the waves of an XCD share cache lines for most of their walk.
 // The reference's launch shape (thread n = particle n, direct stencil gathers)
 // is kept as `direct` mode for ablation (soil_set_particle_mode).
+#include <cstring>
+#include <map>
+#include <thread>
+
 #include "particles_common.hpp"
 
 namespace soil {
@@ -365,8 +369,7 @@ __global__ void __launch_bounds__(kPBlock)
 }
 
 // pass 2: exclusive scan of the tile counts (one work-group; tiles <= a few 1e5)
-__global__ void __launch_bounds__(1024)
-    k_tile_scan(uint32_t* start, const uint32_t* count, int64_t tiles) {
+__device__ __forceinline__ void tile_scan_group(uint32_t* start, const uint32_t* count, int64_t tiles) {
   __shared__ uint32_t part[1024];
   const int tid = threadIdx.x;
   const int64_t chunk = (tiles + 1023) / 1024;
@@ -387,6 +390,10 @@ __global__ void __launch_bounds__(1024)
     run += count[i];
   }
   if (tid == 1023) start[tiles] = part[1023];  // total number of owned particles
+}
+__global__ void __launch_bounds__(1024)
+    k_tile_scan(uint32_t* start, const uint32_t* count, int64_t tiles) {
+  tile_scan_group(start, count, tiles);
 }
 
 // pass 3: drop every owned spawn point into its tile's range
@@ -463,6 +470,22 @@ static int materialise(const Streams& st, int64_t N, hipStream_t s) {
   if (!st.uniform) return SOIL_OK;
   if (!st.rng) return fail(SOIL_ERR_INVALID_ARGUMENT, "uniform streams on a small launch need a tensor to seed");
   return soil_rng_seed(st.rng, N, st.seed, st.offset, s);
+}
+
+int check_batch(int64_t B, int64_t H, int64_t W, int64_t N, const uint64_t* seeds, const char* what) {
+  const std::string w(what);
+  SOIL_REQUIRE(B >= 1, w + ": a batch needs at least one model (B >= 1)");
+  SOIL_REQUIRE(H >= 1 && W >= 1, w + ": empty grid (H and W must be >= 1)");
+  SOIL_REQUIRE(N >= 0, w + ": negative particle count");
+  SOIL_REQUIRE(N == 0 || seeds, w + ": null seeds with N > 0");
+  // the largest arrays of a batch: B x H x W float4 (the staged shape's packed fields), B x N float2 twice;
+  // per-model spawn counts are 32-bit
+  int64_t cells = 0, t = 0;
+  const bool overflow = __builtin_mul_overflow(H, W, &cells) || __builtin_mul_overflow(cells, B, &t) ||
+                        __builtin_mul_overflow(t, int64_t{16}, &t) || __builtin_mul_overflow(N, B, &t) ||
+                        __builtin_mul_overflow(t, int64_t{16}, &t) || N > 0x7fffffffll;
+  SOIL_REQUIRE(!overflow, w + ": B, H, W, N too large (byte offsets overflow)");
+  return SOIL_OK;
 }
 
 int clear_flux(const soil_erosion_planes* P, const soil_colour_planes* C, int kind, int64_t cells, hipStream_t st) {
@@ -581,6 +604,256 @@ int particles_debris(const Launch& L) {
   }
   SOIL_LAUNCH_CHECK();
   return SOIL_OK;
+}
+
+// ---- batches: B independent models of one (H, W) grid ------------------------------------
+//
+// soil_particles_batch (soil_hip.h).  Every plane holds B whole-grid models one after the other (model b of
+// a plane of C channels starts at element b * H * W * C) and grid.y is the model: a lane walks walker n of
+// model blockIdx.y through trace_fluvial / trace_debris on that model's planes, so what it deposits stays in
+// its model, a NaN walker's (0, 0) included.  The streams are uniform (Streams): walker n of model b draws
+// from (seeds[b], n, offset), the state soil_erode_step seeds into its tensor for that model alone.  The host
+// launches at most kMaxGridY models at a time, every pointer advanced past the models launched before.
+
+constexpr int64_t kMaxGridY = 65535;
+
+__device__ __forceinline__ int64_t model_base(int64_t cells) { return static_cast<int64_t>(blockIdx.y) * cells; }
+__device__ __forceinline__ FluvialPlanes model_of(FluvialPlanes P, int64_t cells) {
+  const int64_t m = model_base(cells);
+  P.waterFlux += m, P.massFlux += m, P.velocityFlux += 2 * m, P.waterSource += m, P.waterHeight += m;
+  return P;
+}
+__device__ __forceinline__ DebrisPlanes model_of(DebrisPlanes P, int64_t cells) {
+  const int64_t m = model_base(cells);
+  P.massFlux += m, P.velocityFlux += 2 * m;
+  return P;
+}
+__device__ __forceinline__ DirectFields model_of(DirectFields F, int64_t cells) {
+  const int64_t m = model_base(cells);
+  F.layers += m, F.velocity += m;
+  return F;
+}
+__device__ __forceinline__ Streams model_streams(const uint64_t* __restrict__ seeds, uint64_t offset) {
+  return Streams{nullptr, true, seeds[blockIdx.y], offset};
+}
+
+// direct: thread n = walker n of model blockIdx.y (every spawn lies in the whole grid: no ownership test)
+__global__ void __launch_bounds__(kPBlock)
+    k_fluvial_direct_batch(FluvialPlanes P, const uint64_t* __restrict__ seeds, uint64_t offset, int64_t N,
+                           DirectFields F, Param param) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
+  if (n >= N) return;
+  const int64_t cells = F.d.H * F.d.W;
+  const float2 pos = spawn_position(model_streams(seeds, offset), n, F.d);
+  trace_fluvial(model_of(F, cells), model_of(P, cells), pos.x, pos.y, N, F.d, F.s, param);
+}
+
+__global__ void __launch_bounds__(kPBlock)
+    k_debris_direct_batch(DebrisPlanes P, const uint64_t* __restrict__ seeds, uint64_t offset, int64_t N,
+                          DirectFields F, Param param) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
+  if (n >= N) return;
+  const int64_t cells = F.d.H * F.d.W;
+  const float2 pos = spawn_position(model_streams(seeds, offset), n, F.d);
+  trace_debris(model_of(F, cells), model_of(P, cells), pos.x, pos.y, N, F.d, F.s, param);
+}
+
+// staged: k_pack_fields .. k_*_sorted per model; model b's spawn and sorted arrays start at b * N, its tile
+// counts, fills and starts at b * (tiles + 1)
+__global__ void __launch_bounds__(kPBlock)
+    k_pack_fields_batch(float4* __restrict__ p4, const float2* __restrict__ layers,
+                        const float2* __restrict__ velocity, Dom d, Scale3 s, float exitSlope) {
+  const int64_t cells = d.H * d.W;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
+  if (t >= cells) return;
+  const int64_t m = model_base(cells);
+  const float2 g = glocal(layers + m, d, s, t / d.W, t % d.W, exitSlope);
+  const float2 v = velocity[m + t];
+  p4[m + t] = make_float4(g.x, g.y, v.x, v.y);
+}
+
+__global__ void __launch_bounds__(kPBlock)
+    k_spawn_count_batch(float2* __restrict__ spawn, uint32_t* __restrict__ count,
+                        const uint64_t* __restrict__ seeds, uint64_t offset, int64_t N, Dom d, int64_t tiles_w,
+                        int64_t tiles) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
+  if (n >= N) return;
+  const float2 pos = spawn_position(model_streams(seeds, offset), n, d);
+  spawn[model_base(N) + n] = pos;
+  atomicAdd(&count[model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w)], 1u);
+}
+
+// one work-group per model
+__global__ void __launch_bounds__(1024)
+    k_tile_scan_batch(uint32_t* start, const uint32_t* count, int64_t tiles) {
+  const int64_t m = static_cast<int64_t>(blockIdx.x) * (tiles + 1);
+  tile_scan_group(start + m, count + m, tiles);
+}
+
+__global__ void __launch_bounds__(kPBlock)
+    k_spawn_scatter_batch(float2* __restrict__ sorted, uint32_t* __restrict__ fill,
+                          const uint32_t* __restrict__ start, const float2* __restrict__ spawn, int64_t N, Dom d,
+                          int64_t tiles_w, int64_t tiles) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
+  if (n >= N) return;
+  const float2 pos = spawn[model_base(N) + n];
+  const int64_t tile = model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w);
+  sorted[model_base(N) + start[tile] + atomicAdd(&fill[tile], 1u)] = pos;
+}
+
+__global__ void __launch_bounds__(kPBlock)
+    k_fluvial_sorted_batch(FluvialPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
+                           int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
+  const int64_t t = sorted_slot(start + model_base(tiles + 1) + tiles);
+  if (t < 0) return;
+  const int64_t cells = d.H * d.W;
+  const float2 pos = sorted[model_base(N) + t];
+  trace_fluvial(PackedFields{F.p4 + model_base(cells)}, model_of(P, cells), pos.x, pos.y, N, d, s, param);
+}
+
+__global__ void __launch_bounds__(kPBlock)
+    k_debris_sorted_batch(DebrisPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
+                          int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
+  const int64_t t = sorted_slot(start + model_base(tiles + 1) + tiles);
+  if (t < 0) return;
+  const int64_t cells = d.H * d.W;
+  const float2 pos = sorted[model_base(N) + t];
+  trace_debris(PackedFields{F.p4 + model_base(cells)}, model_of(P, cells), pos.x, pos.y, N, d, s, param);
+}
+
+// The seeds of a batch reach the device through a pinned buffer of the host thread (the caller's array may go
+// as soon as the call returns): before it is written again, the copy queued from it the call before has been
+// made — which lets the host queue one batch ahead of the device, and not further.
+namespace {
+const std::thread::id g_seed_loader = std::this_thread::get_id();
+struct SeedStaging {
+  void* host = nullptr;
+  size_t bytes = 0;
+  hipEvent_t copied = nullptr;
+  ~SeedStaging() {  // a thread's buffer goes with it (not the loading thread's: HIP may be gone by then)
+    if (std::this_thread::get_id() == g_seed_loader) return;
+    if (copied) (void)hipEventSynchronize(copied), (void)hipEventDestroy(copied);
+    if (host) (void)hipHostFree(host);
+    (void)hipGetLastError();
+  }
+};
+}  // namespace
+
+static int upload_seeds(uint64_t* dst, const uint64_t* seeds, int64_t B, hipStream_t st) {
+  static thread_local std::map<int, SeedStaging> staging;  // device -> staging
+  int dev = 0;
+  SOIL_HIP(hipGetDevice(&dev));
+  SeedStaging& u = staging[dev];
+  const size_t bytes = sizeof(uint64_t) * static_cast<size_t>(B);
+  if (u.copied) SOIL_HIP(hipEventSynchronize(u.copied));
+  else SOIL_HIP(hipEventCreateWithFlags(&u.copied, hipEventDisableTiming));
+  if (u.bytes < bytes) {
+    if (u.host) SOIL_HIP(hipHostFree(u.host));
+    u.host = nullptr;
+    u.bytes = 0;
+    SOIL_HIP(hipHostMalloc(&u.host, bytes, hipHostMallocDefault));
+    u.bytes = bytes;
+  }
+  std::memcpy(u.host, seeds, bytes);
+  SOIL_HIP(hipMemcpyAsync(dst, u.host, bytes, hipMemcpyHostToDevice, st));
+  SOIL_HIP(hipEventRecord(u.copied, st));
+  return SOIL_OK;
+}
+
+namespace {
+// One launch of a batch: the planes, the device seeds, the first draw of the kind's streams.
+struct BatchLaunch {
+  const soil_erosion_planes* P;
+  int64_t B, N;
+  const uint64_t* seeds;
+  uint64_t offset;
+  Dom d;
+  Scale3 s;
+  Param p;
+  hipStream_t st;
+};
+// the staged shape's scratch for all B models (the workspace's; valid until the next batch launch)
+struct BatchScratch {
+  float4* p4;
+  float2 *spawn, *sorted;
+  uint32_t *count, *fill, *start;  // count and fill adjacent
+  int64_t tiles_w, tiles;
+};
+}  // namespace
+
+static int launch_batch(int kind, const BatchLaunch& L, const BatchScratch& w, bool staged) {
+  const int64_t N = L.N, cells = L.d.H * L.d.W;
+  unsigned long long* steps = nullptr;
+  if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& Q = *L.P;
+  const bool fluvial = kind == FLUVIAL;
+  const uint64_t offset = fluvial ? L.offset : L.offset + 2;  // the debris launch: two draws on
+  const int64_t cnt = w.tiles + 1;
+  if (staged) SOIL_HIP(hipMemsetAsync(w.count, 0, 2 * sizeof(uint32_t) * static_cast<size_t>(L.B * cnt), L.st));
+  for (int64_t b0 = 0; b0 < L.B; b0 += kMaxGridY) {
+    const unsigned nb = static_cast<unsigned>(L.B - b0 < kMaxGridY ? L.B - b0 : kMaxGridY);
+    const int64_t m = b0 * cells;
+    const uint64_t* seeds = L.seeds + b0;
+    const float2* layers = reinterpret_cast<const float2*>(Q.layers) + m;
+    const float2* velocity = reinterpret_cast<const float2*>(fluvial ? Q.velocity : Q.debrisVelocity) + m;
+    const FluvialPlanes PF{Q.waterFlux + m, Q.massFlux + m, Q.velocityFlux + 2 * m, nullptr, Q.rainfall + m,
+                           Q.waterHeight + m, nullptr, nullptr, steps};
+    const DebrisPlanes PD{Q.debrisFlux + m, Q.debrisVelocityFlux + 2 * m, nullptr, nullptr, nullptr, steps};
+    const dim3 walkers(blocks_for(N, kPBlock), nb);
+    if (!staged) {
+      const DirectFields F{layers, velocity, L.d, L.s, L.p.exitSlope};
+      if (fluvial) k_fluvial_direct_batch<<<walkers, kPBlock, 0, L.st>>>(PF, seeds, offset, N, F, L.p);
+      else k_debris_direct_batch<<<walkers, kPBlock, 0, L.st>>>(PD, seeds, offset, N, F, L.p);
+      SOIL_LAUNCH_CHECK();
+      continue;
+    }
+    float4* p4 = w.p4 + m;
+    float2 *spawn = w.spawn + b0 * N, *sorted = w.sorted + b0 * N;
+    uint32_t *count = w.count + b0 * cnt, *fill = w.fill + b0 * cnt, *start = w.start + b0 * cnt;
+    k_pack_fields_batch<<<dim3(blocks_for(cells, kPBlock), nb), kPBlock, 0, L.st>>>(p4, layers, velocity, L.d, L.s,
+                                                                                     L.p.exitSlope);
+    k_spawn_count_batch<<<walkers, kPBlock, 0, L.st>>>(spawn, count, seeds, offset, N, L.d, w.tiles_w, w.tiles);
+    k_tile_scan_batch<<<nb, 1024, 0, L.st>>>(start, count, w.tiles);
+    k_spawn_scatter_batch<<<walkers, kPBlock, 0, L.st>>>(sorted, fill, start, spawn, N, L.d, w.tiles_w, w.tiles);
+    const dim3 traced(blocks_for(N, kPBlock) + 8, nb);
+    if (fluvial)
+      k_fluvial_sorted_batch<<<traced, kPBlock, 0, L.st>>>(PF, sorted, start, w.tiles, N, PackedFields{p4}, L.d, L.s,
+                                                            L.p);
+    else
+      k_debris_sorted_batch<<<traced, kPBlock, 0, L.st>>>(PD, sorted, start, w.tiles, N, PackedFields{p4}, L.d, L.s,
+                                                           L.p);
+    SOIL_LAUNCH_CHECK();
+  }
+  return SOIL_OK;
+}
+
+int particles_batch(const soil_erosion_planes* P, int64_t B, int64_t H, int64_t W, int64_t N, const uint64_t* seeds,
+                    uint64_t step_index, const float scale[3], const soil_param* param, hipStream_t st) {
+  if (N == 0) return SOIL_OK;
+  const bool staged = use_staged(N);  // the single model's rule; what would be tiled alone runs staged
+  const Dom d = full_domain(H, W);
+  BatchScratch w{};
+  w.tiles_w = (W + kTile - 1) / kTile;
+  w.tiles = w.tiles_w * ((H + kTile - 1) / kTile);
+  auto align = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
+  const size_t b_seeds = align(sizeof(uint64_t) * static_cast<size_t>(B));
+  const size_t b_p4 = staged ? align(sizeof(float4) * static_cast<size_t>(B * H * W)) : 0;
+  const size_t b_pos = staged ? align(sizeof(float2) * static_cast<size_t>(B * N)) : 0;
+  const size_t b_cnt = staged ? align(sizeof(uint32_t) * static_cast<size_t>(B * (w.tiles + 1))) : 0;
+  void* base = nullptr;
+  if (int rc = workspace_get(11, b_seeds + b_p4 + 2 * b_pos + 3 * b_cnt, &base); rc != SOIL_OK) return rc;
+  char* c = static_cast<char*>(base);
+  uint64_t* seeds_dev = reinterpret_cast<uint64_t*>(c);      c += b_seeds;
+  w.p4 = reinterpret_cast<float4*>(c);                       c += b_p4;
+  w.spawn = reinterpret_cast<float2*>(c);                    c += b_pos;
+  w.sorted = reinterpret_cast<float2*>(c);                   c += b_pos;
+  w.count = reinterpret_cast<uint32_t*>(c);                  c += b_cnt;
+  w.fill = w.count + B * (w.tiles + 1);                      c += b_cnt;
+  w.start = reinterpret_cast<uint32_t*>(c);
+  if (int rc = upload_seeds(seeds_dev, seeds, B, st); rc != SOIL_OK) return rc;
+  const BatchLaunch L{P, B, N, seeds_dev, step_index * static_cast<uint64_t>(N), d, s3p(scale), *param, st};
+  if (int rc = launch_batch(FLUVIAL, L, w, staged); rc != SOIL_OK) return rc;
+  return launch_batch(DEBRIS, L, w, staged);
 }
 
 int particles_pair(const Launch& L) {
@@ -792,6 +1065,19 @@ int soil_particles_pair_colour_slab(const soil_erosion_planes* planes, const soi
                                .remote_colour = remote0 ? remote0 + 8 : nullptr, .d = d, .s = s3p(scale),
                                .p = *param, .st = as_stream(stream),
                                .overwrite = (flags & SOIL_FLUX_OVERWRITE) != 0});
+}
+
+int soil_particles_batch(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W, int64_t N,
+                         const uint64_t* seeds, uint64_t step_index, const float scale[3], const soil_param* param,
+                         void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && scale && param, "particles_batch: null argument");
+  if (int rc = check_batch(B, H, W, N, seeds, "particles_batch"); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
+                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
+               "particles_batch: null plane");
+  return particles_batch(planes, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
 }
 
 int soil_particle_steps(uint64_t* total, int reset, void* stream) {

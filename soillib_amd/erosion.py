@@ -19,6 +19,16 @@ The model may be a row slab of a larger grid (see soillib_amd.parallel).
 step (include/soil_hip.h, soil_colour_planes) through every phase:
 `step()` is soil_erode_step_colour, `step_unfused()` the same step through the
 reference ops with their albedo arguments.  Whole grids on one GPU only.
+
+`ErosionBatch(B, H, W, scale, param, n_particles, seeds)` holds B independent
+models of one shape with one seed each, the planes of `ErosionModel` as
+(B, H, W[, C]) tensors, model-major.  `step()` (soil_erode_step_batch) steps every
+model at once and leaves model b where `ErosionModel(..., seed=seeds[b]).step()`
+leaves that model alone, up to the fp32 summation order of the flux planes: a
+few launches for the whole batch where B models take B times their own handful
+(DESIGN.md 3.5).  `particles()` and `cells_fused()` run the two phases
+separately; `model_planes(b)` copies one model's planes to the host.  Physics
+planes only, whole grids, one shared param.
 """
 import ctypes as C
 import os
@@ -222,3 +232,94 @@ class ErosionModel:
         for name in ("waterFlux", "massFlux", "velocityFlux", "debrisFlux", "debrisVelocityFlux"):
             silt.set(getattr(self, name), 0.0)  # silt.set(track.*, 0)
         self.step_index += 1
+
+
+class ErosionBatch:
+    """B independent whole-grid erosion models of one (H, W) shape, stepped together (include/soil_hip.h:
+    soil_erode_step_batch).  Every plane of ErosionModel is a (B, H, W[, C]) GPU tensor, zeroed here; model b
+    has its own terrain, rainfall, uplift and seed, and shares N, scale and param with the others."""
+
+    PLANES_1 = ErosionModel.PLANES_1
+    PLANES_2 = ErosionModel.PLANES_2
+
+    def __init__(self, B, H, W, scale, param, n_particles, seeds):
+        self.B, self.H, self.W = int(B), int(H), int(W)
+        self.seeds = [int(v) for v in seeds]
+        if len(self.seeds) != self.B:
+            raise ValueError("ErosionBatch: %d seeds for %d models" % (len(self.seeds), self.B))
+        if self.B < 1 or self.H < 1 or self.W < 1:
+            raise ValueError("ErosionBatch: B, H and W must be >= 1")
+        self.scale = [float(v) for v in scale]
+        self.param = param
+        self.N = int(n_particles)
+        self.step_index = 0
+        shape = (self.B, self.H, self.W)
+        alloc = lambda *dims: silt.tensor(silt.float32, silt.shape(*dims), silt.gpu)
+        self.layers = alloc(*shape, 2)
+        self.layers_next = alloc(*shape, 2)
+        for name in self.PLANES_1:
+            setattr(self, name, alloc(*shape))
+        for name in self.PLANES_2:
+            setattr(self, name, alloc(*shape, 2))
+        for name in ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2:
+            silt.set(getattr(self, name), 0.0)
+        self._seeds = (C.c_uint64 * self.B)(*self.seeds)
+
+    def _planes(self):
+        p = _abi.ErosionPlanes()
+        for name in _abi._PLANES:
+            setattr(p, name, getattr(self, name).ptr)
+        return p
+
+    def _scale(self):
+        return _abi.vec(self.scale, 3)
+
+    def set_layers(self, layers_tensor):
+        """Copy a (B, H, W, 2) tensor of (bedrock, sediment) into the batch."""
+        if tuple(layers_tensor.shape) != (self.B, self.H, self.W, 2):
+            raise ValueError("set_layers needs a (%d, %d, %d, 2) tensor, got %s" % (
+                self.B, self.H, self.W, tuple(layers_tensor.shape)))
+        silt.set(self.layers, layers_tensor)
+
+    def particles(self):
+        """Both particle launches of this step for every model, adding into the flux planes
+        (soil_particles_batch)."""
+        planes = self._planes()
+        _abi.check(_abi.lib().soil_particles_batch(
+            C.byref(planes), self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(),
+            self.param._ref(), _abi.stream()))
+
+    def cells_fused(self, keep_flux=False):
+        """Fused cell phase of every model (soil_erode_cells_fused_batch); `keep_flux`: the flux planes are
+        left as they are (SOIL_CELLS_KEEP_FLUX)."""
+        planes = self._planes()
+        _abi.check(_abi.lib().soil_erode_cells_fused_batch(
+            C.byref(planes), self.B, self.H, self.W, self._scale(), self.param._ref(),
+            _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0, _abi.stream()))
+
+    def swap_layers(self):
+        self.layers, self.layers_next = self.layers_next, self.layers
+
+    def step(self):
+        """One erosion step of every model (soil_erode_step_batch); swaps the layer buffers."""
+        planes = self._planes()
+        _abi.check(_abi.lib().soil_erode_step_batch(
+            C.byref(planes), self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(),
+            self.param._ref(), _abi.stream()))
+        self.swap_layers()
+        self.step_index += 1
+
+    def model_plane(self, name, b):
+        """Plane `name` of model b as a host numpy array, (H, W[, C])."""
+        if not 0 <= b < self.B:
+            raise IndexError("model %d of a batch of %d" % (b, self.B))
+        t = getattr(self, name)
+        dims = tuple(t.shape)[1:]
+        per = t.nbytes() // self.B
+        view = silt.tensor.from_device(t.ptr + b * per, t.type, dims, keepalive=t)
+        return view.cpu().numpy()
+
+    def model_planes(self, b):
+        """Every plane of model b as host numpy arrays, by name."""
+        return {name: self.model_plane(name, b)
+                for name in ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2}

@@ -1,0 +1,124 @@
+#!/usr/bin/env python
+"""A batch of B independent erosion models stepped together (include/soil_hip.h: soil_erode_step_batch,
+ErosionBatch) against the same B models stepped one after the other through
+ErosionModel.step() on the same stream, both timed in one process.  N = cells / 8 (8192 at 256^2), maxage 256
+and the script's parameters (example/erosion_gpu.py), every model its own noise terrain and seed.
+
+One JSON line per (size, B): ms per batch step and per model-step (median over --steps device-event-timed
+steps after --warmup), the sequential loop's ms per model-step, and seq / batch.  --no-seq leaves the loop
+out (the profiling run: rocprofv3 --kernel-trace --stats)."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from soillib_amd import _abi, silt, soil  # noqa: E402
+from soillib_amd.erosion import ErosionBatch, ErosionModel  # noqa: E402
+from util import script_param  # noqa: E402
+
+DEFAULT = "256:1,256:8,256:64,256:256,512:1,512:8,512:32,1024:1,1024:8,1024:32"
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--configs", default=DEFAULT, help="size:B,size:B,...")
+ap.add_argument("--steps", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--no-seq", action="store_true")
+ap.add_argument("--out", default=None, help="also append the lines to this file")
+args = ap.parse_args()
+lib = _abi.lib()
+param = script_param(soil.param_t())
+param.maxage = 256
+
+
+class Events:
+    def __init__(self):
+        self.ev = []
+
+    def record(self):
+        e = C.c_void_p()
+        _abi.check(lib.soil_event_create(C.byref(e)))
+        _abi.check(lib.soil_event_record(e, _abi.stream()))
+        self.ev.append(e)
+
+    def intervals(self):
+        _abi.check(lib.soil_stream_synchronize(_abi.stream()))
+        out = []
+        for a, b in zip(self.ev[:-1], self.ev[1:]):
+            ms = C.c_float()
+            _abi.check(lib.soil_event_elapsed_ms(a, b, C.byref(ms)))
+            out.append(ms.value)
+        for e in self.ev:
+            lib.soil_event_destroy(e)
+        return out
+
+
+def terrain_into(layers_ptr, S, b):
+    """layers[..., 0] = noise of seed 3 + b, layers[..., 1] = 0 (on the device)."""
+    p = soil.noise_t()
+    p.seed = 3.0 + b
+    p.ext = [S, S]
+    bed = soil.noise(silt.shape(S, S), p, host=silt.gpu)
+    _abi.check(lib.soil_layers_from_planes(C.c_void_p(layers_ptr), bed.c_ptr, None, S * S, _abi.stream()))
+
+
+def timed(step, n):
+    ev = Events()
+    ev.record()
+    for _ in range(n):
+        step()
+        ev.record()
+    return statistics.median(ev.intervals())
+
+
+def run(S, B):
+    N = S * S // 8
+    scale = (20.0 / S, 20.0 / S, 4.0)
+    seeds = [1000 + b for b in range(B)]
+    batch = ErosionBatch(B, S, S, scale, param, N, seeds)
+    for b in range(B):
+        terrain_into(batch.layers.ptr + b * S * S * 8, S, b)
+    silt.set(batch.rainfall, 1.0)
+    for _ in range(args.warmup):
+        batch.step()
+    ms_batch = timed(batch.step, args.steps)
+    line = {"size": S, "B": B, "N": N, "maxage": param.maxage, "steps": args.steps, "warmup": args.warmup,
+            "batch_ms_per_step": round(ms_batch, 4), "batch_ms_per_model_step": round(ms_batch / B, 5)}
+    del batch
+    if not args.no_seq:
+        models = []
+        for b in range(B):
+            m = ErosionModel(S, S, scale, param, N, seed=seeds[b])
+            terrain_into(m.layers.ptr, S, b)
+            silt.set(m.rainfall, 1.0)
+            models.append(m)
+
+        def one_round():
+            for m in models:
+                m.step()
+        for _ in range(args.warmup):
+            one_round()
+        ms_seq = timed(one_round, args.steps)
+        line.update({"seq_ms_per_round": round(ms_seq, 4), "seq_ms_per_model_step": round(ms_seq / B, 5),
+                     "seq_over_batch": round(ms_seq / ms_batch, 3)})
+        del models
+    silt.empty_cache()
+    _abi.check(lib.soil_workspace_release())
+    return line
+
+
+name = C.create_string_buffer(256)
+lib.soil_device_name(name, 256)
+for cfg in args.configs.split(","):
+    S, B = (int(v) for v in cfg.split(":"))
+    line = run(S, B)
+    line["device"] = name.value.decode()
+    s = json.dumps(line)
+    print(s, flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(s + "\n")
