@@ -462,6 +462,36 @@ int soil_erode_step_colour(const soil_erosion_planes* planes, const soil_colour_
                            int64_t W, const float scale[3], const soil_param* param, int flags,
                            void* stream);
 
+/* ------------------------------------------ erosion: coloured batches of models */
+
+/* A coloured batch: the batch of soil_erode_step_batch (B whole-grid models of (H, W), N walkers each, one seed
+ * per model, the same rules, refusals and launch shapes) carrying the four colour planes of the coloured step.
+ * Every pointer of `colour` is model 0 of B consecutive (H, W, 3) models: model b starts at element
+ * b * H * W * 3.  Model b ends each step holding what soil_erode_step_colour leaves on that model alone with
+ * seed = seeds[b]: before the fluvial launch albedo_fluvial and albedo_debris of all B models are cleared, and
+ * they then hold the step's normalised transport colour; a NaN walker's colour deposit lands in cell (0, 0) of
+ * its own model; no colour of one model reaches another.  Exact arithmetic, every walker walked to the end; only
+ * the fp32 order of the flux atomics may differ from the single model's.  A null `colour` or a null colour plane
+ * is SOIL_ERR_INVALID_ARGUMENT ("colour plane"), as are the sizes soil_erode_step_batch refuses.
+ *
+ * One coloured step of every model: soil_particles_batch_colour, then soil_erode_cells_fused_batch_colour with
+ * flags 0.  The physics flux planes are zero on entry and on exit. */
+int soil_erode_step_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                 int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
+                                 const float scale[3], const soil_param* param, void* stream);
+/* soil_particles_batch with colour: the two colour flux planes of every model are cleared first (also when
+ * N == 0), then the fluvial launch adds its colour flux to albedo_fluvial, the debris launch to albedo_debris,
+ * both reading the spawn cell's colour from albedo_surface. */
+int soil_particles_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
+                                const float scale[3], const soil_param* param, void* stream);
+/* The coloured cell phase of every model of a batch, bit-identical per model to soil_erode_cells_fused_colour
+ * on that model's planes with the same flags (SOIL_CELLS_KEEP_FLUX).  168 algorithmic bytes per cell with
+ * SOIL_CELLS_KEEP_FLUX; without it one more pass re-zeroes the physics flux planes of all B models (28). */
+int soil_erode_cells_fused_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                        int64_t B, int64_t H, int64_t W, const float scale[3],
+                                        const soil_param* param, int flags, void* stream);
+
 /* The containers of the legacy API (example/erosion_gpu.py:44-71): model_t, the `data` and the
  * `track` buffers.  All float32 device planes of H*W cells ((H,W,2) for the momenta). */
 typedef struct soil_erode_model {

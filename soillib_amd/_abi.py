@@ -146,6 +146,12 @@ SIGNATURES = {
                                     C.POINTER(Param), vp]),
     "soil_erode_cells_fused_batch": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, F3, C.POINTER(Param), cint,
                                             vp]),
+    "soil_erode_step_batch_colour": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64, i64, i64,
+                                            C.POINTER(u64), u64, F3, C.POINTER(Param), vp]),
+    "soil_particles_batch_colour": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64, i64, i64,
+                                           C.POINTER(u64), u64, F3, C.POINTER(Param), vp]),
+    "soil_erode_cells_fused_batch_colour": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64,
+                                                   i64, F3, C.POINTER(Param), cint, vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),

@@ -66,8 +66,9 @@ int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* c
 // naming `what` for B < 1, an empty grid, N < 0, null seeds with N > 0, byte offsets that overflow
 // (erosion_particles.hip).  The cell phase of a batch (erosion_cells.hip).
 int check_batch(int64_t B, int64_t H, int64_t W, int64_t N, const uint64_t* seeds, const char* what);
-int erode_cells_fused_batch(const soil_erosion_planes* pl, int64_t B, int64_t H, int64_t W, const float scale[3],
-                            const soil_param* param, int flags, hipStream_t st);
+// `colour` null: physics only; otherwise the four colour planes of all B models (soil_erode_cells_fused_batch_colour)
+int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
+                            int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st);
 
 // Launch shape of the per-cell kernels: threads along the contiguous axis, and a
 // work-group walks a band of kRowBand consecutive rows (SOIL_ROW_LOOP).  A 64-bit

@@ -233,13 +233,21 @@ struct Planes {  // soil_erosion_planes by value, typed
   float* albedoDebris;
 };
 
-// the planes of model blockIdx.y of a batch (physics planes only)
+// the planes of model blockIdx.y of a batch; ALB: the four vec3 colour planes too, where set (a coloured
+// batch) — without it they are not touched, and the physics batch's kernels compile as they did
+template <bool ALB = false>
 __device__ __forceinline__ Planes model_planes(Planes P, int64_t cells) {
   const int64_t m = static_cast<int64_t>(blockIdx.y) * cells;
   P.layers += m, P.layers_next += m, P.uplift += m, P.rainfall += m, P.waterHeight += m, P.waterFlux += m;
   P.mass += m, P.massFlux += m, P.velocity += m, P.velocityFlux += m, P.debris += m, P.debrisFlux += m;
   P.debrisVelocity += m, P.debrisVelocityFlux += m;
   if (P.height) P.height += m;
+  if constexpr (ALB) {
+    if (P.albedoBedrock) P.albedoBedrock += 3 * m;
+    if (P.albedoSurface) P.albedoSurface += 3 * m;
+    if (P.albedoFluvial) P.albedoFluvial += 3 * m;
+    if (P.albedoDebris) P.albedoDebris += 3 * m;
+  }
   return P;
 }
 
@@ -337,14 +345,14 @@ __device__ __forceinline__ void colour_cell(float fluvial[3], float debris[3], f
 // ALB: the coloured step (soil_erode_cells_fused_colour) — the four vec3 planes of Planes too: a lane's
 // four cells are 48 contiguous, 16-byte aligned bytes of each (three 16-byte accesses), 168 bytes per cell
 // with REZERO = false.
-// BATCH: grid.y is the model of a batch of whole-grid models (soil_erode_cells_fused_batch): every plane is
-// advanced to model blockIdx.y, H x W cells per model.
+// BATCH: grid.y is the model of a batch of whole-grid models (soil_erode_cells_fused_batch, with ALB
+// soil_erode_cells_fused_batch_colour): every plane is advanced to model blockIdx.y, H x W cells per model.
 template <bool XCD_REMAP, bool NT, int BLOCK = kBlock, bool DIRECT = false, bool REZERO = true, bool ALB = false,
           bool BATCH = false>
 __global__ void __launch_bounds__(BLOCK)
     k_erode_cells_fused(Planes P, Dom d, Scale3 s, Param p, int64_t groups_per_row,
                         int64_t total_groups) {
-  if constexpr (BATCH) P = model_planes(P, d.H * d.W);
+  if constexpr (BATCH) P = model_planes<ALB>(P, d.H * d.W);
   // group = kVec consecutive cells of one row; one thread per group
   int64_t blk = blockIdx.x;
   if (XCD_REMAP) {
@@ -513,11 +521,12 @@ __global__ void __launch_bounds__(kBlock)
   zv[0] = z, zv[1] = z, zd[0] = z, zd[1] = z;
 }
 
-// scalar path for W % 4 != 0 (ragged widths): one thread per cell (BATCH: as k_erode_cells_fused's)
-template <bool BATCH = false>
+// scalar path for W % 4 != 0 (ragged widths): one thread per cell (BATCH, ALB: as k_erode_cells_fused's; the
+// colour branch is taken wherever albedoSurface is set)
+template <bool BATCH = false, bool ALB = false>
 __global__ void __launch_bounds__(kBlock)
     k_erode_cells_fused_scalar(Planes P, Dom d, Scale3 s, Param p, bool rezero) {
-  if constexpr (BATCH) P = model_planes(P, d.H * d.W);
+  if constexpr (BATCH) P = model_planes<ALB>(P, d.H * d.W);
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (t >= (d.r1 - d.r0) * d.W) return;
   const int64_t lx = d.r0 + t / d.W, y = t % d.W;
@@ -821,19 +830,24 @@ int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* c
 // The cell phase of a batch: grid.y is the model, at most 65535 models per launch (the planes advanced past
 // the models launched before).  The same kernel and the same per-cell arithmetic as a single model's
 // erode_cells_fused, which makes every model bit-identical to it; the five flux planes are re-zeroed in the
-// kernel (112 bytes per cell) unless SOIL_CELLS_KEEP_FLUX (84).
-int erode_cells_fused_batch(const soil_erosion_planes* pl, int64_t B, int64_t H, int64_t W, const float scale[3],
-                            const soil_param* param, int flags, hipStream_t st) {
+// kernel (112 bytes per cell) unless SOIL_CELLS_KEEP_FLUX (84).  With `colour` the coloured single model's
+// shape: the 168-byte kernel (ALB, flux planes kept), then one re-zero pass over the flux planes of all B
+// models unless SOIL_CELLS_KEEP_FLUX.
+int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
+                            int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st) {
   const Dom d = full_domain(H, W);
   const int64_t cells = H * W;
   const bool keep = (flags & SOIL_CELLS_KEEP_FLUX) != 0;
-  // W % 4 == 0 keeps every model's planes 16-byte aligned when model 0's are
+  // W % 4 == 0 keeps every model's planes 16-byte aligned when model 0's are (a vec3 plane's model is 12 H W
+  // bytes, a multiple of 16 too)
   const bool vec_ok = (W % kVec == 0) && aligned16(pl->layers) && aligned16(pl->layers_next) &&
                       (!pl->height || aligned16(pl->height)) && aligned16(pl->uplift) && aligned16(pl->rainfall) &&
                       aligned16(pl->waterHeight) && aligned16(pl->waterFlux) && aligned16(pl->mass) &&
                       aligned16(pl->massFlux) && aligned16(pl->velocity) && aligned16(pl->velocityFlux) &&
                       aligned16(pl->debris) && aligned16(pl->debrisFlux) && aligned16(pl->debrisVelocity) &&
-                      aligned16(pl->debrisVelocityFlux);
+                      aligned16(pl->debrisVelocityFlux) &&
+                      (!colour || (aligned16(colour->albedo_bedrock) && aligned16(colour->albedo_surface) &&
+                                   aligned16(colour->albedo_fluvial) && aligned16(colour->albedo_debris)));
   const int64_t groups_per_row = W / kVec, total = H * groups_per_row;
   const unsigned nblk = vec_ok ? blocks_for(total, kBlock) : blocks_for(cells, kBlock);
   const bool remap = nblk % 8 == 0 && nblk >= 64;
@@ -858,7 +872,20 @@ int erode_cells_fused_batch(const soil_erosion_planes* pl, int64_t B, int64_t H,
     P.debrisVelocity = reinterpret_cast<float2*>(pl->debrisVelocity) + m;
     P.debrisVelocityFlux = reinterpret_cast<float2*>(pl->debrisVelocityFlux) + m;
     const dim3 grid(nblk, nb);
-    if (!vec_ok)
+    if (colour) {
+      P.albedoBedrock = colour->albedo_bedrock + 3 * m;
+      P.albedoSurface = colour->albedo_surface + 3 * m;
+      P.albedoFluvial = colour->albedo_fluvial + 3 * m;
+      P.albedoDebris = colour->albedo_debris + 3 * m;
+      if (!vec_ok)
+        k_erode_cells_fused_scalar<true, true><<<grid, kBlock, 0, st>>>(P, d, s3(scale), *param, !keep);
+      else if (remap)
+        k_erode_cells_fused<true, false, kBlock, false, false, true, true><<<grid, kBlock, 0, st>>>(
+            P, d, s3(scale), *param, groups_per_row, total);
+      else
+        k_erode_cells_fused<false, false, kBlock, false, false, true, true><<<grid, kBlock, 0, st>>>(
+            P, d, s3(scale), *param, groups_per_row, total);
+    } else if (!vec_ok)
       k_erode_cells_fused_scalar<true><<<grid, kBlock, 0, st>>>(P, d, s3(scale), *param, !keep);
     else if (remap && keep)
       k_erode_cells_fused<true, false, kBlock, false, false, false, true><<<grid, kBlock, 0, st>>>(
@@ -872,6 +899,14 @@ int erode_cells_fused_batch(const soil_erosion_planes* pl, int64_t B, int64_t H,
     else
       k_erode_cells_fused<false, false, kBlock, false, true, false, true><<<grid, kBlock, 0, st>>>(
           P, d, s3(scale), *param, groups_per_row, total);
+    SOIL_LAUNCH_CHECK();
+  }
+  if (colour && vec_ok && !keep) {  // the models are consecutive in every flux plane: one pass over all B
+    Planes Z{};
+    Z.waterFlux = pl->waterFlux, Z.massFlux = pl->massFlux, Z.debrisFlux = pl->debrisFlux;
+    Z.velocityFlux = reinterpret_cast<float2*>(pl->velocityFlux);
+    Z.debrisVelocityFlux = reinterpret_cast<float2*>(pl->debrisVelocityFlux);
+    k_zero_flux<<<blocks_for(B * total, kBlock), kBlock, 0, st>>>(Z, 0, B * total);
     SOIL_LAUNCH_CHECK();
   }
   return SOIL_OK;
@@ -892,7 +927,26 @@ int soil_erode_cells_fused_batch(const soil_erosion_planes* planes, int64_t B, i
                    P.debrisVelocityFlux,
                "erode_cells_fused_batch: null plane (only `height` is optional)");
   SOIL_REQUIRE(P.layers != P.layers_next, "erode_cells_fused_batch: layers and layers_next must be distinct buffers");
-  return erode_cells_fused_batch(planes, B, H, W, scale, param, flags, as_stream(stream));
+  return erode_cells_fused_batch(planes, nullptr, B, H, W, scale, param, flags, as_stream(stream));
+}
+
+int soil_erode_cells_fused_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                        int64_t B, int64_t H, int64_t W, const float scale[3],
+                                        const soil_param* param, int flags, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && scale && param, "erode_cells_fused_batch_colour: null argument");
+  SOIL_REQUIRE(colour && colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial &&
+                   colour->albedo_debris,
+               "erode_cells_fused_batch_colour: every colour plane is required");
+  if (int rc = check_batch(B, H, W, 0, nullptr, "erode_cells_fused_batch_colour"); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux && P.mass &&
+                   P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux && P.debrisVelocity &&
+                   P.debrisVelocityFlux,
+               "erode_cells_fused_batch_colour: null plane (only `height` is optional)");
+  SOIL_REQUIRE(P.layers != P.layers_next,
+               "erode_cells_fused_batch_colour: layers and layers_next must be distinct buffers");
+  return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, flags, as_stream(stream));
 }
 
 int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* dom,

@@ -618,14 +618,26 @@ int particles_debris(const Launch& L) {
 constexpr int64_t kMaxGridY = 65535;
 
 __device__ __forceinline__ int64_t model_base(int64_t cells) { return static_cast<int64_t>(blockIdx.y) * cells; }
+// ALB: a coloured batch (soil_particles_batch_colour) — the colour flux plane and the spawn colours
+// (albedo_surface) are advanced too, where set; the physics batch's kernels never touch them
+template <bool ALB>
 __device__ __forceinline__ FluvialPlanes model_of(FluvialPlanes P, int64_t cells) {
   const int64_t m = model_base(cells);
   P.waterFlux += m, P.massFlux += m, P.velocityFlux += 2 * m, P.waterSource += m, P.waterHeight += m;
+  if constexpr (ALB) {
+    if (P.albedoFlux) P.albedoFlux += 3 * m;
+    if (P.albedoSource) P.albedoSource += 3 * m;
+  }
   return P;
 }
+template <bool ALB>
 __device__ __forceinline__ DebrisPlanes model_of(DebrisPlanes P, int64_t cells) {
   const int64_t m = model_base(cells);
   P.massFlux += m, P.velocityFlux += 2 * m;
+  if constexpr (ALB) {
+    if (P.albedoFlux) P.albedoFlux += 3 * m;
+    if (P.albedoSource) P.albedoSource += 3 * m;
+  }
   return P;
 }
 __device__ __forceinline__ DirectFields model_of(DirectFields F, int64_t cells) {
@@ -638,6 +650,7 @@ __device__ __forceinline__ Streams model_streams(const uint64_t* __restrict__ se
 }
 
 // direct: thread n = walker n of model blockIdx.y (every spawn lies in the whole grid: no ownership test)
+template <bool ALB>
 __global__ void __launch_bounds__(kPBlock)
     k_fluvial_direct_batch(FluvialPlanes P, const uint64_t* __restrict__ seeds, uint64_t offset, int64_t N,
                            DirectFields F, Param param) {
@@ -645,9 +658,10 @@ __global__ void __launch_bounds__(kPBlock)
   if (n >= N) return;
   const int64_t cells = F.d.H * F.d.W;
   const float2 pos = spawn_position(model_streams(seeds, offset), n, F.d);
-  trace_fluvial(model_of(F, cells), model_of(P, cells), pos.x, pos.y, N, F.d, F.s, param);
+  trace_fluvial(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
 }
 
+template <bool ALB>
 __global__ void __launch_bounds__(kPBlock)
     k_debris_direct_batch(DebrisPlanes P, const uint64_t* __restrict__ seeds, uint64_t offset, int64_t N,
                           DirectFields F, Param param) {
@@ -655,7 +669,7 @@ __global__ void __launch_bounds__(kPBlock)
   if (n >= N) return;
   const int64_t cells = F.d.H * F.d.W;
   const float2 pos = spawn_position(model_streams(seeds, offset), n, F.d);
-  trace_debris(model_of(F, cells), model_of(P, cells), pos.x, pos.y, N, F.d, F.s, param);
+  trace_debris(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
 }
 
 // staged: k_pack_fields .. k_*_sorted per model; model b's spawn and sorted arrays start at b * N, its tile
@@ -701,6 +715,7 @@ __global__ void __launch_bounds__(kPBlock)
   sorted[model_base(N) + start[tile] + atomicAdd(&fill[tile], 1u)] = pos;
 }
 
+template <bool ALB>
 __global__ void __launch_bounds__(kPBlock)
     k_fluvial_sorted_batch(FluvialPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
                            int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
@@ -708,9 +723,10 @@ __global__ void __launch_bounds__(kPBlock)
   if (t < 0) return;
   const int64_t cells = d.H * d.W;
   const float2 pos = sorted[model_base(N) + t];
-  trace_fluvial(PackedFields{F.p4 + model_base(cells)}, model_of(P, cells), pos.x, pos.y, N, d, s, param);
+  trace_fluvial(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
 }
 
+template <bool ALB>
 __global__ void __launch_bounds__(kPBlock)
     k_debris_sorted_batch(DebrisPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
                           int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
@@ -718,7 +734,7 @@ __global__ void __launch_bounds__(kPBlock)
   if (t < 0) return;
   const int64_t cells = d.H * d.W;
   const float2 pos = sorted[model_base(N) + t];
-  trace_debris(PackedFields{F.p4 + model_base(cells)}, model_of(P, cells), pos.x, pos.y, N, d, s, param);
+  trace_debris(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
 }
 
 // The seeds of a batch reach the device through a pinned buffer of the host thread (the caller's array may go
@@ -761,9 +777,11 @@ static int upload_seeds(uint64_t* dst, const uint64_t* seeds, int64_t B, hipStre
 }
 
 namespace {
-// One launch of a batch: the planes, the device seeds, the first draw of the kind's streams.
+// One launch of a batch: the planes, the colour planes (null: physics only), the device seeds, the first draw
+// of the kind's streams.
 struct BatchLaunch {
   const soil_erosion_planes* P;
+  const soil_colour_planes* C;
   int64_t B, N;
   const uint64_t* seeds;
   uint64_t offset;
@@ -796,14 +814,23 @@ static int launch_batch(int kind, const BatchLaunch& L, const BatchScratch& w, b
     const uint64_t* seeds = L.seeds + b0;
     const float2* layers = reinterpret_cast<const float2*>(Q.layers) + m;
     const float2* velocity = reinterpret_cast<const float2*>(fluvial ? Q.velocity : Q.debrisVelocity) + m;
-    const FluvialPlanes PF{Q.waterFlux + m, Q.massFlux + m, Q.velocityFlux + 2 * m, nullptr, Q.rainfall + m,
-                           Q.waterHeight + m, nullptr, nullptr, steps};
-    const DebrisPlanes PD{Q.debrisFlux + m, Q.debrisVelocityFlux + 2 * m, nullptr, nullptr, nullptr, steps};
+    // with colour: the kind's colour flux plane and the spawn colours (albedo_surface, also in the staged
+    // shape: the packed fields hold none), both vec3 planes
+    float* const albedoFlux = L.C ? (fluvial ? L.C->albedo_fluvial : L.C->albedo_debris) + 3 * m : nullptr;
+    const float* const albedoSource = L.C ? L.C->albedo_surface + 3 * m : nullptr;
+    const FluvialPlanes PF{Q.waterFlux + m, Q.massFlux + m, Q.velocityFlux + 2 * m, albedoFlux, Q.rainfall + m,
+                           Q.waterHeight + m, albedoSource, nullptr, steps};
+    const DebrisPlanes PD{Q.debrisFlux + m, Q.debrisVelocityFlux + 2 * m, albedoFlux, albedoSource, nullptr, steps};
     const dim3 walkers(blocks_for(N, kPBlock), nb);
+    const bool alb = L.C != nullptr;
     if (!staged) {
       const DirectFields F{layers, velocity, L.d, L.s, L.p.exitSlope};
-      if (fluvial) k_fluvial_direct_batch<<<walkers, kPBlock, 0, L.st>>>(PF, seeds, offset, N, F, L.p);
-      else k_debris_direct_batch<<<walkers, kPBlock, 0, L.st>>>(PD, seeds, offset, N, F, L.p);
+      if (fluvial)
+        (alb ? k_fluvial_direct_batch<true> : k_fluvial_direct_batch<false>)<<<walkers, kPBlock, 0, L.st>>>(
+            PF, seeds, offset, N, F, L.p);
+      else
+        (alb ? k_debris_direct_batch<true> : k_debris_direct_batch<false>)<<<walkers, kPBlock, 0, L.st>>>(
+            PD, seeds, offset, N, F, L.p);
       SOIL_LAUNCH_CHECK();
       continue;
     }
@@ -817,18 +844,23 @@ static int launch_batch(int kind, const BatchLaunch& L, const BatchScratch& w, b
     k_spawn_scatter_batch<<<walkers, kPBlock, 0, L.st>>>(sorted, fill, start, spawn, N, L.d, w.tiles_w, w.tiles);
     const dim3 traced(blocks_for(N, kPBlock) + 8, nb);
     if (fluvial)
-      k_fluvial_sorted_batch<<<traced, kPBlock, 0, L.st>>>(PF, sorted, start, w.tiles, N, PackedFields{p4}, L.d, L.s,
-                                                            L.p);
+      (alb ? k_fluvial_sorted_batch<true> : k_fluvial_sorted_batch<false>)<<<traced, kPBlock, 0, L.st>>>(
+          PF, sorted, start, w.tiles, N, PackedFields{p4}, L.d, L.s, L.p);
     else
-      k_debris_sorted_batch<<<traced, kPBlock, 0, L.st>>>(PD, sorted, start, w.tiles, N, PackedFields{p4}, L.d, L.s,
-                                                           L.p);
+      (alb ? k_debris_sorted_batch<true> : k_debris_sorted_batch<false>)<<<traced, kPBlock, 0, L.st>>>(
+          PD, sorted, start, w.tiles, N, PackedFields{p4}, L.d, L.s, L.p);
     SOIL_LAUNCH_CHECK();
   }
   return SOIL_OK;
 }
 
-int particles_batch(const soil_erosion_planes* P, int64_t B, int64_t H, int64_t W, int64_t N, const uint64_t* seeds,
-                    uint64_t step_index, const float scale[3], const soil_param* param, hipStream_t st) {
+int particles_batch(const soil_erosion_planes* P, const soil_colour_planes* C, int64_t B, int64_t H, int64_t W,
+                    int64_t N, const uint64_t* seeds, uint64_t step_index, const float scale[3],
+                    const soil_param* param, hipStream_t st) {
+  // the colour flux planes of all B models (consecutive): one memset each, also when N == 0, as the single
+  // coloured pair does
+  if (C)
+    if (int rc = clear_flux(nullptr, C, BOTH_KINDS, B * H * W, st); rc != SOIL_OK) return rc;
   if (N == 0) return SOIL_OK;
   const bool staged = use_staged(N);  // the single model's rule; what would be tiled alone runs staged
   const Dom d = full_domain(H, W);
@@ -851,7 +883,7 @@ int particles_batch(const soil_erosion_planes* P, int64_t B, int64_t H, int64_t 
   w.fill = w.count + B * (w.tiles + 1);                      c += b_cnt;
   w.start = reinterpret_cast<uint32_t*>(c);
   if (int rc = upload_seeds(seeds_dev, seeds, B, st); rc != SOIL_OK) return rc;
-  const BatchLaunch L{P, B, N, seeds_dev, step_index * static_cast<uint64_t>(N), d, s3p(scale), *param, st};
+  const BatchLaunch L{P, C, B, N, seeds_dev, step_index * static_cast<uint64_t>(N), d, s3p(scale), *param, st};
   if (int rc = launch_batch(FLUVIAL, L, w, staged); rc != SOIL_OK) return rc;
   return launch_batch(DEBRIS, L, w, staged);
 }
@@ -1077,7 +1109,23 @@ int soil_particles_batch(const soil_erosion_planes* planes, int64_t B, int64_t H
   SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
                    P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
                "particles_batch: null plane");
-  return particles_batch(planes, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
+  return particles_batch(planes, nullptr, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
+}
+
+int soil_particles_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
+                                const float scale[3], const soil_param* param, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && scale && param, "particles_batch_colour: null argument");
+  SOIL_REQUIRE(colour && colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial &&
+                   colour->albedo_debris,
+               "particles_batch_colour: every colour plane is required");
+  if (int rc = check_batch(B, H, W, N, seeds, "particles_batch_colour"); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
+                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
+               "particles_batch_colour: null plane");
+  return particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
 }
 
 int soil_particle_steps(uint64_t* total, int reset, void* stream) {

@@ -169,8 +169,33 @@ int soil_erode_step_batch(const soil_erosion_planes* planes, int64_t B, int64_t 
                "erode_step_batch: every plane but `height` is required");
   SOIL_REQUIRE(P.layers != P.layers_next, "erode_step_batch: layers and layers_next must be distinct buffers");
   const hipStream_t st = as_stream(stream);
-  if (int rc = particles_batch(planes, B, H, W, N, seeds, step_index, scale, param, st); rc != SOIL_OK) return rc;
-  return erode_cells_fused_batch(planes, B, H, W, scale, param, 0, st);
+  if (int rc = particles_batch(planes, nullptr, B, H, W, N, seeds, step_index, scale, param, st); rc != SOIL_OK)
+    return rc;
+  return erode_cells_fused_batch(planes, nullptr, B, H, W, scale, param, 0, st);
+}
+
+// A coloured batch step: as soil_erode_step_batch, the colour flux planes of every model cleared before the
+// fluvial launch and the four colour planes carried through the cell phase.
+int soil_erode_step_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                 int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
+                                 const float scale[3], const soil_param* param, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && scale && param, "erode_step_batch_colour: null argument");
+  SOIL_REQUIRE(colour && colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial &&
+                   colour->albedo_debris,
+               "erode_step_batch_colour: every colour plane is required");
+  if (int rc = check_batch(B, H, W, N, seeds, "erode_step_batch_colour"); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux &&
+                   P.mass && P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux &&
+                   P.debrisVelocity && P.debrisVelocityFlux,
+               "erode_step_batch_colour: every plane but `height` is required");
+  SOIL_REQUIRE(P.layers != P.layers_next,
+               "erode_step_batch_colour: layers and layers_next must be distinct buffers");
+  const hipStream_t st = as_stream(stream);
+  if (int rc = particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, param, st); rc != SOIL_OK)
+    return rc;
+  return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, 0, st);
 }
 
 int soil_erode(const soil_erode_model* model, int64_t H, int64_t W, int64_t N, uint64_t seed,

@@ -131,9 +131,12 @@ int particles_pair(const Launch& L);
 
 // Both particle launches of a batch (soil_particles_batch, soil_hip.h): B whole-grid models of (H, W), N walkers
 // each, model b's streams at (seeds[b], step_index * N) — seeds a host array of B — the debris launch two draws
-// on; direct or staged shape by the single model's rule, one launch after the other on `st` (erosion_particles.hip)
-int particles_batch(const soil_erosion_planes* P, int64_t B, int64_t H, int64_t W, int64_t N, const uint64_t* seeds,
-                    uint64_t step_index, const float scale[3], const soil_param* param, hipStream_t st);
+// on; direct or staged shape by the single model's rule, one launch after the other on `st` (erosion_particles.hip).
+// With `C` (soil_particles_batch_colour): the two colour flux planes of all B models are cleared first, and the
+// launches deposit colour from albedo_surface into them.
+int particles_batch(const soil_erosion_planes* P, const soil_colour_planes* C, int64_t B, int64_t H, int64_t W,
+                    int64_t N, const uint64_t* seeds, uint64_t step_index, const float scale[3],
+                    const soil_param* param, hipStream_t st);
 
 // the launch shape a launch of N particles on domain d gets (erosion_particles.hip)
 bool use_tiled_launch(int64_t N, const Dom& d);

@@ -27,8 +27,10 @@ model at once and leaves model b where `ErosionModel(..., seed=seeds[b]).step()`
 leaves that model alone, up to the fp32 summation order of the flux planes: a
 few launches for the whole batch where B models take B times their own handful
 (DESIGN.md 3.5).  `particles()` and `cells_fused()` run the two phases
-separately; `model_planes(b)` copies one model's planes to the host.  Physics
-planes only, whole grids, one shared param.
+separately; `model_planes(b)` copies one model's planes to the host.  Whole
+grids, one shared param.  `ErosionBatch(..., colour=True)` carries the four colour
+planes of the coloured step too (soil_erode_step_batch_colour): model b ends where
+`ErosionModel(..., seed=seeds[b], colour=True).step()` leaves it.
 """
 import ctypes as C
 import os
@@ -237,12 +239,15 @@ class ErosionModel:
 class ErosionBatch:
     """B independent whole-grid erosion models of one (H, W) shape, stepped together (include/soil_hip.h:
     soil_erode_step_batch).  Every plane of ErosionModel is a (B, H, W[, C]) GPU tensor, zeroed here; model b
-    has its own terrain, rainfall, uplift and seed, and shares N, scale and param with the others."""
+    has its own terrain, rainfall, uplift and seed, and shares N, scale and param with the others.  `colour`:
+    the four colour planes of ErosionModel(colour=True) too, (B, H, W, 3) each, and the coloured entry points
+    (soil_erode_step_batch_colour)."""
 
     PLANES_1 = ErosionModel.PLANES_1
     PLANES_2 = ErosionModel.PLANES_2
+    PLANES_3 = ErosionModel.PLANES_3
 
-    def __init__(self, B, H, W, scale, param, n_particles, seeds):
+    def __init__(self, B, H, W, scale, param, n_particles, seeds, colour=False):
         self.B, self.H, self.W = int(B), int(H), int(W)
         self.seeds = [int(v) for v in seeds]
         if len(self.seeds) != self.B:
@@ -252,6 +257,7 @@ class ErosionBatch:
         self.scale = [float(v) for v in scale]
         self.param = param
         self.N = int(n_particles)
+        self.colour = bool(colour)
         self.step_index = 0
         shape = (self.B, self.H, self.W)
         alloc = lambda *dims: silt.tensor(silt.float32, silt.shape(*dims), silt.gpu)
@@ -261,15 +267,29 @@ class ErosionBatch:
             setattr(self, name, alloc(*shape))
         for name in self.PLANES_2:
             setattr(self, name, alloc(*shape, 2))
-        for name in ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2:
+        for name in self._colour_names():
+            setattr(self, name, alloc(*shape, 3))
+        for name in self._names():
             silt.set(getattr(self, name), 0.0)
         self._seeds = (C.c_uint64 * self.B)(*self.seeds)
+
+    def _colour_names(self):
+        return self.PLANES_3 if self.colour else ()
+
+    def _names(self):
+        return ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2 + self._colour_names()
 
     def _planes(self):
         p = _abi.ErosionPlanes()
         for name in _abi._PLANES:
             setattr(p, name, getattr(self, name).ptr)
         return p
+
+    def _colour(self):
+        c = _abi.ColourPlanes()
+        for field, name in zip(_abi.COLOUR_PLANES, self.PLANES_3):
+            setattr(c, field, getattr(self, name).ptr)
+        return c
 
     def _scale(self):
         return _abi.vec(self.scale, 3)
@@ -281,31 +301,56 @@ class ErosionBatch:
                 self.B, self.H, self.W, tuple(layers_tensor.shape)))
         silt.set(self.layers, layers_tensor)
 
+    def set_colour(self, name, tensor):
+        """Copy a (B, H, W, 3) tensor into colour plane `name` (one of PLANES_3) of a coloured batch."""
+        if not self.colour:
+            raise ValueError("set_colour: the batch was made without colour planes (colour=False)")
+        if name not in self.PLANES_3:
+            raise ValueError("set_colour: %r is not a colour plane (%s)" % (name, ", ".join(self.PLANES_3)))
+        if tuple(tensor.shape) != (self.B, self.H, self.W, 3):
+            raise ValueError("set_colour needs a (%d, %d, %d, 3) tensor, got %s" % (
+                self.B, self.H, self.W, tuple(tensor.shape)))
+        silt.set(getattr(self, name), tensor)
+
     def particles(self):
         """Both particle launches of this step for every model, adding into the flux planes
-        (soil_particles_batch)."""
+        (soil_particles_batch); with colour the two colour flux planes are cleared first and receive this
+        step's colour flux (soil_particles_batch_colour)."""
         planes = self._planes()
-        _abi.check(_abi.lib().soil_particles_batch(
-            C.byref(planes), self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(),
-            self.param._ref(), _abi.stream()))
+        args = (self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(), self.param._ref(),
+                _abi.stream())
+        if self.colour:
+            colour = self._colour()
+            _abi.check(_abi.lib().soil_particles_batch_colour(C.byref(planes), C.byref(colour), *args))
+        else:
+            _abi.check(_abi.lib().soil_particles_batch(C.byref(planes), *args))
 
     def cells_fused(self, keep_flux=False):
-        """Fused cell phase of every model (soil_erode_cells_fused_batch); `keep_flux`: the flux planes are
-        left as they are (SOIL_CELLS_KEEP_FLUX)."""
+        """Fused cell phase of every model (soil_erode_cells_fused_batch[_colour]); `keep_flux`: the flux
+        planes are left as they are (SOIL_CELLS_KEEP_FLUX)."""
         planes = self._planes()
-        _abi.check(_abi.lib().soil_erode_cells_fused_batch(
-            C.byref(planes), self.B, self.H, self.W, self._scale(), self.param._ref(),
-            _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0, _abi.stream()))
+        args = (self.B, self.H, self.W, self._scale(), self.param._ref(),
+                _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0, _abi.stream())
+        if self.colour:
+            colour = self._colour()
+            _abi.check(_abi.lib().soil_erode_cells_fused_batch_colour(C.byref(planes), C.byref(colour), *args))
+        else:
+            _abi.check(_abi.lib().soil_erode_cells_fused_batch(C.byref(planes), *args))
 
     def swap_layers(self):
         self.layers, self.layers_next = self.layers_next, self.layers
 
     def step(self):
-        """One erosion step of every model (soil_erode_step_batch); swaps the layer buffers."""
+        """One erosion step of every model (soil_erode_step_batch, with colour soil_erode_step_batch_colour);
+        swaps the layer buffers."""
         planes = self._planes()
-        _abi.check(_abi.lib().soil_erode_step_batch(
-            C.byref(planes), self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(),
-            self.param._ref(), _abi.stream()))
+        args = (self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(), self.param._ref(),
+                _abi.stream())
+        if self.colour:
+            colour = self._colour()
+            _abi.check(_abi.lib().soil_erode_step_batch_colour(C.byref(planes), C.byref(colour), *args))
+        else:
+            _abi.check(_abi.lib().soil_erode_step_batch(C.byref(planes), *args))
         self.swap_layers()
         self.step_index += 1
 
@@ -320,6 +365,5 @@ class ErosionBatch:
         return view.cpu().numpy()
 
     def model_planes(self, b):
-        """Every plane of model b as host numpy arrays, by name."""
-        return {name: self.model_plane(name, b)
-                for name in ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2}
+        """Every plane of model b as host numpy arrays, by name (the colour planes too, with colour)."""
+        return {name: self.model_plane(name, b) for name in self._names()}

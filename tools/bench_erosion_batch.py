@@ -6,7 +6,9 @@ and the script's parameters (example/erosion_gpu.py), every model its own noise 
 
 One JSON line per (size, B): ms per batch step and per model-step (median over --steps device-event-timed
 steps after --warmup), the sequential loop's ms per model-step, and seq / batch.  --no-seq leaves the loop
-out (the profiling run: rocprofv3 --kernel-trace --stats)."""
+out (the profiling run: rocprofv3 --kernel-trace --stats).  --colour times the coloured batch
+(ErosionBatch(colour=True), soil_erode_step_batch_colour) against ErosionModel(colour=True).step(), bedrock and
+surface colours set on every model."""
 import argparse
 import ctypes as C
 import json
@@ -22,14 +24,19 @@ from soillib_amd.erosion import ErosionBatch, ErosionModel  # noqa: E402
 from util import script_param  # noqa: E402
 
 DEFAULT = "256:1,256:8,256:64,256:256,512:1,512:8,512:32,1024:1,1024:8,1024:32"
+COLOUR_DEFAULT = "256:1,256:8,256:64,256:256,512:1,512:8,512:32,1024:1,1024:8"
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--configs", default=DEFAULT, help="size:B,size:B,...")
+ap.add_argument("--configs", default=None, help="size:B,size:B,... (default: %s; with --colour %s)" % (
+    DEFAULT, COLOUR_DEFAULT))
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--no-seq", action="store_true")
 ap.add_argument("--out", default=None, help="also append the lines to this file")
+ap.add_argument("--colour", action="store_true", help="the coloured batch against coloured single models")
 args = ap.parse_args()
+if args.configs is None:
+    args.configs = COLOUR_DEFAULT if args.colour else DEFAULT
 lib = _abi.lib()
 param = script_param(soil.param_t())
 param.maxage = 256
@@ -66,6 +73,13 @@ def terrain_into(layers_ptr, S, b):
     _abi.check(lib.soil_layers_from_planes(C.c_void_p(layers_ptr), bed.c_ptr, None, S * S, _abi.stream()))
 
 
+def colours_into(m):
+    """Bedrock and surface colours of a coloured batch or model (the transport colours are the step's own)."""
+    if args.colour:
+        silt.set(m.albedoBedrock, 0.6)
+        silt.set(m.albedoSurface, 0.3)
+
+
 def timed(step, n):
     ev = Events()
     ev.record()
@@ -79,22 +93,24 @@ def run(S, B):
     N = S * S // 8
     scale = (20.0 / S, 20.0 / S, 4.0)
     seeds = [1000 + b for b in range(B)]
-    batch = ErosionBatch(B, S, S, scale, param, N, seeds)
+    batch = ErosionBatch(B, S, S, scale, param, N, seeds, colour=args.colour)
     for b in range(B):
         terrain_into(batch.layers.ptr + b * S * S * 8, S, b)
     silt.set(batch.rainfall, 1.0)
+    colours_into(batch)
     for _ in range(args.warmup):
         batch.step()
     ms_batch = timed(batch.step, args.steps)
-    line = {"size": S, "B": B, "N": N, "maxage": param.maxage, "steps": args.steps, "warmup": args.warmup,
+    line = {"size": S, "B": B, "N": N, "colour": args.colour, "maxage": param.maxage, "steps": args.steps, "warmup": args.warmup,
             "batch_ms_per_step": round(ms_batch, 4), "batch_ms_per_model_step": round(ms_batch / B, 5)}
     del batch
     if not args.no_seq:
         models = []
         for b in range(B):
-            m = ErosionModel(S, S, scale, param, N, seed=seeds[b])
+            m = ErosionModel(S, S, scale, param, N, seed=seeds[b], colour=args.colour)
             terrain_into(m.layers.ptr, S, b)
             silt.set(m.rainfall, 1.0)
+            colours_into(m)
             models.append(m)
 
         def one_round():
