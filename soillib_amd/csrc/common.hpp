@@ -66,6 +66,18 @@ int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* c
 // naming `what` for B < 1, an empty grid, N < 0, null seeds with N > 0, byte offsets that overflow
 // (erosion_particles.hip).  The cell phase of a batch (erosion_cells.hip).
 int check_batch(int64_t B, int64_t H, int64_t W, int64_t N, const uint64_t* seeds, const char* what);
+// The entries' null-plane checks (true: every plane of the set is there).  The particle launches read and add to
+// ten physics planes; the step and the cell phase need all fourteen but `height`.  The colour entries need all
+// four colour planes, the coloured slab pair every one but albedo_bedrock.
+enum PlaneSet { PARTICLE_PLANES, STEP_PLANES };
+inline bool has_planes(const soil_erosion_planes& P, PlaneSet set) {
+  return P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity && P.velocityFlux &&
+         P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux &&
+         (set == PARTICLE_PLANES || (P.layers_next && P.uplift && P.mass && P.debris));
+}
+inline bool has_colour(const soil_colour_planes* C, bool bedrock = true) {
+  return C && (C->albedo_bedrock || !bedrock) && C->albedo_surface && C->albedo_fluvial && C->albedo_debris;
+}
 // `colour` null: physics only; otherwise the four colour planes of all B models (soil_erode_cells_fused_batch_colour)
 int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
                             int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st);

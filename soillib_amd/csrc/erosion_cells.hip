@@ -724,15 +724,52 @@ int soil_erode_cells_fused(const soil_erosion_planes* pl, const soil_domain* dom
 
 namespace soil {
 
+// The kernels' planes from model `m`'s first cell on (a batch's planes hold its models one after the other;
+// m = 0: a single model).  Without `colour` the colour planes stay null.
+static Planes planes_of(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t m) {
+  Planes P{};
+  P.layers = reinterpret_cast<const float2*>(pl->layers) + m;
+  P.layers_next = reinterpret_cast<float2*>(pl->layers_next) + m;
+  P.height = pl->height ? pl->height + m : nullptr;
+  P.uplift = pl->uplift + m;
+  P.rainfall = pl->rainfall + m;
+  P.waterHeight = pl->waterHeight + m;
+  P.waterFlux = pl->waterFlux + m;
+  P.mass = pl->mass + m;
+  P.massFlux = pl->massFlux + m;
+  P.velocity = reinterpret_cast<float2*>(pl->velocity) + m;
+  P.velocityFlux = reinterpret_cast<float2*>(pl->velocityFlux) + m;
+  P.debris = pl->debris + m;
+  P.debrisFlux = pl->debrisFlux + m;
+  P.debrisVelocity = reinterpret_cast<float2*>(pl->debrisVelocity) + m;
+  P.debrisVelocityFlux = reinterpret_cast<float2*>(pl->debrisVelocityFlux) + m;
+  if (colour) {
+    P.albedoBedrock = colour->albedo_bedrock + 3 * m;
+    P.albedoSurface = colour->albedo_surface + 3 * m;
+    P.albedoFluvial = colour->albedo_fluvial + 3 * m;
+    P.albedoDebris = colour->albedo_debris + 3 * m;
+  }
+  return P;
+}
+
+// The vector kernels' condition: rows of whole kVec-cell groups and every plane 16-byte aligned (`height` where
+// set, the colour planes with `colour`).  In a batch, W % 4 == 0 keeps every model's planes aligned when model
+// 0's are (a vec3 plane's model is 12 H W bytes, a multiple of 16 too).
+static bool vec_path(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t W) {
+  return (W % kVec == 0) && aligned16(pl->layers) && aligned16(pl->layers_next) &&
+         (!pl->height || aligned16(pl->height)) && aligned16(pl->uplift) && aligned16(pl->rainfall) &&
+         aligned16(pl->waterHeight) && aligned16(pl->waterFlux) && aligned16(pl->mass) && aligned16(pl->massFlux) &&
+         aligned16(pl->velocity) && aligned16(pl->velocityFlux) && aligned16(pl->debris) &&
+         aligned16(pl->debrisFlux) && aligned16(pl->debrisVelocity) && aligned16(pl->debrisVelocityFlux) &&
+         (!colour || (aligned16(colour->albedo_bedrock) && aligned16(colour->albedo_surface) &&
+                      aligned16(colour->albedo_fluvial) && aligned16(colour->albedo_debris)));
+}
+
 int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* colour,
                       const soil_domain* dom, const float scale[3], const soil_param* param,
                       int flags, void* stream) {
   SOIL_REQUIRE(pl && dom && scale && param, "erode_cells_fused: null argument");
-  SOIL_REQUIRE(pl->layers && pl->layers_next && pl->uplift && pl->rainfall && pl->waterHeight &&
-                   pl->waterFlux && pl->mass && pl->massFlux && pl->velocity &&
-                   pl->velocityFlux && pl->debris && pl->debrisFlux && pl->debrisVelocity &&
-                   pl->debrisVelocityFlux,
-               "erode_cells_fused: null plane (only `height` is optional)");
+  SOIL_REQUIRE(has_planes(*pl, STEP_PLANES), "erode_cells_fused: null plane (only `height` is optional)");
   SOIL_REQUIRE(pl->layers != pl->layers_next,
                "erode_cells_fused: layers and layers_next must be distinct buffers");
   const Dom d = to_dom(dom);
@@ -741,38 +778,8 @@ int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* c
   const int64_t cells = (d.r1 - d.r0) * d.W;
   if (cells <= 0) return SOIL_OK;
 
-  Planes P{};
-  P.layers = reinterpret_cast<const float2*>(pl->layers);
-  P.layers_next = reinterpret_cast<float2*>(pl->layers_next);
-  P.height = pl->height;
-  P.uplift = pl->uplift;
-  P.rainfall = pl->rainfall;
-  P.waterHeight = pl->waterHeight;
-  P.waterFlux = pl->waterFlux;
-  P.mass = pl->mass;
-  P.massFlux = pl->massFlux;
-  P.velocity = reinterpret_cast<float2*>(pl->velocity);
-  P.velocityFlux = reinterpret_cast<float2*>(pl->velocityFlux);
-  P.debris = pl->debris;
-  P.debrisFlux = pl->debrisFlux;
-  P.debrisVelocity = reinterpret_cast<float2*>(pl->debrisVelocity);
-  P.debrisVelocityFlux = reinterpret_cast<float2*>(pl->debrisVelocityFlux);
-  if (colour) {
-    P.albedoBedrock = colour->albedo_bedrock;
-    P.albedoSurface = colour->albedo_surface;
-    P.albedoFluvial = colour->albedo_fluvial;
-    P.albedoDebris = colour->albedo_debris;
-  }
-
-  const bool vec_ok = (d.W % kVec == 0) && aligned16(pl->layers) && aligned16(pl->layers_next) &&
-                      (!pl->height || aligned16(pl->height)) && aligned16(pl->uplift) &&
-                      aligned16(pl->rainfall) && aligned16(pl->waterHeight) &&
-                      aligned16(pl->waterFlux) && aligned16(pl->mass) && aligned16(pl->massFlux) &&
-                      aligned16(pl->velocity) && aligned16(pl->velocityFlux) &&
-                      aligned16(pl->debris) && aligned16(pl->debrisFlux) &&
-                      aligned16(pl->debrisVelocity) && aligned16(pl->debrisVelocityFlux) &&
-                      (!colour || (aligned16(colour->albedo_bedrock) && aligned16(colour->albedo_surface) &&
-                                   aligned16(colour->albedo_fluvial) && aligned16(colour->albedo_debris)));
+  const Planes P = planes_of(pl, colour, 0);
+  const bool vec_ok = vec_path(pl, colour, d.W);
   hipStream_t st = as_stream(stream);
   if (vec_ok && colour) {
     // the coloured step: the 168-byte kernel, and the flux planes' re-zero as a pass of its own unless
@@ -838,45 +845,16 @@ int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_pla
   const Dom d = full_domain(H, W);
   const int64_t cells = H * W;
   const bool keep = (flags & SOIL_CELLS_KEEP_FLUX) != 0;
-  // W % 4 == 0 keeps every model's planes 16-byte aligned when model 0's are (a vec3 plane's model is 12 H W
-  // bytes, a multiple of 16 too)
-  const bool vec_ok = (W % kVec == 0) && aligned16(pl->layers) && aligned16(pl->layers_next) &&
-                      (!pl->height || aligned16(pl->height)) && aligned16(pl->uplift) && aligned16(pl->rainfall) &&
-                      aligned16(pl->waterHeight) && aligned16(pl->waterFlux) && aligned16(pl->mass) &&
-                      aligned16(pl->massFlux) && aligned16(pl->velocity) && aligned16(pl->velocityFlux) &&
-                      aligned16(pl->debris) && aligned16(pl->debrisFlux) && aligned16(pl->debrisVelocity) &&
-                      aligned16(pl->debrisVelocityFlux) &&
-                      (!colour || (aligned16(colour->albedo_bedrock) && aligned16(colour->albedo_surface) &&
-                                   aligned16(colour->albedo_fluvial) && aligned16(colour->albedo_debris)));
+  const bool vec_ok = vec_path(pl, colour, W);
   const int64_t groups_per_row = W / kVec, total = H * groups_per_row;
   const unsigned nblk = vec_ok ? blocks_for(total, kBlock) : blocks_for(cells, kBlock);
   const bool remap = nblk % 8 == 0 && nblk >= 64;
   constexpr int64_t kMaxModels = 65535;  // grid.y
   for (int64_t b0 = 0; b0 < B; b0 += kMaxModels) {
     const unsigned nb = static_cast<unsigned>(B - b0 < kMaxModels ? B - b0 : kMaxModels);
-    const int64_t m = b0 * cells;
-    Planes P{};
-    P.layers = reinterpret_cast<const float2*>(pl->layers) + m;
-    P.layers_next = reinterpret_cast<float2*>(pl->layers_next) + m;
-    P.height = pl->height ? pl->height + m : nullptr;
-    P.uplift = pl->uplift + m;
-    P.rainfall = pl->rainfall + m;
-    P.waterHeight = pl->waterHeight + m;
-    P.waterFlux = pl->waterFlux + m;
-    P.mass = pl->mass + m;
-    P.massFlux = pl->massFlux + m;
-    P.velocity = reinterpret_cast<float2*>(pl->velocity) + m;
-    P.velocityFlux = reinterpret_cast<float2*>(pl->velocityFlux) + m;
-    P.debris = pl->debris + m;
-    P.debrisFlux = pl->debrisFlux + m;
-    P.debrisVelocity = reinterpret_cast<float2*>(pl->debrisVelocity) + m;
-    P.debrisVelocityFlux = reinterpret_cast<float2*>(pl->debrisVelocityFlux) + m;
+    const Planes P = planes_of(pl, colour, b0 * cells);
     const dim3 grid(nblk, nb);
     if (colour) {
-      P.albedoBedrock = colour->albedo_bedrock + 3 * m;
-      P.albedoSurface = colour->albedo_surface + 3 * m;
-      P.albedoFluvial = colour->albedo_fluvial + 3 * m;
-      P.albedoDebris = colour->albedo_debris + 3 * m;
       if (!vec_ok)
         k_erode_cells_fused_scalar<true, true><<<grid, kBlock, 0, st>>>(P, d, s3(scale), *param, !keep);
       else if (remap)
@@ -902,11 +880,7 @@ int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_pla
     SOIL_LAUNCH_CHECK();
   }
   if (colour && vec_ok && !keep) {  // the models are consecutive in every flux plane: one pass over all B
-    Planes Z{};
-    Z.waterFlux = pl->waterFlux, Z.massFlux = pl->massFlux, Z.debrisFlux = pl->debrisFlux;
-    Z.velocityFlux = reinterpret_cast<float2*>(pl->velocityFlux);
-    Z.debrisVelocityFlux = reinterpret_cast<float2*>(pl->debrisVelocityFlux);
-    k_zero_flux<<<blocks_for(B * total, kBlock), kBlock, 0, st>>>(Z, 0, B * total);
+    k_zero_flux<<<blocks_for(B * total, kBlock), kBlock, 0, st>>>(planes_of(pl, nullptr, 0), 0, B * total);
     SOIL_LAUNCH_CHECK();
   }
   return SOIL_OK;
@@ -922,10 +896,7 @@ int soil_erode_cells_fused_batch(const soil_erosion_planes* planes, int64_t B, i
   SOIL_REQUIRE(planes && scale && param, "erode_cells_fused_batch: null argument");
   if (int rc = check_batch(B, H, W, 0, nullptr, "erode_cells_fused_batch"); rc != SOIL_OK) return rc;
   const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux && P.mass &&
-                   P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux && P.debrisVelocity &&
-                   P.debrisVelocityFlux,
-               "erode_cells_fused_batch: null plane (only `height` is optional)");
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_cells_fused_batch: null plane (only `height` is optional)");
   SOIL_REQUIRE(P.layers != P.layers_next, "erode_cells_fused_batch: layers and layers_next must be distinct buffers");
   return erode_cells_fused_batch(planes, nullptr, B, H, W, scale, param, flags, as_stream(stream));
 }
@@ -935,15 +906,10 @@ int soil_erode_cells_fused_batch_colour(const soil_erosion_planes* planes, const
                                         const soil_param* param, int flags, void* stream) {
   SOIL_DEVICE();
   SOIL_REQUIRE(planes && scale && param, "erode_cells_fused_batch_colour: null argument");
-  SOIL_REQUIRE(colour && colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial &&
-                   colour->albedo_debris,
-               "erode_cells_fused_batch_colour: every colour plane is required");
+  SOIL_REQUIRE(has_colour(colour), "erode_cells_fused_batch_colour: every colour plane is required");
   if (int rc = check_batch(B, H, W, 0, nullptr, "erode_cells_fused_batch_colour"); rc != SOIL_OK) return rc;
   const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux && P.mass &&
-                   P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux && P.debrisVelocity &&
-                   P.debrisVelocityFlux,
-               "erode_cells_fused_batch_colour: null plane (only `height` is optional)");
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_cells_fused_batch_colour: null plane (only `height` is optional)");
   SOIL_REQUIRE(P.layers != P.layers_next,
                "erode_cells_fused_batch_colour: layers and layers_next must be distinct buffers");
   return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, flags, as_stream(stream));
@@ -959,9 +925,7 @@ int soil_erode_cells_fused_colour(const soil_erosion_planes* pl, const soil_colo
                                   const soil_domain* dom, const float scale[3], const soil_param* param,
                                   int flags, void* stream) {
   SOIL_DEVICE();
-  SOIL_REQUIRE(colour && colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial &&
-                   colour->albedo_debris,
-               "erode_cells_fused_colour: every colour plane is required");
+  SOIL_REQUIRE(has_colour(colour), "erode_cells_fused_colour: every colour plane is required");
   return erode_cells_fused(pl, colour, dom, scale, param, flags, stream);
 }
 

@@ -314,40 +314,99 @@ __device__ __forceinline__ void trace_debris(const Fields& F, const DebrisPlanes
   atomicAdd(P.steps, static_cast<unsigned long long>(nsteps));
 }
 
-// ---- direct mode: thread n = particle n ---------------------------------------
+// ---- the small-N shapes: direct and staged -------------------------------------------
+//
+// One kernel per step of a shape, for a single model and for a batch of B independent models alike: grid.y is
+// the model (a single model: gridDim.y == 1, model 0), and model b's planes start b * rows * W cells on (C
+// channels: b * rows * W * C elements), its spawn and sorted arrays b * N walkers on, its tile counters, fills
+// and starts b * (tiles + 1) on.  A batch is B whole-grid models (Dom{H, W, 0, H, 0, H}): every spawn is owned,
+// the stencil covers every row, and no deposit leaves its model (remote0 / remoteA null).
 
-__global__ void __launch_bounds__(kPBlock)
-    k_fluvial_direct(FluvialPlanes P, soil_rng* __restrict__ rng, int64_t N, DirectFields F,
-                     Param param) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
-  const float2 pos = spawn_position(rng, n, F.d);
-  if (!owns_spawn(F.d, pos.x)) return;
-  trace_fluvial(F, P, pos.x, pos.y, N, F.d, F.s, param);
+constexpr int64_t kMaxGridY = 65535;  // models per launch
+
+__device__ __forceinline__ int64_t model_base(int64_t per_model) {
+  return static_cast<int64_t>(blockIdx.y) * per_model;
 }
 
-__global__ void __launch_bounds__(kPBlock)
-    k_debris_direct(DebrisPlanes P, soil_rng* __restrict__ rng, int64_t N, DirectFields F,
-                    Param param) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
-  const float2 pos = spawn_position(rng, n, F.d);
-  if (!owns_spawn(F.d, pos.x)) return;
-  trace_debris(F, P, pos.x, pos.y, N, F.d, F.s, param);
+// Where a launch's walkers take their first two draws from, a compile-time choice.  (Streams, the tiled
+// shape's runtime switch, stays as it is: its kernels take it by value.)
+struct TensorDraws {  // a single model's soil_rng tensor: every state read, drawn from and written back
+  soil_rng* __restrict__ rng;
+  __device__ __forceinline__ float2 spawn(int64_t n, const Dom& d) const { return spawn_position(rng, n, d); }
+  TensorDraws from_model(int64_t) const { return *this; }  // (B == 1)
+};
+struct SeedDraws {  // a batch's uniform streams: walker n of model b at (seeds[b], n, offset), nothing stored
+  const uint64_t* __restrict__ seeds;
+  uint64_t offset;
+  __device__ __forceinline__ float2 spawn(int64_t n, const Dom& d) const {
+    return spawn_position(Streams{nullptr, true, seeds[blockIdx.y], offset}, n, d);
+  }
+  SeedDraws from_model(int64_t b0) const { return SeedDraws{seeds + b0, offset}; }
+};
+
+// the planes of model blockIdx.y.  ALB: a coloured batch (soil_particles_batch_colour) — the colour flux plane
+// and the spawn colours (albedo_surface) are advanced too, where set; no other launch needs them advanced
+template <bool ALB>
+__device__ __forceinline__ FluvialPlanes model_of(FluvialPlanes P, int64_t cells) {
+  const int64_t m = model_base(cells);
+  P.waterFlux += m, P.massFlux += m, P.velocityFlux += 2 * m, P.waterSource += m, P.waterHeight += m;
+  if constexpr (ALB) {
+    if (P.albedoFlux) P.albedoFlux += 3 * m;
+    if (P.albedoSource) P.albedoSource += 3 * m;
+  }
+  return P;
+}
+template <bool ALB>
+__device__ __forceinline__ DebrisPlanes model_of(DebrisPlanes P, int64_t cells) {
+  const int64_t m = model_base(cells);
+  P.massFlux += m, P.velocityFlux += 2 * m;
+  if constexpr (ALB) {
+    if (P.albedoFlux) P.albedoFlux += 3 * m;
+    if (P.albedoSource) P.albedoSource += 3 * m;
+  }
+  return P;
+}
+__device__ __forceinline__ DirectFields model_of(DirectFields F, int64_t cells) {
+  const int64_t m = model_base(cells);
+  F.layers += m, F.velocity += m;
+  return F;
 }
 
-// ---- staged mode ------------------------------------------------------------------
+// direct: thread n = walker n of model blockIdx.y
+template <class Draws, bool ALB>
+__global__ void __launch_bounds__(kPBlock)
+    k_fluvial_direct(FluvialPlanes P, Draws draws, int64_t N, DirectFields F, Param param) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
+  if (n >= N) return;
+  const float2 pos = draws.spawn(n, F.d);
+  if (!owns_spawn(F.d, pos.x)) return;
+  const int64_t cells = F.d.rows * F.d.W;
+  trace_fluvial(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
+}
 
-// pre-pass: p4[cell] = {__glocal(cell), velocity[cell]} for every row with a full stencil
+template <class Draws, bool ALB>
+__global__ void __launch_bounds__(kPBlock)
+    k_debris_direct(DebrisPlanes P, Draws draws, int64_t N, DirectFields F, Param param) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
+  if (n >= N) return;
+  const float2 pos = draws.spawn(n, F.d);
+  if (!owns_spawn(F.d, pos.x)) return;
+  const int64_t cells = F.d.rows * F.d.W;
+  trace_debris(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
+}
+
+// staged, pre-pass: p4[cell] = {__glocal(cell), velocity[cell]} for every row with a full stencil (`cells` of
+// them per model from local row `row_lo`)
 __global__ void __launch_bounds__(kPBlock)
     k_pack_fields(float4* __restrict__ p4, const float2* __restrict__ layers,
                   const float2* __restrict__ velocity, Dom d, Scale3 s, float exitSlope,
                   int64_t row_lo, int64_t cells) {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
   if (t >= cells) return;
+  const int64_t m = model_base(d.rows * d.W);
   const int64_t lx = row_lo + t / d.W, y = t % d.W;
-  const int64_t l = lx * d.W + y;
-  const float2 g = glocal(layers, d, s, d.x0 + lx, y, exitSlope);
+  const int64_t l = m + lx * d.W + y;
+  const float2 g = glocal(layers + m, d, s, d.x0 + lx, y, exitSlope);
   const float2 v = velocity[l];
   p4[l] = make_float4(g.x, g.y, v.x, v.y);
 }
@@ -357,19 +416,24 @@ __device__ __forceinline__ int64_t tile_of(const Dom& d, float px, float py, int
   return (lx / kTile) * tiles_w + cy / kTile;
 }
 
-// pass 1: draw the spawn points (advancing every particle's stream) and count per tile
+// pass 1: draw the spawn points (advancing every walker's stream) and count per tile
+template <class Draws>
 __global__ void __launch_bounds__(kPBlock)
-    k_spawn_count(float2* __restrict__ spawn, uint32_t* __restrict__ count,
-                  soil_rng* __restrict__ rng, int64_t N, Dom d, int64_t tiles_w) {
+    k_spawn_count(float2* __restrict__ spawn, uint32_t* __restrict__ count, Draws draws, int64_t N, Dom d,
+                  int64_t tiles_w, int64_t tiles) {
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
   if (n >= N) return;
-  const float2 pos = spawn_position(rng, n, d);
-  spawn[n] = pos;
-  if (owns_spawn(d, pos.x)) atomicAdd(&count[tile_of(d, pos.x, pos.y, tiles_w)], 1u);
+  const float2 pos = draws.spawn(n, d);
+  spawn[model_base(N) + n] = pos;
+  if (owns_spawn(d, pos.x)) atomicAdd(&count[model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w)], 1u);
 }
 
-// pass 2: exclusive scan of the tile counts (one work-group; tiles <= a few 1e5)
-__device__ __forceinline__ void tile_scan_group(uint32_t* start, const uint32_t* count, int64_t tiles) {
+// pass 2: exclusive scan of the tile counts, start[tiles] = the number of owned walkers (one work-group per
+// model: grid.x is the model here; tiles <= a few 1e5)
+__global__ void __launch_bounds__(1024)
+    k_tile_scan(uint32_t* start, const uint32_t* count, int64_t tiles) {
+  const int64_t m = static_cast<int64_t>(blockIdx.x) * (tiles + 1);
+  start += m, count += m;
   __shared__ uint32_t part[1024];
   const int tid = threadIdx.x;
   const int64_t chunk = (tiles + 1023) / 1024;
@@ -389,24 +453,20 @@ __device__ __forceinline__ void tile_scan_group(uint32_t* start, const uint32_t*
     start[i] = run;
     run += count[i];
   }
-  if (tid == 1023) start[tiles] = part[1023];  // total number of owned particles
-}
-__global__ void __launch_bounds__(1024)
-    k_tile_scan(uint32_t* start, const uint32_t* count, int64_t tiles) {
-  tile_scan_group(start, count, tiles);
+  if (tid == 1023) start[tiles] = part[1023];
 }
 
 // pass 3: drop every owned spawn point into its tile's range
 __global__ void __launch_bounds__(kPBlock)
     k_spawn_scatter(float2* __restrict__ sorted, uint32_t* __restrict__ fill,
                     const uint32_t* __restrict__ start, const float2* __restrict__ spawn,
-                    int64_t N, Dom d, int64_t tiles_w) {
+                    int64_t N, Dom d, int64_t tiles_w, int64_t tiles) {
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
   if (n >= N) return;
-  const float2 pos = spawn[n];
+  const float2 pos = spawn[model_base(N) + n];
   if (!owns_spawn(d, pos.x)) return;
-  const int64_t tile = tile_of(d, pos.x, pos.y, tiles_w);
-  sorted[start[tile] + atomicAdd(&fill[tile], 1u)] = pos;
+  const int64_t tile = model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w);
+  sorted[model_base(N) + start[tile] + atomicAdd(&fill[tile], 1u)] = pos;
 }
 
 // work-group -> slot in the sorted order: block b runs on XCD b % 8; give every
@@ -423,24 +483,27 @@ __device__ __forceinline__ int64_t sorted_slot(const uint32_t* __restrict__ tota
   return (blk < nb && t < total) ? t : -1;
 }
 
+// pass 4: trace the owned walkers in tile order
+template <bool ALB>
 __global__ void __launch_bounds__(kPBlock)
-    k_fluvial_sorted(FluvialPlanes P, const float2* __restrict__ sorted,
-                     const uint32_t* __restrict__ total, int64_t N, PackedFields F, Dom d,
-                     Scale3 s, Param param) {
-  const int64_t t = sorted_slot(total);
+    k_fluvial_sorted(FluvialPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
+                     int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
+  const int64_t t = sorted_slot(start + model_base(tiles + 1) + tiles);
   if (t < 0) return;
-  const float2 pos = sorted[t];
-  trace_fluvial(F, P, pos.x, pos.y, N, d, s, param);
+  const int64_t cells = d.rows * d.W;
+  const float2 pos = sorted[model_base(N) + t];
+  trace_fluvial(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
 }
 
+template <bool ALB>
 __global__ void __launch_bounds__(kPBlock)
-    k_debris_sorted(DebrisPlanes P, const float2* __restrict__ sorted,
-                    const uint32_t* __restrict__ total, int64_t N, PackedFields F, Dom d, Scale3 s,
-                    Param param) {
-  const int64_t t = sorted_slot(total);
+    k_debris_sorted(DebrisPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
+                    int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
+  const int64_t t = sorted_slot(start + model_base(tiles + 1) + tiles);
   if (t < 0) return;
-  const float2 pos = sorted[t];
-  trace_debris(F, P, pos.x, pos.y, N, d, s, param);
+  const int64_t cells = d.rows * d.W;
+  const float2 pos = sorted[model_base(N) + t];
+  trace_debris(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
 }
 
 static Scale3 s3p(const float* s) { return Scale3{s[0], s[1], s[2]}; }
@@ -501,46 +564,105 @@ int clear_flux(const soil_erosion_planes* P, const soil_colour_planes* C, int ki
   return SOIL_OK;
 }
 
-// Shared staging: pack the fields, bucket the spawn points.  Returns device
-// pointers into the per-device workspace (valid until the next staged call).
-struct Staged {
+// The staged shape's scratch for B models in the workspace's `slot` (valid until the slot's next use), behind
+// `lead` bytes the caller keeps for itself (a batch's device seeds).  Not staged: the lead alone.
+struct Scratch {
+  void* lead;
   float4* p4;
-  float2* sorted;
-  uint32_t* total;
+  float2 *spawn, *sorted;
+  uint32_t *count, *fill, *start;  // three blocks of equal size, count and fill adjacent
+  int64_t tiles_w, tiles;
 };
 
-static int stage(Staged* out, soil_rng* rng, int64_t N, const float* layers,
-                 const float* velocity, const Dom& d, Scale3 s, const Param& p, hipStream_t st) {
-  const int64_t tiles_w = (d.W + kTile - 1) / kTile, tiles_h = (d.rows + kTile - 1) / kTile;
-  const int64_t tiles = tiles_w * tiles_h;
+static int scratch_get(int slot, size_t lead, int64_t B, int64_t N, const Dom& d, bool staged, Scratch* w) {
+  w->tiles_w = (d.W + kTile - 1) / kTile;
+  w->tiles = w->tiles_w * ((d.rows + kTile - 1) / kTile);
   auto align = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
-  const size_t b_p4 = align(sizeof(float4) * d.rows * d.W);
-  const size_t b_pos = align(sizeof(float2) * N);
-  const size_t b_cnt = align(sizeof(uint32_t) * (tiles + 1));
+  const size_t b_lead = align(lead);
+  const size_t b_p4 = staged ? align(sizeof(float4) * static_cast<size_t>(B * d.rows * d.W)) : 0;
+  const size_t b_pos = staged ? align(sizeof(float2) * static_cast<size_t>(B * N)) : 0;
+  const size_t b_cnt = staged ? align(sizeof(uint32_t) * static_cast<size_t>(B * (w->tiles + 1))) : 0;
   void* base = nullptr;
-  int rc = workspace_get(1, b_p4 + 2 * b_pos + 3 * b_cnt, &base);
-  if (rc != SOIL_OK) return rc;
-  char* w = static_cast<char*>(base);
-  out->p4 = reinterpret_cast<float4*>(w);      w += b_p4;
-  float2* spawn = reinterpret_cast<float2*>(w); w += b_pos;
-  out->sorted = reinterpret_cast<float2*>(w);  w += b_pos;
-  uint32_t* count = reinterpret_cast<uint32_t*>(w); w += b_cnt;
-  uint32_t* fill = reinterpret_cast<uint32_t*>(w);  w += b_cnt;
-  uint32_t* start = reinterpret_cast<uint32_t*>(w);
-  out->total = start + tiles;
+  if (int rc = workspace_get(slot, b_lead + b_p4 + 2 * b_pos + 3 * b_cnt, &base); rc != SOIL_OK) return rc;
+  char* c = static_cast<char*>(base);
+  w->lead = c;                                   c += b_lead;
+  w->p4 = reinterpret_cast<float4*>(c);          c += b_p4;
+  w->spawn = reinterpret_cast<float2*>(c);       c += b_pos;
+  w->sorted = reinterpret_cast<float2*>(c);      c += b_pos;
+  w->count = reinterpret_cast<uint32_t*>(c);     c += b_cnt;
+  w->fill = reinterpret_cast<uint32_t*>(c);      c += b_cnt;
+  w->start = reinterpret_cast<uint32_t*>(c);
+  return SOIL_OK;
+}
 
-  const int64_t lo = stencil_lo(d), hi = stencil_hi(d);
-  const int64_t cells = (hi - lo + 1) * d.W;
-  if (cells > 0)
-    k_pack_fields<<<blocks_for(cells, kPBlock), kPBlock, 0, st>>>(
-        out->p4, reinterpret_cast<const float2*>(layers),
-        reinterpret_cast<const float2*>(velocity), d, s, p.exitSlope, lo, cells);
-  SOIL_HIP(hipMemsetAsync(count, 0, 2 * b_cnt, st));  // count and fill are adjacent
-  k_spawn_count<<<blocks_for(N, kPBlock), kPBlock, 0, st>>>(spawn, count, rng, N, d, tiles_w);
-  k_tile_scan<<<1, 1024, 0, st>>>(start, count, tiles);
-  k_spawn_scatter<<<blocks_for(N, kPBlock), kPBlock, 0, st>>>(out->sorted, fill, start, spawn, N,
-                                                              d, tiles_w);
-  SOIL_LAUNCH_CHECK();
+// One launch of the small-N shapes: B models of domain d side by side (model b's planes b * rows * W cells on),
+// N walkers each.  `albedoFlux` / `albedoSource`: the kind's colour flux plane and the spawn colours, or null.
+struct SmallLaunch {
+  const soil_erosion_planes* P;
+  float* albedoFlux;
+  const float* albedoSource;
+  float* remote0;
+  float* remoteA;
+  int64_t B, N;
+  Dom d;
+  Scale3 s;
+  Param p;
+  hipStream_t st;
+};
+
+// The direct shape (`w` null) or the staged shape in `w`, at most kMaxGridY models per launch (every pointer
+// advanced past the models launched before).  ALB: a coloured batch (model_of).
+template <bool ALB, class Draws>
+static int launch_small(int kind, const SmallLaunch& L, Draws draws, const Scratch* w) {
+  const int64_t N = L.N, cells = L.d.rows * L.d.W;
+  unsigned long long* steps = nullptr;
+  if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& Q = *L.P;
+  const bool fluvial = kind == FLUVIAL;
+  const int64_t cnt = w ? w->tiles + 1 : 0;
+  if (w) SOIL_HIP(hipMemsetAsync(w->count, 0, 2 * sizeof(uint32_t) * (w->fill - w->count), L.st));  // count, fill
+  // the packed rows: every row whose stencil the slab holds
+  const int64_t lo = stencil_lo(L.d), packed = (stencil_hi(L.d) - lo + 1) * L.d.W;
+  for (int64_t b0 = 0; b0 < L.B; b0 += kMaxGridY) {
+    const unsigned nb = static_cast<unsigned>(L.B - b0 < kMaxGridY ? L.B - b0 : kMaxGridY);
+    const int64_t m = b0 * cells;
+    const Draws dr = draws.from_model(b0);
+    const float2* layers = reinterpret_cast<const float2*>(Q.layers) + m;
+    const float2* velocity = reinterpret_cast<const float2*>(fluvial ? Q.velocity : Q.debrisVelocity) + m;
+    float* const albedoFlux = L.albedoFlux ? L.albedoFlux + 3 * m : nullptr;
+    const float* const albedoSource = L.albedoSource ? L.albedoSource + 3 * m : nullptr;
+    const FluvialPlanes PF{Q.waterFlux + m, Q.massFlux + m, Q.velocityFlux + 2 * m, albedoFlux, Q.rainfall + m,
+                           Q.waterHeight + m, albedoSource, L.remote0, steps, L.remoteA};
+    const DebrisPlanes PD{Q.debrisFlux + m, Q.debrisVelocityFlux + 2 * m, albedoFlux, albedoSource, L.remote0,
+                          steps, L.remoteA};
+    const dim3 walkers(blocks_for(N, kPBlock), nb);
+    if (!w) {
+      const DirectFields F{layers, velocity, L.d, L.s, L.p.exitSlope};
+      if (fluvial)
+        k_fluvial_direct<Draws, ALB><<<walkers, kPBlock, 0, L.st>>>(PF, dr, N, F, L.p);
+      else
+        k_debris_direct<Draws, ALB><<<walkers, kPBlock, 0, L.st>>>(PD, dr, N, F, L.p);
+      SOIL_LAUNCH_CHECK();
+      continue;
+    }
+    float4* p4 = w->p4 + m;
+    float2 *spawn = w->spawn + b0 * N, *sorted = w->sorted + b0 * N;
+    uint32_t *count = w->count + b0 * cnt, *fill = w->fill + b0 * cnt, *start = w->start + b0 * cnt;
+    if (packed > 0)
+      k_pack_fields<<<dim3(blocks_for(packed, kPBlock), nb), kPBlock, 0, L.st>>>(p4, layers, velocity, L.d, L.s,
+                                                                                  L.p.exitSlope, lo, packed);
+    k_spawn_count<<<walkers, kPBlock, 0, L.st>>>(spawn, count, dr, N, L.d, w->tiles_w, w->tiles);
+    k_tile_scan<<<nb, 1024, 0, L.st>>>(start, count, w->tiles);
+    k_spawn_scatter<<<walkers, kPBlock, 0, L.st>>>(sorted, fill, start, spawn, N, L.d, w->tiles_w, w->tiles);
+    const dim3 traced(blocks_for(N, kPBlock) + 8, nb);
+    if (fluvial)
+      k_fluvial_sorted<ALB><<<traced, kPBlock, 0, L.st>>>(PF, sorted, start, w->tiles, N, PackedFields{p4}, L.d,
+                                                          L.s, L.p);
+    else
+      k_debris_sorted<ALB><<<traced, kPBlock, 0, L.st>>>(PD, sorted, start, w->tiles, N, PackedFields{p4}, L.d,
+                                                         L.s, L.p);
+    SOIL_LAUNCH_CHECK();
+  }
   return SOIL_OK;
 }
 
@@ -549,193 +671,28 @@ static float* colour_flux(const Launch& L, int kind) {
   return L.C ? (kind == FLUVIAL ? L.C->albedo_fluvial : L.C->albedo_debris) : nullptr;
 }
 
-int particles_fluvial(const Launch& L) {
+// One launch of a single model: the tiled shape, or the small-N shapes on the kind's tensor (workspace slot 1)
+static int particles_single(int kind, const Launch& L) {
   const int64_t N = L.N;
   if (N <= 0) return SOIL_OK;
-  if (use_tiled(N, L.d)) return launch_pass_tiled(FLUVIAL, L);
-  if (int rc = materialise(L.fluvial, N, L.st); rc != SOIL_OK) return rc;
-  unsigned long long* steps = nullptr;
-  if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& Q = *L.P;
-  float* const albedoFlux = colour_flux(L, FLUVIAL);
-  const FluvialPlanes P{Q.waterFlux, Q.massFlux, Q.velocityFlux, albedoFlux, Q.rainfall, Q.waterHeight,
-                        albedoFlux ? L.C->albedo_surface : nullptr, L.remote0, steps,
-                        albedoFlux ? L.remote_colour : nullptr};
-  soil_rng* const rng = L.fluvial.rng;
-  if (use_staged(N)) {
-    Staged sg;
-    int rc = stage(&sg, rng, N, Q.layers, Q.velocity, L.d, L.s, L.p, L.st);
-    if (rc != SOIL_OK) return rc;
-    k_fluvial_sorted<<<blocks_for(N, kPBlock) + 8, kPBlock, 0, L.st>>>(
-        P, sg.sorted, sg.total, N, PackedFields{sg.p4}, L.d, L.s, L.p);
-  } else {
-    const DirectFields F{reinterpret_cast<const float2*>(Q.layers),
-                         reinterpret_cast<const float2*>(Q.velocity), L.d, L.s, L.p.exitSlope};
-    k_fluvial_direct<<<blocks_for(N, kPBlock), kPBlock, 0, L.st>>>(P, rng, N, F, L.p);
-  }
-  SOIL_LAUNCH_CHECK();
-  return SOIL_OK;
+  if (use_tiled(N, L.d)) return launch_pass_tiled(kind, L);
+  const Streams& streams = kind == FLUVIAL ? L.fluvial : L.debris;
+  if (int rc = materialise(streams, N, L.st); rc != SOIL_OK) return rc;
+  Scratch w{};
+  const bool staged = use_staged(N);
+  if (staged)
+    if (int rc = scratch_get(1, 0, 1, N, L.d, true, &w); rc != SOIL_OK) return rc;
+  float* const albedoFlux = colour_flux(L, kind);
+  const SmallLaunch S{L.P, albedoFlux, albedoFlux ? L.C->albedo_surface : nullptr, L.remote0,
+                      albedoFlux ? L.remote_colour : nullptr, 1, N, L.d, L.s, L.p, L.st};
+  return launch_small<false>(kind, S, TensorDraws{streams.rng}, staged ? &w : nullptr);
 }
+
+int particles_fluvial(const Launch& L) { return particles_single(FLUVIAL, L); }
 
 // (with colour planes every walker is walked to the end: retirement makes no difference to the planes, and only
 // the overlapped pair retires with colour)
-int particles_debris(const Launch& L) {
-  const int64_t N = L.N;
-  if (N <= 0) return SOIL_OK;
-  if (use_tiled(N, L.d)) return launch_pass_tiled(DEBRIS, L);
-  if (int rc = materialise(L.debris, N, L.st); rc != SOIL_OK) return rc;
-  unsigned long long* steps = nullptr;
-  if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& Q = *L.P;
-  float* const albedoFlux = colour_flux(L, DEBRIS);
-  const DebrisPlanes P{Q.debrisFlux, Q.debrisVelocityFlux, albedoFlux, albedoFlux ? L.C->albedo_surface : nullptr,
-                       L.remote0, steps, albedoFlux ? L.remote_colour : nullptr};
-  soil_rng* const rng = L.debris.rng;
-  if (use_staged(N)) {
-    Staged sg;
-    int rc = stage(&sg, rng, N, Q.layers, Q.debrisVelocity, L.d, L.s, L.p, L.st);
-    if (rc != SOIL_OK) return rc;
-    k_debris_sorted<<<blocks_for(N, kPBlock) + 8, kPBlock, 0, L.st>>>(
-        P, sg.sorted, sg.total, N, PackedFields{sg.p4}, L.d, L.s, L.p);
-  } else {
-    const DirectFields F{reinterpret_cast<const float2*>(Q.layers),
-                         reinterpret_cast<const float2*>(Q.debrisVelocity), L.d, L.s, L.p.exitSlope};
-    k_debris_direct<<<blocks_for(N, kPBlock), kPBlock, 0, L.st>>>(P, rng, N, F, L.p);
-  }
-  SOIL_LAUNCH_CHECK();
-  return SOIL_OK;
-}
-
-// ---- batches: B independent models of one (H, W) grid ------------------------------------
-//
-// soil_particles_batch (soil_hip.h).  Every plane holds B whole-grid models one after the other (model b of
-// a plane of C channels starts at element b * H * W * C) and grid.y is the model: a lane walks walker n of
-// model blockIdx.y through trace_fluvial / trace_debris on that model's planes, so what it deposits stays in
-// its model, a NaN walker's (0, 0) included.  The streams are uniform (Streams): walker n of model b draws
-// from (seeds[b], n, offset), the state soil_erode_step seeds into its tensor for that model alone.  The host
-// launches at most kMaxGridY models at a time, every pointer advanced past the models launched before.
-
-constexpr int64_t kMaxGridY = 65535;
-
-__device__ __forceinline__ int64_t model_base(int64_t cells) { return static_cast<int64_t>(blockIdx.y) * cells; }
-// ALB: a coloured batch (soil_particles_batch_colour) — the colour flux plane and the spawn colours
-// (albedo_surface) are advanced too, where set; the physics batch's kernels never touch them
-template <bool ALB>
-__device__ __forceinline__ FluvialPlanes model_of(FluvialPlanes P, int64_t cells) {
-  const int64_t m = model_base(cells);
-  P.waterFlux += m, P.massFlux += m, P.velocityFlux += 2 * m, P.waterSource += m, P.waterHeight += m;
-  if constexpr (ALB) {
-    if (P.albedoFlux) P.albedoFlux += 3 * m;
-    if (P.albedoSource) P.albedoSource += 3 * m;
-  }
-  return P;
-}
-template <bool ALB>
-__device__ __forceinline__ DebrisPlanes model_of(DebrisPlanes P, int64_t cells) {
-  const int64_t m = model_base(cells);
-  P.massFlux += m, P.velocityFlux += 2 * m;
-  if constexpr (ALB) {
-    if (P.albedoFlux) P.albedoFlux += 3 * m;
-    if (P.albedoSource) P.albedoSource += 3 * m;
-  }
-  return P;
-}
-__device__ __forceinline__ DirectFields model_of(DirectFields F, int64_t cells) {
-  const int64_t m = model_base(cells);
-  F.layers += m, F.velocity += m;
-  return F;
-}
-__device__ __forceinline__ Streams model_streams(const uint64_t* __restrict__ seeds, uint64_t offset) {
-  return Streams{nullptr, true, seeds[blockIdx.y], offset};
-}
-
-// direct: thread n = walker n of model blockIdx.y (every spawn lies in the whole grid: no ownership test)
-template <bool ALB>
-__global__ void __launch_bounds__(kPBlock)
-    k_fluvial_direct_batch(FluvialPlanes P, const uint64_t* __restrict__ seeds, uint64_t offset, int64_t N,
-                           DirectFields F, Param param) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
-  const int64_t cells = F.d.H * F.d.W;
-  const float2 pos = spawn_position(model_streams(seeds, offset), n, F.d);
-  trace_fluvial(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
-}
-
-template <bool ALB>
-__global__ void __launch_bounds__(kPBlock)
-    k_debris_direct_batch(DebrisPlanes P, const uint64_t* __restrict__ seeds, uint64_t offset, int64_t N,
-                          DirectFields F, Param param) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
-  const int64_t cells = F.d.H * F.d.W;
-  const float2 pos = spawn_position(model_streams(seeds, offset), n, F.d);
-  trace_debris(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
-}
-
-// staged: k_pack_fields .. k_*_sorted per model; model b's spawn and sorted arrays start at b * N, its tile
-// counts, fills and starts at b * (tiles + 1)
-__global__ void __launch_bounds__(kPBlock)
-    k_pack_fields_batch(float4* __restrict__ p4, const float2* __restrict__ layers,
-                        const float2* __restrict__ velocity, Dom d, Scale3 s, float exitSlope) {
-  const int64_t cells = d.H * d.W;
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (t >= cells) return;
-  const int64_t m = model_base(cells);
-  const float2 g = glocal(layers + m, d, s, t / d.W, t % d.W, exitSlope);
-  const float2 v = velocity[m + t];
-  p4[m + t] = make_float4(g.x, g.y, v.x, v.y);
-}
-
-__global__ void __launch_bounds__(kPBlock)
-    k_spawn_count_batch(float2* __restrict__ spawn, uint32_t* __restrict__ count,
-                        const uint64_t* __restrict__ seeds, uint64_t offset, int64_t N, Dom d, int64_t tiles_w,
-                        int64_t tiles) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
-  const float2 pos = spawn_position(model_streams(seeds, offset), n, d);
-  spawn[model_base(N) + n] = pos;
-  atomicAdd(&count[model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w)], 1u);
-}
-
-// one work-group per model
-__global__ void __launch_bounds__(1024)
-    k_tile_scan_batch(uint32_t* start, const uint32_t* count, int64_t tiles) {
-  const int64_t m = static_cast<int64_t>(blockIdx.x) * (tiles + 1);
-  tile_scan_group(start + m, count + m, tiles);
-}
-
-__global__ void __launch_bounds__(kPBlock)
-    k_spawn_scatter_batch(float2* __restrict__ sorted, uint32_t* __restrict__ fill,
-                          const uint32_t* __restrict__ start, const float2* __restrict__ spawn, int64_t N, Dom d,
-                          int64_t tiles_w, int64_t tiles) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
-  const float2 pos = spawn[model_base(N) + n];
-  const int64_t tile = model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w);
-  sorted[model_base(N) + start[tile] + atomicAdd(&fill[tile], 1u)] = pos;
-}
-
-template <bool ALB>
-__global__ void __launch_bounds__(kPBlock)
-    k_fluvial_sorted_batch(FluvialPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
-                           int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
-  const int64_t t = sorted_slot(start + model_base(tiles + 1) + tiles);
-  if (t < 0) return;
-  const int64_t cells = d.H * d.W;
-  const float2 pos = sorted[model_base(N) + t];
-  trace_fluvial(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
-}
-
-template <bool ALB>
-__global__ void __launch_bounds__(kPBlock)
-    k_debris_sorted_batch(DebrisPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
-                          int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
-  const int64_t t = sorted_slot(start + model_base(tiles + 1) + tiles);
-  if (t < 0) return;
-  const int64_t cells = d.H * d.W;
-  const float2 pos = sorted[model_base(N) + t];
-  trace_debris(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
-}
+int particles_debris(const Launch& L) { return particles_single(DEBRIS, L); }
 
 // The seeds of a batch reach the device through a pinned buffer of the host thread (the caller's array may go
 // as soon as the call returns): before it is written again, the copy queued from it the call before has been
@@ -776,84 +733,10 @@ static int upload_seeds(uint64_t* dst, const uint64_t* seeds, int64_t B, hipStre
   return SOIL_OK;
 }
 
-namespace {
-// One launch of a batch: the planes, the colour planes (null: physics only), the device seeds, the first draw
-// of the kind's streams.
-struct BatchLaunch {
-  const soil_erosion_planes* P;
-  const soil_colour_planes* C;
-  int64_t B, N;
-  const uint64_t* seeds;
-  uint64_t offset;
-  Dom d;
-  Scale3 s;
-  Param p;
-  hipStream_t st;
-};
-// the staged shape's scratch for all B models (the workspace's; valid until the next batch launch)
-struct BatchScratch {
-  float4* p4;
-  float2 *spawn, *sorted;
-  uint32_t *count, *fill, *start;  // count and fill adjacent
-  int64_t tiles_w, tiles;
-};
-}  // namespace
-
-static int launch_batch(int kind, const BatchLaunch& L, const BatchScratch& w, bool staged) {
-  const int64_t N = L.N, cells = L.d.H * L.d.W;
-  unsigned long long* steps = nullptr;
-  if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& Q = *L.P;
-  const bool fluvial = kind == FLUVIAL;
-  const uint64_t offset = fluvial ? L.offset : L.offset + 2;  // the debris launch: two draws on
-  const int64_t cnt = w.tiles + 1;
-  if (staged) SOIL_HIP(hipMemsetAsync(w.count, 0, 2 * sizeof(uint32_t) * static_cast<size_t>(L.B * cnt), L.st));
-  for (int64_t b0 = 0; b0 < L.B; b0 += kMaxGridY) {
-    const unsigned nb = static_cast<unsigned>(L.B - b0 < kMaxGridY ? L.B - b0 : kMaxGridY);
-    const int64_t m = b0 * cells;
-    const uint64_t* seeds = L.seeds + b0;
-    const float2* layers = reinterpret_cast<const float2*>(Q.layers) + m;
-    const float2* velocity = reinterpret_cast<const float2*>(fluvial ? Q.velocity : Q.debrisVelocity) + m;
-    // with colour: the kind's colour flux plane and the spawn colours (albedo_surface, also in the staged
-    // shape: the packed fields hold none), both vec3 planes
-    float* const albedoFlux = L.C ? (fluvial ? L.C->albedo_fluvial : L.C->albedo_debris) + 3 * m : nullptr;
-    const float* const albedoSource = L.C ? L.C->albedo_surface + 3 * m : nullptr;
-    const FluvialPlanes PF{Q.waterFlux + m, Q.massFlux + m, Q.velocityFlux + 2 * m, albedoFlux, Q.rainfall + m,
-                           Q.waterHeight + m, albedoSource, nullptr, steps};
-    const DebrisPlanes PD{Q.debrisFlux + m, Q.debrisVelocityFlux + 2 * m, albedoFlux, albedoSource, nullptr, steps};
-    const dim3 walkers(blocks_for(N, kPBlock), nb);
-    const bool alb = L.C != nullptr;
-    if (!staged) {
-      const DirectFields F{layers, velocity, L.d, L.s, L.p.exitSlope};
-      if (fluvial)
-        (alb ? k_fluvial_direct_batch<true> : k_fluvial_direct_batch<false>)<<<walkers, kPBlock, 0, L.st>>>(
-            PF, seeds, offset, N, F, L.p);
-      else
-        (alb ? k_debris_direct_batch<true> : k_debris_direct_batch<false>)<<<walkers, kPBlock, 0, L.st>>>(
-            PD, seeds, offset, N, F, L.p);
-      SOIL_LAUNCH_CHECK();
-      continue;
-    }
-    float4* p4 = w.p4 + m;
-    float2 *spawn = w.spawn + b0 * N, *sorted = w.sorted + b0 * N;
-    uint32_t *count = w.count + b0 * cnt, *fill = w.fill + b0 * cnt, *start = w.start + b0 * cnt;
-    k_pack_fields_batch<<<dim3(blocks_for(cells, kPBlock), nb), kPBlock, 0, L.st>>>(p4, layers, velocity, L.d, L.s,
-                                                                                     L.p.exitSlope);
-    k_spawn_count_batch<<<walkers, kPBlock, 0, L.st>>>(spawn, count, seeds, offset, N, L.d, w.tiles_w, w.tiles);
-    k_tile_scan_batch<<<nb, 1024, 0, L.st>>>(start, count, w.tiles);
-    k_spawn_scatter_batch<<<walkers, kPBlock, 0, L.st>>>(sorted, fill, start, spawn, N, L.d, w.tiles_w, w.tiles);
-    const dim3 traced(blocks_for(N, kPBlock) + 8, nb);
-    if (fluvial)
-      (alb ? k_fluvial_sorted_batch<true> : k_fluvial_sorted_batch<false>)<<<traced, kPBlock, 0, L.st>>>(
-          PF, sorted, start, w.tiles, N, PackedFields{p4}, L.d, L.s, L.p);
-    else
-      (alb ? k_debris_sorted_batch<true> : k_debris_sorted_batch<false>)<<<traced, kPBlock, 0, L.st>>>(
-          PD, sorted, start, w.tiles, N, PackedFields{p4}, L.d, L.s, L.p);
-    SOIL_LAUNCH_CHECK();
-  }
-  return SOIL_OK;
-}
-
+// soil_particles_batch (soil_hip.h): B whole-grid models, one after the other in every plane; walker n of model b
+// draws from (seeds[b], n, offset), the state soil_erode_step seeds into its tensor for that model alone.  What
+// a lane deposits stays in its model, a NaN walker's (0, 0) included.  Workspace slot 11: the device seeds, then
+// the staged scratch of all B models.
 int particles_batch(const soil_erosion_planes* P, const soil_colour_planes* C, int64_t B, int64_t H, int64_t W,
                     int64_t N, const uint64_t* seeds, uint64_t step_index, const float scale[3],
                     const soil_param* param, hipStream_t st) {
@@ -864,28 +747,23 @@ int particles_batch(const soil_erosion_planes* P, const soil_colour_planes* C, i
   if (N == 0) return SOIL_OK;
   const bool staged = use_staged(N);  // the single model's rule; what would be tiled alone runs staged
   const Dom d = full_domain(H, W);
-  BatchScratch w{};
-  w.tiles_w = (W + kTile - 1) / kTile;
-  w.tiles = w.tiles_w * ((H + kTile - 1) / kTile);
-  auto align = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
-  const size_t b_seeds = align(sizeof(uint64_t) * static_cast<size_t>(B));
-  const size_t b_p4 = staged ? align(sizeof(float4) * static_cast<size_t>(B * H * W)) : 0;
-  const size_t b_pos = staged ? align(sizeof(float2) * static_cast<size_t>(B * N)) : 0;
-  const size_t b_cnt = staged ? align(sizeof(uint32_t) * static_cast<size_t>(B * (w.tiles + 1))) : 0;
-  void* base = nullptr;
-  if (int rc = workspace_get(11, b_seeds + b_p4 + 2 * b_pos + 3 * b_cnt, &base); rc != SOIL_OK) return rc;
-  char* c = static_cast<char*>(base);
-  uint64_t* seeds_dev = reinterpret_cast<uint64_t*>(c);      c += b_seeds;
-  w.p4 = reinterpret_cast<float4*>(c);                       c += b_p4;
-  w.spawn = reinterpret_cast<float2*>(c);                    c += b_pos;
-  w.sorted = reinterpret_cast<float2*>(c);                   c += b_pos;
-  w.count = reinterpret_cast<uint32_t*>(c);                  c += b_cnt;
-  w.fill = w.count + B * (w.tiles + 1);                      c += b_cnt;
-  w.start = reinterpret_cast<uint32_t*>(c);
+  Scratch w{};
+  if (int rc = scratch_get(11, sizeof(uint64_t) * static_cast<size_t>(B), B, N, d, staged, &w); rc != SOIL_OK)
+    return rc;
+  uint64_t* const seeds_dev = static_cast<uint64_t*>(w.lead);
   if (int rc = upload_seeds(seeds_dev, seeds, B, st); rc != SOIL_OK) return rc;
-  const BatchLaunch L{P, C, B, N, seeds_dev, step_index * static_cast<uint64_t>(N), d, s3p(scale), *param, st};
-  if (int rc = launch_batch(FLUVIAL, L, w, staged); rc != SOIL_OK) return rc;
-  return launch_batch(DEBRIS, L, w, staged);
+  const uint64_t offset = step_index * static_cast<uint64_t>(N);
+  for (int kind : {FLUVIAL, DEBRIS}) {
+    // with colour: the kind's colour flux plane and the spawn colours (albedo_surface, also in the staged
+    // shape: the packed fields hold none)
+    const SmallLaunch S{P, C ? (kind == FLUVIAL ? C->albedo_fluvial : C->albedo_debris) : nullptr,
+                        C ? C->albedo_surface : nullptr, nullptr, nullptr, B, N, d, s3p(scale), *param, st};
+    const SeedDraws draws{seeds_dev, kind == FLUVIAL ? offset : offset + 2};  // the debris launch: two draws on
+    const int rc = C ? launch_small<true>(kind, S, draws, staged ? &w : nullptr)
+                     : launch_small<false>(kind, S, draws, staged ? &w : nullptr);
+    if (rc != SOIL_OK) return rc;
+  }
+  return SOIL_OK;
 }
 
 int particles_pair(const Launch& L) {
@@ -1041,10 +919,7 @@ int soil_particles_pair_slab_ex(const soil_erosion_planes* planes, soil_rng* rng
                                 int flags, void* stream) {
   SOIL_DEVICE();
   SOIL_REQUIRE(planes && dom && scale && param, "particles_pair_slab: null argument");
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
-                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
-               "particles_pair_slab: null plane");
+  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_pair_slab: null plane");
   SOIL_REQUIRE(N >= 0 && (N == 0 || (rng_fluvial && rng_debris && rng_fluvial != rng_debris)),
                "particles_pair_slab: needs two distinct rng tensors");
   const Dom d = to_dom(dom);
@@ -1059,12 +934,8 @@ int soil_particles_pair_colour(const soil_erosion_planes* planes, const soil_col
                                const float scale[3], const soil_param* param, int flags, void* stream) {
   SOIL_DEVICE();
   SOIL_REQUIRE(planes && colour && scale && param, "particles_pair_colour: null argument");
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
-                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
-               "particles_pair_colour: null plane");
-  SOIL_REQUIRE(colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial && colour->albedo_debris,
-               "particles_pair_colour: every colour plane is required");
+  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_pair_colour: null plane");
+  SOIL_REQUIRE(has_colour(colour), "particles_pair_colour: every colour plane is required");
   SOIL_REQUIRE(H > 0 && W > 0, "particles_pair_colour: empty grid");
   SOIL_REQUIRE(N >= 0 && (N == 0 || (rng_fluvial && rng_debris && rng_fluvial != rng_debris)),
                "particles_pair_colour: needs two distinct rng tensors");
@@ -1082,11 +953,8 @@ int soil_particles_pair_colour_slab(const soil_erosion_planes* planes, const soi
                                     void* stream) {
   SOIL_DEVICE();
   SOIL_REQUIRE(planes && colour && dom && scale && param, "particles_pair_colour_slab: null argument");
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
-                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
-               "particles_pair_colour_slab: null plane");
-  SOIL_REQUIRE(colour->albedo_surface && colour->albedo_fluvial && colour->albedo_debris,
+  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_pair_colour_slab: null plane");
+  SOIL_REQUIRE(has_colour(colour, false),
                "particles_pair_colour_slab: albedo_surface, albedo_fluvial and albedo_debris are required");
   SOIL_REQUIRE(N >= 0 && (N == 0 || (rng_fluvial && rng_debris && rng_fluvial != rng_debris)),
                "particles_pair_colour_slab: needs two distinct rng tensors");
@@ -1105,10 +973,7 @@ int soil_particles_batch(const soil_erosion_planes* planes, int64_t B, int64_t H
   SOIL_DEVICE();
   SOIL_REQUIRE(planes && scale && param, "particles_batch: null argument");
   if (int rc = check_batch(B, H, W, N, seeds, "particles_batch"); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
-                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
-               "particles_batch: null plane");
+  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch: null plane");
   return particles_batch(planes, nullptr, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
 }
 
@@ -1117,14 +982,9 @@ int soil_particles_batch_colour(const soil_erosion_planes* planes, const soil_co
                                 const float scale[3], const soil_param* param, void* stream) {
   SOIL_DEVICE();
   SOIL_REQUIRE(planes && scale && param, "particles_batch_colour: null argument");
-  SOIL_REQUIRE(colour && colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial &&
-                   colour->albedo_debris,
-               "particles_batch_colour: every colour plane is required");
+  SOIL_REQUIRE(has_colour(colour), "particles_batch_colour: every colour plane is required");
   if (int rc = check_batch(B, H, W, N, seeds, "particles_batch_colour"); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.rainfall && P.waterHeight && P.waterFlux && P.massFlux && P.velocity &&
-                   P.velocityFlux && P.debrisFlux && P.debrisVelocity && P.debrisVelocityFlux,
-               "particles_batch_colour: null plane");
+  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch_colour: null plane");
   return particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
 }
 

@@ -101,10 +101,7 @@ int soil_erode_step_ex(const soil_erosion_planes* planes, soil_rng* rng, int64_t
   SOIL_REQUIRE(planes && rng && scale && param, "erode_step: null argument");
   SOIL_REQUIRE(H > 0 && W > 0 && N > 0, "erode_step: empty grid or no particles");
   const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux &&
-                   P.mass && P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux &&
-                   P.debrisVelocity && P.debrisVelocityFlux,
-               "erode_step: every plane but `height` is required");
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step: every plane but `height` is required");
   const soil_domain dom{H, W, 0, H, 0, H};
   // One stream of draws per particle and step: (seed, subsequence n, offset step * N).  The
   // fluvial launch takes draws 0 and 1 of every stream, the debris launch draws 2 and 3.
@@ -143,12 +140,8 @@ int soil_erode_step_colour(const soil_erosion_planes* planes, const soil_colour_
   SOIL_REQUIRE(planes && colour && rng && scale && param, "erode_step_colour: null argument");
   SOIL_REQUIRE(H > 0 && W > 0 && N > 0, "erode_step_colour: empty grid or no particles");
   const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux &&
-                   P.mass && P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux &&
-                   P.debrisVelocity && P.debrisVelocityFlux,
-               "erode_step_colour: every plane but `height` is required");
-  SOIL_REQUIRE(colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial && colour->albedo_debris,
-               "erode_step_colour: every colour plane is required");
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_colour: every plane but `height` is required");
+  SOIL_REQUIRE(has_colour(colour), "erode_step_colour: every colour plane is required");
   // the overlapped launches whatever SOIL_STEP_PAIR says
   return erode_step(planes, colour, rng, N, seed, step_index * static_cast<uint64_t>(N), H, W, scale, param, flags,
                     stream);
@@ -163,10 +156,7 @@ int soil_erode_step_batch(const soil_erosion_planes* planes, int64_t B, int64_t 
   SOIL_REQUIRE(planes && scale && param, "erode_step_batch: null argument");
   if (int rc = check_batch(B, H, W, N, seeds, "erode_step_batch"); rc != SOIL_OK) return rc;
   const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux &&
-                   P.mass && P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux &&
-                   P.debrisVelocity && P.debrisVelocityFlux,
-               "erode_step_batch: every plane but `height` is required");
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch: every plane but `height` is required");
   SOIL_REQUIRE(P.layers != P.layers_next, "erode_step_batch: layers and layers_next must be distinct buffers");
   const hipStream_t st = as_stream(stream);
   if (int rc = particles_batch(planes, nullptr, B, H, W, N, seeds, step_index, scale, param, st); rc != SOIL_OK)
@@ -181,15 +171,10 @@ int soil_erode_step_batch_colour(const soil_erosion_planes* planes, const soil_c
                                  const float scale[3], const soil_param* param, void* stream) {
   SOIL_DEVICE();
   SOIL_REQUIRE(planes && scale && param, "erode_step_batch_colour: null argument");
-  SOIL_REQUIRE(colour && colour->albedo_bedrock && colour->albedo_surface && colour->albedo_fluvial &&
-                   colour->albedo_debris,
-               "erode_step_batch_colour: every colour plane is required");
+  SOIL_REQUIRE(has_colour(colour), "erode_step_batch_colour: every colour plane is required");
   if (int rc = check_batch(B, H, W, N, seeds, "erode_step_batch_colour"); rc != SOIL_OK) return rc;
   const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(P.layers && P.layers_next && P.uplift && P.rainfall && P.waterHeight && P.waterFlux &&
-                   P.mass && P.massFlux && P.velocity && P.velocityFlux && P.debris && P.debrisFlux &&
-                   P.debrisVelocity && P.debrisVelocityFlux,
-               "erode_step_batch_colour: every plane but `height` is required");
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch_colour: every plane but `height` is required");
   SOIL_REQUIRE(P.layers != P.layers_next,
                "erode_step_batch_colour: layers and layers_next must be distinct buffers");
   const hipStream_t st = as_stream(stream);

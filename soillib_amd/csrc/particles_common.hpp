@@ -143,11 +143,6 @@ bool use_tiled_launch(int64_t N, const Dom& d);
 int debris_retire_mode();    // soil_set_debris_retire / SOIL_DEBRIS_RETIRE (erosion_particles.hip): 0 off, 1 on, 2 watched
 bool particle_arith_fast();  // soil_set_particle_arith(1) / SOIL_PARTICLE_DIV=fast (erosion_particles.hip)
 
-// exclusive scan of per-tile counts, start[tiles] = total (one 1024-thread group;
-// defined in erosion_particles.hip)
-__global__ void __launch_bounds__(1024)
-    k_tile_scan(uint32_t* start, const uint32_t* count, int64_t tiles);
-
 // tiled launch shape (erosion_particles_tiled.hip)
 // One launch of `kind` (FLUVIAL, DEBRIS) in the tiled shape whatever N: from the streams' spawns (`inbox` null)
 // or from `n_in` handed-over records; leavers into `box` (none: dropped).

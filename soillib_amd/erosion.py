@@ -279,20 +279,9 @@ class ErosionBatch:
     def _names(self):
         return ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2 + self._colour_names()
 
-    def _planes(self):
-        p = _abi.ErosionPlanes()
-        for name in _abi._PLANES:
-            setattr(p, name, getattr(self, name).ptr)
-        return p
-
-    def _colour(self):
-        c = _abi.ColourPlanes()
-        for field, name in zip(_abi.COLOUR_PLANES, self.PLANES_3):
-            setattr(c, field, getattr(self, name).ptr)
-        return c
-
-    def _scale(self):
-        return _abi.vec(self.scale, 3)
+    _planes = ErosionModel._planes
+    _colour = ErosionModel._colour
+    _scale = ErosionModel._scale
 
     def set_layers(self, layers_tensor):
         """Copy a (B, H, W, 2) tensor of (bedrock, sediment) into the batch."""
