@@ -492,6 +492,42 @@ int soil_erode_cells_fused_batch_colour(const soil_erosion_planes* planes, const
                                         int64_t B, int64_t H, int64_t W, const float scale[3],
                                         const soil_param* param, int flags, void* stream);
 
+/* ------------------------------------------ erosion: parameter sweeps */
+
+/* A sweep: a batch (soil_erode_step_batch, or with a non-NULL `colour` the coloured batch of
+ * soil_erode_step_batch_colour) in which model b steps with params[b], a soil_param of its own.  `params` is a
+ * host array of B values, copied before the call returns (as `seeds`); a change between calls takes effect at the
+ * next call.  Model b ends each step holding what soil_erode_step (with colour: soil_erode_step_colour) leaves on
+ * that model alone with seed = seeds[b] and param = params[b].  Every other rule of the batch holds: one (H, W),
+ * N, scale and step_index, model-major planes, a NaN walker's deposits in cell (0, 0) of its own model, flux
+ * planes zero on entry and exit, exact arithmetic, every walker walked to the end; only the fp32 order of the
+ * flux atomics may differ.  SOIL_ERR_INVALID_ARGUMENT for a NULL `params`, the sizes soil_erode_step_batch
+ * refuses, and a non-NULL `colour` with a NULL plane ("colour plane").
+ *
+ * Launch shapes: those of the (coloured) batch at the same B, N and (H, W), with the same kernels, each model
+ * reading its params[b] once per work-group (grid.y = model).  No launch shape depends on a value of `params`:
+ * a per-model maxage is only each walker's loop bound.  The params reach the device with the seeds in the
+ * batch's one host-to-device copy, so a sweep step issues as many dispatches as the batch step (14 physics, 17
+ * coloured, in the staged shape).  Algorithmic bytes: the batch's, plus one 112-byte parameter read per
+ * work-group of every launch (4 bytes per work-group of the pack pass) and B x 112 bytes copied per step.
+ *
+ * One step of every model: soil_particles_batch_params, then soil_erode_cells_fused_batch_params with flags 0,
+ * the params uploaded once for both. */
+int soil_erode_step_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                 int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
+                                 const float scale[3], const soil_param* params, void* stream);
+/* Both particle launches of a sweep step (soil_particles_batch / soil_particles_batch_colour, model b with
+ * params[b]).  With colour the two colour flux planes of all B models are cleared first, also when N == 0. */
+int soil_particles_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
+                                const float scale[3], const soil_param* params, void* stream);
+/* The cell phase of a sweep (soil_erode_cells_fused_batch / _colour, model b with params[b]), bit-identical per
+ * model to the single model's cell phase with params[b]; its own upload of `params` (one copy) before the
+ * batch's launches.  Bytes as there. */
+int soil_erode_cells_fused_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                        int64_t B, int64_t H, int64_t W, const float scale[3],
+                                        const soil_param* params, int flags, void* stream);
+
 /* The containers of the legacy API (example/erosion_gpu.py:44-71): model_t, the `data` and the
  * `track` buffers.  All float32 device planes of H*W cells ((H,W,2) for the momenta). */
 typedef struct soil_erode_model {

@@ -152,6 +152,13 @@ SIGNATURES = {
                                            C.POINTER(u64), u64, F3, C.POINTER(Param), vp]),
     "soil_erode_cells_fused_batch_colour": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64,
                                                    i64, F3, C.POINTER(Param), cint, vp]),
+    # a sweep: model b with params[b] (a host array of B); the colour planes may be NULL
+    "soil_erode_step_batch_params": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64, i64, i64,
+                                            C.POINTER(u64), u64, F3, C.POINTER(Param), vp]),
+    "soil_particles_batch_params": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64, i64, i64,
+                                           C.POINTER(u64), u64, F3, C.POINTER(Param), vp]),
+    "soil_erode_cells_fused_batch_params": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64,
+                                                   i64, F3, C.POINTER(Param), cint, vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),

@@ -78,9 +78,14 @@ inline bool has_planes(const soil_erosion_planes& P, PlaneSet set) {
 inline bool has_colour(const soil_colour_planes* C, bool bedrock = true) {
   return C && (C->albedo_bedrock || !bedrock) && C->albedo_surface && C->albedo_fluvial && C->albedo_debris;
 }
-// `colour` null: physics only; otherwise the four colour planes of all B models (soil_erode_cells_fused_batch_colour)
+// `colour` null: physics only; otherwise the four colour planes of all B models (soil_erode_cells_fused_batch_colour).
+// `params_dev` (a device array of B, or null: every model `param`): a sweep, model b with params_dev[b].
 int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
-                            int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st);
+                            int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st,
+                            const soil_param* params_dev = nullptr);
+// A sweep's B params (a host array) copied to the device in one copy through the batches' pinned staging, into
+// workspace slot 11 (erosion_particles.hip); *params_dev valid in stream order until the slot's next use.
+int batch_params_to_device(const soil_param* params, int64_t B, hipStream_t st, const soil_param** params_dev);
 
 // Launch shape of the per-cell kernels: threads along the contiguous axis, and a
 // work-group walks a band of kRowBand consecutive rows (SOIL_ROW_LOOP).  A 64-bit
@@ -124,6 +129,25 @@ struct Scale2 {
 
 // param_t travels to the kernels by value, like in the reference.
 using Param = soil_param;
+
+// Where a kernel's Param comes from, a compile-time choice (the batch kernels: grid.y is the model).  Every
+// kernel takes its model's Param once at entry into a local copy (`model()`); blockIdx.y is uniform over the
+// work-group, so a sweep's read is scalar loads, and the walks and cells see register-resident constants either
+// way.  `from_model(b0)`: the source of a launch whose model 0 is model b0 of the batch (grid.y <= 65535).
+struct UniformParam {  // one param_t for every model: the kernel argument itself
+  Param p;
+  static constexpr bool kPerModel = false;
+  UniformParam() = default;
+  UniformParam(const Param& q) : p(q) {}  // (implicit: the single-model launches pass a Param)
+  __device__ __forceinline__ Param model() const { return p; }
+  UniformParam from_model(int64_t) const { return *this; }
+};
+struct ModelParams {  // a sweep (soil_*_batch_params): model b steps with params[b], a device array of B
+  const Param* __restrict__ params;
+  static constexpr bool kPerModel = true;
+  __device__ __forceinline__ Param model() const { return params[blockIdx.y]; }
+  ModelParams from_model(int64_t b0) const { return ModelParams{params + b0}; }
+};
 
 // ---- device helpers shared by the erosion kernels --------------------------
 

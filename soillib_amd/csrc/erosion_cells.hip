@@ -5,6 +5,7 @@
 //   __transfer :453-574   __mass_creep :633-710   __layer_merge :733-745
 //   __albedo_layer :759-791   __albedo_stratum :794-826   __albedo_discharge :857-875
 #include <cstdlib>
+#include <type_traits>
 
 #include "cell_math.hpp"
 #include "window.hpp"
@@ -347,11 +348,15 @@ __device__ __forceinline__ void colour_cell(float fluvial[3], float debris[3], f
 // with REZERO = false.
 // BATCH: grid.y is the model of a batch of whole-grid models (soil_erode_cells_fused_batch, with ALB
 // soil_erode_cells_fused_batch_colour): every plane is advanced to model blockIdx.y, H x W cells per model.
+// Params: UniformParam, or with BATCH a sweep's ModelParams (soil_erode_cells_fused_batch_params, common.hpp); not
+// deduced, so that the single-model launches, which pass a Param, get UniformParam.
 template <bool XCD_REMAP, bool NT, int BLOCK = kBlock, bool DIRECT = false, bool REZERO = true, bool ALB = false,
-          bool BATCH = false>
+          bool BATCH = false, class Params = UniformParam>
 __global__ void __launch_bounds__(BLOCK)
-    k_erode_cells_fused(Planes P, Dom d, Scale3 s, Param p, int64_t groups_per_row,
+    k_erode_cells_fused(Planes P, Dom d, Scale3 s, std::type_identity_t<Params> ps, int64_t groups_per_row,
                         int64_t total_groups) {
+  static_assert(BATCH || !Params::kPerModel, "per-model params need the batch's grid.y");
+  const Param p = ps.model();
   if constexpr (BATCH) P = model_planes<ALB>(P, d.H * d.W);
   // group = kVec consecutive cells of one row; one thread per group
   int64_t blk = blockIdx.x;
@@ -521,11 +526,13 @@ __global__ void __launch_bounds__(kBlock)
   zv[0] = z, zv[1] = z, zd[0] = z, zd[1] = z;
 }
 
-// scalar path for W % 4 != 0 (ragged widths): one thread per cell (BATCH, ALB: as k_erode_cells_fused's; the
-// colour branch is taken wherever albedoSurface is set)
-template <bool BATCH = false, bool ALB = false>
+// scalar path for W % 4 != 0 (ragged widths): one thread per cell (BATCH, ALB, Params: as k_erode_cells_fused's;
+// the colour branch is taken wherever albedoSurface is set)
+template <bool BATCH = false, bool ALB = false, class Params = UniformParam>
 __global__ void __launch_bounds__(kBlock)
-    k_erode_cells_fused_scalar(Planes P, Dom d, Scale3 s, Param p, bool rezero) {
+    k_erode_cells_fused_scalar(Planes P, Dom d, Scale3 s, std::type_identity_t<Params> ps, bool rezero) {
+  static_assert(BATCH || !Params::kPerModel, "per-model params need the batch's grid.y");
+  const Param p = ps.model();
   if constexpr (BATCH) P = model_planes<ALB>(P, d.H * d.W);
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (t >= (d.r1 - d.r0) * d.W) return;
@@ -839,9 +846,10 @@ int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* c
 // erode_cells_fused, which makes every model bit-identical to it; the five flux planes are re-zeroed in the
 // kernel (112 bytes per cell) unless SOIL_CELLS_KEEP_FLUX (84).  With `colour` the coloured single model's
 // shape: the 168-byte kernel (ALB, flux planes kept), then one re-zero pass over the flux planes of all B
-// models unless SOIL_CELLS_KEEP_FLUX.
-int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
-                            int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st) {
+// models unless SOIL_CELLS_KEEP_FLUX.  Params: UniformParam{*param}, or a sweep's ModelParams (the same launches).
+template <class Params>
+static int cells_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
+                       int64_t W, const float scale[3], Params params, int flags, hipStream_t st) {
   const Dom d = full_domain(H, W);
   const int64_t cells = H * W;
   const bool keep = (flags & SOIL_CELLS_KEEP_FLUX) != 0;
@@ -853,30 +861,31 @@ int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_pla
   for (int64_t b0 = 0; b0 < B; b0 += kMaxModels) {
     const unsigned nb = static_cast<unsigned>(B - b0 < kMaxModels ? B - b0 : kMaxModels);
     const Planes P = planes_of(pl, colour, b0 * cells);
+    const Params ps = params.from_model(b0);
     const dim3 grid(nblk, nb);
     if (colour) {
       if (!vec_ok)
-        k_erode_cells_fused_scalar<true, true><<<grid, kBlock, 0, st>>>(P, d, s3(scale), *param, !keep);
+        k_erode_cells_fused_scalar<true, true, Params><<<grid, kBlock, 0, st>>>(P, d, s3(scale), ps, !keep);
       else if (remap)
-        k_erode_cells_fused<true, false, kBlock, false, false, true, true><<<grid, kBlock, 0, st>>>(
-            P, d, s3(scale), *param, groups_per_row, total);
+        k_erode_cells_fused<true, false, kBlock, false, false, true, true, Params><<<grid, kBlock, 0, st>>>(
+            P, d, s3(scale), ps, groups_per_row, total);
       else
-        k_erode_cells_fused<false, false, kBlock, false, false, true, true><<<grid, kBlock, 0, st>>>(
-            P, d, s3(scale), *param, groups_per_row, total);
+        k_erode_cells_fused<false, false, kBlock, false, false, true, true, Params><<<grid, kBlock, 0, st>>>(
+            P, d, s3(scale), ps, groups_per_row, total);
     } else if (!vec_ok)
-      k_erode_cells_fused_scalar<true><<<grid, kBlock, 0, st>>>(P, d, s3(scale), *param, !keep);
+      k_erode_cells_fused_scalar<true, false, Params><<<grid, kBlock, 0, st>>>(P, d, s3(scale), ps, !keep);
     else if (remap && keep)
-      k_erode_cells_fused<true, false, kBlock, false, false, false, true><<<grid, kBlock, 0, st>>>(
-          P, d, s3(scale), *param, groups_per_row, total);
+      k_erode_cells_fused<true, false, kBlock, false, false, false, true, Params><<<grid, kBlock, 0, st>>>(
+          P, d, s3(scale), ps, groups_per_row, total);
     else if (remap)
-      k_erode_cells_fused<true, false, kBlock, false, true, false, true><<<grid, kBlock, 0, st>>>(
-          P, d, s3(scale), *param, groups_per_row, total);
+      k_erode_cells_fused<true, false, kBlock, false, true, false, true, Params><<<grid, kBlock, 0, st>>>(
+          P, d, s3(scale), ps, groups_per_row, total);
     else if (keep)
-      k_erode_cells_fused<false, false, kBlock, false, false, false, true><<<grid, kBlock, 0, st>>>(
-          P, d, s3(scale), *param, groups_per_row, total);
+      k_erode_cells_fused<false, false, kBlock, false, false, false, true, Params><<<grid, kBlock, 0, st>>>(
+          P, d, s3(scale), ps, groups_per_row, total);
     else
-      k_erode_cells_fused<false, false, kBlock, false, true, false, true><<<grid, kBlock, 0, st>>>(
-          P, d, s3(scale), *param, groups_per_row, total);
+      k_erode_cells_fused<false, false, kBlock, false, true, false, true, Params><<<grid, kBlock, 0, st>>>(
+          P, d, s3(scale), ps, groups_per_row, total);
     SOIL_LAUNCH_CHECK();
   }
   if (colour && vec_ok && !keep) {  // the models are consecutive in every flux plane: one pass over all B
@@ -884,6 +893,13 @@ int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_pla
     SOIL_LAUNCH_CHECK();
   }
   return SOIL_OK;
+}
+
+int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
+                            int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st,
+                            const soil_param* params_dev) {
+  if (params_dev) return cells_batch(pl, colour, B, H, W, scale, ModelParams{params_dev}, flags, st);
+  return cells_batch(pl, colour, B, H, W, scale, UniformParam{*param}, flags, st);
 }
 
 }  // namespace soil
@@ -913,6 +929,24 @@ int soil_erode_cells_fused_batch_colour(const soil_erosion_planes* planes, const
   SOIL_REQUIRE(P.layers != P.layers_next,
                "erode_cells_fused_batch_colour: layers and layers_next must be distinct buffers");
   return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, flags, as_stream(stream));
+}
+
+// A sweep's cell phase: its own upload of the B params (one copy), then the batch's launches with ModelParams.
+int soil_erode_cells_fused_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                        int64_t B, int64_t H, int64_t W, const float scale[3],
+                                        const soil_param* params, int flags, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && scale && params, "erode_cells_fused_batch_params: null argument");
+  SOIL_REQUIRE(!colour || has_colour(colour), "erode_cells_fused_batch_params: every colour plane is required");
+  if (int rc = check_batch(B, H, W, 0, nullptr, "erode_cells_fused_batch_params"); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_cells_fused_batch_params: null plane (only `height` is optional)");
+  SOIL_REQUIRE(P.layers != P.layers_next,
+               "erode_cells_fused_batch_params: layers and layers_next must be distinct buffers");
+  const hipStream_t st = as_stream(stream);
+  const soil_param* params_dev = nullptr;
+  if (int rc = batch_params_to_device(params, B, st, &params_dev); rc != SOIL_OK) return rc;
+  return erode_cells_fused_batch(planes, colour, B, H, W, scale, nullptr, flags, st, params_dev);
 }
 
 int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* dom,

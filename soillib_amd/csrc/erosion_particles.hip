@@ -20,6 +20,7 @@
 // The reference's launch shape (thread n = particle n, direct stencil gathers)
 // is kept as `direct` mode for ablation (soil_set_particle_mode).
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <thread>
 
@@ -372,10 +373,13 @@ __device__ __forceinline__ DirectFields model_of(DirectFields F, int64_t cells) 
   return F;
 }
 
-// direct: thread n = walker n of model blockIdx.y
-template <class Draws, bool ALB>
+// direct: thread n = walker n of model blockIdx.y.  Params: UniformParam, or a sweep's ModelParams (common.hpp),
+// whose model's exitSlope replaces the one F was made with
+template <class Draws, bool ALB, class Params = UniformParam>
 __global__ void __launch_bounds__(kPBlock)
-    k_fluvial_direct(FluvialPlanes P, Draws draws, int64_t N, DirectFields F, Param param) {
+    k_fluvial_direct(FluvialPlanes P, Draws draws, int64_t N, DirectFields F, Params ps) {
+  const Param param = ps.model();
+  if constexpr (Params::kPerModel) F.exitSlope = param.exitSlope;
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
   if (n >= N) return;
   const float2 pos = draws.spawn(n, F.d);
@@ -384,9 +388,11 @@ __global__ void __launch_bounds__(kPBlock)
   trace_fluvial(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
 }
 
-template <class Draws, bool ALB>
+template <class Draws, bool ALB, class Params = UniformParam>
 __global__ void __launch_bounds__(kPBlock)
-    k_debris_direct(DebrisPlanes P, Draws draws, int64_t N, DirectFields F, Param param) {
+    k_debris_direct(DebrisPlanes P, Draws draws, int64_t N, DirectFields F, Params ps) {
+  const Param param = ps.model();
+  if constexpr (Params::kPerModel) F.exitSlope = param.exitSlope;
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
   if (n >= N) return;
   const float2 pos = draws.spawn(n, F.d);
@@ -395,12 +401,21 @@ __global__ void __launch_bounds__(kPBlock)
   trace_debris(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
 }
 
+// The pack pass's exitSlope: one for every model (the kernel argument), or a sweep's ModelParams
+struct ExitSlope {
+  float v;
+};
+__device__ __forceinline__ float exit_slope_of(const ExitSlope& e) { return e.v; }
+__device__ __forceinline__ float exit_slope_of(const ModelParams& m) { return m.params[blockIdx.y].exitSlope; }
+
 // staged, pre-pass: p4[cell] = {__glocal(cell), velocity[cell]} for every row with a full stencil (`cells` of
 // them per model from local row `row_lo`)
+template <class Slope = ExitSlope>
 __global__ void __launch_bounds__(kPBlock)
     k_pack_fields(float4* __restrict__ p4, const float2* __restrict__ layers,
-                  const float2* __restrict__ velocity, Dom d, Scale3 s, float exitSlope,
+                  const float2* __restrict__ velocity, Dom d, Scale3 s, Slope slope,
                   int64_t row_lo, int64_t cells) {
+  const float exitSlope = exit_slope_of(slope);
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
   if (t >= cells) return;
   const int64_t m = model_base(d.rows * d.W);
@@ -484,10 +499,11 @@ __device__ __forceinline__ int64_t sorted_slot(const uint32_t* __restrict__ tota
 }
 
 // pass 4: trace the owned walkers in tile order
-template <bool ALB>
+template <bool ALB, class Params = UniformParam>
 __global__ void __launch_bounds__(kPBlock)
     k_fluvial_sorted(FluvialPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
-                     int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
+                     int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Params ps) {
+  const Param param = ps.model();
   const int64_t t = sorted_slot(start + model_base(tiles + 1) + tiles);
   if (t < 0) return;
   const int64_t cells = d.rows * d.W;
@@ -495,10 +511,11 @@ __global__ void __launch_bounds__(kPBlock)
   trace_fluvial(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
 }
 
-template <bool ALB>
+template <bool ALB, class Params = UniformParam>
 __global__ void __launch_bounds__(kPBlock)
     k_debris_sorted(DebrisPlanes P, const float2* __restrict__ sorted, const uint32_t* __restrict__ start,
-                    int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Param param) {
+                    int64_t tiles, int64_t N, PackedFields F, Dom d, Scale3 s, Params ps) {
+  const Param param = ps.model();
   const int64_t t = sorted_slot(start + model_base(tiles + 1) + tiles);
   if (t < 0) return;
   const int64_t cells = d.rows * d.W;
@@ -597,6 +614,7 @@ static int scratch_get(int slot, size_t lead, int64_t B, int64_t N, const Dom& d
 
 // One launch of the small-N shapes: B models of domain d side by side (model b's planes b * rows * W cells on),
 // N walkers each.  `albedoFlux` / `albedoSource`: the kind's colour flux plane and the spawn colours, or null.
+// `p`: every model's param; a sweep's come from the ModelParams handed to launch_small instead.
 struct SmallLaunch {
   const soil_erosion_planes* P;
   float* albedoFlux;
@@ -610,10 +628,16 @@ struct SmallLaunch {
   hipStream_t st;
 };
 
+// the pack pass's exitSlope source for a launch's parameter source
+static ExitSlope pack_slope(const UniformParam& u) { return ExitSlope{u.p.exitSlope}; }
+static ModelParams pack_slope(const ModelParams& m) { return m; }
+
 // The direct shape (`w` null) or the staged shape in `w`, at most kMaxGridY models per launch (every pointer
-// advanced past the models launched before).  ALB: a coloured batch (model_of).
-template <bool ALB, class Draws>
-static int launch_small(int kind, const SmallLaunch& L, Draws draws, const Scratch* w) {
+// advanced past the models launched before).  ALB: a coloured batch (model_of).  Params: UniformParam{L.p}, or
+// a sweep's ModelParams (nothing about the launch depends on its values: per-model maxage is a walker's bound).
+template <bool ALB, class Draws, class Params = UniformParam>
+static int launch_small(int kind, const SmallLaunch& L, Draws draws, const Scratch* w, Params params = {}) {
+  if constexpr (!Params::kPerModel) params = UniformParam{L.p};
   const int64_t N = L.N, cells = L.d.rows * L.d.W;
   unsigned long long* steps = nullptr;
   if (int rc = step_counter(&steps); rc != SOIL_OK) return rc;
@@ -627,6 +651,7 @@ static int launch_small(int kind, const SmallLaunch& L, Draws draws, const Scrat
     const unsigned nb = static_cast<unsigned>(L.B - b0 < kMaxGridY ? L.B - b0 : kMaxGridY);
     const int64_t m = b0 * cells;
     const Draws dr = draws.from_model(b0);
+    const Params ps = params.from_model(b0);
     const float2* layers = reinterpret_cast<const float2*>(Q.layers) + m;
     const float2* velocity = reinterpret_cast<const float2*>(fluvial ? Q.velocity : Q.debrisVelocity) + m;
     float* const albedoFlux = L.albedoFlux ? L.albedoFlux + 3 * m : nullptr;
@@ -637,11 +662,11 @@ static int launch_small(int kind, const SmallLaunch& L, Draws draws, const Scrat
                           steps, L.remoteA};
     const dim3 walkers(blocks_for(N, kPBlock), nb);
     if (!w) {
-      const DirectFields F{layers, velocity, L.d, L.s, L.p.exitSlope};
+      const DirectFields F{layers, velocity, L.d, L.s, L.p.exitSlope};  // (a sweep's kernels take the model's)
       if (fluvial)
-        k_fluvial_direct<Draws, ALB><<<walkers, kPBlock, 0, L.st>>>(PF, dr, N, F, L.p);
+        k_fluvial_direct<Draws, ALB, Params><<<walkers, kPBlock, 0, L.st>>>(PF, dr, N, F, ps);
       else
-        k_debris_direct<Draws, ALB><<<walkers, kPBlock, 0, L.st>>>(PD, dr, N, F, L.p);
+        k_debris_direct<Draws, ALB, Params><<<walkers, kPBlock, 0, L.st>>>(PD, dr, N, F, ps);
       SOIL_LAUNCH_CHECK();
       continue;
     }
@@ -650,17 +675,17 @@ static int launch_small(int kind, const SmallLaunch& L, Draws draws, const Scrat
     uint32_t *count = w->count + b0 * cnt, *fill = w->fill + b0 * cnt, *start = w->start + b0 * cnt;
     if (packed > 0)
       k_pack_fields<<<dim3(blocks_for(packed, kPBlock), nb), kPBlock, 0, L.st>>>(p4, layers, velocity, L.d, L.s,
-                                                                                  L.p.exitSlope, lo, packed);
+                                                                                  pack_slope(ps), lo, packed);
     k_spawn_count<<<walkers, kPBlock, 0, L.st>>>(spawn, count, dr, N, L.d, w->tiles_w, w->tiles);
     k_tile_scan<<<nb, 1024, 0, L.st>>>(start, count, w->tiles);
     k_spawn_scatter<<<walkers, kPBlock, 0, L.st>>>(sorted, fill, start, spawn, N, L.d, w->tiles_w, w->tiles);
     const dim3 traced(blocks_for(N, kPBlock) + 8, nb);
     if (fluvial)
-      k_fluvial_sorted<ALB><<<traced, kPBlock, 0, L.st>>>(PF, sorted, start, w->tiles, N, PackedFields{p4}, L.d,
-                                                          L.s, L.p);
+      k_fluvial_sorted<ALB, Params><<<traced, kPBlock, 0, L.st>>>(PF, sorted, start, w->tiles, N,
+                                                                  PackedFields{p4}, L.d, L.s, ps);
     else
-      k_debris_sorted<ALB><<<traced, kPBlock, 0, L.st>>>(PD, sorted, start, w->tiles, N, PackedFields{p4}, L.d,
-                                                         L.s, L.p);
+      k_debris_sorted<ALB, Params><<<traced, kPBlock, 0, L.st>>>(PD, sorted, start, w->tiles, N,
+                                                                 PackedFields{p4}, L.d, L.s, ps);
     SOIL_LAUNCH_CHECK();
   }
   return SOIL_OK;
@@ -694,9 +719,9 @@ int particles_fluvial(const Launch& L) { return particles_single(FLUVIAL, L); }
 // the overlapped pair retires with colour)
 int particles_debris(const Launch& L) { return particles_single(DEBRIS, L); }
 
-// The seeds of a batch reach the device through a pinned buffer of the host thread (the caller's array may go
-// as soon as the call returns): before it is written again, the copy queued from it the call before has been
-// made — which lets the host queue one batch ahead of the device, and not further.
+// The seeds of a batch (and a sweep's params) reach the device through a pinned buffer of the host thread (the
+// caller's arrays may go as soon as the call returns): before it is written again, the copy queued from it the
+// call before has been made — which lets the host queue one batch ahead of the device, and not further.
 namespace {
 const std::thread::id g_seed_loader = std::this_thread::get_id();
 struct SeedStaging {
@@ -712,12 +737,14 @@ struct SeedStaging {
 };
 }  // namespace
 
-static int upload_seeds(uint64_t* dst, const uint64_t* seeds, int64_t B, hipStream_t st) {
+// One host-to-device copy: the host arrays of `parts` (pointer, bytes; null: left out) one after the other at dst.
+static int upload_seeds(void* dst, std::initializer_list<std::pair<const void*, size_t>> parts, hipStream_t st) {
   static thread_local std::map<int, SeedStaging> staging;  // device -> staging
   int dev = 0;
   SOIL_HIP(hipGetDevice(&dev));
   SeedStaging& u = staging[dev];
-  const size_t bytes = sizeof(uint64_t) * static_cast<size_t>(B);
+  size_t bytes = 0;
+  for (const auto& [src, n] : parts) bytes += src ? n : 0;
   if (u.copied) SOIL_HIP(hipEventSynchronize(u.copied));
   else SOIL_HIP(hipEventCreateWithFlags(&u.copied, hipEventDisableTiming));
   if (u.bytes < bytes) {
@@ -727,40 +754,63 @@ static int upload_seeds(uint64_t* dst, const uint64_t* seeds, int64_t B, hipStre
     SOIL_HIP(hipHostMalloc(&u.host, bytes, hipHostMallocDefault));
     u.bytes = bytes;
   }
-  std::memcpy(u.host, seeds, bytes);
+  size_t at = 0;
+  for (const auto& [src, n] : parts)
+    if (src) std::memcpy(static_cast<char*>(u.host) + at, src, n), at += n;
   SOIL_HIP(hipMemcpyAsync(dst, u.host, bytes, hipMemcpyHostToDevice, st));
   SOIL_HIP(hipEventRecord(u.copied, st));
+  return SOIL_OK;
+}
+
+// A sweep's params on the device without seeds (the cell phase alone, or a step with N == 0): workspace slot 11.
+int batch_params_to_device(const soil_param* params, int64_t B, hipStream_t st, const Param** params_dev) {
+  const size_t bytes = sizeof(Param) * static_cast<size_t>(B);
+  void* base = nullptr;
+  if (int rc = workspace_get(11, bytes, &base); rc != SOIL_OK) return rc;
+  if (int rc = upload_seeds(base, {{params, bytes}}, st); rc != SOIL_OK) return rc;
+  *params_dev = static_cast<const Param*>(base);
   return SOIL_OK;
 }
 
 // soil_particles_batch (soil_hip.h): B whole-grid models, one after the other in every plane; walker n of model b
 // draws from (seeds[b], n, offset), the state soil_erode_step seeds into its tensor for that model alone.  What
 // a lane deposits stays in its model, a NaN walker's (0, 0) included.  Workspace slot 11: the device seeds, then
-// the staged scratch of all B models.
+// the staged scratch of all B models.  A sweep (`params`, soil_particles_batch_params): slot 11 starts with the
+// B params, the seeds behind them, both in one copy.
 int particles_batch(const soil_erosion_planes* P, const soil_colour_planes* C, int64_t B, int64_t H, int64_t W,
                     int64_t N, const uint64_t* seeds, uint64_t step_index, const float scale[3],
-                    const soil_param* param, hipStream_t st) {
+                    const soil_param* param, hipStream_t st, const soil_param* params, const Param** params_dev) {
   // the colour flux planes of all B models (consecutive): one memset each, also when N == 0, as the single
   // coloured pair does
   if (C)
     if (int rc = clear_flux(nullptr, C, BOTH_KINDS, B * H * W, st); rc != SOIL_OK) return rc;
-  if (N == 0) return SOIL_OK;
+  if (N == 0)
+    return params && params_dev ? batch_params_to_device(params, B, st, params_dev) : SOIL_OK;
   const bool staged = use_staged(N);  // the single model's rule; what would be tiled alone runs staged
   const Dom d = full_domain(H, W);
   Scratch w{};
-  if (int rc = scratch_get(11, sizeof(uint64_t) * static_cast<size_t>(B), B, N, d, staged, &w); rc != SOIL_OK)
-    return rc;
-  uint64_t* const seeds_dev = static_cast<uint64_t*>(w.lead);
-  if (int rc = upload_seeds(seeds_dev, seeds, B, st); rc != SOIL_OK) return rc;
+  const size_t b_params = params ? sizeof(Param) * static_cast<size_t>(B) : 0;  // (112 B: seeds stay 8-aligned)
+  const size_t b_seeds = sizeof(uint64_t) * static_cast<size_t>(B);
+  if (int rc = scratch_get(11, b_params + b_seeds, B, N, d, staged, &w); rc != SOIL_OK) return rc;
+  const Param* const params_on = static_cast<const Param*>(w.lead);
+  uint64_t* const seeds_dev = reinterpret_cast<uint64_t*>(static_cast<char*>(w.lead) + b_params);
+  if (int rc = upload_seeds(w.lead, {{params, b_params}, {seeds, b_seeds}}, st); rc != SOIL_OK) return rc;
+  if (params && params_dev) *params_dev = params_on;
   const uint64_t offset = step_index * static_cast<uint64_t>(N);
   for (int kind : {FLUVIAL, DEBRIS}) {
     // with colour: the kind's colour flux plane and the spawn colours (albedo_surface, also in the staged
     // shape: the packed fields hold none)
     const SmallLaunch S{P, C ? (kind == FLUVIAL ? C->albedo_fluvial : C->albedo_debris) : nullptr,
-                        C ? C->albedo_surface : nullptr, nullptr, nullptr, B, N, d, s3p(scale), *param, st};
+                        C ? C->albedo_surface : nullptr, nullptr, nullptr, B, N, d, s3p(scale),
+                        params ? params[0] : *param, st};
     const SeedDraws draws{seeds_dev, kind == FLUVIAL ? offset : offset + 2};  // the debris launch: two draws on
-    const int rc = C ? launch_small<true>(kind, S, draws, staged ? &w : nullptr)
-                     : launch_small<false>(kind, S, draws, staged ? &w : nullptr);
+    const Scratch* const ws = staged ? &w : nullptr;
+    const ModelParams sweep{params_on};
+    int rc;
+    if (params)
+      rc = C ? launch_small<true>(kind, S, draws, ws, sweep) : launch_small<false>(kind, S, draws, ws, sweep);
+    else
+      rc = C ? launch_small<true>(kind, S, draws, ws) : launch_small<false>(kind, S, draws, ws);
     if (rc != SOIL_OK) return rc;
   }
   return SOIL_OK;
@@ -986,6 +1036,17 @@ int soil_particles_batch_colour(const soil_erosion_planes* planes, const soil_co
   if (int rc = check_batch(B, H, W, N, seeds, "particles_batch_colour"); rc != SOIL_OK) return rc;
   SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch_colour: null plane");
   return particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
+}
+
+int soil_particles_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
+                                const float scale[3], const soil_param* params, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && scale && params, "particles_batch_params: null argument");
+  SOIL_REQUIRE(!colour || has_colour(colour), "particles_batch_params: every colour plane is required");
+  if (int rc = check_batch(B, H, W, N, seeds, "particles_batch_params"); rc != SOIL_OK) return rc;
+  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch_params: null plane");
+  return particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, nullptr, as_stream(stream), params);
 }
 
 int soil_particle_steps(uint64_t* total, int reset, void* stream) {

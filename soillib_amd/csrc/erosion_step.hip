@@ -183,6 +183,27 @@ int soil_erode_step_batch_colour(const soil_erosion_planes* planes, const soil_c
   return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, 0, st);
 }
 
+// A sweep step: as the (coloured) batch step, model b with params[b].  The params reach the device once, in the
+// particle phase's copy of the seeds, and the cell phase reads that copy.
+int soil_erode_step_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                 int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
+                                 const float scale[3], const soil_param* params, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes && scale && params, "erode_step_batch_params: null argument");
+  SOIL_REQUIRE(!colour || has_colour(colour), "erode_step_batch_params: every colour plane is required");
+  if (int rc = check_batch(B, H, W, N, seeds, "erode_step_batch_params"); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch_params: every plane but `height` is required");
+  SOIL_REQUIRE(P.layers != P.layers_next,
+               "erode_step_batch_params: layers and layers_next must be distinct buffers");
+  const hipStream_t st = as_stream(stream);
+  const soil_param* params_dev = nullptr;
+  if (int rc = particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, nullptr, st, params, &params_dev);
+      rc != SOIL_OK)
+    return rc;
+  return erode_cells_fused_batch(planes, colour, B, H, W, scale, nullptr, 0, st, params_dev);
+}
+
 int soil_erode(const soil_erode_model* model, int64_t H, int64_t W, int64_t N, uint64_t seed,
                uint64_t first_step, int steps, const float scale[3], const soil_param* param,
                void* stream) {

@@ -30,7 +30,9 @@ few launches for the whole batch where B models take B times their own handful
 separately; `model_planes(b)` copies one model's planes to the host.  Whole
 grids, one shared param.  `ErosionBatch(..., colour=True)` carries the four colour
 planes of the coloured step too (soil_erode_step_batch_colour): model b ends where
-`ErosionModel(..., seed=seeds[b], colour=True).step()` leaves it.
+`ErosionModel(..., seed=seeds[b], colour=True).step()` leaves it.  A sequence of B
+param_t in place of `param` makes the batch a parameter sweep (soil_erode_step_batch_params):
+model b steps with params[b], as `ErosionModel(..., params[b], ..., seed=seeds[b])` would.
 """
 import ctypes as C
 import os
@@ -239,9 +241,15 @@ class ErosionModel:
 class ErosionBatch:
     """B independent whole-grid erosion models of one (H, W) shape, stepped together (include/soil_hip.h:
     soil_erode_step_batch).  Every plane of ErosionModel is a (B, H, W[, C]) GPU tensor, zeroed here; model b
-    has its own terrain, rainfall, uplift and seed, and shares N, scale and param with the others.  `colour`:
-    the four colour planes of ErosionModel(colour=True) too, (B, H, W, 3) each, and the coloured entry points
-    (soil_erode_step_batch_colour)."""
+    has its own terrain, rainfall, uplift and seed, and shares N and scale with the others.  `colour`: the four
+    colour planes of ErosionModel(colour=True) too, (B, H, W, 3) each, and the coloured entry points
+    (soil_erode_step_batch_colour).
+
+    `param` is one param_t shared by every model, or a sequence of B param_t: a parameter sweep, in which model b
+    steps with params[b] (soil_erode_step_batch_params, with or without colour).  A sweep holds them as
+    `self.params` (`self.param` is None) and reads them at every call of particles(), cells_fused() and step(): a
+    change to one of the objects, or a replaced element, takes effect at the next call.  A wrong count or an
+    element that is not a param_t raises ValueError before any device work."""
 
     PLANES_1 = ErosionModel.PLANES_1
     PLANES_2 = ErosionModel.PLANES_2
@@ -255,7 +263,16 @@ class ErosionBatch:
         if self.B < 1 or self.H < 1 or self.W < 1:
             raise ValueError("ErosionBatch: B, H and W must be >= 1")
         self.scale = [float(v) for v in scale]
-        self.param = param
+        from .soil import param_t
+        if isinstance(param, param_t):
+            self.param, self.params = param, None
+        else:
+            try:
+                self.params = list(param)
+            except TypeError:
+                raise ValueError("ErosionBatch: param must be a param_t or a sequence of %d param_t" % self.B)
+            self.param = None
+            self._check_params()
         self.N = int(n_particles)
         self.colour = bool(colour)
         self.step_index = 0
@@ -283,6 +300,24 @@ class ErosionBatch:
     _colour = ErosionModel._colour
     _scale = ErosionModel._scale
 
+    def _check_params(self):
+        from .soil import param_t
+        if len(self.params) != self.B:
+            raise ValueError("ErosionBatch: %d params for %d models" % (len(self.params), self.B))
+        for b, p in enumerate(self.params):
+            if not isinstance(p, param_t):
+                raise ValueError("ErosionBatch: params[%d] is a %s, not a param_t" % (b, type(p).__name__))
+
+    def _params(self):
+        """The sweep's params as they are now, a C array of B soil_param (copied by the entry points)."""
+        self._check_params()
+        return (_abi.Param * self.B).from_buffer_copy(b"".join(bytes(p._c) for p in self.params))
+
+    def _sweep(self, name, args):
+        """A sweep's entry `name` (soil_*_batch_params): planes, colour (or NULL), then `args`."""
+        colour = C.byref(self._colour()) if self.colour else None
+        _abi.check(getattr(_abi.lib(), name)(C.byref(self._planes()), colour, *args))
+
     def set_layers(self, layers_tensor):
         """Copy a (B, H, W, 2) tensor of (bedrock, sediment) into the batch."""
         if tuple(layers_tensor.shape) != (self.B, self.H, self.W, 2):
@@ -304,7 +339,11 @@ class ErosionBatch:
     def particles(self):
         """Both particle launches of this step for every model, adding into the flux planes
         (soil_particles_batch); with colour the two colour flux planes are cleared first and receive this
-        step's colour flux (soil_particles_batch_colour)."""
+        step's colour flux (soil_particles_batch_colour).  A sweep: soil_particles_batch_params."""
+        if self.params is not None:
+            self._sweep("soil_particles_batch_params", (self.B, self.H, self.W, self.N, self._seeds, self.step_index,
+                                                        self._scale(), self._params(), _abi.stream()))
+            return
         planes = self._planes()
         args = (self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(), self.param._ref(),
                 _abi.stream())
@@ -316,7 +355,12 @@ class ErosionBatch:
 
     def cells_fused(self, keep_flux=False):
         """Fused cell phase of every model (soil_erode_cells_fused_batch[_colour]); `keep_flux`: the flux
-        planes are left as they are (SOIL_CELLS_KEEP_FLUX)."""
+        planes are left as they are (SOIL_CELLS_KEEP_FLUX).  A sweep: soil_erode_cells_fused_batch_params."""
+        if self.params is not None:
+            self._sweep("soil_erode_cells_fused_batch_params", (self.B, self.H, self.W, self._scale(), self._params(),
+                                                                _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0,
+                                                                _abi.stream()))
+            return
         planes = self._planes()
         args = (self.B, self.H, self.W, self._scale(), self.param._ref(),
                 _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0, _abi.stream())
@@ -331,7 +375,13 @@ class ErosionBatch:
 
     def step(self):
         """One erosion step of every model (soil_erode_step_batch, with colour soil_erode_step_batch_colour);
-        swaps the layer buffers."""
+        swaps the layer buffers.  A sweep: soil_erode_step_batch_params."""
+        if self.params is not None:
+            self._sweep("soil_erode_step_batch_params", (self.B, self.H, self.W, self.N, self._seeds, self.step_index,
+                                                         self._scale(), self._params(), _abi.stream()))
+            self.swap_layers()
+            self.step_index += 1
+            return
         planes = self._planes()
         args = (self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(), self.param._ref(),
                 _abi.stream())

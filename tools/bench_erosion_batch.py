@@ -8,7 +8,10 @@ One JSON line per (size, B): ms per batch step and per model-step (median over -
 steps after --warmup), the sequential loop's ms per model-step, and seq / batch.  --no-seq leaves the loop
 out (the profiling run: rocprofv3 --kernel-trace --stats).  --colour times the coloured batch
 (ErosionBatch(colour=True), soil_erode_step_batch_colour) against ErosionModel(colour=True).step(), bedrock and
-surface colours set on every model."""
+surface colours set on every model.  --sweep times a parameter sweep (ErosionBatch with a sequence of B param_t,
+soil_erode_step_batch_params; with --colour the coloured one) against the uniform batch at the same shapes: B
+separate param_t of equal values, so that both walk the same walks and only the sweep's mechanism differs, the
+two alternated --rounds times in blocks of --steps steps, medians of each.  No sequential loop then."""
 import argparse
 import ctypes as C
 import json
@@ -25,6 +28,7 @@ from util import script_param  # noqa: E402
 
 DEFAULT = "256:1,256:8,256:64,256:256,512:1,512:8,512:32,1024:1,1024:8,1024:32"
 COLOUR_DEFAULT = "256:1,256:8,256:64,256:256,512:1,512:8,512:32,1024:1,1024:8"
+SWEEP_DEFAULT = "256:1,256:8,256:64,256:256,512:8,512:32"
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--configs", default=None, help="size:B,size:B,... (default: %s; with --colour %s)" % (
@@ -34,9 +38,12 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--no-seq", action="store_true")
 ap.add_argument("--out", default=None, help="also append the lines to this file")
 ap.add_argument("--colour", action="store_true", help="the coloured batch against coloured single models")
+ap.add_argument("--sweep", action="store_true", help="a parameter sweep against the uniform batch (default configs: %s)"
+                % SWEEP_DEFAULT)
+ap.add_argument("--rounds", type=int, default=5, help="--sweep: alternations of the two")
 args = ap.parse_args()
 if args.configs is None:
-    args.configs = COLOUR_DEFAULT if args.colour else DEFAULT
+    args.configs = SWEEP_DEFAULT if args.sweep else COLOUR_DEFAULT if args.colour else DEFAULT
 lib = _abi.lib()
 param = script_param(soil.param_t())
 param.maxage = 256
@@ -127,11 +134,49 @@ def run(S, B):
     return line
 
 
+def run_sweep(S, B):
+    """The uniform batch and a sweep of B equal params, alternated in blocks of args.steps steps."""
+    N = S * S // 8
+    scale = (20.0 / S, 20.0 / S, 4.0)
+    seeds = [1000 + b for b in range(B)]
+    params = []
+    for _ in range(B):
+        p = soil.param_t()
+        for name in soil.param_t._FIELDS + ("force",):
+            setattr(p, name, getattr(param, name))
+        params.append(p)
+    batches = {}
+    for kind, prm in (("uniform", param), ("sweep", params)):
+        bt = ErosionBatch(B, S, S, scale, prm, N, seeds, colour=args.colour)
+        for b in range(B):
+            terrain_into(bt.layers.ptr + b * S * S * 8, S, b)
+        silt.set(bt.rainfall, 1.0)
+        colours_into(bt)
+        for _ in range(args.warmup):
+            bt.step()
+        batches[kind] = bt
+    ms = {"uniform": [], "sweep": []}
+    for _ in range(args.rounds):
+        for kind in ("uniform", "sweep"):
+            ms[kind].append(timed(batches[kind].step, args.steps))
+    u, w = statistics.median(ms["uniform"]), statistics.median(ms["sweep"])
+    line = {"size": S, "B": B, "N": N, "colour": args.colour, "sweep": True, "maxage": param.maxage,
+            "steps": args.steps, "warmup": args.warmup, "rounds": args.rounds,
+            "uniform_ms_per_step": round(u, 4), "sweep_ms_per_step": round(w, 4),
+            "uniform_rounds_ms": [round(v, 4) for v in ms["uniform"]],
+            "sweep_rounds_ms": [round(v, 4) for v in ms["sweep"]],
+            "sweep_over_uniform": round(w / u, 4)}
+    del batches
+    silt.empty_cache()
+    _abi.check(lib.soil_workspace_release())
+    return line
+
+
 name = C.create_string_buffer(256)
 lib.soil_device_name(name, 256)
 for cfg in args.configs.split(","):
     S, B = (int(v) for v in cfg.split(":"))
-    line = run(S, B)
+    line = run_sweep(S, B) if args.sweep else run(S, B)
     line["device"] = name.value.decode()
     s = json.dumps(line)
     print(s, flush=True)
