@@ -366,7 +366,7 @@ int soil_erode_step_ex(const soil_erosion_planes* planes, soil_rng* rng, int64_t
 /* ------------------------------------------ erosion: batches of models */
 
 /* A batch: B independent whole-grid models of one shape (H, W), N walkers each, one `param`, one `scale`, one
- * step_index, one seed per model.  Every pointer of `planes` is model 0 of B consecutive models: model b of a
+ * step_index, one seed per model (models that differ in param, scale, N or step index: soil_erode_step_batch_models).  Every pointer of `planes` is model 0 of B consecutive models: model b of a
  * plane of C channels starts at element b * H * W * C (rainfall and uplift too: they are per model).  `seeds`
  * is a host array of B values, copied before the call returns.  A batch leaves model b holding what the
  * single-model entry leaves on that model alone with seed = seeds[b] (soil_erode_step; the streams of model b
@@ -504,12 +504,13 @@ int soil_erode_cells_fused_batch_colour(const soil_erosion_planes* planes, const
  * flux atomics may differ.  SOIL_ERR_INVALID_ARGUMENT for a NULL `params`, the sizes soil_erode_step_batch
  * refuses, and a non-NULL `colour` with a NULL plane ("colour plane").
  *
- * Launch shapes: those of the (coloured) batch at the same B, N and (H, W), with the same kernels, each model
- * reading its params[b] once per work-group (grid.y = model).  No launch shape depends on a value of `params`:
- * a per-model maxage is only each walker's loop bound.  The params reach the device with the seeds in the
- * batch's one host-to-device copy, so a sweep step issues as many dispatches as the batch step (14 physics, 17
- * coloured, in the staged shape).  Algorithmic bytes: the batch's, plus one 112-byte parameter read per
- * work-group of every launch (4 bytes per work-group of the pack pass) and B x 112 bytes copied per step.
+ * Launch shapes: those of the (coloured) batch at the same B, N and (H, W), each model reading its params[b]
+ * once per work-group (grid.y = model).  No launch shape depends on a value of `params`: a per-model maxage is
+ * only each walker's loop bound.  A sweep is the batch of different models below with the shared scale, N and
+ * step_index in every record: the records reach the device in the batch's one host-to-device copy, so a sweep
+ * step issues as many dispatches as the batch step (14 physics, 17 coloured, in the staged shape).  Algorithmic
+ * bytes: the batch's, plus one 152-byte record read per work-group of every launch and B x 152 bytes copied per
+ * step.
  *
  * One step of every model: soil_particles_batch_params, then soil_erode_cells_fused_batch_params with flags 0,
  * the params uploaded once for both. */
@@ -527,6 +528,55 @@ int soil_particles_batch_params(const soil_erosion_planes* planes, const soil_co
 int soil_erode_cells_fused_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour,
                                         int64_t B, int64_t H, int64_t W, const float scale[3],
                                         const soil_param* params, int flags, void* stream);
+
+/* ------------------------------------------ erosion: batches of different models */
+
+/* One model of a batch whose models differ in more than their param: everything the single model's step takes
+ * beside its planes.  152 bytes (4 bytes of padding after `scale`), 8-aligned. */
+typedef struct soil_batch_model {
+  soil_param param;    /* 112 bytes, 8-aligned (maxage is uint64_t) */
+  float scale[3];      /* {sx, sy, sz}, as every entry point's `scale` */
+  int64_t N;           /* walkers of this model, 0 <= N < 2^31 */
+  uint64_t seed;
+  uint64_t step_index; /* this model's streams at (seed, n, step_index * N) */
+} soil_batch_model;
+
+/* A batch of B whole-grid models of one (H, W) in which model b steps with models[b]: its own param, scale, walker
+ * count N_b, seed and step index (with a non-NULL `colour`, the coloured batch of soil_erode_step_batch_colour).
+ * `models` is a host array of B records, copied before the call returns; the caller advances each step_index.
+ * Model b ends a step holding what soil_erode_step (with colour: soil_erode_step_colour) leaves on that model alone
+ * with param, scale, N, seed and step_index taken from models[b]; only the fp32 order of the flux atomics may
+ * differ.  A model with N_b = 0 runs no walkers: its step is the cell phase alone.  Every other rule of the batch
+ * holds: model-major planes, a NaN walker's deposits in cell (0, 0) of its own model, flux planes zero on entry
+ * and exit, exact arithmetic, every walker walked to the end, at most 65535 models per launch, the particle step
+ * counter adding every walker's steps.  SOIL_ERR_INVALID_ARGUMENT for a NULL `models`, any N_b < 0 or
+ * N_b >= 2^31, what soil_erode_step_batch refuses with N = max N_b, and a non-NULL `colour` with a NULL plane
+ * ("colour plane").  The soil_*_batch_params entries are this batch with the shared scale, N and step_index
+ * filled into every record.
+ *
+ * Launch shapes: the batch's at N = max N_b (direct below 1024, staged at or above; what would be tiled alone runs
+ * staged), grid.x sized by max N_b; lane n of model b exits before drawing when n >= N_b.  Spawn and sorted
+ * arrays keep a stride of max N_b per model.  Every work-group reads its model's record once (grid.y = model).
+ * The records reach the device in one host-to-device copy per step, and the step's cell phase reads that copy,
+ * so a step issues as many dispatches as the batch step (14 physics, 17 coloured, in the staged shape).
+ * Algorithmic bytes: the batch's at each model's own N_b, plus one 152-byte record read per work-group of every
+ * launch and B x 152 bytes copied per step.
+ *
+ * One step of every model: soil_particles_batch_models, then soil_erode_cells_fused_batch_models with flags 0,
+ * the records uploaded once for both. */
+int soil_erode_step_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                 int64_t H, int64_t W, const soil_batch_model* models, void* stream);
+/* Both particle launches of such a step (model b: N_b walkers from (seed_b, n, step_index_b * N_b), the debris
+ * launch two draws on).  With colour the two colour flux planes of all B models are cleared first, also when
+ * every N_b is 0. */
+int soil_particles_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                int64_t H, int64_t W, const soil_batch_model* models, void* stream);
+/* The cell phase of such a batch, bit-identical per model to soil_erode_cells_fused_ex (with colour:
+ * soil_erode_cells_fused_colour) with models[b].param and models[b].scale and the same flags; N, seed and
+ * step_index are not read.  Its own upload of the records (one copy) before the batch's launches. */
+int soil_erode_cells_fused_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                        int64_t B, int64_t H, int64_t W, const soil_batch_model* models,
+                                        int flags, void* stream);
 
 /* The containers of the legacy API (example/erosion_gpu.py:44-71): model_t, the `data` and the
  * `track` buffers.  All float32 device planes of H*W cells ((H,W,2) for the momenta). */

@@ -38,6 +38,13 @@ class Param(C.Structure):
                 [("force", C.c_float * 2), ("_pad", C.c_float)])
 
 
+class BatchModel(C.Structure):
+    """soil_batch_model: one model of a batch whose models differ in param, scale, walker count, seed and step
+    index (152 bytes; 4 bytes of padding after `scale`)."""
+    _fields_ = [("param", Param), ("scale", C.c_float * 3), ("N", C.c_int64), ("seed", C.c_uint64),
+                ("step_index", C.c_uint64)]
+
+
 class Rng(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("offset", C.c_uint64)]
 
@@ -159,6 +166,13 @@ SIGNATURES = {
                                            C.POINTER(u64), u64, F3, C.POINTER(Param), vp]),
     "soil_erode_cells_fused_batch_params": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64,
                                                    i64, F3, C.POINTER(Param), cint, vp]),
+    # a batch of different models: model b with models[b] (a host array of B); the colour planes may be NULL
+    "soil_erode_step_batch_models": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64, i64,
+                                            C.POINTER(BatchModel), vp]),
+    "soil_particles_batch_models": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64, i64,
+                                           C.POINTER(BatchModel), vp]),
+    "soil_erode_cells_fused_batch_models": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64,
+                                                   i64, C.POINTER(BatchModel), cint, vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),

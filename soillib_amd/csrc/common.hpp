@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <string>
+#include <vector>
 
 #include "../../include/soil_hip.h"
 #include "soil_math.hpp"
@@ -79,13 +80,23 @@ inline bool has_colour(const soil_colour_planes* C, bool bedrock = true) {
   return C && (C->albedo_bedrock || !bedrock) && C->albedo_surface && C->albedo_fluvial && C->albedo_debris;
 }
 // `colour` null: physics only; otherwise the four colour planes of all B models (soil_erode_cells_fused_batch_colour).
-// `params_dev` (a device array of B, or null: every model `param`): a sweep, model b with params_dev[b].
+// `models_dev` (a device array of B records, or null: every model `param` and `scale`): model b with the param and
+// scale of models_dev[b].
 int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
                             int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st,
-                            const soil_param* params_dev = nullptr);
-// A sweep's B params (a host array) copied to the device in one copy through the batches' pinned staging, into
-// workspace slot 11 (erosion_particles.hip); *params_dev valid in stream order until the slot's next use.
-int batch_params_to_device(const soil_param* params, int64_t B, hipStream_t st, const soil_param** params_dev);
+                            const soil_batch_model* models_dev = nullptr);
+// B records (a host array) copied to the device in one copy through the batches' pinned staging, into workspace
+// slot 11 (erosion_particles.hip); *models_dev valid in stream order until the slot's next use.
+int batch_models_to_device(const soil_batch_model* models, int64_t B, hipStream_t st,
+                           const soil_batch_model** models_dev);
+// The checks of the soil_*_batch_models entries (soil_hip.h): a NULL `models`, an N_b < 0 or >= 2^31, and what
+// check_batch refuses with N = max N_b (seeds are in the records); *N_max receives max N_b.
+int check_batch_models(int64_t B, int64_t H, int64_t W, const soil_batch_model* models, const char* what,
+                       int64_t* N_max);
+// The B records of a sweep (soil_*_batch_params): params[b] with the shared scale, N and step_index, and seeds[b]
+// (seeds may be null: seed 0).
+std::vector<soil_batch_model> sweep_records(int64_t B, const soil_param* params, const float scale[3], int64_t N,
+                                            const uint64_t* seeds, uint64_t step_index);
 
 // Launch shape of the per-cell kernels: threads along the contiguous axis, and a
 // work-group walks a band of kRowBand consecutive rows (SOIL_ROW_LOOP).  A 64-bit
@@ -130,23 +141,35 @@ struct Scale2 {
 // param_t travels to the kernels by value, like in the reference.
 using Param = soil_param;
 
-// Where a kernel's Param comes from, a compile-time choice (the batch kernels: grid.y is the model).  Every
-// kernel takes its model's Param once at entry into a local copy (`model()`); blockIdx.y is uniform over the
-// work-group, so a sweep's read is scalar loads, and the walks and cells see register-resident constants either
-// way.  `from_model(b0)`: the source of a launch whose model 0 is model b0 of the batch (grid.y <= 65535).
-struct UniformParam {  // one param_t for every model: the kernel argument itself
+// Where a kernel's Param, scale and walker count come from, a compile-time choice (the batch kernels: grid.y is
+// the model).  Every kernel takes its model's Param once at entry into a local copy (`model()`), and its scale and
+// walker count through `scale(s)` and `walkers(N)`, which are handed the kernel's own arguments; blockIdx.y is
+// uniform over the work-group, so a record's reads are scalar loads, and the walks and cells see
+// register-resident constants either way.  `from_model(b0)`: the source of a launch whose model 0 is model b0 of
+// the batch (grid.y <= 65535).
+struct UniformParam {  // one param_t for every model: the kernel arguments themselves
   Param p;
   static constexpr bool kPerModel = false;
   UniformParam() = default;
   UniformParam(const Param& q) : p(q) {}  // (implicit: the single-model launches pass a Param)
   __device__ __forceinline__ Param model() const { return p; }
+  __device__ __forceinline__ Scale3 scale(Scale3 s) const { return s; }
+  __device__ __forceinline__ int64_t walkers(int64_t N) const { return N; }
   UniformParam from_model(int64_t) const { return *this; }
 };
-struct ModelParams {  // a sweep (soil_*_batch_params): model b steps with params[b], a device array of B
-  const Param* __restrict__ params;
+// a batch of different models (soil_*_batch_models, and the sweeps built on it): model b steps with models[b], a
+// device array of B records; the kernel's scale and N arguments are not read
+struct ModelParams {
+  const soil_batch_model* __restrict__ models;
   static constexpr bool kPerModel = true;
-  __device__ __forceinline__ Param model() const { return params[blockIdx.y]; }
-  ModelParams from_model(int64_t b0) const { return ModelParams{params + b0}; }
+  __device__ __forceinline__ const soil_batch_model& record() const { return models[blockIdx.y]; }
+  __device__ __forceinline__ Param model() const { return record().param; }
+  __device__ __forceinline__ Scale3 scale(Scale3) const {
+    const soil_batch_model& m = record();
+    return Scale3{m.scale[0], m.scale[1], m.scale[2]};
+  }
+  __device__ __forceinline__ int64_t walkers(int64_t) const { return record().N; }
+  ModelParams from_model(int64_t b0) const { return ModelParams{models + b0}; }
 };
 
 // ---- device helpers shared by the erosion kernels --------------------------

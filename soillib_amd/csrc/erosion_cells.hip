@@ -348,8 +348,8 @@ __device__ __forceinline__ void colour_cell(float fluvial[3], float debris[3], f
 // with REZERO = false.
 // BATCH: grid.y is the model of a batch of whole-grid models (soil_erode_cells_fused_batch, with ALB
 // soil_erode_cells_fused_batch_colour): every plane is advanced to model blockIdx.y, H x W cells per model.
-// Params: UniformParam, or with BATCH a sweep's ModelParams (soil_erode_cells_fused_batch_params, common.hpp); not
-// deduced, so that the single-model launches, which pass a Param, get UniformParam.
+// Params: UniformParam, or with BATCH a batch's ModelParams (soil_erode_cells_fused_batch_models, common.hpp: the
+// model's param and scale); not deduced, so that the single-model launches, which pass a Param, get UniformParam.
 template <bool XCD_REMAP, bool NT, int BLOCK = kBlock, bool DIRECT = false, bool REZERO = true, bool ALB = false,
           bool BATCH = false, class Params = UniformParam>
 __global__ void __launch_bounds__(BLOCK)
@@ -357,6 +357,7 @@ __global__ void __launch_bounds__(BLOCK)
                         int64_t total_groups) {
   static_assert(BATCH || !Params::kPerModel, "per-model params need the batch's grid.y");
   const Param p = ps.model();
+  s = ps.scale(s);
   if constexpr (BATCH) P = model_planes<ALB>(P, d.H * d.W);
   // group = kVec consecutive cells of one row; one thread per group
   int64_t blk = blockIdx.x;
@@ -533,6 +534,7 @@ __global__ void __launch_bounds__(kBlock)
     k_erode_cells_fused_scalar(Planes P, Dom d, Scale3 s, std::type_identity_t<Params> ps, bool rezero) {
   static_assert(BATCH || !Params::kPerModel, "per-model params need the batch's grid.y");
   const Param p = ps.model();
+  s = ps.scale(s);
   if constexpr (BATCH) P = model_planes<ALB>(P, d.H * d.W);
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (t >= (d.r1 - d.r0) * d.W) return;
@@ -846,7 +848,8 @@ int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* c
 // erode_cells_fused, which makes every model bit-identical to it; the five flux planes are re-zeroed in the
 // kernel (112 bytes per cell) unless SOIL_CELLS_KEEP_FLUX (84).  With `colour` the coloured single model's
 // shape: the 168-byte kernel (ALB, flux planes kept), then one re-zero pass over the flux planes of all B
-// models unless SOIL_CELLS_KEEP_FLUX.  Params: UniformParam{*param}, or a sweep's ModelParams (the same launches).
+// models unless SOIL_CELLS_KEEP_FLUX.  Params: UniformParam{*param}, or a batch's ModelParams (the same launches;
+// `scale` is then not read).
 template <class Params>
 static int cells_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
                        int64_t W, const float scale[3], Params params, int flags, hipStream_t st) {
@@ -897,8 +900,9 @@ static int cells_batch(const soil_erosion_planes* pl, const soil_colour_planes* 
 
 int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
                             int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st,
-                            const soil_param* params_dev) {
-  if (params_dev) return cells_batch(pl, colour, B, H, W, scale, ModelParams{params_dev}, flags, st);
+                            const soil_batch_model* models_dev) {
+  static constexpr float kRecords[3] = {0.0f, 0.0f, 0.0f};  // (the kernels take each model's from its record)
+  if (models_dev) return cells_batch(pl, colour, B, H, W, kRecords, ModelParams{models_dev}, flags, st);
   return cells_batch(pl, colour, B, H, W, scale, UniformParam{*param}, flags, st);
 }
 
@@ -931,7 +935,7 @@ int soil_erode_cells_fused_batch_colour(const soil_erosion_planes* planes, const
   return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, flags, as_stream(stream));
 }
 
-// A sweep's cell phase: its own upload of the B params (one copy), then the batch's launches with ModelParams.
+// A sweep's cell phase: the cell phase of a batch of different models whose records share `scale` (one copy).
 int soil_erode_cells_fused_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour,
                                         int64_t B, int64_t H, int64_t W, const float scale[3],
                                         const soil_param* params, int flags, void* stream) {
@@ -944,9 +948,30 @@ int soil_erode_cells_fused_batch_params(const soil_erosion_planes* planes, const
   SOIL_REQUIRE(P.layers != P.layers_next,
                "erode_cells_fused_batch_params: layers and layers_next must be distinct buffers");
   const hipStream_t st = as_stream(stream);
-  const soil_param* params_dev = nullptr;
-  if (int rc = batch_params_to_device(params, B, st, &params_dev); rc != SOIL_OK) return rc;
-  return erode_cells_fused_batch(planes, colour, B, H, W, scale, nullptr, flags, st, params_dev);
+  const std::vector<soil_batch_model> models = sweep_records(B, params, scale, 0, nullptr, 0);
+  const soil_batch_model* models_dev = nullptr;
+  if (int rc = batch_models_to_device(models.data(), B, st, &models_dev); rc != SOIL_OK) return rc;
+  return erode_cells_fused_batch(planes, colour, B, H, W, nullptr, nullptr, flags, st, models_dev);
+}
+
+// The cell phase of a batch of different models: its own upload of the B records (one copy), then the batch's
+// launches with ModelParams.
+int soil_erode_cells_fused_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour,
+                                        int64_t B, int64_t H, int64_t W, const soil_batch_model* models,
+                                        int flags, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes, "erode_cells_fused_batch_models: null argument");
+  SOIL_REQUIRE(!colour || has_colour(colour), "erode_cells_fused_batch_models: every colour plane is required");
+  int64_t N = 0;  // (the cell phase reads no N, but refuses what the step refuses)
+  if (int rc = check_batch_models(B, H, W, models, "erode_cells_fused_batch_models", &N); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_cells_fused_batch_models: null plane (only `height` is optional)");
+  SOIL_REQUIRE(P.layers != P.layers_next,
+               "erode_cells_fused_batch_models: layers and layers_next must be distinct buffers");
+  const hipStream_t st = as_stream(stream);
+  const soil_batch_model* models_dev = nullptr;
+  if (int rc = batch_models_to_device(models, B, st, &models_dev); rc != SOIL_OK) return rc;
+  return erode_cells_fused_batch(planes, colour, B, H, W, nullptr, nullptr, flags, st, models_dev);
 }
 
 int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* dom,

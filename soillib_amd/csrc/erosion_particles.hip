@@ -19,6 +19,7 @@
 //     wave and the waves of an XCD share cache lines for most of their walk.
 // The reference's launch shape (thread n = particle n, direct stencil gathers)
 // is kept as `direct` mode for ablation (soil_set_particle_mode).
+#include <cstddef>
 #include <cstring>
 #include <initializer_list>
 #include <map>
@@ -331,9 +332,11 @@ __device__ __forceinline__ int64_t model_base(int64_t per_model) {
 
 // Where a launch's walkers take their first two draws from, a compile-time choice.  (Streams, the tiled
 // shape's runtime switch, stays as it is: its kernels take it by value.)
+// `walkers(N)`: how many of a launch's N walkers per model model blockIdx.y draws (the others exit first).
 struct TensorDraws {  // a single model's soil_rng tensor: every state read, drawn from and written back
   soil_rng* __restrict__ rng;
   __device__ __forceinline__ float2 spawn(int64_t n, const Dom& d) const { return spawn_position(rng, n, d); }
+  __device__ __forceinline__ int64_t walkers(int64_t N) const { return N; }
   TensorDraws from_model(int64_t) const { return *this; }  // (B == 1)
 };
 struct SeedDraws {  // a batch's uniform streams: walker n of model b at (seeds[b], n, offset), nothing stored
@@ -342,7 +345,21 @@ struct SeedDraws {  // a batch's uniform streams: walker n of model b at (seeds[
   __device__ __forceinline__ float2 spawn(int64_t n, const Dom& d) const {
     return spawn_position(Streams{nullptr, true, seeds[blockIdx.y], offset}, n, d);
   }
+  __device__ __forceinline__ int64_t walkers(int64_t N) const { return N; }
   SeedDraws from_model(int64_t b0) const { return SeedDraws{seeds + b0, offset}; }
+};
+// a batch of different models' uniform streams (ModelParams): walker n < N_b of model b at
+// (seed_b, n, step_index_b * N_b + extra), `extra` 2 for the debris launch; nothing stored
+struct ModelDraws {
+  ModelParams m;
+  uint64_t extra;
+  __device__ __forceinline__ float2 spawn(int64_t n, const Dom& d) const {
+    const soil_batch_model& r = m.record();
+    const uint64_t offset = r.step_index * static_cast<uint64_t>(r.N) + extra;
+    return spawn_position(Streams{nullptr, true, r.seed, offset}, n, d);
+  }
+  __device__ __forceinline__ int64_t walkers(int64_t N) const { return m.walkers(N); }
+  ModelDraws from_model(int64_t b0) const { return ModelDraws{m.from_model(b0), extra}; }
 };
 
 // the planes of model blockIdx.y.  ALB: a coloured batch (soil_particles_batch_colour) — the colour flux plane
@@ -373,40 +390,44 @@ __device__ __forceinline__ DirectFields model_of(DirectFields F, int64_t cells) 
   return F;
 }
 
-// direct: thread n = walker n of model blockIdx.y.  Params: UniformParam, or a sweep's ModelParams (common.hpp),
-// whose model's exitSlope replaces the one F was made with
+// direct: thread n = walker n of model blockIdx.y, of N_b = ps.walkers(N).  Params: UniformParam, or a batch's
+// ModelParams (common.hpp), whose model's exitSlope and scale replace those F was made with
 template <class Draws, bool ALB, class Params = UniformParam>
 __global__ void __launch_bounds__(kPBlock)
     k_fluvial_direct(FluvialPlanes P, Draws draws, int64_t N, DirectFields F, Params ps) {
   const Param param = ps.model();
-  if constexpr (Params::kPerModel) F.exitSlope = param.exitSlope;
+  if constexpr (Params::kPerModel) F.exitSlope = param.exitSlope, F.s = ps.scale(F.s);
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
+  const int64_t Nb = ps.walkers(N);
+  if (n >= Nb) return;
   const float2 pos = draws.spawn(n, F.d);
   if (!owns_spawn(F.d, pos.x)) return;
   const int64_t cells = F.d.rows * F.d.W;
-  trace_fluvial(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
+  trace_fluvial(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, Nb, F.d, F.s, param);
 }
 
 template <class Draws, bool ALB, class Params = UniformParam>
 __global__ void __launch_bounds__(kPBlock)
     k_debris_direct(DebrisPlanes P, Draws draws, int64_t N, DirectFields F, Params ps) {
   const Param param = ps.model();
-  if constexpr (Params::kPerModel) F.exitSlope = param.exitSlope;
+  if constexpr (Params::kPerModel) F.exitSlope = param.exitSlope, F.s = ps.scale(F.s);
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
+  const int64_t Nb = ps.walkers(N);
+  if (n >= Nb) return;
   const float2 pos = draws.spawn(n, F.d);
   if (!owns_spawn(F.d, pos.x)) return;
   const int64_t cells = F.d.rows * F.d.W;
-  trace_debris(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, N, F.d, F.s, param);
+  trace_debris(model_of(F, cells), model_of<ALB>(P, cells), pos.x, pos.y, Nb, F.d, F.s, param);
 }
 
-// The pack pass's exitSlope: one for every model (the kernel argument), or a sweep's ModelParams
+// The pack pass's exitSlope and scale: one for every model (the kernel arguments), or a batch's ModelParams
 struct ExitSlope {
   float v;
 };
 __device__ __forceinline__ float exit_slope_of(const ExitSlope& e) { return e.v; }
-__device__ __forceinline__ float exit_slope_of(const ModelParams& m) { return m.params[blockIdx.y].exitSlope; }
+__device__ __forceinline__ float exit_slope_of(const ModelParams& m) { return m.model().exitSlope; }
+__device__ __forceinline__ Scale3 scale_of(const ExitSlope&, Scale3 s) { return s; }
+__device__ __forceinline__ Scale3 scale_of(const ModelParams& m, Scale3 s) { return m.scale(s); }
 
 // staged, pre-pass: p4[cell] = {__glocal(cell), velocity[cell]} for every row with a full stencil (`cells` of
 // them per model from local row `row_lo`)
@@ -416,6 +437,7 @@ __global__ void __launch_bounds__(kPBlock)
                   const float2* __restrict__ velocity, Dom d, Scale3 s, Slope slope,
                   int64_t row_lo, int64_t cells) {
   const float exitSlope = exit_slope_of(slope);
+  s = scale_of(slope, s);
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
   if (t >= cells) return;
   const int64_t m = model_base(d.rows * d.W);
@@ -431,13 +453,14 @@ __device__ __forceinline__ int64_t tile_of(const Dom& d, float px, float py, int
   return (lx / kTile) * tiles_w + cy / kTile;
 }
 
-// pass 1: draw the spawn points (advancing every walker's stream) and count per tile
+// pass 1: draw the spawn points (advancing every walker's stream) and count per tile; N walkers per model in
+// the spawn array, of which model blockIdx.y draws draws.walkers(N)
 template <class Draws>
 __global__ void __launch_bounds__(kPBlock)
     k_spawn_count(float2* __restrict__ spawn, uint32_t* __restrict__ count, Draws draws, int64_t N, Dom d,
                   int64_t tiles_w, int64_t tiles) {
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
-  if (n >= N) return;
+  if (n >= draws.walkers(N)) return;
   const float2 pos = draws.spawn(n, d);
   spawn[model_base(N) + n] = pos;
   if (owns_spawn(d, pos.x)) atomicAdd(&count[model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w)], 1u);
@@ -483,6 +506,18 @@ __global__ void __launch_bounds__(kPBlock)
   const int64_t tile = model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w);
   sorted[model_base(N) + start[tile] + atomicAdd(&fill[tile], 1u)] = pos;
 }
+// the same for a batch of different models: of the N walkers per model, model blockIdx.y drew its record's N_b
+__global__ void __launch_bounds__(kPBlock)
+    k_spawn_scatter_models(float2* __restrict__ sorted, uint32_t* __restrict__ fill,
+                           const uint32_t* __restrict__ start, const float2* __restrict__ spawn,
+                           int64_t N, Dom d, int64_t tiles_w, int64_t tiles, ModelParams ps) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x;
+  if (n >= ps.walkers(N)) return;
+  const float2 pos = spawn[model_base(N) + n];
+  if (!owns_spawn(d, pos.x)) return;
+  const int64_t tile = model_base(tiles + 1) + tile_of(d, pos.x, pos.y, tiles_w);
+  sorted[model_base(N) + start[tile] + atomicAdd(&fill[tile], 1u)] = pos;
+}
 
 // work-group -> slot in the sorted order: block b runs on XCD b % 8; give every
 // XCD one contiguous eighth of the tile sequence
@@ -508,7 +543,8 @@ __global__ void __launch_bounds__(kPBlock)
   if (t < 0) return;
   const int64_t cells = d.rows * d.W;
   const float2 pos = sorted[model_base(N) + t];
-  trace_fluvial(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
+  trace_fluvial(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, ps.walkers(N), d,
+                ps.scale(s), param);
 }
 
 template <bool ALB, class Params = UniformParam>
@@ -520,7 +556,8 @@ __global__ void __launch_bounds__(kPBlock)
   if (t < 0) return;
   const int64_t cells = d.rows * d.W;
   const float2 pos = sorted[model_base(N) + t];
-  trace_debris(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, N, d, s, param);
+  trace_debris(PackedFields{F.p4 + model_base(cells)}, model_of<ALB>(P, cells), pos.x, pos.y, ps.walkers(N), d,
+               ps.scale(s), param);
 }
 
 static Scale3 s3p(const float* s) { return Scale3{s[0], s[1], s[2]}; }
@@ -614,7 +651,8 @@ static int scratch_get(int slot, size_t lead, int64_t B, int64_t N, const Dom& d
 
 // One launch of the small-N shapes: B models of domain d side by side (model b's planes b * rows * W cells on),
 // N walkers each.  `albedoFlux` / `albedoSource`: the kind's colour flux plane and the spawn colours, or null.
-// `p`: every model's param; a sweep's come from the ModelParams handed to launch_small instead.
+// `s`, `p`: every model's scale and param; a batch of different models takes them, and each model's N_b <= N,
+// from the ModelParams handed to launch_small instead.
 struct SmallLaunch {
   const soil_erosion_planes* P;
   float* albedoFlux;
@@ -634,7 +672,8 @@ static ModelParams pack_slope(const ModelParams& m) { return m; }
 
 // The direct shape (`w` null) or the staged shape in `w`, at most kMaxGridY models per launch (every pointer
 // advanced past the models launched before).  ALB: a coloured batch (model_of).  Params: UniformParam{L.p}, or
-// a sweep's ModelParams (nothing about the launch depends on its values: per-model maxage is a walker's bound).
+// a batch's ModelParams: the launch is sized by L.N = max N_b, and nothing else about it depends on the records
+// (per-model maxage is a walker's bound, N_b a lane's).
 template <bool ALB, class Draws, class Params = UniformParam>
 static int launch_small(int kind, const SmallLaunch& L, Draws draws, const Scratch* w, Params params = {}) {
   if constexpr (!Params::kPerModel) params = UniformParam{L.p};
@@ -678,7 +717,11 @@ static int launch_small(int kind, const SmallLaunch& L, Draws draws, const Scrat
                                                                                   pack_slope(ps), lo, packed);
     k_spawn_count<<<walkers, kPBlock, 0, L.st>>>(spawn, count, dr, N, L.d, w->tiles_w, w->tiles);
     k_tile_scan<<<nb, 1024, 0, L.st>>>(start, count, w->tiles);
-    k_spawn_scatter<<<walkers, kPBlock, 0, L.st>>>(sorted, fill, start, spawn, N, L.d, w->tiles_w, w->tiles);
+    if constexpr (Params::kPerModel)
+      k_spawn_scatter_models<<<walkers, kPBlock, 0, L.st>>>(sorted, fill, start, spawn, N, L.d, w->tiles_w,
+                                                            w->tiles, ps);
+    else
+      k_spawn_scatter<<<walkers, kPBlock, 0, L.st>>>(sorted, fill, start, spawn, N, L.d, w->tiles_w, w->tiles);
     const dim3 traced(blocks_for(N, kPBlock) + 8, nb);
     if (fluvial)
       k_fluvial_sorted<ALB, Params><<<traced, kPBlock, 0, L.st>>>(PF, sorted, start, w->tiles, N,
@@ -719,9 +762,10 @@ int particles_fluvial(const Launch& L) { return particles_single(FLUVIAL, L); }
 // the overlapped pair retires with colour)
 int particles_debris(const Launch& L) { return particles_single(DEBRIS, L); }
 
-// The seeds of a batch (and a sweep's params) reach the device through a pinned buffer of the host thread (the
-// caller's arrays may go as soon as the call returns): before it is written again, the copy queued from it the
-// call before has been made — which lets the host queue one batch ahead of the device, and not further.
+// The seeds of a batch (or the records of a batch of different models) reach the device through a pinned buffer
+// of the host thread (the caller's arrays may go as soon as the call returns): before it is written again, the
+// copy queued from it the call before has been made — which lets the host queue one batch ahead of the device, and
+// not further.
 namespace {
 const std::thread::id g_seed_loader = std::this_thread::get_id();
 struct SeedStaging {
@@ -762,55 +806,95 @@ static int upload_seeds(void* dst, std::initializer_list<std::pair<const void*, 
   return SOIL_OK;
 }
 
-// A sweep's params on the device without seeds (the cell phase alone, or a step with N == 0): workspace slot 11.
-int batch_params_to_device(const soil_param* params, int64_t B, hipStream_t st, const Param** params_dev) {
-  const size_t bytes = sizeof(Param) * static_cast<size_t>(B);
+static_assert(sizeof(soil_batch_model) == 152 && alignof(soil_batch_model) == 8, "soil_batch_model: 152 bytes");
+static_assert(offsetof(soil_batch_model, param) == 0 && offsetof(soil_batch_model, scale) == 112 &&
+                  offsetof(soil_batch_model, N) == 128 && offsetof(soil_batch_model, seed) == 136 &&
+                  offsetof(soil_batch_model, step_index) == 144,
+              "soil_batch_model: field offsets as soil_hip.h");
+
+// A batch's records on the device without walkers (the cell phase alone, or a step with every N_b == 0):
+// workspace slot 11.
+int batch_models_to_device(const soil_batch_model* models, int64_t B, hipStream_t st,
+                           const soil_batch_model** models_dev) {
+  const size_t bytes = sizeof(soil_batch_model) * static_cast<size_t>(B);
   void* base = nullptr;
   if (int rc = workspace_get(11, bytes, &base); rc != SOIL_OK) return rc;
-  if (int rc = upload_seeds(base, {{params, bytes}}, st); rc != SOIL_OK) return rc;
-  *params_dev = static_cast<const Param*>(base);
+  if (int rc = upload_seeds(base, {{models, bytes}}, st); rc != SOIL_OK) return rc;
+  *models_dev = static_cast<const soil_batch_model*>(base);
   return SOIL_OK;
+}
+
+int check_batch_models(int64_t B, int64_t H, int64_t W, const soil_batch_model* models, const char* what,
+                       int64_t* N_max) {
+  const std::string w(what);
+  SOIL_REQUIRE(models, w + ": null models");
+  int64_t N = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    SOIL_REQUIRE(models[b].N >= 0 && models[b].N <= 0x7fffffffll,
+                 w + ": models[" + std::to_string(b) + "].N outside [0, 2^31)");
+    N = models[b].N > N ? models[b].N : N;
+  }
+  if (int rc = check_batch(B, H, W, N, &models->seed, what); rc != SOIL_OK) return rc;  // (the seeds: records)
+  *N_max = N;
+  return SOIL_OK;
+}
+
+std::vector<soil_batch_model> sweep_records(int64_t B, const soil_param* params, const float scale[3], int64_t N,
+                                            const uint64_t* seeds, uint64_t step_index) {
+  std::vector<soil_batch_model> models(static_cast<size_t>(B));
+  for (int64_t b = 0; b < B; ++b) {
+    soil_batch_model& m = models[b];
+    m.param = params[b];
+    std::memcpy(m.scale, scale, sizeof(m.scale));
+    m.N = N;
+    m.seed = seeds ? seeds[b] : 0;
+    m.step_index = step_index;
+  }
+  return models;
 }
 
 // soil_particles_batch (soil_hip.h): B whole-grid models, one after the other in every plane; walker n of model b
 // draws from (seeds[b], n, offset), the state soil_erode_step seeds into its tensor for that model alone.  What
 // a lane deposits stays in its model, a NaN walker's (0, 0) included.  Workspace slot 11: the device seeds, then
-// the staged scratch of all B models.  A sweep (`params`, soil_particles_batch_params): slot 11 starts with the
-// B params, the seeds behind them, both in one copy.
+// the staged scratch of all B models.  A batch of different models (`models`, soil_particles_batch_models): slot
+// 11 starts with the B records in place of the seeds, in one copy.
 int particles_batch(const soil_erosion_planes* P, const soil_colour_planes* C, int64_t B, int64_t H, int64_t W,
                     int64_t N, const uint64_t* seeds, uint64_t step_index, const float scale[3],
-                    const soil_param* param, hipStream_t st, const soil_param* params, const Param** params_dev) {
+                    const soil_param* param, hipStream_t st, const soil_batch_model* models,
+                    const soil_batch_model** models_dev) {
   // the colour flux planes of all B models (consecutive): one memset each, also when N == 0, as the single
   // coloured pair does
   if (C)
     if (int rc = clear_flux(nullptr, C, BOTH_KINDS, B * H * W, st); rc != SOIL_OK) return rc;
   if (N == 0)
-    return params && params_dev ? batch_params_to_device(params, B, st, params_dev) : SOIL_OK;
+    return models && models_dev ? batch_models_to_device(models, B, st, models_dev) : SOIL_OK;
   const bool staged = use_staged(N);  // the single model's rule; what would be tiled alone runs staged
   const Dom d = full_domain(H, W);
   Scratch w{};
-  const size_t b_params = params ? sizeof(Param) * static_cast<size_t>(B) : 0;  // (112 B: seeds stay 8-aligned)
-  const size_t b_seeds = sizeof(uint64_t) * static_cast<size_t>(B);
-  if (int rc = scratch_get(11, b_params + b_seeds, B, N, d, staged, &w); rc != SOIL_OK) return rc;
-  const Param* const params_on = static_cast<const Param*>(w.lead);
-  uint64_t* const seeds_dev = reinterpret_cast<uint64_t*>(static_cast<char*>(w.lead) + b_params);
-  if (int rc = upload_seeds(w.lead, {{params, b_params}, {seeds, b_seeds}}, st); rc != SOIL_OK) return rc;
-  if (params && params_dev) *params_dev = params_on;
+  // (152-byte records, 8-byte seeds: the scratch behind them is 256-aligned either way)
+  const size_t lead = (models ? sizeof(soil_batch_model) : sizeof(uint64_t)) * static_cast<size_t>(B);
+  if (int rc = scratch_get(11, lead, B, N, d, staged, &w); rc != SOIL_OK) return rc;
+  if (int rc = upload_seeds(w.lead, {{models ? static_cast<const void*>(models) : seeds, lead}}, st); rc != SOIL_OK)
+    return rc;
+  const ModelParams records{static_cast<const soil_batch_model*>(w.lead)};
+  if (models && models_dev) *models_dev = records.models;
   const uint64_t offset = step_index * static_cast<uint64_t>(N);
   for (int kind : {FLUVIAL, DEBRIS}) {
     // with colour: the kind's colour flux plane and the spawn colours (albedo_surface, also in the staged
-    // shape: the packed fields hold none)
+    // shape: the packed fields hold none); a batch of different models: scale and param from the records
     const SmallLaunch S{P, C ? (kind == FLUVIAL ? C->albedo_fluvial : C->albedo_debris) : nullptr,
-                        C ? C->albedo_surface : nullptr, nullptr, nullptr, B, N, d, s3p(scale),
-                        params ? params[0] : *param, st};
-    const SeedDraws draws{seeds_dev, kind == FLUVIAL ? offset : offset + 2};  // the debris launch: two draws on
+                        C ? C->albedo_surface : nullptr, nullptr, nullptr, B, N, d,
+                        models ? Scale3{} : s3p(scale), models ? Param{} : *param, st};
+    const uint64_t debris = kind == FLUVIAL ? 0 : 2;  // the debris launch: two draws on
     const Scratch* const ws = staged ? &w : nullptr;
-    const ModelParams sweep{params_on};
     int rc;
-    if (params)
-      rc = C ? launch_small<true>(kind, S, draws, ws, sweep) : launch_small<false>(kind, S, draws, ws, sweep);
-    else
+    if (models) {
+      const ModelDraws draws{records, debris};
+      rc = C ? launch_small<true>(kind, S, draws, ws, records) : launch_small<false>(kind, S, draws, ws, records);
+    } else {
+      const SeedDraws draws{static_cast<const uint64_t*>(w.lead), offset + debris};
       rc = C ? launch_small<true>(kind, S, draws, ws) : launch_small<false>(kind, S, draws, ws);
+    }
     if (rc != SOIL_OK) return rc;
   }
   return SOIL_OK;
@@ -1046,7 +1130,21 @@ int soil_particles_batch_params(const soil_erosion_planes* planes, const soil_co
   SOIL_REQUIRE(!colour || has_colour(colour), "particles_batch_params: every colour plane is required");
   if (int rc = check_batch(B, H, W, N, seeds, "particles_batch_params"); rc != SOIL_OK) return rc;
   SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch_params: null plane");
-  return particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, nullptr, as_stream(stream), params);
+  // a batch of different models whose records share scale, N and step_index
+  const std::vector<soil_batch_model> models = sweep_records(B, params, scale, N, seeds, step_index);
+  return particles_batch(planes, colour, B, H, W, N, nullptr, 0, nullptr, nullptr, as_stream(stream),
+                         models.data());
+}
+
+int soil_particles_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                int64_t H, int64_t W, const soil_batch_model* models, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes, "particles_batch_models: null argument");
+  SOIL_REQUIRE(!colour || has_colour(colour), "particles_batch_models: every colour plane is required");
+  int64_t N = 0;
+  if (int rc = check_batch_models(B, H, W, models, "particles_batch_models", &N); rc != SOIL_OK) return rc;
+  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch_models: null plane");
+  return particles_batch(planes, colour, B, H, W, N, nullptr, 0, nullptr, nullptr, as_stream(stream), models);
 }
 
 int soil_particle_steps(uint64_t* total, int reset, void* stream) {

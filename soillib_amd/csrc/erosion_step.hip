@@ -183,8 +183,19 @@ int soil_erode_step_batch_colour(const soil_erosion_planes* planes, const soil_c
   return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, 0, st);
 }
 
-// A sweep step: as the (coloured) batch step, model b with params[b].  The params reach the device once, in the
-// particle phase's copy of the seeds, and the cell phase reads that copy.
+// A step of a batch of different models: the records reach the device once, in place of the seeds of the
+// particle phase's copy, and the cell phase reads that copy.
+static int step_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                             int64_t H, int64_t W, int64_t N, const soil_batch_model* models, hipStream_t st) {
+  const soil_batch_model* models_dev = nullptr;
+  if (int rc = particles_batch(planes, colour, B, H, W, N, nullptr, 0, nullptr, nullptr, st, models, &models_dev);
+      rc != SOIL_OK)
+    return rc;
+  return erode_cells_fused_batch(planes, colour, B, H, W, nullptr, nullptr, 0, st, models_dev);
+}
+
+// A sweep step: as the (coloured) batch step, model b with params[b]: a batch of different models whose records
+// share scale, N and step_index.
 int soil_erode_step_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
                                  int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
                                  const float scale[3], const soil_param* params, void* stream) {
@@ -196,12 +207,23 @@ int soil_erode_step_batch_params(const soil_erosion_planes* planes, const soil_c
   SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch_params: every plane but `height` is required");
   SOIL_REQUIRE(P.layers != P.layers_next,
                "erode_step_batch_params: layers and layers_next must be distinct buffers");
-  const hipStream_t st = as_stream(stream);
-  const soil_param* params_dev = nullptr;
-  if (int rc = particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, nullptr, st, params, &params_dev);
-      rc != SOIL_OK)
-    return rc;
-  return erode_cells_fused_batch(planes, colour, B, H, W, scale, nullptr, 0, st, params_dev);
+  const std::vector<soil_batch_model> models = sweep_records(B, params, scale, N, seeds, step_index);
+  return step_batch_models(planes, colour, B, H, W, N, models.data(), as_stream(stream));
+}
+
+// A step of a batch of different models (soil_hip.h): model b with models[b].
+int soil_erode_step_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
+                                 int64_t H, int64_t W, const soil_batch_model* models, void* stream) {
+  SOIL_DEVICE();
+  SOIL_REQUIRE(planes, "erode_step_batch_models: null argument");
+  SOIL_REQUIRE(!colour || has_colour(colour), "erode_step_batch_models: every colour plane is required");
+  int64_t N = 0;
+  if (int rc = check_batch_models(B, H, W, models, "erode_step_batch_models", &N); rc != SOIL_OK) return rc;
+  const soil_erosion_planes& P = *planes;
+  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch_models: every plane but `height` is required");
+  SOIL_REQUIRE(P.layers != P.layers_next,
+               "erode_step_batch_models: layers and layers_next must be distinct buffers");
+  return step_batch_models(planes, colour, B, H, W, N, models, as_stream(stream));
 }
 
 int soil_erode(const soil_erode_model* model, int64_t H, int64_t W, int64_t N, uint64_t seed,

@@ -33,8 +33,14 @@ planes of the coloured step too (soil_erode_step_batch_colour): model b ends whe
 `ErosionModel(..., seed=seeds[b], colour=True).step()` leaves it.  A sequence of B
 param_t in place of `param` makes the batch a parameter sweep (soil_erode_step_batch_params):
 model b steps with params[b], as `ErosionModel(..., params[b], ..., seed=seeds[b])` would.
+B scale triples in place of `scale`, or B walker counts in place of `n_particles`, make
+a batch of different models (soil_erode_step_batch_models): model b steps as
+`ErosionModel(H, W, scales[b], params[b], Ns[b], seed=seeds[b])` would.
+`ErosionBatch.from_models(models)` copies B whole-grid `ErosionModel`s into such a batch,
+each at its own step index, and `to_models()` copies them back out.
 """
 import ctypes as C
+import numbers
 import os
 
 from . import _abi, silt
@@ -249,7 +255,15 @@ class ErosionBatch:
     steps with params[b] (soil_erode_step_batch_params, with or without colour).  A sweep holds them as
     `self.params` (`self.param` is None) and reads them at every call of particles(), cells_fused() and step(): a
     change to one of the objects, or a replaced element, takes effect at the next call.  A wrong count or an
-    element that is not a param_t raises ValueError before any device work."""
+    element that is not a param_t raises ValueError before any device work.
+
+    `scale` is one (sx, sy, sz) triple, or a sequence of B triples held as `self.scales` (`self.scale` is None)
+    and read at every call as a sweep's params are.  `n_particles` is one walker count, or a sequence of B counts
+    fixed at construction as `self.Ns` (`self.N` is None).  Either makes the batch one of different models
+    (soil_erode_step_batch_models): model b steps with its own param, scale, walker count, seed and step index
+    `first_step[b] + step_index`, where `first_step` is 0 unless the batch came from from_models().  A wrong
+    count, an element that is not 3 numbers or a negative walker count raises ValueError before any device
+    work."""
 
     PLANES_1 = ErosionModel.PLANES_1
     PLANES_2 = ErosionModel.PLANES_2
@@ -262,7 +276,7 @@ class ErosionBatch:
             raise ValueError("ErosionBatch: %d seeds for %d models" % (len(self.seeds), self.B))
         if self.B < 1 or self.H < 1 or self.W < 1:
             raise ValueError("ErosionBatch: B, H and W must be >= 1")
-        self.scale = [float(v) for v in scale]
+        self.scale, self.scales = self._scale_arg(scale)
         from .soil import param_t
         if isinstance(param, param_t):
             self.param, self.params = param, None
@@ -273,9 +287,10 @@ class ErosionBatch:
                 raise ValueError("ErosionBatch: param must be a param_t or a sequence of %d param_t" % self.B)
             self.param = None
             self._check_params()
-        self.N = int(n_particles)
+        self.N, self.Ns = self._n_arg(n_particles)
         self.colour = bool(colour)
         self.step_index = 0
+        self.first_step = [0] * self.B
         shape = (self.B, self.H, self.W)
         alloc = lambda *dims: silt.tensor(silt.float32, silt.shape(*dims), silt.gpu)
         self.layers = alloc(*shape, 2)
@@ -300,6 +315,63 @@ class ErosionBatch:
     _colour = ErosionModel._colour
     _scale = ErosionModel._scale
 
+    def _scale_arg(self, scale):
+        """(scale, None) for one triple, (None, scales) for a sequence of B triples."""
+        try:
+            items = list(scale)
+        except TypeError:
+            raise ValueError("ErosionBatch: scale must be a triple or a sequence of %d triples" % self.B)
+        if len(items) == 3 and all(isinstance(v, numbers.Real) for v in items):
+            return [float(v) for v in items], None
+        self.scales = items
+        self._check_scales()
+        return None, items
+
+    def _check_scales(self):
+        if len(self.scales) != self.B:
+            raise ValueError("ErosionBatch: %d scales for %d models" % (len(self.scales), self.B))
+        for b, s in enumerate(self.scales):
+            try:
+                ok = len(s) == 3 and all(isinstance(v, numbers.Real) for v in s)
+            except TypeError:
+                ok = False
+            if not ok:
+                raise ValueError("ErosionBatch: scales[%d] is not 3 numbers: %r" % (b, s))
+
+    def _n_arg(self, n_particles):
+        """(N, None) for one walker count, (None, Ns) for a sequence of B counts."""
+        try:
+            items = list(n_particles)
+        except TypeError:
+            return int(n_particles), None
+        if len(items) != self.B:
+            raise ValueError("ErosionBatch: %d walker counts for %d models" % (len(items), self.B))
+        Ns = []
+        for b, n in enumerate(items):
+            if not isinstance(n, numbers.Integral) or isinstance(n, bool) or n < 0:
+                raise ValueError("ErosionBatch: Ns[%d] = %r is not a walker count >= 0" % (b, n))
+            Ns.append(int(n))
+        return None, Ns
+
+    def _per_model(self):
+        """True when the models differ in more than their param: the soil_*_batch_models entries."""
+        return self.scales is not None or self.Ns is not None or any(self.first_step)
+
+    def _models(self):
+        """The B records as they are now, a C array of soil_batch_model (copied by the entry points)."""
+        if self.params is not None:
+            self._check_params()
+        if self.scales is not None:
+            self._check_scales()
+        models = (_abi.BatchModel * self.B)()
+        for b, m in enumerate(models):
+            m.param = (self.params[b] if self.params is not None else self.param)._c
+            m.scale[:] = [float(v) for v in (self.scales[b] if self.scales is not None else self.scale)]
+            m.N = self.Ns[b] if self.Ns is not None else self.N
+            m.seed = self.seeds[b]
+            m.step_index = self.first_step[b] + self.step_index
+        return models
+
     def _check_params(self):
         from .soil import param_t
         if len(self.params) != self.B:
@@ -317,6 +389,65 @@ class ErosionBatch:
         """A sweep's entry `name` (soil_*_batch_params): planes, colour (or NULL), then `args`."""
         colour = C.byref(self._colour()) if self.colour else None
         _abi.check(getattr(_abi.lib(), name)(C.byref(self._planes()), colour, *args))
+
+    @classmethod
+    def from_models(cls, models):
+        """A new batch holding copies (device to device) of the planes of B whole-grid ErosionModels of one (H, W)
+        and one colour setting, model b with the param, scale, walker count, seed and step index of models[b].  An
+        empty list, mixed shapes or colour settings, or a row slab raise ValueError before any device work."""
+        models = list(models)
+        if not models:
+            raise ValueError("ErosionBatch.from_models: no models")
+        m0 = models[0]
+        for b, m in enumerate(models):
+            if not isinstance(m, ErosionModel):
+                raise ValueError("ErosionBatch.from_models: models[%d] is a %s, not an ErosionModel" % (
+                    b, type(m).__name__))
+            if m.rows != m.H:
+                raise ValueError("ErosionBatch.from_models: models[%d] is a row slab (%d of %d rows)" % (
+                    b, m.rows, m.H))
+            if (m.H, m.W) != (m0.H, m0.W):
+                raise ValueError("ErosionBatch.from_models: models[%d] is %dx%d, models[0] %dx%d" % (
+                    b, m.H, m.W, m0.H, m0.W))
+            if m.colour != m0.colour:
+                raise ValueError("ErosionBatch.from_models: models[%d] has colour=%s, models[0] colour=%s" % (
+                    b, m.colour, m0.colour))
+        batch = cls(len(models), m0.H, m0.W, [list(m.scale) for m in models], [m.param for m in models],
+                    [m.N for m in models], [m.seed for m in models], colour=m0.colour)
+        batch.first_step = [int(m.step_index) for m in models]
+        for b, m in enumerate(models):
+            for name in batch._names():
+                batch._copy(name, b, m, into_batch=True)
+        return batch
+
+    def to_models(self):
+        """B new ErosionModels holding copies of the planes, model b at step index first_step[b] + step_index
+        with its own param, scale, walker count and seed."""
+        out = []
+        for b in range(self.B):
+            m = ErosionModel(self.H, self.W, list(self.scales[b]) if self.scales is not None else list(self.scale),
+                             self.params[b] if self.params is not None else self.param,
+                             self.Ns[b] if self.Ns is not None else self.N, seed=self.seeds[b], colour=self.colour)
+            for name in self._names():
+                self._copy(name, b, m, into_batch=False)
+            m.step_index = self.first_step[b] + self.step_index
+            out.append(m)
+        return out
+
+    def _copy(self, name, b, model, into_batch):
+        """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""
+        t, single = getattr(self, name), getattr(model, name)
+        per = t.nbytes() // self.B
+        if single.nbytes() != per:
+            raise ValueError("plane %s: %d bytes per model, the single model holds %d" % (name, per, single.nbytes()))
+        here = t.ptr + b * per
+        dst, src = (here, single.ptr) if into_batch else (single.ptr, here)
+        _abi.check(_abi.lib().soil_memcpy_d2d(C.c_void_p(dst), C.c_void_p(src), per, _abi.stream()))
+
+    def _batch_models(self, name, *args):
+        """An entry `name` of a batch of different models (soil_*_batch_models): planes, colour (or NULL), B, H, W,
+        the records, then `args`."""
+        self._sweep(name, (self.B, self.H, self.W, self._models()) + args)
 
     def set_layers(self, layers_tensor):
         """Copy a (B, H, W, 2) tensor of (bedrock, sediment) into the batch."""
@@ -339,7 +470,11 @@ class ErosionBatch:
     def particles(self):
         """Both particle launches of this step for every model, adding into the flux planes
         (soil_particles_batch); with colour the two colour flux planes are cleared first and receive this
-        step's colour flux (soil_particles_batch_colour).  A sweep: soil_particles_batch_params."""
+        step's colour flux (soil_particles_batch_colour).  A sweep: soil_particles_batch_params; different
+        models: soil_particles_batch_models."""
+        if self._per_model():
+            self._batch_models("soil_particles_batch_models", _abi.stream())
+            return
         if self.params is not None:
             self._sweep("soil_particles_batch_params", (self.B, self.H, self.W, self.N, self._seeds, self.step_index,
                                                         self._scale(), self._params(), _abi.stream()))
@@ -355,7 +490,12 @@ class ErosionBatch:
 
     def cells_fused(self, keep_flux=False):
         """Fused cell phase of every model (soil_erode_cells_fused_batch[_colour]); `keep_flux`: the flux
-        planes are left as they are (SOIL_CELLS_KEEP_FLUX).  A sweep: soil_erode_cells_fused_batch_params."""
+        planes are left as they are (SOIL_CELLS_KEEP_FLUX).  A sweep: soil_erode_cells_fused_batch_params;
+        different models: soil_erode_cells_fused_batch_models."""
+        if self._per_model():
+            self._batch_models("soil_erode_cells_fused_batch_models", _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0,
+                               _abi.stream())
+            return
         if self.params is not None:
             self._sweep("soil_erode_cells_fused_batch_params", (self.B, self.H, self.W, self._scale(), self._params(),
                                                                 _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0,
@@ -375,7 +515,13 @@ class ErosionBatch:
 
     def step(self):
         """One erosion step of every model (soil_erode_step_batch, with colour soil_erode_step_batch_colour);
-        swaps the layer buffers.  A sweep: soil_erode_step_batch_params."""
+        swaps the layer buffers.  A sweep: soil_erode_step_batch_params; different models:
+        soil_erode_step_batch_models."""
+        if self._per_model():
+            self._batch_models("soil_erode_step_batch_models", _abi.stream())
+            self.swap_layers()
+            self.step_index += 1
+            return
         if self.params is not None:
             self._sweep("soil_erode_step_batch_params", (self.B, self.H, self.W, self.N, self._seeds, self.step_index,
                                                          self._scale(), self._params(), _abi.stream()))
