@@ -1016,31 +1016,19 @@ def test_transport_random_parameter_sets(hip, oracle, seed):
     (log-uniform over several decades around the script's values, random cell sizes, an
     external force every other draw) against the oracle: same walks step for step, flux
     within the summation-order tolerance."""
+    random_parameter_transport(hip, oracle, seed, 3)
+
+
+def random_parameter_transport(hip, oracle, seed, mode):
+    """test_transport_random_parameter_sets in launch shape `mode` (soil_set_particle_mode; 0 afterwards)."""
     from soillib_amd import soil
     import ctypes as C
     from soillib_amd import _abi
+    from util import random_param
     r = np.random.default_rng(1000 + seed)
     H, W, N = int(r.integers(70, 140)), int(r.integers(70, 140)), 6000
-    op = script_param(oracle.default_param())
-    op.maxage = int(r.integers(40, 130))
+    op = random_param(oracle, r, force=seed % 2)
     lu = lambda lo, hi: float(np.exp(r.uniform(np.log(lo), np.log(hi))))
-    op.gravity = lu(1.0, 30.0)
-    op.evapRate = lu(1e-5, 1e-2)
-    op.viscosityWater = lu(1e-7, 1e-2)
-    op.bedShearWater = lu(0.05, 60.0)
-    op.frictionFactor = lu(0.01, 1.0)
-    op.depositionRateFluvial = lu(1e-7, 1e-2)
-    op.suspensionRateFluvial = lu(1e-5, 1e-2)
-    op.fluvialExponent = lu(0.01, 1.5)
-    op.viscosityDebris = lu(1e-4, 0.1)
-    op.bedShearDebris = lu(1e-3, 1.0)
-    op.yieldStress = lu(1e-3, 1e7)
-    op.critSlopeBedrock = lu(0.02, 0.8)
-    op.landslideRateDebris = lu(1e-4, 1e-1)
-    op.suspensionRateDebris = lu(1e-5, 1e-2)
-    op.depositionRateDebris = lu(1e-5, 1e-2)
-    if seed % 2:
-        op.force[0], op.force[1] = float(r.normal(0, 0.3)), float(r.normal(0, 0.3))
     pp = product_param(op)
     scale = (lu(0.01, 3.0), lu(0.01, 3.0), lu(0.5, 8.0))
     layers = terrain(oracle, H, W, sediment=0.01, rng_seed=seed)
@@ -1053,7 +1041,7 @@ def test_transport_random_parameter_sets(hip, oracle, seed):
     steps_f = oracle.particles_fluvial(o["wf"], o["mf"], o["vf"], None, orng, layers, rain, wh0, vel0,
                                        None, scale, op)
     rule_d = oracle.particles_debris_retire(o["df"], o["dvf"], None, orng, layers, vel0, None, scale, op)
-    assert hip.soil_set_particle_mode(3) == 0
+    assert hip.soil_set_particle_mode(mode) == 0
     try:
         g = {k: to_gpu(v) for k, v in dict(wf=z1, mf=z1, vf=z2, df=z1, dvf=z2).items()}
         grng = rng_to_gpu(oracle.rng_seed(N, 11, 5 * seed))
@@ -1071,7 +1059,7 @@ def test_transport_random_parameter_sets(hip, oracle, seed):
     finally:
         hip.soil_set_particle_mode(0)
     from util import debris_steps_agree
-    assert got_f == steps_f and debris_steps_agree(got_d, rule_d, N), (got_f, got_d, steps_f, rule_d)
+    assert got_f == steps_f and debris_steps_agree(got_d, rule_d, N, tiled=mode == 3), (got_f, got_d, steps_f, rule_d)
     for k in ("wf", "mf", "vf", "df", "dvf"):
         _flux_close(to_np(g[k]), o[k], "random parameters, flux " + k)
 

@@ -418,6 +418,45 @@ def test_slab_particles_partition_exactly(oracle):
     np.testing.assert_allclose(parts.ravel()[1:], full.ravel()[1:], rtol=1e-5, atol=1e-9)
 
 
+@pytest.mark.parametrize("seed,start", [(0, 0), (7, 2 ** 32 - 1), (2 ** 64 - 1, 2 ** 32 - 1), (2 ** 63 + 11, 2 ** 32 - 2),
+                                        (2 ** 32 + 5, 2 ** 42 + 3)])
+def test_fluvial_launch_leaves_every_stream_two_draws_on(oracle, seed, start):
+    """The batched step (include/soil_hip.h, soil_particles_batch) starts its debris launch from fresh streams at
+    offset + 2; the oracle's debris launch continues the fluvial launch's streams.  The two agree because the
+    fluvial launch takes exactly two draws of every stream: offsets start + 2 afterwards, across the 32-bit carry
+    of the offset and with a 64-bit seed, and a debris launch from the continued streams equals one from fresh
+    streams at start + 2 bit for bit (its planes and its step count)."""
+    H, W, N = 40, 52, 700
+    layers = terrain(oracle, H, W, sediment=0.01)
+    r = np.random.default_rng(17)
+    vel = (r.standard_normal((H, W, 2)) * 0.5).astype(np.float32)
+    rain = np.ones((H, W), np.float32)
+    p = oracle.default_param()
+    p.maxage = 48
+    p.critSlopeBedrock = 0.05                        # landslides on the synthetic terrain
+    p.yieldStress = 0.001
+    scale = (20.0 / H, 20.0 / W, 4.0)
+    z1, z2 = np.zeros((H, W), np.float32), np.zeros((H, W, 2), np.float32)
+    rng = oracle.rng_seed(N, seed, start)
+    oracle.particles_fluvial(z1.copy(), z1.copy(), z2.copy(), None, rng, layers, rain, z1.copy(), vel.copy(), None,
+                             scale, p)
+    assert (rng["seed"] == seed).all()
+    assert (rng["offset"] == start + 2).all(), np.unique(rng["offset"])
+    out = []
+    for streams in (rng, oracle.rng_seed(N, seed, start + 2)):
+        mf, vf = z1.copy(), z2.copy()
+        steps = oracle.particles_debris(mf, vf, None, streams, layers, vel.copy(), None, scale, p)
+        out.append((steps, mf, vf))
+    (steps_a, mf_a, vf_a), (steps_b, mf_b, vf_b) = out
+    assert steps_a == steps_b > N and np.nanmax(mf_a) > 0
+    assert np.array_equal(mf_a, mf_b, equal_nan=True) and np.array_equal(vf_a, vf_b, equal_nan=True)
+    # the seed's high word and the offset's take part: another high word, other walks
+    other = oracle.rng_seed(N, seed ^ (1 << 40), start + 2)
+    mf_c = z1.copy()
+    oracle.particles_debris(mf_c, z2.copy(), None, other, layers, vel.copy(), None, scale, p)
+    assert not np.array_equal(mf_c, mf_a, equal_nan=True)
+
+
 # ------------------------------------------------ build-defined operators (no reference definition)
 
 def test_fill_depressions_known_answers(oracle):

@@ -42,6 +42,38 @@ def script_param(oracle_or_param):
     return p
 
 
+def log_uniform(r, lo, hi):
+    """One draw of numpy Generator `r`, log-uniform in [lo, hi)."""
+    return float(np.exp(r.uniform(np.log(lo), np.log(hi))))
+
+
+def random_param(oracle, r, force=False):
+    """An oracle Param drawn with numpy Generator `r` (test_gpu_parity.test_transport_random_parameter_sets): the
+    script's values, maxage in [40, 130), the rates log-uniform over several decades around the script's, and with
+    `force` an external force of N(0, 0.3) per axis.  The draws come in this order, one each."""
+    op = script_param(oracle.default_param())
+    op.maxage = int(r.integers(40, 130))
+    lu = lambda lo, hi: log_uniform(r, lo, hi)
+    op.gravity = lu(1.0, 30.0)
+    op.evapRate = lu(1e-5, 1e-2)
+    op.viscosityWater = lu(1e-7, 1e-2)
+    op.bedShearWater = lu(0.05, 60.0)
+    op.frictionFactor = lu(0.01, 1.0)
+    op.depositionRateFluvial = lu(1e-7, 1e-2)
+    op.suspensionRateFluvial = lu(1e-5, 1e-2)
+    op.fluvialExponent = lu(0.01, 1.5)
+    op.viscosityDebris = lu(1e-4, 0.1)
+    op.bedShearDebris = lu(1e-3, 1.0)
+    op.yieldStress = lu(1e-3, 1e7)
+    op.critSlopeBedrock = lu(0.02, 0.8)
+    op.landslideRateDebris = lu(1e-4, 1e-1)
+    op.suspensionRateDebris = lu(1e-5, 1e-2)
+    op.depositionRateDebris = lu(1e-5, 1e-2)
+    if force:
+        op.force[0], op.force[1] = float(r.normal(0, 0.3)), float(r.normal(0, 0.3))
+    return op
+
+
 def copy_param(src, dst):
     """Copy a ctypes Param (oracle or product) field by field."""
     for name, _ in src._fields_:
