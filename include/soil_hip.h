@@ -578,6 +578,38 @@ int soil_erode_cells_fused_batch_models(const soil_erosion_planes* planes, const
                                         int64_t B, int64_t H, int64_t W, const soil_batch_model* models,
                                         int flags, void* stream);
 
+/* ------------------------------------------ erosion: changing resolution */
+
+/* Every plane of every model of a batch resampled to a new resolution by one kernel: the step of the multiscale
+ * schedule (erode coarse, resample, erode finer) for whole models.  `src` holds B whole-grid models of (Ho, Wo),
+ * `dst` B models of (Hn, Wn), both model-major as in soil_erode_step_batch; B = 1 is a single model.  Any
+ * Hn, Wn, Ho, Wo >= 1: finer, coarser, non-square, another ratio on each axis.  Per model b:
+ *  - resampled (the persistent state): layers (2 channels), uplift, rainfall, waterHeight, mass, debris (1),
+ *    velocity, debrisVelocity (2) and, with colour, the four planes of soil_colour_planes (3 channels each).  Every
+ *    value is bit-identical to what soil_resize writes for that plane of that model alone: corner-aligned sample
+ *    positions, clamped corner indices, weights written 1 + -1*w and 0 + 1*w, columns interpolated first, then
+ *    rows, every fp32 operation as written.  So equal resolutions give the identity, the four corner cells are
+ *    kept, planes that are non-negative stay so, and no value of one model reaches another.
+ *  - dst->height (may be NULL) is layers'.x + layers'.y of the resampled layers, the layer_merge every step leaves
+ *    behind, and NOT the resample of src->height, which differs from it in the last bit.
+ *  - the five flux planes of dst are written zero (a step requires them zero on entry); the flux planes, height
+ *    and layers_next of src are not read and may be NULL.  dst->layers_next is not touched.
+ *  - dst->layers, dst->uplift and dst->rainfall are written, and with colour dst_colour->albedo_bedrock, although
+ *    the structs declare them `const float*` for the step's sake.
+ * `dst_colour` and `src_colour` are both NULL (physics only) or both set, then with every colour plane.
+ * SOIL_ERR_INVALID_ARGUMENT before any launch for B < 1, a size < 1, a NULL required plane, one colour struct
+ * without the other, dst->layers == src->layers (in place is not supported: the planes of dst and src must not
+ * overlap), and sizes whose byte offsets overflow int64.
+ *
+ * One launch per 65535 models (grid.z is the model), on `stream`, no host synchronisation, no workspace.  One
+ * thread per new column, a band of rows per work-group; the column index and weight are computed once per thread
+ * and the row index and weight once per row for all 12 (24 with colour) floats of the cell.  Algorithmic bytes per
+ * new cell, r = Hn*Wn / (Ho*Wo): written 48 state + 4 height + 28 zeros = 80 (128 with colour), read 44 / r
+ * (92 / r with colour). */
+int soil_erode_resize_batch(const soil_erosion_planes* dst, const soil_erosion_planes* src,
+                            const soil_colour_planes* dst_colour, const soil_colour_planes* src_colour,
+                            int64_t B, int64_t Hn, int64_t Wn, int64_t Ho, int64_t Wo, void* stream);
+
 /* The containers of the legacy API (example/erosion_gpu.py:44-71): model_t, the `data` and the
  * `track` buffers.  All float32 device planes of H*W cells ((H,W,2) for the momenta). */
 typedef struct soil_erode_model {

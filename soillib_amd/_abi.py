@@ -173,6 +173,8 @@ SIGNATURES = {
                                            C.POINTER(BatchModel), vp]),
     "soil_erode_cells_fused_batch_models": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes), i64, i64,
                                                    i64, C.POINTER(BatchModel), cint, vp]),
+    "soil_erode_resize_batch": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes),
+                                       C.POINTER(ColourPlanes), i64, i64, i64, i64, i64, vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),

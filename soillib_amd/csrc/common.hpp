@@ -278,4 +278,19 @@ __device__ __forceinline__ float2 glocal(const float2* __restrict__ layers, cons
   return glocal_from_heights(h, hn0, hp0, h0n, h0p, s, exitSlope);
 }
 
+// soil.resize of the multiscale driver (example/erosion_gpu_multiscale.py:104-141).
+// The reference snapshot holds no definition of it; defined here as
+// bilinear resampling at corner-aligned positions: new cell (i, j) samples the old
+// grid at (i*(Ho-1)/(Hn-1), j*(Wo-1)/(Wn-1)), with the weights written as in the
+// reference's sampler, (1 - t)*a + t*b (sample.hpp:48-60) — exact at t = 0 and 1, so
+// equal resolutions give the identity and the corners are kept.  (That sampler itself
+// stops interpolating in the last cell of each axis, sample.hpp:172-173; a resize
+// must not.)  Shared by k_resize (stencil.hip: one plane) and k_erode_resize
+// (erosion_resize.hip: every plane of a model).
+__device__ __forceinline__ float resize_pos(int64_t i, int64_t n_new, int64_t n_old) {
+  if (n_new <= 1) return 0.0f;
+  const float step = static_cast<float>(n_old - 1) / static_cast<float>(n_new - 1);
+  return fminf(static_cast<float>(i) * step, static_cast<float>(n_old - 1));
+}
+
 }  // namespace soil

@@ -38,6 +38,12 @@ a batch of different models (soil_erode_step_batch_models): model b steps as
 `ErosionModel(H, W, scales[b], params[b], Ns[b], seed=seeds[b])` would.
 `ErosionBatch.from_models(models)` copies B whole-grid `ErosionModel`s into such a batch,
 each at its own step index, and `to_models()` copies them back out.
+
+`ErosionModel.resized(H, W)` and `ErosionBatch.resized(H, W)` return a new model or batch of another resolution
+holding the resampled state (soil_erode_resize_batch: every plane of every model in one launch, `height` rebuilt,
+flux planes zero), with the seeds, params, step indices and walker counts carried over and each scale rescaled to
+the same world extent: the multiscale schedule (erode coarse, resample, erode finer) for whole models and batches
+(DESIGN.md 3.5).
 """
 import ctypes as C
 import numbers
@@ -46,11 +52,36 @@ import os
 from . import _abi, silt
 
 
+def _check_size(who, H, W):
+    for v in (H, W):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or v < 1:
+            raise ValueError("%s.resized: H and W must be integers >= 1, got %r x %r" % (who, H, W))
+
+
+def _rescaled(scale, Ho, Wo, H, W):
+    """The scale of the same world at (H, W) cells: the cell size times old / new, sz as it is."""
+    return [float(scale[0]) * Ho / H, float(scale[1]) * Wo / W, float(scale[2])]
+
+
+def _resize_into(new, old, B):
+    """Every plane of `old` (B models) resampled into `new` by one soil_erode_resize_batch; `new` was allocated with
+    every plane the entry point writes in full left unzeroed."""
+    dst, src = new._planes(), old._planes()
+    dst_c = src_c = None
+    if old.colour:
+        dst_colour, src_colour = new._colour(), old._colour()
+        dst_c, src_c = C.byref(dst_colour), C.byref(src_colour)
+    _abi.check(_abi.lib().soil_erode_resize_batch(C.byref(dst), C.byref(src), dst_c, src_c, B, new.H, new.W, old.H,
+                                                  old.W, _abi.stream()))
+
+
 class ErosionModel:
     """Planes of one erosion model (or one row slab of it), resident in HBM.
 
     rows    local rows held (owned + ghost), W columns
     dom     _abi.Domain describing where the slab sits in the global grid
+
+    `resized(H, W)` returns a new whole-grid model of (H, W) with the state resampled (soil_erode_resize_batch).
     """
 
     PLANES_1 = ("height", "uplift", "rainfall", "waterHeight", "waterFlux", "mass", "massFlux",
@@ -59,7 +90,11 @@ class ErosionModel:
     # soil_colour_planes, in its order: (rows, W, 3) each
     PLANES_3 = ("albedoBedrock", "albedoSurface", "albedoFluvial", "albedoDebris")
 
-    def __init__(self, H, W, scale, param, n_particles, seed=0, dom=None, alloc=None, colour=False):
+    # what soil_erode_resize_batch writes in full: every plane but layers_next
+    RESIZED = ("layers",) + PLANES_1 + PLANES_2 + PLANES_3
+
+    def __init__(self, H, W, scale, param, n_particles, seed=0, dom=None, alloc=None, colour=False, _written=()):
+        """`_written`: planes the caller is about to write in full, not zeroed here (resized())."""
         self.H, self.W = int(H), int(W)
         self.scale = [float(v) for v in scale]
         self.param = param
@@ -85,7 +120,8 @@ class ErosionModel:
         for name in self.PLANES_3 if self.colour else ():
             setattr(self, name, alloc(silt.float32, (r, w, 3)))
         for name in ("layers", "layers_next") + self.PLANES_1 + self.PLANES_2 + (self.PLANES_3 if self.colour else ()):
-            silt.set(getattr(self, name), 0.0)
+            if name not in _written:
+                silt.set(getattr(self, name), 0.0)
         silt.seed(self.rng, self.seed, 0)
 
     # -- helpers -------------------------------------------------------------
@@ -107,6 +143,34 @@ class ErosionModel:
     def set_layers(self, layers_tensor):
         """Copy an (rows, W, 2) tensor of (bedrock, sediment) into the model."""
         silt.set(self.layers, layers_tensor)
+
+    def resized(self, H, W, scale=None, n_particles=None):
+        """A new ErosionModel of (H, W) holding this model's state resampled (soil_erode_resize_batch, one launch:
+        every persistent plane bilinear as soil_resize, `height` = the new layers merged, flux planes zero); this
+        model is left as it is.  The new model has the same param object, seed and colour setting and continues
+        at this model's step index.  `scale` defaults to the same world with more (or fewer) cells,
+        [sx * Ho / H, sy * Wo / W, sz]; `n_particles` to this model's.  A row slab, H or W < 1, a scale that is not
+        3 numbers or a negative walker count raise ValueError before any device work."""
+        if self.rows != self.H:
+            raise ValueError("ErosionModel.resized: the model is a row slab (%d of %d rows)" % (self.rows, self.H))
+        _check_size("ErosionModel", H, W)
+        if scale is None:
+            scale = _rescaled(self.scale, self.H, self.W, H, W)
+        else:
+            try:
+                scale = list(scale)
+                ok = len(scale) == 3 and all(isinstance(v, numbers.Real) for v in scale)
+            except TypeError:
+                ok = False
+            if not ok:
+                raise ValueError("ErosionModel.resized: scale is not 3 numbers: %r" % (scale,))
+        N = self.N if n_particles is None else n_particles
+        if not isinstance(N, numbers.Integral) or isinstance(N, bool) or N < 0:
+            raise ValueError("ErosionModel.resized: n_particles = %r is not a walker count >= 0" % (N,))
+        new = ErosionModel(H, W, scale, self.param, N, seed=self.seed, colour=self.colour, _written=self.RESIZED)
+        new.step_index = self.step_index
+        _resize_into(new, self, 1)
+        return new
 
     # -- the three phases ------------------------------------------------------
     def seed_step(self):
@@ -263,13 +327,18 @@ class ErosionBatch:
     (soil_erode_step_batch_models): model b steps with its own param, scale, walker count, seed and step index
     `first_step[b] + step_index`, where `first_step` is 0 unless the batch came from from_models().  A wrong
     count, an element that is not 3 numbers or a negative walker count raises ValueError before any device
-    work."""
+    work.
+
+    `resized(H, W)` returns a new batch of (H, W) with every plane of every model resampled in one launch
+    (soil_erode_resize_batch) and the seeds, params, step indices, walker counts and rescaled scales carried
+    over."""
 
     PLANES_1 = ErosionModel.PLANES_1
     PLANES_2 = ErosionModel.PLANES_2
     PLANES_3 = ErosionModel.PLANES_3
 
-    def __init__(self, B, H, W, scale, param, n_particles, seeds, colour=False):
+    def __init__(self, B, H, W, scale, param, n_particles, seeds, colour=False, _written=()):
+        """`_written`: planes the caller is about to write in full, not zeroed here (resized())."""
         self.B, self.H, self.W = int(B), int(H), int(W)
         self.seeds = [int(v) for v in seeds]
         if len(self.seeds) != self.B:
@@ -302,7 +371,8 @@ class ErosionBatch:
         for name in self._colour_names():
             setattr(self, name, alloc(*shape, 3))
         for name in self._names():
-            silt.set(getattr(self, name), 0.0)
+            if name not in _written:
+                silt.set(getattr(self, name), 0.0)
         self._seeds = (C.c_uint64 * self.B)(*self.seeds)
 
     def _colour_names(self):
@@ -433,6 +503,33 @@ class ErosionBatch:
             m.step_index = self.first_step[b] + self.step_index
             out.append(m)
         return out
+
+    def resized(self, H, W, scale=None, n_particles=None):
+        """A new ErosionBatch of the same B and colour setting at (H, W), every plane of every model resampled by
+        one launch whatever B is (soil_erode_resize_batch; `height` = the new layers merged, flux planes zero); this
+        batch is left as it is.  Carried over: seeds, the param or the params (the same objects), step_index and
+        first_step, and whichever of scale / scales and N / Ns the batch uses, so the new batch steps through the
+        entry points this one would.  Each scale defaults to the same world with more (or fewer) cells,
+        [sx * Ho / H, sy * Wo / W, sz]; `scale` (one triple or B triples) and `n_particles` (one count or B counts)
+        replace them, under the constructor's checks.  Raises ValueError before any device work, as the
+        constructor does."""
+        _check_size("ErosionBatch", H, W)
+        if scale is None:
+            if self.scales is not None:
+                self._check_scales()
+                scale = [_rescaled(s, self.H, self.W, H, W) for s in self.scales]
+            else:
+                scale = _rescaled(self.scale, self.H, self.W, H, W)
+        if n_particles is None:
+            n_particles = list(self.Ns) if self.Ns is not None else self.N
+        elif isinstance(n_particles, numbers.Integral) and not isinstance(n_particles, bool) and n_particles < 0:
+            raise ValueError("ErosionBatch.resized: n_particles = %r is not a walker count >= 0" % (n_particles,))
+        new = ErosionBatch(self.B, H, W, scale, self.param if self.params is None else list(self.params), n_particles,
+                           self.seeds, colour=self.colour, _written=ErosionModel.RESIZED)
+        new.step_index = self.step_index
+        new.first_step = list(self.first_step)
+        _resize_into(new, self, self.B)
+        return new
 
     def _copy(self, name, b, model, into_batch):
         """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""
