@@ -509,3 +509,103 @@ def test_resize_known_answers(oracle):
     for c in range(2):
         np.testing.assert_array_equal(got[..., c], oracle.resize(np.ascontiguousarray(two[..., c]), (10, 12)))
     assert oracle.resize(src, (1, 1))[0, 0] == src[0, 0]
+
+
+# ------------------------------------------------------------ accumulate on built graphs
+# What tests/test_gpu_accumulate_oracle.py leans on, pinned on the oracle alone.
+
+def _outlets_sum(acc, g):
+    return float(acc[g < 0].astype(np.float64).sum())
+
+
+@pytest.mark.parametrize("H,W,edge", [(64, 64, D4), (64, 64, D8), (37, 53, D4), (37, 53, D8), (301, 257, D8),
+                                      (1, 300, D8), (300, 1, D4), (1024, 1024, D8)])
+def test_accumulate_snake_ends_with_every_cell_at_its_outlet(oracle, H, W, edge):
+    """One chain through all H W cells: the round count 2 (ceil(log2(HW) / 2) + 1) is just enough for it."""
+    from util import graph_snake
+    g = graph_snake(H, W)
+    assert (g < 0).sum() == 1
+    acc = oracle.accumulate(g, np.ones((H, W), np.float32), edge)
+    assert acc[g < 0][0] == H * W
+    # and along the chain the area grows by one per cell
+    order = np.empty(H * W, np.int64)
+    n = 0
+    for i in range(H * W):
+        order[i] = n
+        n = int(g.reshape(-1)[n])
+    assert n == -1
+    assert (acc.reshape(-1)[order] == np.arange(1, H * W + 1)).all()
+
+
+@pytest.mark.parametrize("H,W", [(64, 64), (37, 53), (1, 300), (300, 1), (2, 40), (5, 1028)])
+@pytest.mark.parametrize("edge", [D4, D8])
+def test_accumulate_built_graphs_drain_every_cell(oracle, H, W, edge):
+    from util import built_graphs
+    K = 4 if edge == D4 else 8
+    ones = np.ones((H, W), np.float32)
+    for name, g in built_graphs(H, W, edge).items():
+        acc = oracle.accumulate(g, ones, edge)
+        if name == "no_edges":
+            assert (acc == 1).all()
+        else:
+            assert _outlets_sum(acc, g) == H * W, name
+    if H >= 3 and W >= 3:
+        g = built_graphs(H, W, edge)["fan"]
+        acc = oracle.accumulate(g, ones, edge)
+        assert acc[1, 1] == 9 and g[1, 1] == -1          # a cell with all K donors (D4: 4 + the corners behind them)
+        idx = np.arange(H * W).reshape(H, W)
+        assert (g == idx[1, 1]).sum() == K
+        if W >= 6:
+            gc = built_graphs(H, W, edge)["fan_chain"]
+            assert (gc == idx[1, 4]).sum() == K - 1 and gc[1, 4] == idx[1, 5]   # K - 1 donors, on a chain
+
+
+@pytest.mark.parametrize("edge", [D4, D8])
+def test_accumulate_is_repeatable_and_finite_on_cycles_and_wild_graphs(oracle, edge):
+    from util import graph_cycles, graph_wild
+    H, W = 40, 52
+    h = terrain(oracle, H, W)[..., 0].copy()
+    base = oracle.random_weighted(h, edge, 0, 1, 10.0)
+    r = np.random.default_rng(4)
+    src = (0.5 + r.random((H, W))).astype(np.float32)
+    decay = (0.8 + 0.2 * r.random((H, W))).astype(np.float32)
+    for g in (graph_cycles(base), graph_wild(base)):
+        assert (g != base).any()
+        for d in (None, decay):
+            a = oracle.accumulate(g, src, edge, decay=d)
+            b = oracle.accumulate(g.copy(), src.copy(), edge, decay=None if d is None else d.copy())
+            assert np.isfinite(a).all()
+            assert (a.view(np.uint32) == b.view(np.uint32)).all()
+    cyc = graph_cycles(base)
+    idx = np.arange(H * W).reshape(H, W)
+    two = (cyc.reshape(-1)[np.clip(cyc, 0, None)] == idx) & (cyc >= 0)
+    assert two.sum() >= 2                                  # there are cells that point at each other
+    # a cell on a cycle never finishes: it keeps collecting, so it ends above what the same cell holds without
+    assert (oracle.accumulate(cyc, src, edge)[two] > src[two]).all()
+
+
+@pytest.mark.parametrize("edge", [D4, D8])
+def test_accumulate_of_stacked_tiles_is_the_tiles_accumulations_stacked(oracle, edge):
+    """The stacking rule: T tiles one under the other, tile t's graph shifted by t h W.  A graph never drains across
+    a tile border, a round is local to a connected component and a finished cell no longer changes, so the
+    accumulation of the stack is the tiles' own accumulations stacked — provided every tile has finished within its
+    own (smaller) round count: with unit sources its outlets then hold h W."""
+    from util import stack_graphs
+    T, h, W = 8, 64, 256
+    graphs, srcs, decays, accs, accs_d = [], [], [], [], []
+    for t in range(T):
+        dem = terrain(oracle, h, W, seed=3.0 + t)[..., 0].copy()
+        g = oracle.random_weighted(dem, edge, 1, t, 10.0)
+        r = np.random.default_rng(100 + t)
+        s = (0.5 + r.random((h, W))).astype(np.float32)
+        d = (0.8 + 0.2 * r.random((h, W))).astype(np.float32)
+        assert _outlets_sum(oracle.accumulate(g, np.ones((h, W), np.float32), edge), g) == h * W
+        graphs.append(g), srcs.append(s), decays.append(d)
+        accs.append(oracle.accumulate(g, s, edge))
+        accs_d.append(oracle.accumulate(g, s, edge, decay=d))
+    assert any((graphs[0] != g).any() for g in graphs[1:])
+    G, S, D = stack_graphs(graphs), np.concatenate(srcs), np.concatenate(decays)
+    assert G.shape == (T * h, W) and G.max() >= (T - 1) * h * W
+    from util import assert_bit_equal
+    assert_bit_equal(oracle.accumulate(G, S, edge), np.concatenate(accs), "stack, no decay")
+    assert_bit_equal(oracle.accumulate(G, S, edge, decay=D), np.concatenate(accs_d), "stack, decay tensor")

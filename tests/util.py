@@ -196,3 +196,118 @@ def debris_steps_agree(got, r, N, tiled=True):
     if tiled and soil.debris_retire() == 1:
         return retired_steps_close(got, r, N)
     return got == r["steps"]
+
+
+# ---- flow graphs for the accumulation tests (numpy, deterministic, any H x W, D4 and D8) -------------------
+# A graph holds the flat index of each cell's receiver, or -1.  `accumulate` only ever compares graph[d] with the
+# index of one of d's K neighbours, so any int32 is a legal entry; a value that is no neighbour's index is no edge.
+
+def _cells(H, W):
+    return np.arange(H * W, dtype=np.int64).reshape(H, W)
+
+
+def graph_snake(H, W):
+    """One chain through every cell: row by row, alternate rows reversed; the last cell is the only outlet."""
+    idx = _cells(H, W)
+    g = np.empty((H, W), np.int64)
+    g[0::2, :-1] = idx[0::2, 1:]          # even rows run east ...
+    g[0::2, -1] = idx[0::2, -1] + W       # ... and step down at their east end
+    g[1::2, 1:] = idx[1::2, :-1]          # odd rows run west
+    g[1::2, 0] = idx[1::2, 0] + W
+    g[H - 1, W - 1 if (H - 1) % 2 == 0 else 0] = -1
+    return g.astype(np.int32)
+
+
+def _fan_centres(H, W):
+    """Row and column of the centre of each cell's 3 x 3 block (blocks ragged at the far edges)."""
+    x, y = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    return x, y, np.minimum(x // 3 * 3 + 1, H - 1), np.minimum(y // 3 * 3 + 1, W - 1)
+
+
+def graph_fan(H, W, edge):
+    """3 x 3 blocks whose cells all drain into the block's centre, an outlet.  D8: the centre has all 8 donors.
+    D4: its 4-neighbours drain into it, each corner into the edge cell of its column."""
+    x, y, cx, cy = _fan_centres(H, W)
+    g = cx * W + cy
+    if edge == 0:
+        corner = (x != cx) & (y != cy)
+        g[corner] = (cx * W + y)[corner]
+    g[(x == cx) & (y == cy)] = -1
+    return g.astype(np.int32)
+
+
+def graph_fan_chain(H, W, edge):
+    """graph_fan, but a centre drains into its east neighbour and that one east again into the next block's west
+    cell (which drains into that block's centre): cells with K - 1 donors on a chain along each row of blocks."""
+    x, y, cx, cy = _fan_centres(H, W)
+    g = graph_fan(H, W, edge).astype(np.int64)
+    idx = _cells(H, W)
+    centre = (x == cx) & (y == cy) & (y + 2 < W)
+    east = np.zeros((H, W), bool)
+    east[:, 1:] = centre[:, :-1]
+    g[centre] = idx[centre] + 1
+    g[east] = idx[east] + 1
+    return g.astype(np.int32)
+
+
+def graph_no_edges(H, W):
+    return np.full((H, W), -1, np.int32)
+
+
+def graph_one_sink(H, W):
+    """Every cell steps towards cell (0, 0): up, then left along row 0.  W chains that merge on one line."""
+    idx = _cells(H, W)
+    g = idx - W
+    g[0, 1:] = idx[0, :-1]
+    g[0, 0] = -1
+    return g.astype(np.int32)
+
+
+def graph_cycles(base, seed=5):
+    """`base` (a legal graph) with about a tenth of the horizontally adjacent pairs rewired to point at each other,
+    plus a few 4-cycles.  Such cells never finish; the rounds are synchronous, so the plane after the fixed number
+    of rounds is still one definite plane."""
+    H, W = base.shape
+    g = base.astype(np.int64).copy()
+    idx = _cells(H, W)
+    r = np.random.default_rng(seed)
+    if W >= 2:
+        pair = r.random((H, W // 2)) < 0.1
+        a, b = idx[:, 0:W // 2 * 2:2], idx[:, 1:W // 2 * 2:2]
+        ga, gb = g[:, 0:W // 2 * 2:2], g[:, 1:W // 2 * 2:2]     # views
+        ga[pair] = b[pair]
+        gb[pair] = a[pair]
+    if H >= 2 and W >= 2:
+        for _ in range(max(1, H * W // 500)):
+            x, y = int(r.integers(0, H - 1)), int(r.integers(0, W - 1))
+            g[x, y], g[x, y + 1], g[x + 1, y + 1], g[x + 1, y] = idx[x, y + 1], idx[x + 1, y + 1], idx[x + 1, y], idx[x, y]
+    return g.astype(np.int32)
+
+
+def graph_wild(base, seed=9):
+    """`base` (a legal graph) mixed with entries that are no edge: random values in [-5, 2 H W), receivers two rows
+    away, across a row's end, "down-left" from column 0, the cell itself."""
+    H, W = base.shape
+    g = base.astype(np.int64).copy()
+    idx = _cells(H, W)
+    r = np.random.default_rng(seed)
+    noise = r.random((H, W)) < 0.25
+    g[noise] = r.integers(-5, 2 * H * W, size=(H, W))[noise]
+    g[::3, ::2] = idx[::3, ::2] + 2 * W
+    g[1::3, -1] = idx[1::3, -1] + 1
+    g[2::3, 0] = idx[2::3, 0] + W - 1
+    own = r.random((H, W)) < 0.02
+    g[own] = idx[own]
+    return g.astype(np.int32)
+
+
+def built_graphs(H, W, edge):
+    """name -> graph for the builders that need nothing but the grid."""
+    return {"snake": graph_snake(H, W), "fan": graph_fan(H, W, edge), "fan_chain": graph_fan_chain(H, W, edge),
+            "no_edges": graph_no_edges(H, W), "one_sink": graph_one_sink(H, W)}
+
+
+def stack_graphs(tiles):
+    """Tiles of (h, W) one under the other: tile t's receivers shifted by t h W, its -1 kept."""
+    h, W = tiles[0].shape
+    return np.concatenate([np.where(g >= 0, g + np.int32(t * h * W), g).astype(np.int32) for t, g in enumerate(tiles)])
