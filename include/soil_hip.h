@@ -610,6 +610,68 @@ int soil_erode_resize_batch(const soil_erosion_planes* dst, const soil_erosion_p
                             const soil_colour_planes* dst_colour, const soil_colour_planes* src_colour,
                             int64_t B, int64_t Hn, int64_t Wn, int64_t Ho, int64_t Wo, void* stream);
 
+/* ------------------------------------------ erosion: summaries */
+
+/* What a sweep or an ensemble asks of a batch, reduced on the device: one small record per model
+ * (soil_erode_batch_stats) and one map per quantity across the models (soil_erode_batch_ensemble), where the
+ * only other way to look at model b is to copy its planes to the host.  `planes` holds B whole-grid models of
+ * (H, W), model-major as in soil_erode_step_batch; B = 1 is a single model.  Both are deterministic (no
+ * floating-point atomics anywhere, every sum in an order fixed by H*W alone), leave the planes as they are, run on
+ * `stream` without host synchronisation, and take a number of dispatches that does not depend on B. */
+
+/* The statistics of one channel of one model over its H*W cells.  A value v is finite when v - v == 0; the
+ * values that are not (NaN, +-inf) are counted in `nonfinite` and leave the other four fields alone.  `sum` adds
+ * (double)v and `sumsq` (double)v * (double)v (exact: the product of two fp32 values fits fp64), both accumulated
+ * in fp64 throughout; `min` and `max` are over the finite values (which of +0 and -0 a tie returns is not
+ * specified). */
+typedef struct soil_channel_stats { /* 32 bytes */
+  double sum;        /* of the finite values */
+  double sumsq;      /* of their squares */
+  int64_t nonfinite; /* cells holding NaN or +-inf */
+  float min, max;    /* over the finite values; +inf / -inf when there is none */
+} soil_channel_stats;
+/* The channels of a record, in this order: bedrock (layers.x), sediment (layers.y), height, waterHeight, mass,
+ * debris, velocity.x, velocity.y, debrisVelocity.x, debrisVelocity.y.  "height" is layers.x + layers.y in fp32,
+ * the value layer_merge leaves, computed from `layers` (so +inf bedrock under -inf sediment is one non-finite
+ * height). */
+#define SOIL_STAT_CHANNELS 10
+typedef struct soil_model_stats { soil_channel_stats ch[SOIL_STAT_CHANNELS]; } soil_model_stats; /* 320 bytes */
+
+/* out[b] (device, B records) = the statistics of model b.  Reads layers, waterHeight, mass, debris, velocity and
+ * debrisVelocity: 36 algorithmic bytes per cell; `height`, the flux planes, layers_next, uplift and rainfall are
+ * not read and may be NULL.
+ * The reduction tree is fixed by n = H*W alone: a model's cells, flattened, are cut into chunks (a multiple of
+ * 1024 cells, at least 4096, at most 4096 chunks to a model); a work-group reduces one chunk, lane-local first
+ * (lane t of 256 takes cells 4t .. 4t+3 of every 1024), then across the wave, then across the four waves through
+ * LDS, and writes one partial record to the library's workspace; a second launch folds each model's partials in
+ * index order into out[b].  Neither B, nor b, nor the alignment of a model's first cell enters (loads are 16-byte
+ * where the model's base allows and scalar otherwise, the same cells to the same lanes either way), so out[b] is
+ * bit-identical to the record of model b alone, in a batch of another B or at another position, and from call to
+ * call.  Two dispatches per 65535 models (grid.z is the model); the workspace is written in full before it is
+ * read.
+ * SOIL_ERR_INVALID_ARGUMENT before any launch for B < 1, a size < 1, sizes whose byte offsets overflow int64, a
+ * NULL `planes` or `out`, or a NULL plane among the six read. */
+int soil_erode_batch_stats(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W,
+                           soil_model_stats* out, void* stream);
+
+/* Per cell, the mean and the population variance across the B models of bedrock, sediment, height (layers.x +
+ * layers.y in fp32), waterHeight, mass and debris, in this order: `mean` and `var` are (H, W, 6) device planes;
+ * `var` may be NULL (mean only).  Per cell and channel, every operation as written and none contracted:
+ *   s = sum of (double)v_b, q = sum of (double)v_b * (double)v_b, for b = 0 ... B-1 in that order, in fp64;
+ *   m = s / B;  mean = (float)m;  v = q / B - m * m;  var = (float)(v < 0 ? 0 : v).
+ * The one-pass variance cancels: its relative error is about 2^-53 * m*m / v, so a variance below about
+ * 2^-53 * m*m is noise (fp32 inputs one ulp apart have v / (m*m) of about 2^-46 / B, where the result keeps some
+ * 7 - log2(B) bits; a spread of 2^-12 of the mean keeps full fp32 precision).  A NaN or an infinity in one
+ * model's cell reaches the outputs of that cell and of no other cell.
+ * Reads layers, waterHeight, mass and debris: 20 algorithmic bytes per cell and model, and writes 24 per cell (48
+ * with `var`).  One dispatch whatever B is, no workspace: one thread per cell walks the models, every load
+ * coalesced along W.
+ * SOIL_ERR_INVALID_ARGUMENT before any launch for B < 1, a size < 1, sizes whose byte offsets overflow int64, a
+ * NULL `planes` or `mean`, or a NULL plane among the four read. */
+#define SOIL_ENSEMBLE_CHANNELS 6 /* bedrock, sediment, height, waterHeight, mass, debris */
+int soil_erode_batch_ensemble(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W,
+                              float* mean /* (H, W, 6) */, float* var /* (H, W, 6) or NULL */, void* stream);
+
 /* The containers of the legacy API (example/erosion_gpu.py:44-71): model_t, the `data` and the
  * `track` buffers.  All float32 device planes of H*W cells ((H,W,2) for the momenta). */
 typedef struct soil_erode_model {

@@ -45,6 +45,21 @@ class BatchModel(C.Structure):
                 ("step_index", C.c_uint64)]
 
 
+SOIL_STAT_CHANNELS = 10
+SOIL_ENSEMBLE_CHANNELS = 6
+
+
+class ChannelStats(C.Structure):
+    """soil_channel_stats: one channel of one model reduced over its cells (32 bytes)."""
+    _fields_ = [("sum", C.c_double), ("sumsq", C.c_double), ("nonfinite", C.c_int64), ("min", C.c_float),
+                ("max", C.c_float)]
+
+
+class ModelStats(C.Structure):
+    """soil_model_stats: the record soil_erode_batch_stats writes per model (320 bytes)."""
+    _fields_ = [("ch", ChannelStats * SOIL_STAT_CHANNELS)]
+
+
 class Rng(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("offset", C.c_uint64)]
 
@@ -175,6 +190,9 @@ SIGNATURES = {
                                                    i64, C.POINTER(BatchModel), cint, vp]),
     "soil_erode_resize_batch": (cint, [C.POINTER(ErosionPlanes), C.POINTER(ErosionPlanes), C.POINTER(ColourPlanes),
                                        C.POINTER(ColourPlanes), i64, i64, i64, i64, i64, vp]),
+    # summaries: B records of soil_model_stats (device); the (H, W, 6) mean and variance maps (var may be NULL)
+    "soil_erode_batch_stats": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, vp, vp]),
+    "soil_erode_batch_ensemble": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, vp, vp, vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),

@@ -44,12 +44,35 @@ holding the resampled state (soil_erode_resize_batch: every plane of every model
 flux planes zero), with the seeds, params, step indices and walker counts carried over and each scale rescaled to
 the same world extent: the multiscale schedule (erode coarse, resample, erode finer) for whole models and batches
 (DESIGN.md 3.5).
+
+`ErosionBatch.stats()` and `ErosionModel.stats()` reduce every model on the device to one small record
+(soil_erode_batch_stats: sum, sum of squares, min, max and the count of non-finite cells of the ten STAT_CHANNELS), and
+`ErosionBatch.ensemble()` reduces the batch to per-cell mean and variance maps of the six ENSEMBLE_CHANNELS
+(soil_erode_batch_ensemble): what a sweep or an ensemble wants to know without copying a plane to the host.
 """
 import ctypes as C
 import numbers
 import os
 
+import numpy as np
+
 from . import _abi, silt
+
+# the channels of a soil_model_stats record and of the ensemble maps, in the order of include/soil_hip.h
+STAT_CHANNELS = ("bedrock", "sediment", "height", "waterHeight", "mass", "debris", "velocity.x", "velocity.y",
+                 "debrisVelocity.x", "debrisVelocity.y")
+ENSEMBLE_CHANNELS = ("bedrock", "sediment", "height", "waterHeight", "mass", "debris")
+# soil_channel_stats as a numpy record (32 bytes)
+STATS_DTYPE = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("nonfinite", "<i8"), ("min", "<f4"), ("max", "<f4")])
+
+
+def _stats(planes, B, H, W):
+    """The (B, 10) records of B models: one soil_erode_batch_stats into a device buffer of B x 320 bytes, then one
+    copy of that buffer to the host (the only synchronisation)."""
+    words = C.sizeof(_abi.ModelStats) // 4
+    out = silt.tensor(silt.float32, silt.shape(B, words), silt.gpu)
+    _abi.check(_abi.lib().soil_erode_batch_stats(C.byref(planes), B, H, W, out.c_ptr, _abi.stream()))
+    return out.cpu().numpy().view(STATS_DTYPE).reshape(B, len(STAT_CHANNELS))
 
 
 def _check_size(who, H, W):
@@ -171,6 +194,16 @@ class ErosionModel:
         new.step_index = self.step_index
         _resize_into(new, self, 1)
         return new
+
+    def stats(self):
+        """This model reduced on the device (soil_erode_batch_stats with B = 1): a numpy structured array of shape
+        (10,), one element per channel of STAT_CHANNELS, with the fields sum, sumsq (fp64, over the finite cells),
+        nonfinite (cells holding NaN or an infinity), min and max (over the finite cells; +inf / -inf when there
+        is none).  The bytes are those of this model's row of ErosionBatch.stats().  One copy of 320 bytes to the
+        host, the only synchronisation.  A row slab raises ValueError before any device work."""
+        if self.rows != self.H:
+            raise ValueError("ErosionModel.stats: the model is a row slab (%d of %d rows)" % (self.rows, self.H))
+        return _stats(self._planes(), 1, self.H, self.W)[0]
 
     # -- the three phases ------------------------------------------------------
     def seed_step(self):
@@ -530,6 +563,26 @@ class ErosionBatch:
         new.first_step = list(self.first_step)
         _resize_into(new, self, self.B)
         return new
+
+    def stats(self):
+        """Every model reduced on the device by two launches whatever B is (soil_erode_batch_stats): a numpy
+        structured array of shape (B, 10), element [b, c] channel STAT_CHANNELS[c] of model b, with the fields sum,
+        sumsq (fp64, over the finite cells), nonfinite (cells holding NaN or an infinity), min and max (over the
+        finite cells; +inf / -inf when there is none); the dtype mirrors soil_channel_stats.  Deterministic: row b
+        carries the bytes of ErosionModel.stats() of that model alone.  One entry-point call into a device buffer
+        of B x 320 bytes, then one copy of that buffer to the host, the only synchronisation."""
+        return _stats(self._planes(), self.B, self.H, self.W)
+
+    def ensemble(self, var=True):
+        """(mean, var): per cell, the mean and the population variance across the B models of the six
+        ENSEMBLE_CHANNELS, two silt GPU tensors of (H, W, 6) written by one launch whatever B is
+        (soil_erode_batch_ensemble: fp64 sums over b in order, var = max(q / B - m * m, 0)).  `var=False`: mean
+        only, and the second element is None.  The batch is left as it is; nothing synchronises."""
+        mean = silt.tensor(silt.float32, silt.shape(self.H, self.W, len(ENSEMBLE_CHANNELS)), silt.gpu)
+        variance = silt.tensor(silt.float32, silt.shape(self.H, self.W, len(ENSEMBLE_CHANNELS)), silt.gpu) if var else None
+        _abi.check(_abi.lib().soil_erode_batch_ensemble(C.byref(self._planes()), self.B, self.H, self.W, mean.c_ptr,
+                                                        variance.c_ptr if var else None, _abi.stream()))
+        return mean, variance
 
     def _copy(self, name, b, model, into_batch):
         """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""
