@@ -477,6 +477,27 @@ def solve_uniform(flow, source, decay, rng, scale, count):
     return flux
 
 
+# why a solve_uniform walker ended (soil_oracle.h: ORC_SU_*)
+SU_DROPPED, SU_NO_SOURCE, SU_LEFT, SU_SPENT, SU_MAXSTEP, SU_STALLED, SU_NAN = range(7)
+
+
+def solve_uniform_detail(flow, source, decay, rng, scale, count):
+    """solve_uniform's walk with its bookkeeping: a dict of `flux` (what solve_uniform returns), `acc64` and
+    `absacc64` (float64 sums of the fp32 deposits of each cell and channel, and of their absolute values),
+    `visits` (int64, their number) and `reason` (int8 per walker, SU_*).  Advances `rng` as solve_uniform does."""
+    H, W, K = source.shape
+    N = len(rng)
+    out = {"flux": np.empty((H, W, K), np.float32), "acc64": np.empty((H, W, K), np.float64),
+           "absacc64": np.empty((H, W, K), np.float64), "visits": np.empty((H, W, K), np.int64),
+           "reason": np.empty(N, np.int8)}
+    vp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+    lib().orc_solve_uniform_detail(_f(out["flux"]), vp(out["acc64"]), vp(out["absacc64"]), vp(out["visits"]),
+                                   vp(out["reason"]), _f(_chk(flow)), _f(_chk(source)), _f(_chk(decay)),
+                                   vp(rng), C.c_int64(N), C.c_int64(H), C.c_int64(W), C.c_int(K),
+                                   _scale(scale, 2), C.c_uint64(count))
+    return out
+
+
 def noise(H, W, frequency=1.0, octaves=8, gain=0.6, lacunarity=2.0, seed=0.0, ext=(512.0, 512.0)):
     p = NoiseParam(frequency, octaves, gain, lacunarity, seed, (C.c_float * 2)(*ext))
     out = np.empty((H, W), np.float32)

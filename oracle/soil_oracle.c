@@ -1276,13 +1276,23 @@ void orc_resize(float* dst, const float* src, int64_t Hn, int64_t Wn, int64_t Ho
   }
 }
 
-/* __solve_uniform<K> (path.cu:52-139) + __normalize<K> (:142-170), host :180-219 */
-void orc_solve_uniform(float* flux, const float* flow, const float* source, const float* decay,
-                       orc_rng* rng, int64_t N, int64_t H, int64_t W, int K,
-                       const float scale[2], uint64_t count) {
+/* __solve_uniform<K> (path.cu:52-139) + __normalize<K> (:142-170), host :180-219.
+ * One walk for both entry points.  The detail arrays may be NULL (orc_solve_uniform); where given
+ * they are filled beside the fp32 plane, which is computed by the same statements either way:
+ *   acc64 / absacc64 [H*W*K]  double sums of the fp32 products S[c]*att a cell received / of their
+ *                             absolute values (what an order-free accumulation would hold),
+ *   visits [H*W*K]            how many products that was,
+ *   reason [N]                why walker n ended (ORC_SU_*). */
+static void orc_solve_uniform_walk(float* flux, const float* flow, const float* source,
+                                   const float* decay, orc_rng* rng, int64_t N, int64_t H, int64_t W,
+                                   int K, const float scale[2], uint64_t count, double* acc64,
+                                   double* absacc64, int64_t* visits, int8_t* reason) {
   const float epsilon = 1E-16f;         /* :199 */
   const float maxstep = (float)(H + W); /* :200 */
   memset(flux, 0, sizeof(float) * H * W * K); /* :196 */
+  if (acc64) memset(acc64, 0, sizeof(double) * H * W * K);
+  if (absacc64) memset(absacc64, 0, sizeof(double) * H * W * K);
+  if (visits) memset(visits, 0, sizeof(int64_t) * H * W * K);
   orc_domain d = {H, W, 0, H, 0, H};
   for (int64_t n = 0; n < N; ++n) {
     float att = 1.0f;                                             /* :78 */
@@ -1290,6 +1300,7 @@ void orc_solve_uniform(float* flux, const float* flow, const float* source, cons
     float py = orc_rng_uniform(&rng[n], (uint64_t)n) * (float)W;  /* :82 */
     /* u == 1 puts the spawn on the far edge; the reference then indexes out
      * of bounds at :90 (undefined behaviour) — such a sample is dropped here. */
+    if (reason) reason[n] = ORC_SU_DROPPED;
     if (orc_oob(&d, px, py)) continue;
     int64_t ind = orc_cell(px) * W + orc_cell(py);                  /* :84 */
     const float L = orc_length2(scale[0], scale[1]);              /* :87 */
@@ -1298,25 +1309,40 @@ void orc_solve_uniform(float* flux, const float* flow, const float* source, cons
     float S[2] = {0, 0};
     for (int c = 0; c < K; ++c) S[c] = source[K * ind + c] / P;   /* :90 */
     const float Slen = (K == 1) ? sqrtf(S[0] * S[0]) : orc_length2(S[0], S[1]);
+    if (reason) reason[n] = ORC_SU_NO_SOURCE;
     if (Slen < epsilon) continue; /* :91-92 */
     float v[2];
     orc_bilinear(flow, H, W, px, py, v); /* :99-100 */
     int step = 0;
+    int stalled = 0;
     while (!orc_oob(&d, px, py) && epsilon < fabsf(att) && (float)(++step) < maxstep) { /* :104 */
       const int64_t nind = orc_cell(px) * W + orc_cell(py); /* :107 */
       if (nind != ind) {                                  /* :108-116 */
         ind = nind;
-        for (int c = 0; c < K; ++c) flux[K * ind + c] += S[c] * att;
+        for (int c = 0; c < K; ++c) {
+          const float add = S[c] * att;
+          flux[K * ind + c] += add;
+          if (acc64) acc64[K * ind + c] += (double)add;
+          if (absacc64) absacc64[K * ind + c] += fabs((double)add);
+          if (visits) visits[K * ind + c] += 1;
+        }
       }
       orc_bilinear(flow, H, W, px, py, v);         /* :119-120 */
       const float v_len = orc_length2(v[0], v[1]); /* :123 */
-      if (v_len < epsilon) break;                  /* :124-125 */
+      if (v_len < epsilon) { stalled = 1; break; } /* :124-125 */
       const float ux = v[0] / v_len, uy = v[1] / v_len; /* :128 */
       const float st = orc_stepsize(px, py, ux, uy);    /* :129 */
       px += st * ux;                                    /* :130 */
       py += st * uy;
       const float dlambda = st * L / v_len;             /* :133 */
       att *= orc_expf(-dlambda * decay[ind]);           /* :134 */
+    }
+    if (reason) { /* which clause of :104 (or the break) ended the walk; the state is as the loop left it */
+      if (px != px || py != py || att != att) reason[n] = ORC_SU_NAN;
+      else if (stalled) reason[n] = ORC_SU_STALLED;
+      else if (orc_oob(&d, px, py)) reason[n] = ORC_SU_LEFT;
+      else if (!(epsilon < fabsf(att))) reason[n] = ORC_SU_SPENT;
+      else reason[n] = ORC_SU_MAXSTEP;
     }
   }
   for (int64_t n = 0; n < H * W; ++n) { /* __normalize, :142-170 */
@@ -1326,6 +1352,20 @@ void orc_solve_uniform(float* flux, const float* flow, const float* source, cons
     for (int c = 0; c < K; ++c)
       flux[K * n + c] = (source[K * n + c] * A + flux[K * n + c] / (float)count) / norm; /* :168 */
   }
+}
+
+void orc_solve_uniform(float* flux, const float* flow, const float* source, const float* decay,
+                       orc_rng* rng, int64_t N, int64_t H, int64_t W, int K,
+                       const float scale[2], uint64_t count) {
+  orc_solve_uniform_walk(flux, flow, source, decay, rng, N, H, W, K, scale, count, NULL, NULL, NULL, NULL);
+}
+
+void orc_solve_uniform_detail(float* flux, double* acc64, double* absacc64, int64_t* visits,
+                              int8_t* reason, const float* flow, const float* source,
+                              const float* decay, orc_rng* rng, int64_t N, int64_t H, int64_t W,
+                              int K, const float scale[2], uint64_t count) {
+  orc_solve_uniform_walk(flux, flow, source, decay, rng, N, H, W, K, scale, count, acc64, absacc64,
+                         visits, reason);
 }
 
 /* --------------------------------------------------- depression filling (F5) */

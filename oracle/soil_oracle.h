@@ -143,6 +143,23 @@ void orc_resize(float* dst, const float* src, int64_t Hn, int64_t Wn, int64_t Ho
 void orc_solve_uniform(float* flux, const float* flow, const float* source, const float* decay,
                        orc_rng* rng, int64_t N, int64_t H, int64_t W, int K,
                        const float scale[2], uint64_t count);
+/* The same walk, which also reports, per cell and channel, the double-precision sum of the fp32
+ * products S[c]*att deposited there (acc64), the sum of their absolute values (absacc64) and their
+ * number (visits), and per walker why it ended.  `flux` and the rng are left as orc_solve_uniform
+ * leaves them. */
+enum {
+  ORC_SU_DROPPED = 0,   /* spawned on the far edge (a draw of exactly 1): dropped, rng advanced */
+  ORC_SU_NO_SOURCE = 1, /* |S| < epsilon at the spawn cell */
+  ORC_SU_LEFT = 2,      /* stepped off the grid */
+  ORC_SU_SPENT = 3,     /* |att| <= epsilon */
+  ORC_SU_MAXSTEP = 4,   /* H + W steps */
+  ORC_SU_STALLED = 5,   /* |v| < epsilon */
+  ORC_SU_NAN = 6        /* position or attenuation became NaN (a NaN flow sample, the far strip) */
+};
+void orc_solve_uniform_detail(float* flux, double* acc64, double* absacc64, int64_t* visits,
+                              int8_t* reason, const float* flow, const float* source,
+                              const float* decay, orc_rng* rng, int64_t N, int64_t H, int64_t W,
+                              int K, const float scale[2], uint64_t count);
 
 /* noise (own restatement of OpenSimplex2 FBm; pinned by oracle/_ref fixtures) */
 typedef struct orc_noise_param {

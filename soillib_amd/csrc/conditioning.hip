@@ -279,9 +279,15 @@ static int fill_level(float* out, const float* height, int64_t H, int64_t W, con
   const int tiles_w = static_cast<int>((W + kFT - 1) / kFT);
   const int tiles_h = static_cast<int>((H + kFT - 1) / kFT);
   const size_t ntiles = static_cast<size_t>(tiles_w) * tiles_h;
-  // a launch moves information at least one tile further; H*W launches is a bound
-  // no terrain reaches
-  const int64_t max_launches = 4 * (static_cast<int64_t>(tiles_w) + tiles_h) * kFT + 16;
+  // The number of launches is bounded by the tiles, not by the grid's edge lengths: a level reaches a cell along
+  // its best path to an outlet (a simple path: each cell once), and a launch finishes, in every tile, the stretch of
+  // that path inside the tile up to the next seam — or 4 kFT cells of it, the inner iterations, each of which is
+  // at least one step of the full operator.  A simple path enters a tile through one of its 4 kFT - 4 border cells
+  // each time, and its kFT^2 cells make at most kFT / 4 stretches of 4 kFT: (4 kFT + kFT / 4) launches per tile
+  // bound what any input needs.  (A serpentine corridor of pitch 2 crosses H / 2 * tiles_w seams in series, about
+  // 12 000 at 1280^2, where a cap of 4 (tiles_w + tiles_h) kFT = 10 256 launches refused the DEM:
+  // tests/test_gpu_fill_oracle.py.)
+  const int64_t max_launches = static_cast<int64_t>(ntiles) * (4 * kFT + kFT / 4) + 16;
   // (a value below 1 or not a number would skip the launches and return the unrelaxed start)
   static const int per_check = [] {
     const char* e = std::getenv("SOIL_FILL_PER_CHECK");

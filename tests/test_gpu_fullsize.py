@@ -207,6 +207,22 @@ def test_fill_depressions_properties_at_2048(hip):
     assert (nb <= c).all()
 
 
+@pytest.mark.parametrize("edge", [1, 0], ids=["d8", "d4"])
+def test_fill_depressions_equals_the_oracle_at_2048(hip, oracle, edge):
+    """The DEM of the property test above (two coarse levels at this size), bit for bit against priority-flood."""
+    from soillib_amd import silt, soil
+    S = 2048
+    p = soil.noise_t()
+    p.seed = 9.0
+    p.ext = [S, S]
+    h = soil.noise(silt.shape(S, S), p, host=silt.gpu)
+    silt.multiply(h, 100.0)
+    got = soil.fill_depressions(h, edge).cpu().numpy()
+    want = oracle.fill_depressions(h.cpu().numpy(), edge)
+    assert (got.view(np.uint32) == want.view(np.uint32)).all(), "%d cells differ" % (got != want).sum()
+    assert (want > h.cpu().numpy()).any()
+
+
 def test_device_noise_equals_host_generator_at_8192(hip):
     from soillib_amd import _abi, silt, soil
     S = 8192

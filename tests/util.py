@@ -311,3 +311,31 @@ def stack_graphs(tiles):
     """Tiles of (h, W) one under the other: tile t's receivers shifted by t h W, its -1 kept."""
     h, W = tiles[0].shape
     return np.concatenate([np.where(g >= 0, g + np.int32(t * h * W), g).astype(np.int32) for t, g in enumerate(tiles)])
+
+
+# ---- the particle generator in numpy (solve_uniform's spawn draws) --------------------------------------------
+
+def philox_word0(seed, subsequence, offsets):
+    """Word 0 of Philox4x32-10 at counter {offset, subsequence}, key `seed`, for an array of offsets: the 32 bits
+    a walker's generator (soil_oracle.c: orc_rng_next) turns into its next uniform."""
+    offsets = np.asarray(offsets, np.uint64)
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [offsets & m32, offsets >> np.uint64(32), np.full_like(offsets, int(subsequence) & 0xFFFFFFFF),
+         np.full_like(offsets, int(subsequence) >> 32)]
+    k0, k1 = int(seed) & 0xFFFFFFFF, int(seed) >> 32
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & m32]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c[0].astype(np.uint32)
+
+
+def find_unit_draws(seed, subsequence, start, stop):
+    """The offsets in [start, stop) at which the generator of (seed, subsequence) draws a uniform of exactly 1.0:
+    ((word >> 8) + 1) 2^-24 is 1.0 when the word's upper 24 bits are all set, one draw in 2^24.  How the constants
+    of tests/test_gpu_solve_uniform.py were found: find_unit_draws(1, 0, 0, 1 << 24) -> [8418514]."""
+    found = []
+    for lo in range(start, stop, 1 << 20):
+        off = np.arange(lo, min(stop, lo + (1 << 20)), dtype=np.uint64)
+        found += off[(philox_word0(seed, subsequence, off) >> np.uint32(8)) == 0xFFFFFF].tolist()
+    return found
