@@ -47,10 +47,24 @@ int require_device();
 #define SOIL_LAUNCH_CHECK() SOIL_HIP(hipGetLastError())
 
 // Per-device scratch, grown on demand and reused across calls (the reference
-// cudaMallocs its scratch on every call, graph.cu:539-550, 182-183).  Slot 0:
-// accumulate; slot 1: particle staging.  Calls that share a slot must be
-// stream-ordered with respect to each other.
-int workspace_get(int slot, size_t bytes, void** out);
+// cudaMallocs its scratch on every call, graph.cu:539-550, 182-183).  One slot
+// per user; calls that share a slot must be stream-ordered with respect to
+// each other.
+enum WorkspaceSlot {
+  WS_ACCUMULATE_0 = 0,   // graph.hip: an accumulation, lane 0 (kAccSlot)
+  WS_SMALL_LAUNCH = 1,   // erosion_particles.hip: a single model's staged particle launch
+  WS_TILED_FLUVIAL = 2,  // erosion_particles_tiled.hip: the tiled fluvial launch
+  WS_MULTIFLOW = 3,      // graph.hip: soil_multiflow
+  WS_CONDITIONING = 4,   // conditioning.hip
+  WS_TILED_DEBRIS = 5,   // erosion_particles_tiled.hip: the tiled debris launch
+  WS_ERODE = 6,          // erosion_step.hip: soil_erode's layers and streams
+  WS_STEP_RNG = 7,       // erosion_step.hip: the step's fluvial streams
+  WS_PAIR_GATE = 9,      // erosion_particles_tiled.hip: the overlapped pair's gate
+  WS_ACCUMULATE_1 = 10,  // graph.hip: an accumulation, lane 1 (kAccSlot)
+  WS_BATCH = 11,         // erosion_particles.hip: a batch's seeds or records, then its staged scratch
+  WS_STATS = 12,         // erosion_stats.hip: the partial records
+};
+int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();
 
 // Device counter of particle steps (iterations that pass the loop head and its
@@ -65,7 +79,7 @@ int erode_cells_fused(const soil_erosion_planes* pl, const soil_colour_planes* c
 
 // The batch entries' checks of their sizes (soil_hip.h, soil_*_batch): SOIL_ERR_INVALID_ARGUMENT with a message
 // naming `what` for B < 1, an empty grid, N < 0, null seeds with N > 0, byte offsets that overflow
-// (erosion_particles.hip).  The cell phase of a batch (erosion_cells.hip).
+// (erosion_particles.hip).
 int check_batch(int64_t B, int64_t H, int64_t W, int64_t N, const uint64_t* seeds, const char* what);
 // The entries' null-plane checks (true: every plane of the set is there).  The particle launches read and add to
 // ten physics planes; the step and the cell phase need all fourteen but `height`.  The colour entries need all
@@ -79,24 +93,42 @@ inline bool has_planes(const soil_erosion_planes& P, PlaneSet set) {
 inline bool has_colour(const soil_colour_planes* C, bool bedrock = true) {
   return C && (C->albedo_bedrock || !bedrock) && C->albedo_surface && C->albedo_fluvial && C->albedo_debris;
 }
-// `colour` null: physics only; otherwise the four colour planes of all B models (soil_erode_cells_fused_batch_colour).
-// `models_dev` (a device array of B records, or null: every model `param` and `scale`): model b with the param and
-// scale of models_dev[b].
-int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
-                            int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st,
-                            const soil_batch_model* models_dev = nullptr);
 // B records (a host array) copied to the device in one copy through the batches' pinned staging, into workspace
-// slot 11 (erosion_particles.hip); *models_dev valid in stream order until the slot's next use.
+// slot WS_BATCH (erosion_particles.hip); *models_dev valid in stream order until the slot's next use.
 int batch_models_to_device(const soil_batch_model* models, int64_t B, hipStream_t st,
                            const soil_batch_model** models_dev);
-// The checks of the soil_*_batch_models entries (soil_hip.h): a NULL `models`, an N_b < 0 or >= 2^31, and what
-// check_batch refuses with N = max N_b (seeds are in the records); *N_max receives max N_b.
-int check_batch_models(int64_t B, int64_t H, int64_t W, const soil_batch_model* models, const char* what,
-                       int64_t* N_max);
-// The B records of a sweep (soil_*_batch_params): params[b] with the shared scale, N and step_index, and seeds[b]
-// (seeds may be null: seed 0).
-std::vector<soil_batch_model> sweep_records(int64_t B, const soil_param* params, const float scale[3], int64_t N,
-                                            const uint64_t* seeds, uint64_t step_index);
+
+// One call of a batch entry point (soil_hip.h: soil_erode_step_batch, soil_particles_batch,
+// soil_erode_cells_fused_batch and their _colour, _params and _models forms), as erosion_batch.hip fills and
+// checks it and the two phases below read it: B whole-grid models of (H, W), one after the other in every plane.
+struct BatchCall {
+  const char* what;                        // the entry's name in its messages ("erode_step_batch_colour")
+  const soil_erosion_planes* P;
+  const soil_colour_planes* C = nullptr;   // null: physics only; otherwise the four colour planes of all B models
+  int64_t B, H, W;
+  int64_t N = 0;                           // walkers per model, or max N_b (a cells entry: 0)
+  // a uniform batch: every model with *param and scale, model b's streams at (seeds[b], step_index * N), seeds a
+  // host array of B ...
+  const uint64_t* seeds = nullptr;
+  uint64_t step_index = 0;
+  const float* scale = nullptr;
+  const soil_param* param = nullptr;       // (a sweep's entry: its B params, which become records)
+  // ... or B host records (different models; a sweep's from its params): model b with the param, scale, N_b, seed
+  // and step index of models[b], and the four above are not read
+  const soil_batch_model* models = nullptr;
+  int flags = 0;                           // the cell phase's (SOIL_CELLS_KEEP_FLUX)
+  hipStream_t st;
+};
+// Both particle launches of a batch (erosion_particles.hip): direct or staged shape by the single model's rule, one
+// launch after the other on c.st, the debris launch two draws on.  With c.C the two colour flux planes of all B
+// models are cleared first, and the launches deposit colour from albedo_surface into them.  Records reach the
+// device in place of the seeds; `records_dev` (the step's; may be null) receives that device copy for the cell
+// phase, valid in stream order until WS_BATCH's next use — with N == 0 they are uploaded alone
+// (batch_models_to_device), and only when asked for.
+int particles_batch(const BatchCall& c, const soil_batch_model** records_dev = nullptr);
+// The cell phase of a batch (erosion_cells.hip): a uniform batch's (`records_dev` null), or model b with the param
+// and scale of records_dev[b], a device array of B records.
+int erode_cells_fused_batch(const BatchCall& c, const soil_batch_model* records_dev);
 
 // Launch shape of the per-cell kernels: threads along the contiguous axis, and a
 // work-group walks a band of kRowBand consecutive rows (SOIL_ROW_LOOP).  A 64-bit

@@ -329,7 +329,7 @@ static int fill_impl(float* out, const float* height, int64_t H, int64_t W, hipS
     bytes += 2 * b;
   }
   void* base = nullptr;
-  if (int rc = workspace_get(4, bytes, &base); rc != SOIL_OK) return rc;
+  if (int rc = workspace_get(WS_CONDITIONING, bytes, &base); rc != SOIL_OK) return rc;
   char* ws = static_cast<char*>(base);
   // "some tile moved in this launch": a pinned, device-mapped word the tiles write straight
   // into (a device-to-host copy is a 25-50 us blit kernel on this stack, per launch)

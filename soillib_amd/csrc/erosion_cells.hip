@@ -898,81 +898,16 @@ static int cells_batch(const soil_erosion_planes* pl, const soil_colour_planes* 
   return SOIL_OK;
 }
 
-int erode_cells_fused_batch(const soil_erosion_planes* pl, const soil_colour_planes* colour, int64_t B, int64_t H,
-                            int64_t W, const float scale[3], const soil_param* param, int flags, hipStream_t st,
-                            const soil_batch_model* models_dev) {
+int erode_cells_fused_batch(const BatchCall& c, const soil_batch_model* records_dev) {
   static constexpr float kRecords[3] = {0.0f, 0.0f, 0.0f};  // (the kernels take each model's from its record)
-  if (models_dev) return cells_batch(pl, colour, B, H, W, kRecords, ModelParams{models_dev}, flags, st);
-  return cells_batch(pl, colour, B, H, W, scale, UniformParam{*param}, flags, st);
+  if (records_dev)
+    return cells_batch(c.P, c.C, c.B, c.H, c.W, kRecords, ModelParams{records_dev}, c.flags, c.st);
+  return cells_batch(c.P, c.C, c.B, c.H, c.W, c.scale, UniformParam{*c.param}, c.flags, c.st);
 }
 
 }  // namespace soil
 
 extern "C" {
-
-int soil_erode_cells_fused_batch(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W,
-                                 const float scale[3], const soil_param* param, int flags, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && param, "erode_cells_fused_batch: null argument");
-  if (int rc = check_batch(B, H, W, 0, nullptr, "erode_cells_fused_batch"); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_cells_fused_batch: null plane (only `height` is optional)");
-  SOIL_REQUIRE(P.layers != P.layers_next, "erode_cells_fused_batch: layers and layers_next must be distinct buffers");
-  return erode_cells_fused_batch(planes, nullptr, B, H, W, scale, param, flags, as_stream(stream));
-}
-
-int soil_erode_cells_fused_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour,
-                                        int64_t B, int64_t H, int64_t W, const float scale[3],
-                                        const soil_param* param, int flags, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && param, "erode_cells_fused_batch_colour: null argument");
-  SOIL_REQUIRE(has_colour(colour), "erode_cells_fused_batch_colour: every colour plane is required");
-  if (int rc = check_batch(B, H, W, 0, nullptr, "erode_cells_fused_batch_colour"); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_cells_fused_batch_colour: null plane (only `height` is optional)");
-  SOIL_REQUIRE(P.layers != P.layers_next,
-               "erode_cells_fused_batch_colour: layers and layers_next must be distinct buffers");
-  return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, flags, as_stream(stream));
-}
-
-// A sweep's cell phase: the cell phase of a batch of different models whose records share `scale` (one copy).
-int soil_erode_cells_fused_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour,
-                                        int64_t B, int64_t H, int64_t W, const float scale[3],
-                                        const soil_param* params, int flags, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && params, "erode_cells_fused_batch_params: null argument");
-  SOIL_REQUIRE(!colour || has_colour(colour), "erode_cells_fused_batch_params: every colour plane is required");
-  if (int rc = check_batch(B, H, W, 0, nullptr, "erode_cells_fused_batch_params"); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_cells_fused_batch_params: null plane (only `height` is optional)");
-  SOIL_REQUIRE(P.layers != P.layers_next,
-               "erode_cells_fused_batch_params: layers and layers_next must be distinct buffers");
-  const hipStream_t st = as_stream(stream);
-  const std::vector<soil_batch_model> models = sweep_records(B, params, scale, 0, nullptr, 0);
-  const soil_batch_model* models_dev = nullptr;
-  if (int rc = batch_models_to_device(models.data(), B, st, &models_dev); rc != SOIL_OK) return rc;
-  return erode_cells_fused_batch(planes, colour, B, H, W, nullptr, nullptr, flags, st, models_dev);
-}
-
-// The cell phase of a batch of different models: its own upload of the B records (one copy), then the batch's
-// launches with ModelParams.
-int soil_erode_cells_fused_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour,
-                                        int64_t B, int64_t H, int64_t W, const soil_batch_model* models,
-                                        int flags, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes, "erode_cells_fused_batch_models: null argument");
-  SOIL_REQUIRE(!colour || has_colour(colour), "erode_cells_fused_batch_models: every colour plane is required");
-  int64_t N = 0;  // (the cell phase reads no N, but refuses what the step refuses)
-  if (int rc = check_batch_models(B, H, W, models, "erode_cells_fused_batch_models", &N); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_cells_fused_batch_models: null plane (only `height` is optional)");
-  SOIL_REQUIRE(P.layers != P.layers_next,
-               "erode_cells_fused_batch_models: layers and layers_next must be distinct buffers");
-  const hipStream_t st = as_stream(stream);
-  const soil_batch_model* models_dev = nullptr;
-  if (int rc = batch_models_to_device(models, B, st, &models_dev); rc != SOIL_OK) return rc;
-  return erode_cells_fused_batch(planes, colour, B, H, W, nullptr, nullptr, flags, st, models_dev);
-}
 
 int soil_erode_cells_fused_ex(const soil_erosion_planes* pl, const soil_domain* dom,
                               const float scale[3], const soil_param* param, int flags, void* stream) {

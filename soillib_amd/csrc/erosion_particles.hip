@@ -628,7 +628,7 @@ struct Scratch {
   int64_t tiles_w, tiles;
 };
 
-static int scratch_get(int slot, size_t lead, int64_t B, int64_t N, const Dom& d, bool staged, Scratch* w) {
+static int scratch_get(WorkspaceSlot slot, size_t lead, int64_t B, int64_t N, const Dom& d, bool staged, Scratch* w) {
   w->tiles_w = (d.W + kTile - 1) / kTile;
   w->tiles = w->tiles_w * ((d.rows + kTile - 1) / kTile);
   auto align = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
@@ -739,7 +739,8 @@ static float* colour_flux(const Launch& L, int kind) {
   return L.C ? (kind == FLUVIAL ? L.C->albedo_fluvial : L.C->albedo_debris) : nullptr;
 }
 
-// One launch of a single model: the tiled shape, or the small-N shapes on the kind's tensor (workspace slot 1)
+// One launch of a single model: the tiled shape, or the small-N shapes on the kind's tensor (workspace slot
+// WS_SMALL_LAUNCH)
 static int particles_single(int kind, const Launch& L) {
   const int64_t N = L.N;
   if (N <= 0) return SOIL_OK;
@@ -749,7 +750,7 @@ static int particles_single(int kind, const Launch& L) {
   Scratch w{};
   const bool staged = use_staged(N);
   if (staged)
-    if (int rc = scratch_get(1, 0, 1, N, L.d, true, &w); rc != SOIL_OK) return rc;
+    if (int rc = scratch_get(WS_SMALL_LAUNCH, 0, 1, N, L.d, true, &w); rc != SOIL_OK) return rc;
   float* const albedoFlux = colour_flux(L, kind);
   const SmallLaunch S{L.P, albedoFlux, albedoFlux ? L.C->albedo_surface : nullptr, L.remote0,
                       albedoFlux ? L.remote_colour : nullptr, 1, N, L.d, L.s, L.p, L.st};
@@ -813,82 +814,53 @@ static_assert(offsetof(soil_batch_model, param) == 0 && offsetof(soil_batch_mode
               "soil_batch_model: field offsets as soil_hip.h");
 
 // A batch's records on the device without walkers (the cell phase alone, or a step with every N_b == 0):
-// workspace slot 11.
+// workspace slot WS_BATCH.
 int batch_models_to_device(const soil_batch_model* models, int64_t B, hipStream_t st,
                            const soil_batch_model** models_dev) {
   const size_t bytes = sizeof(soil_batch_model) * static_cast<size_t>(B);
   void* base = nullptr;
-  if (int rc = workspace_get(11, bytes, &base); rc != SOIL_OK) return rc;
+  if (int rc = workspace_get(WS_BATCH, bytes, &base); rc != SOIL_OK) return rc;
   if (int rc = upload_seeds(base, {{models, bytes}}, st); rc != SOIL_OK) return rc;
   *models_dev = static_cast<const soil_batch_model*>(base);
   return SOIL_OK;
 }
 
-int check_batch_models(int64_t B, int64_t H, int64_t W, const soil_batch_model* models, const char* what,
-                       int64_t* N_max) {
-  const std::string w(what);
-  SOIL_REQUIRE(models, w + ": null models");
-  int64_t N = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    SOIL_REQUIRE(models[b].N >= 0 && models[b].N <= 0x7fffffffll,
-                 w + ": models[" + std::to_string(b) + "].N outside [0, 2^31)");
-    N = models[b].N > N ? models[b].N : N;
-  }
-  if (int rc = check_batch(B, H, W, N, &models->seed, what); rc != SOIL_OK) return rc;  // (the seeds: records)
-  *N_max = N;
-  return SOIL_OK;
-}
-
-std::vector<soil_batch_model> sweep_records(int64_t B, const soil_param* params, const float scale[3], int64_t N,
-                                            const uint64_t* seeds, uint64_t step_index) {
-  std::vector<soil_batch_model> models(static_cast<size_t>(B));
-  for (int64_t b = 0; b < B; ++b) {
-    soil_batch_model& m = models[b];
-    m.param = params[b];
-    std::memcpy(m.scale, scale, sizeof(m.scale));
-    m.N = N;
-    m.seed = seeds ? seeds[b] : 0;
-    m.step_index = step_index;
-  }
-  return models;
-}
-
-// soil_particles_batch (soil_hip.h): B whole-grid models, one after the other in every plane; walker n of model b
-// draws from (seeds[b], n, offset), the state soil_erode_step seeds into its tensor for that model alone.  What
-// a lane deposits stays in its model, a NaN walker's (0, 0) included.  Workspace slot 11: the device seeds, then
-// the staged scratch of all B models.  A batch of different models (`models`, soil_particles_batch_models): slot
-// 11 starts with the B records in place of the seeds, in one copy.
-int particles_batch(const soil_erosion_planes* P, const soil_colour_planes* C, int64_t B, int64_t H, int64_t W,
-                    int64_t N, const uint64_t* seeds, uint64_t step_index, const float scale[3],
-                    const soil_param* param, hipStream_t st, const soil_batch_model* models,
-                    const soil_batch_model** models_dev) {
+// soil_particles_batch (soil_hip.h): walker n of model b draws from (seeds[b], n, offset), the state soil_erode_step
+// seeds into its tensor for that model alone.  What a lane deposits stays in its model, a NaN walker's (0, 0)
+// included.  Workspace slot WS_BATCH: the device seeds, then the staged scratch of all B models.  A batch of
+// different models (c.models, soil_particles_batch_models): the slot starts with the B records in place of the
+// seeds, in one copy.
+int particles_batch(const BatchCall& c, const soil_batch_model** records_dev) {
+  const soil_colour_planes* const C = c.C;
+  const int64_t B = c.B, N = c.N;
   // the colour flux planes of all B models (consecutive): one memset each, also when N == 0, as the single
   // coloured pair does
   if (C)
-    if (int rc = clear_flux(nullptr, C, BOTH_KINDS, B * H * W, st); rc != SOIL_OK) return rc;
+    if (int rc = clear_flux(nullptr, C, BOTH_KINDS, B * c.H * c.W, c.st); rc != SOIL_OK) return rc;
   if (N == 0)
-    return models && models_dev ? batch_models_to_device(models, B, st, models_dev) : SOIL_OK;
+    return c.models && records_dev ? batch_models_to_device(c.models, B, c.st, records_dev) : SOIL_OK;
   const bool staged = use_staged(N);  // the single model's rule; what would be tiled alone runs staged
-  const Dom d = full_domain(H, W);
+  const Dom d = full_domain(c.H, c.W);
   Scratch w{};
   // (152-byte records, 8-byte seeds: the scratch behind them is 256-aligned either way)
-  const size_t lead = (models ? sizeof(soil_batch_model) : sizeof(uint64_t)) * static_cast<size_t>(B);
-  if (int rc = scratch_get(11, lead, B, N, d, staged, &w); rc != SOIL_OK) return rc;
-  if (int rc = upload_seeds(w.lead, {{models ? static_cast<const void*>(models) : seeds, lead}}, st); rc != SOIL_OK)
+  const size_t lead = (c.models ? sizeof(soil_batch_model) : sizeof(uint64_t)) * static_cast<size_t>(B);
+  if (int rc = scratch_get(WS_BATCH, lead, B, N, d, staged, &w); rc != SOIL_OK) return rc;
+  if (int rc = upload_seeds(w.lead, {{c.models ? static_cast<const void*>(c.models) : c.seeds, lead}}, c.st);
+      rc != SOIL_OK)
     return rc;
   const ModelParams records{static_cast<const soil_batch_model*>(w.lead)};
-  if (models && models_dev) *models_dev = records.models;
-  const uint64_t offset = step_index * static_cast<uint64_t>(N);
+  if (c.models && records_dev) *records_dev = records.models;
+  const uint64_t offset = c.step_index * static_cast<uint64_t>(N);
   for (int kind : {FLUVIAL, DEBRIS}) {
     // with colour: the kind's colour flux plane and the spawn colours (albedo_surface, also in the staged
     // shape: the packed fields hold none); a batch of different models: scale and param from the records
-    const SmallLaunch S{P, C ? (kind == FLUVIAL ? C->albedo_fluvial : C->albedo_debris) : nullptr,
+    const SmallLaunch S{c.P, C ? (kind == FLUVIAL ? C->albedo_fluvial : C->albedo_debris) : nullptr,
                         C ? C->albedo_surface : nullptr, nullptr, nullptr, B, N, d,
-                        models ? Scale3{} : s3p(scale), models ? Param{} : *param, st};
+                        c.models ? Scale3{} : s3p(c.scale), c.models ? Param{} : *c.param, c.st};
     const uint64_t debris = kind == FLUVIAL ? 0 : 2;  // the debris launch: two draws on
     const Scratch* const ws = staged ? &w : nullptr;
     int rc;
-    if (models) {
+    if (c.models) {
       const ModelDraws draws{records, debris};
       rc = C ? launch_small<true>(kind, S, draws, ws, records) : launch_small<false>(kind, S, draws, ws, records);
     } else {
@@ -1099,52 +1071,6 @@ int soil_particles_pair_colour_slab(const soil_erosion_planes* planes, const soi
                                .remote_colour = remote0 ? remote0 + 8 : nullptr, .d = d, .s = s3p(scale),
                                .p = *param, .st = as_stream(stream),
                                .overwrite = (flags & SOIL_FLUX_OVERWRITE) != 0});
-}
-
-int soil_particles_batch(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W, int64_t N,
-                         const uint64_t* seeds, uint64_t step_index, const float scale[3], const soil_param* param,
-                         void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && param, "particles_batch: null argument");
-  if (int rc = check_batch(B, H, W, N, seeds, "particles_batch"); rc != SOIL_OK) return rc;
-  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch: null plane");
-  return particles_batch(planes, nullptr, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
-}
-
-int soil_particles_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
-                                int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
-                                const float scale[3], const soil_param* param, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && param, "particles_batch_colour: null argument");
-  SOIL_REQUIRE(has_colour(colour), "particles_batch_colour: every colour plane is required");
-  if (int rc = check_batch(B, H, W, N, seeds, "particles_batch_colour"); rc != SOIL_OK) return rc;
-  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch_colour: null plane");
-  return particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, param, as_stream(stream));
-}
-
-int soil_particles_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
-                                int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
-                                const float scale[3], const soil_param* params, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && params, "particles_batch_params: null argument");
-  SOIL_REQUIRE(!colour || has_colour(colour), "particles_batch_params: every colour plane is required");
-  if (int rc = check_batch(B, H, W, N, seeds, "particles_batch_params"); rc != SOIL_OK) return rc;
-  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch_params: null plane");
-  // a batch of different models whose records share scale, N and step_index
-  const std::vector<soil_batch_model> models = sweep_records(B, params, scale, N, seeds, step_index);
-  return particles_batch(planes, colour, B, H, W, N, nullptr, 0, nullptr, nullptr, as_stream(stream),
-                         models.data());
-}
-
-int soil_particles_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
-                                int64_t H, int64_t W, const soil_batch_model* models, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes, "particles_batch_models: null argument");
-  SOIL_REQUIRE(!colour || has_colour(colour), "particles_batch_models: every colour plane is required");
-  int64_t N = 0;
-  if (int rc = check_batch_models(B, H, W, models, "particles_batch_models", &N); rc != SOIL_OK) return rc;
-  SOIL_REQUIRE(has_planes(*planes, PARTICLE_PLANES), "particles_batch_models: null plane");
-  return particles_batch(planes, colour, B, H, W, N, nullptr, 0, nullptr, nullptr, as_stream(stream), models);
 }
 
 int soil_particle_steps(uint64_t* total, int reset, void* stream) {

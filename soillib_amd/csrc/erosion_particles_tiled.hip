@@ -2901,7 +2901,7 @@ struct TiledRun {
     void* base = nullptr;
     // one workspace per kind: the two launches of a step may be in flight together
     const size_t b_blk = align(sizeof(uint4) * (max_tiles + N / 128 + 1));
-    int rc = workspace_get(KIND == FLUVIAL ? 2 : 5, 2 * b_rec + 3 * b_idx + 4 * b_cnt + b_blk + b_p4 + 256, &base);
+    int rc = workspace_get(KIND == FLUVIAL ? WS_TILED_FLUVIAL : WS_TILED_DEBRIS, 2 * b_rec + 3 * b_idx + 4 * b_cnt + b_blk + b_p4 + 256, &base);
     if (rc != SOIL_OK) return rc;
     char* w = static_cast<char*>(base);
     cur = reinterpret_cast<PRec*>(w);    w += b_rec;   // records of this round (any order)
@@ -3293,7 +3293,7 @@ int launch_pair_tiled(const Launch& L, MigrateBox box_fluvial, MigrateBox box_de
   const bool serial_pair = pair_mode == 3;
   if (turns) {
     void* g = nullptr;
-    if (int rc = workspace_get(9, 256, &g); rc != SOIL_OK) return rc;
+    if (int rc = workspace_get(WS_PAIR_GATE, 256, &g); rc != SOIL_OK) return rc;
     SOIL_HIP(hipMemsetAsync(g, 0, sizeof(PairGate), st));  // ahead of the fork
     A.gate = B.gate = static_cast<PairGate*>(g);
   }

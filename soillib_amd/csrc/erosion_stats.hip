@@ -17,7 +17,6 @@ constexpr int64_t kPassCells = int64_t{kSBlock} * kLaneCells;  // cells a work-g
 constexpr int64_t kMinChunk = 4 * kPassCells;                  // the wave and LDS folds are paid once per 16 cells a lane
 constexpr int64_t kMaxPartials = 4096;                         // of one model: what the second pass's one group folds
 constexpr int64_t kMaxModels = 65535;                          // grid.z
-constexpr int kStatsSlot = 12;                                 // workspace_get: the partial records
 
 constexpr int kCh = SOIL_STAT_CHANNELS;
 static_assert(sizeof(soil_channel_stats) == 32 && sizeof(soil_model_stats) == 320, "soil_hip.h: the records' layout");
@@ -251,7 +250,7 @@ int soil_erode_batch_stats(const soil_erosion_planes* planes, int64_t B, int64_t
   const int64_t chunk = stats_chunk(n);
   const int64_t P = (n + chunk - 1) / chunk;  // <= kMaxPartials
   void* base = nullptr;
-  if (int rc = workspace_get(kStatsSlot, sizeof(soil_model_stats) * static_cast<size_t>(B) * static_cast<size_t>(P),
+  if (int rc = workspace_get(WS_STATS, sizeof(soil_model_stats) * static_cast<size_t>(B) * static_cast<size_t>(P),
                              &base);
       rc != SOIL_OK)
     return rc;

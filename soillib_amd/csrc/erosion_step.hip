@@ -77,7 +77,7 @@ static int erode_step(const soil_erosion_planes* planes, const soil_colour_plane
                       uint64_t seed, uint64_t offset, int64_t H, int64_t W, const float scale[3],
                       const soil_param* param, int flags, void* stream) {
   void* scratch = nullptr;
-  if (int rc = workspace_get(7, sizeof(soil_rng) * static_cast<size_t>(N), &scratch); rc != SOIL_OK) return rc;
+  if (int rc = workspace_get(WS_STEP_RNG, sizeof(soil_rng) * static_cast<size_t>(N), &scratch); rc != SOIL_OK) return rc;
   soil_rng* rng_fluvial = static_cast<soil_rng*>(scratch);
   if (int rc = soil_rng_seed(rng_fluvial, N, seed, offset, stream); rc != SOIL_OK) return rc;
   if (int rc = soil_rng_seed(rng, N, seed, offset + 2, stream); rc != SOIL_OK) return rc;
@@ -147,85 +147,6 @@ int soil_erode_step_colour(const soil_erosion_planes* planes, const soil_colour_
                     stream);
 }
 
-// A batch step: the two launches of the batch one after the other, then the batch's cell phase, all on `stream`
-// (no internal streams: a batch fills the device by itself).
-int soil_erode_step_batch(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W, int64_t N,
-                          const uint64_t* seeds, uint64_t step_index, const float scale[3], const soil_param* param,
-                          void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && param, "erode_step_batch: null argument");
-  if (int rc = check_batch(B, H, W, N, seeds, "erode_step_batch"); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch: every plane but `height` is required");
-  SOIL_REQUIRE(P.layers != P.layers_next, "erode_step_batch: layers and layers_next must be distinct buffers");
-  const hipStream_t st = as_stream(stream);
-  if (int rc = particles_batch(planes, nullptr, B, H, W, N, seeds, step_index, scale, param, st); rc != SOIL_OK)
-    return rc;
-  return erode_cells_fused_batch(planes, nullptr, B, H, W, scale, param, 0, st);
-}
-
-// A coloured batch step: as soil_erode_step_batch, the colour flux planes of every model cleared before the
-// fluvial launch and the four colour planes carried through the cell phase.
-int soil_erode_step_batch_colour(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
-                                 int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
-                                 const float scale[3], const soil_param* param, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && param, "erode_step_batch_colour: null argument");
-  SOIL_REQUIRE(has_colour(colour), "erode_step_batch_colour: every colour plane is required");
-  if (int rc = check_batch(B, H, W, N, seeds, "erode_step_batch_colour"); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch_colour: every plane but `height` is required");
-  SOIL_REQUIRE(P.layers != P.layers_next,
-               "erode_step_batch_colour: layers and layers_next must be distinct buffers");
-  const hipStream_t st = as_stream(stream);
-  if (int rc = particles_batch(planes, colour, B, H, W, N, seeds, step_index, scale, param, st); rc != SOIL_OK)
-    return rc;
-  return erode_cells_fused_batch(planes, colour, B, H, W, scale, param, 0, st);
-}
-
-// A step of a batch of different models: the records reach the device once, in place of the seeds of the
-// particle phase's copy, and the cell phase reads that copy.
-static int step_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
-                             int64_t H, int64_t W, int64_t N, const soil_batch_model* models, hipStream_t st) {
-  const soil_batch_model* models_dev = nullptr;
-  if (int rc = particles_batch(planes, colour, B, H, W, N, nullptr, 0, nullptr, nullptr, st, models, &models_dev);
-      rc != SOIL_OK)
-    return rc;
-  return erode_cells_fused_batch(planes, colour, B, H, W, nullptr, nullptr, 0, st, models_dev);
-}
-
-// A sweep step: as the (coloured) batch step, model b with params[b]: a batch of different models whose records
-// share scale, N and step_index.
-int soil_erode_step_batch_params(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
-                                 int64_t H, int64_t W, int64_t N, const uint64_t* seeds, uint64_t step_index,
-                                 const float scale[3], const soil_param* params, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes && scale && params, "erode_step_batch_params: null argument");
-  SOIL_REQUIRE(!colour || has_colour(colour), "erode_step_batch_params: every colour plane is required");
-  if (int rc = check_batch(B, H, W, N, seeds, "erode_step_batch_params"); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch_params: every plane but `height` is required");
-  SOIL_REQUIRE(P.layers != P.layers_next,
-               "erode_step_batch_params: layers and layers_next must be distinct buffers");
-  const std::vector<soil_batch_model> models = sweep_records(B, params, scale, N, seeds, step_index);
-  return step_batch_models(planes, colour, B, H, W, N, models.data(), as_stream(stream));
-}
-
-// A step of a batch of different models (soil_hip.h): model b with models[b].
-int soil_erode_step_batch_models(const soil_erosion_planes* planes, const soil_colour_planes* colour, int64_t B,
-                                 int64_t H, int64_t W, const soil_batch_model* models, void* stream) {
-  SOIL_DEVICE();
-  SOIL_REQUIRE(planes, "erode_step_batch_models: null argument");
-  SOIL_REQUIRE(!colour || has_colour(colour), "erode_step_batch_models: every colour plane is required");
-  int64_t N = 0;
-  if (int rc = check_batch_models(B, H, W, models, "erode_step_batch_models", &N); rc != SOIL_OK) return rc;
-  const soil_erosion_planes& P = *planes;
-  SOIL_REQUIRE(has_planes(P, STEP_PLANES), "erode_step_batch_models: every plane but `height` is required");
-  SOIL_REQUIRE(P.layers != P.layers_next,
-               "erode_step_batch_models: layers and layers_next must be distinct buffers");
-  return step_batch_models(planes, colour, B, H, W, N, models, as_stream(stream));
-}
-
 int soil_erode(const soil_erode_model* model, int64_t H, int64_t W, int64_t N, uint64_t seed,
                uint64_t first_step, int steps, const float scale[3], const soil_param* param,
                void* stream) {
@@ -244,7 +165,7 @@ int soil_erode(const soil_erode_model* model, int64_t H, int64_t W, int64_t N, u
   auto align = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
   const size_t b_layers = align(sizeof(float) * 2 * n), b_rng = align(sizeof(soil_rng) * N);
   void* base = nullptr;
-  if (int rc = workspace_get(6, 2 * b_layers + b_rng, &base); rc != SOIL_OK) return rc;
+  if (int rc = workspace_get(WS_ERODE, 2 * b_layers + b_rng, &base); rc != SOIL_OK) return rc;
   char* w = static_cast<char*>(base);
   float* layers = reinterpret_cast<float*>(w);
   float* layers_next = reinterpret_cast<float*>(w + b_layers);

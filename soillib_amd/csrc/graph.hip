@@ -743,7 +743,7 @@ __global__ void __launch_bounds__(kGBlock)
 
 // Workspace slots of an accumulation: soil_multiflow keeps two of them going side by side (kAccLanes)
 constexpr int kAccLanes = 2;
-constexpr int kAccSlot[kAccLanes] = {0, 10};
+constexpr WorkspaceSlot kAccSlot[kAccLanes] = {WS_ACCUMULATE_0, WS_ACCUMULATE_1};
 
 template <int K>
 static int accumulate_impl(float* out, const int32_t* graph, const float* source,
@@ -1017,7 +1017,7 @@ int soil_multiflow(double* sum, const float* height, const float* source, int64_
   void* base = nullptr;
   const size_t b_graph = align(sizeof(int32_t) * elem), b_acc = align(sizeof(float) * elem);
   // two batches of graphs (the next one is made while the accumulations of this one run) and a result plane per lane
-  if (int rc = workspace_get(3, 2 * kRwBatch * b_graph + kAccLanes * b_acc, &base); rc != SOIL_OK)
+  if (int rc = workspace_get(WS_MULTIFLOW, 2 * kRwBatch * b_graph + kAccLanes * b_acc, &base); rc != SOIL_OK)
     return rc;
   char* ws = static_cast<char*>(base);
   float* acc[kAccLanes];

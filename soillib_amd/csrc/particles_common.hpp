@@ -129,21 +129,6 @@ int particles_fluvial(const Launch& L);
 int particles_debris(const Launch& L);
 int particles_pair(const Launch& L);
 
-// Both particle launches of a batch (soil_particles_batch, soil_hip.h): B whole-grid models of (H, W), N walkers
-// each, model b's streams at (seeds[b], step_index * N) — seeds a host array of B — the debris launch two draws
-// on; direct or staged shape by the single model's rule, one launch after the other on `st` (erosion_particles.hip).
-// With `C` (soil_particles_batch_colour): the two colour flux planes of all B models are cleared first, and the
-// launches deposit colour from albedo_surface into them.  `models` (a host array of B records,
-// soil_particles_batch_models): a batch of different models, N = max N_b, model b with the param, scale, N_b, seed
-// and step index of models[b] (`seeds`, `step_index`, `scale` and `param` are not read); the records reach the
-// device in place of the seeds, and `models_dev` (may be null) receives that device copy for the step's cell phase
-// — with N == 0 they are uploaded alone (batch_models_to_device), and only when asked for.  Valid in stream order
-// until slot 11's next use.
-int particles_batch(const soil_erosion_planes* P, const soil_colour_planes* C, int64_t B, int64_t H, int64_t W,
-                    int64_t N, const uint64_t* seeds, uint64_t step_index, const float scale[3],
-                    const soil_param* param, hipStream_t st, const soil_batch_model* models = nullptr,
-                    const soil_batch_model** models_dev = nullptr);
-
 // the launch shape a launch of N particles on domain d gets (erosion_particles.hip)
 bool use_tiled_launch(int64_t N, const Dom& d);
 int debris_retire_mode();    // soil_set_debris_retire / SOIL_DEBRIS_RETIRE (erosion_particles.hip): 0 off, 1 on, 2 watched

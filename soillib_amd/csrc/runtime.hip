@@ -96,7 +96,7 @@ struct WsThreadGuard {
   }
 };
 
-int workspace_get(int slot, size_t bytes, void** out) {
+int workspace_get(WorkspaceSlot slot, size_t bytes, void** out) {
   int dev = 0;
   SOIL_HIP(hipGetDevice(&dev));
   static thread_local WsThreadGuard guard;

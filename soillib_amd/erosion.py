@@ -488,11 +488,6 @@ class ErosionBatch:
         self._check_params()
         return (_abi.Param * self.B).from_buffer_copy(b"".join(bytes(p._c) for p in self.params))
 
-    def _sweep(self, name, args):
-        """A sweep's entry `name` (soil_*_batch_params): planes, colour (or NULL), then `args`."""
-        colour = C.byref(self._colour()) if self.colour else None
-        _abi.check(getattr(_abi.lib(), name)(C.byref(self._planes()), colour, *args))
-
     @classmethod
     def from_models(cls, models):
         """A new batch holding copies (device to device) of the planes of B whole-grid ErosionModels of one (H, W)
@@ -594,10 +589,22 @@ class ErosionBatch:
         dst, src = (here, single.ptr) if into_batch else (single.ptr, here)
         _abi.check(_abi.lib().soil_memcpy_d2d(C.c_void_p(dst), C.c_void_p(src), per, _abi.stream()))
 
-    def _batch_models(self, name, *args):
-        """An entry `name` of a batch of different models (soil_*_batch_models): planes, colour (or NULL), B, H, W,
-        the records, then `args`."""
-        self._sweep(name, (self.B, self.H, self.W, self._models()) + args)
+    def _call(self, entry, walkers, *flags):
+        """The batch's form of `entry` (soil_erode_step_batch, soil_particles_batch, soil_erode_cells_fused_batch):
+        _models for different models, _params for a sweep, _colour with colour planes, else `entry` itself, with
+        the arguments that form takes.  `walkers`: the entry takes N, the seeds and the step index; `flags`: what
+        goes before the stream."""
+        args = (self.B, self.H, self.W)
+        if self._per_model():
+            suffix, args = "_models", args + (self._models(),)
+        else:
+            suffix = "_params" if self.params is not None else "_colour" if self.colour else ""
+            if walkers:
+                args += (self.N, self._seeds, self.step_index)
+            args += (self._scale(), self._params() if self.params is not None else self.param._ref())
+        # the plain entries take no colour planes, _colour needs them, _params and _models take them or NULL
+        colour = (C.byref(self._colour()) if self.colour else None,) if suffix else ()
+        _abi.check(getattr(_abi.lib(), entry + suffix)(C.byref(self._planes()), *colour, *args, *flags, _abi.stream()))
 
     def set_layers(self, layers_tensor):
         """Copy a (B, H, W, 2) tensor of (bedrock, sediment) into the batch."""
@@ -622,43 +629,13 @@ class ErosionBatch:
         (soil_particles_batch); with colour the two colour flux planes are cleared first and receive this
         step's colour flux (soil_particles_batch_colour).  A sweep: soil_particles_batch_params; different
         models: soil_particles_batch_models."""
-        if self._per_model():
-            self._batch_models("soil_particles_batch_models", _abi.stream())
-            return
-        if self.params is not None:
-            self._sweep("soil_particles_batch_params", (self.B, self.H, self.W, self.N, self._seeds, self.step_index,
-                                                        self._scale(), self._params(), _abi.stream()))
-            return
-        planes = self._planes()
-        args = (self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(), self.param._ref(),
-                _abi.stream())
-        if self.colour:
-            colour = self._colour()
-            _abi.check(_abi.lib().soil_particles_batch_colour(C.byref(planes), C.byref(colour), *args))
-        else:
-            _abi.check(_abi.lib().soil_particles_batch(C.byref(planes), *args))
+        self._call("soil_particles_batch", True)
 
     def cells_fused(self, keep_flux=False):
         """Fused cell phase of every model (soil_erode_cells_fused_batch[_colour]); `keep_flux`: the flux
         planes are left as they are (SOIL_CELLS_KEEP_FLUX).  A sweep: soil_erode_cells_fused_batch_params;
         different models: soil_erode_cells_fused_batch_models."""
-        if self._per_model():
-            self._batch_models("soil_erode_cells_fused_batch_models", _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0,
-                               _abi.stream())
-            return
-        if self.params is not None:
-            self._sweep("soil_erode_cells_fused_batch_params", (self.B, self.H, self.W, self._scale(), self._params(),
-                                                                _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0,
-                                                                _abi.stream()))
-            return
-        planes = self._planes()
-        args = (self.B, self.H, self.W, self._scale(), self.param._ref(),
-                _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0, _abi.stream())
-        if self.colour:
-            colour = self._colour()
-            _abi.check(_abi.lib().soil_erode_cells_fused_batch_colour(C.byref(planes), C.byref(colour), *args))
-        else:
-            _abi.check(_abi.lib().soil_erode_cells_fused_batch(C.byref(planes), *args))
+        self._call("soil_erode_cells_fused_batch", False, _abi.SOIL_CELLS_KEEP_FLUX if keep_flux else 0)
 
     def swap_layers(self):
         self.layers, self.layers_next = self.layers_next, self.layers
@@ -667,25 +644,7 @@ class ErosionBatch:
         """One erosion step of every model (soil_erode_step_batch, with colour soil_erode_step_batch_colour);
         swaps the layer buffers.  A sweep: soil_erode_step_batch_params; different models:
         soil_erode_step_batch_models."""
-        if self._per_model():
-            self._batch_models("soil_erode_step_batch_models", _abi.stream())
-            self.swap_layers()
-            self.step_index += 1
-            return
-        if self.params is not None:
-            self._sweep("soil_erode_step_batch_params", (self.B, self.H, self.W, self.N, self._seeds, self.step_index,
-                                                         self._scale(), self._params(), _abi.stream()))
-            self.swap_layers()
-            self.step_index += 1
-            return
-        planes = self._planes()
-        args = (self.B, self.H, self.W, self.N, self._seeds, self.step_index, self._scale(), self.param._ref(),
-                _abi.stream())
-        if self.colour:
-            colour = self._colour()
-            _abi.check(_abi.lib().soil_erode_step_batch_colour(C.byref(planes), C.byref(colour), *args))
-        else:
-            _abi.check(_abi.lib().soil_erode_step_batch(C.byref(planes), *args))
+        self._call("soil_erode_step_batch", True)
         self.swap_layers()
         self.step_index += 1
 

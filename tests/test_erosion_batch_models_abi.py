@@ -1,94 +1,7 @@
-"""The C ABI of batches of different models (include/soil_hip.h: soil_batch_model, soil_erode_step_batch_models,
-soil_particles_batch_models, soil_erode_cells_fused_batch_models) is declared, exported and bound, its record has
-the layout the header states, and ErosionBatch / ErosionBatch.from_models refuse bad per-model inputs before any
-device work (no compute calls succeed here: this runs without a GPU)."""
-import ctypes as C
-import os
-import re
-
+"""ErosionBatch and ErosionBatch.from_models refuse bad per-model inputs (scales, walker counts, the models handed
+to from_models) before any device work; this runs without a GPU.  The C ABI of the soil_*_batch_models entry points
+and the soil_batch_model record: test_erosion_batch_abi.py."""
 import pytest
-
-from test_abi_symbols import declared_symbols
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRY_POINTS = ("soil_erode_step_batch_models", "soil_particles_batch_models", "soil_erode_cells_fused_batch_models")
-OFFSETS = {"param": 0, "scale": 112, "N": 128, "seed": 136, "step_index": 144}
-
-
-def test_header_declares_the_entry_points_and_the_record():
-    syms = declared_symbols()
-    for name in ENTRY_POINTS:
-        assert name in syms, name
-    text = open(os.path.join(ROOT, "include", "soil_hip.h")).read()
-    m = re.search(r"typedef struct soil_batch_model \{(.*?)\} soil_batch_model;", text, re.S)
-    assert m, "soil_batch_model is not declared"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = re.findall(r"\b(\w+)(?:\[\d+\])?;", body)
-    assert fields == list(OFFSETS), fields
-
-
-def test_library_exports_and_binds_the_entry_points():
-    from soillib_amd import _abi
-    lib = _abi.lib()
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
-        assert name in _abi.SIGNATURES, name
-        args = _abi.SIGNATURES[name][1]
-        assert args[0] is C.POINTER(_abi.ErosionPlanes), name
-        assert args[1] is C.POINTER(_abi.ColourPlanes), name
-        assert args[5] is C.POINTER(_abi.BatchModel), name
-    assert lib.soil_abi_version() == 1
-    # (planes, colour, B, H, W, models[, flags], stream)
-    assert len(_abi.SIGNATURES["soil_erode_step_batch_models"][1]) == 7
-    assert len(_abi.SIGNATURES["soil_particles_batch_models"][1]) == 7
-    assert len(_abi.SIGNATURES["soil_erode_cells_fused_batch_models"][1]) == 8
-
-
-def test_the_record_is_152_bytes_with_the_header_offsets():
-    from soillib_amd import _abi
-    assert C.sizeof(_abi.BatchModel) == 152
-    assert C.alignment(_abi.BatchModel) == 8
-    for name, offset in OFFSETS.items():
-        assert getattr(_abi.BatchModel, name).offset == offset, name
-    assert C.sizeof(_abi.Param) == 112
-    # the library checks the same numbers at compile time
-    src = open(os.path.join(ROOT, "soillib_amd", "csrc", "erosion_particles.hip")).read()
-    assert re.search(r"static_assert\(sizeof\(soil_batch_model\) == 152", src)
-    for name, offset in OFFSETS.items():
-        assert re.search(r"offsetof\(soil_batch_model, %s\) == %d\b" % (name, offset), src), name
-
-
-def _no_device():
-    from soillib_amd import _abi
-    if _abi.lib().soil_device_count() > 0:
-        pytest.skip("a HIP device is present")
-
-
-def _records(B, Ns=None):
-    from soillib_amd import _abi, soil
-    models = (_abi.BatchModel * B)()
-    for b, m in enumerate(models):
-        m.param = soil.param_t()._c
-        m.scale[:] = [1.0, 1.0, 1.0 + b]
-        m.N = 16 if Ns is None else Ns[b]
-        m.seed = b + 1
-        m.step_index = b
-    return models
-
-
-def test_entry_points_fail_loudly_without_a_device():
-    _no_device()
-    from soillib_amd import _abi
-    lib = _abi.lib()
-    planes = _abi.ErosionPlanes()
-    models = _records(2)
-    for colour in (None, C.byref(_abi.ColourPlanes())):
-        assert lib.soil_erode_step_batch_models(C.byref(planes), colour, 2, 8, 8, models,
-                                                None) == _abi.SOIL_ERR_NO_DEVICE
-        assert lib.soil_particles_batch_models(C.byref(planes), colour, 2, 8, 8, models,
-                                               None) == _abi.SOIL_ERR_NO_DEVICE
-        assert lib.soil_erode_cells_fused_batch_models(C.byref(planes), colour, 2, 8, 8, models, 0,
-                                                       None) == _abi.SOIL_ERR_NO_DEVICE
 
 
 def _batch(**kw):
