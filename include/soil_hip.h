@@ -672,6 +672,52 @@ int soil_erode_batch_stats(const soil_erosion_planes* planes, int64_t B, int64_t
 int soil_erode_batch_ensemble(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W,
                               float* mean /* (H, W, 6) */, float* var /* (H, W, 6) or NULL */, void* stream);
 
+/* Order statistics across the models.  Per cell and channel (the six SOIL_ENSEMBLE_CHANNELS in their order, height
+ * being layers.x + layers.y in fp32), the B values v_0 .. v_{B-1} are ordered by an integer key and never by a
+ * float compare (which may canonicalise or flush).  From the value's bits u:
+ *   every NaN first becomes 0x7FC00000;  key = (u >> 31) ? ~u : u | 0x80000000;  keys are compared unsigned.
+ * That is -inf < ... < -denormal < -0 < +0 < +denormal < ... < +inf < NaN, so the k-th order statistic s_k is one
+ * definite bit pattern, denormals kept, whatever the order of the models and whichever path computed it.
+ *
+ * out[j] (device, (nq, H, W, 6)) = the value at fractional rank pos[j] (host array, each in [0, B-1]; 0 the
+ * minimum, B-1 the maximum, (B-1)/2 the median).  The host splits pos[j] in fp64 into lo = floor(pos) and
+ * frac = pos - lo; with a = s_lo and b = s_min(lo+1, B-1) the result is
+ *   a, bit for bit, when frac == 0 or a == b (float equality: -0 next to +0 gives -0);
+ *   (float)((double)a + frac * ((double)b - (double)a)) otherwise: three fp64 operations as written, none
+ *   contracted.
+ * Infinities and NaN get what that arithmetic gives and no special case: -inf next to a finite value (or to +inf)
+ * is NaN at a fractional position between them, +inf above a finite value is +inf; a model holding NaN in a cell
+ * occupies the top ranks of that cell, so it spoils only positions above B - 1 - (number of NaN models) there, and
+ * no other cell.  Which NaN an interpolation returns (sign, payload) is the fp64 unit's; an order statistic that
+ * is a NaN is 0x7FC00000.
+ * Reads layers, waterHeight, mass and debris (20 algorithmic bytes per cell and model), the other planes may be
+ * NULL; writes 24 * nq bytes per cell, once.  The planes are left as they are.  One dispatch on `stream` whatever
+ * B is, no host synchronisation, no workspace; the (lo, frac) pairs travel in the launch arguments, hence
+ * SOIL_QUANTILES_MAX.  Three paths, the same bytes; a wave is 64 consecutive cells of one channel on each, so every
+ * load is coalesced along W.  "reg" (B <= 64): a thread sorts its cell-channel's keys in registers, a bitonic
+ * network padded to a power of two with key 0xFFFFFFFF.  "lds" (B <= 256): a work-group sorts 64 cells, a thread
+ * holding 16 keys, the network's wide steps exchanged through LDS.  "bisect" (any B): each rank is found by
+ * bisecting the key space, 32 walks over the models counting keys <= mid.  Left to itself the entry takes reg up to
+ * B = 16, lds up to B = 256 and bisect above; SOIL_QUANTILE_PATH = auto | reg | lds | bisect forces one
+ * (docs/KNOBS.md), and forcing one at a B it cannot hold is refused.
+ * SOIL_ERR_INVALID_ARGUMENT before any launch for B < 1, a size < 1, sizes whose byte offsets overflow int64, a
+ * NULL `planes`, `out` or `pos`, a NULL plane among the four read, nq < 1 or nq > SOIL_QUANTILES_MAX, a pos[j]
+ * that is not finite or lies outside [0, B-1], and an output whose byte size overflows int64. */
+#define SOIL_QUANTILES_MAX 16
+int soil_erode_batch_quantiles(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W,
+                               const double* pos /* host, nq fractional ranks in [0, B-1] */, int nq,
+                               float* out /* (nq, H, W, 6) device */, void* stream);
+
+/* out (device, (H, W, 6)) = per cell and channel, the share of the models whose value exceeds thresholds[ch] (host
+ * array, the six SOIL_ENSEMBLE_CHANNELS in their order): c = the number of b with v_b > thresholds[ch], a float
+ * compare that is false with a NaN on either side, and out = (float)((double)c / (double)B).  Planes read, bytes,
+ * stream and dispatch count as for soil_erode_batch_quantiles with nq = 1: one thread per cell walks the models.
+ * SOIL_ERR_INVALID_ARGUMENT before any launch for what soil_erode_batch_quantiles refuses of B, H, W and the
+ * planes, and a NULL `planes`, `out` or `thresholds`. */
+int soil_erode_batch_exceedance(const soil_erosion_planes* planes, int64_t B, int64_t H, int64_t W,
+                                const float thresholds[SOIL_ENSEMBLE_CHANNELS] /* host */,
+                                float* out /* (H, W, 6) device */, void* stream);
+
 /* The containers of the legacy API (example/erosion_gpu.py:44-71): model_t, the `data` and the
  * `track` buffers.  All float32 device planes of H*W cells ((H,W,2) for the momenta). */
 typedef struct soil_erode_model {

@@ -47,6 +47,7 @@ class BatchModel(C.Structure):
 
 SOIL_STAT_CHANNELS = 10
 SOIL_ENSEMBLE_CHANNELS = 6
+SOIL_QUANTILES_MAX = 16
 
 
 class ChannelStats(C.Structure):
@@ -193,6 +194,10 @@ SIGNATURES = {
     # summaries: B records of soil_model_stats (device); the (H, W, 6) mean and variance maps (var may be NULL)
     "soil_erode_batch_stats": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, vp, vp]),
     "soil_erode_batch_ensemble": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, vp, vp, vp]),
+    # order statistics: nq host positions -> (nq, H, W, 6); six host thresholds -> (H, W, 6)
+    "soil_erode_batch_quantiles": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, C.POINTER(C.c_double), cint, vp,
+                                          vp]),
+    "soil_erode_batch_exceedance": (cint, [C.POINTER(ErosionPlanes), i64, i64, i64, F3, vp, vp]),
     "soil_erode": (cint, [C.POINTER(ErodeModel), i64, i64, i64, u64, u64, cint, F3, C.POINTER(Param),
                           vp]),
     "soil_set_particle_mode": (cint, [cint]),

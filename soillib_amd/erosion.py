@@ -49,6 +49,9 @@ the same world extent: the multiscale schedule (erode coarse, resample, erode fi
 (soil_erode_batch_stats: sum, sum of squares, min, max and the count of non-finite cells of the ten STAT_CHANNELS), and
 `ErosionBatch.ensemble()` reduces the batch to per-cell mean and variance maps of the six ENSEMBLE_CHANNELS
 (soil_erode_batch_ensemble): what a sweep or an ensemble wants to know without copying a plane to the host.
+`ErosionBatch.quantiles(q)`, `order_statistics(ranks)` and `median()` give per-cell order statistics across the models
+(soil_erode_batch_quantiles), and `exceedance(thresholds)` the share of the models above a threshold per cell
+(soil_erode_batch_exceedance): the summaries of a heavy-tailed ensemble.
 """
 import ctypes as C
 import numbers
@@ -578,6 +581,92 @@ class ErosionBatch:
         _abi.check(_abi.lib().soil_erode_batch_ensemble(C.byref(self._planes()), self.B, self.H, self.W, mean.c_ptr,
                                                         variance.c_ptr if var else None, _abi.stream()))
         return mean, variance
+
+    def _positions(self, who, values, what, top):
+        """`values` (one number or a sequence) as a list of floats in [0, top], or ValueError."""
+        if isinstance(values, numbers.Real) and not isinstance(values, bool):
+            values = [values]
+        try:
+            items = list(values)
+        except TypeError:
+            raise ValueError("ErosionBatch.%s: %s must be a number or a sequence of numbers" % (who, what))
+        if not items:
+            raise ValueError("ErosionBatch.%s: no %s given" % (who, what))
+        out = []
+        for v in items:
+            if not isinstance(v, numbers.Real) or isinstance(v, bool):
+                raise ValueError("ErosionBatch.%s: %r is not a number" % (who, v))
+            f = float(v)
+            if f != f or not 0.0 <= f <= top:
+                raise ValueError("ErosionBatch.%s: %r is outside [0, %r]" % (who, v, top))
+            out.append(f)
+        return out
+
+    def _at_positions(self, pos):
+        """(len(pos), H, W, 6): the values at the fractional ranks `pos`, SOIL_QUANTILES_MAX to a call of
+        soil_erode_batch_quantiles, each call into its slice of the one tensor."""
+        out = silt.tensor(silt.float32, silt.shape(len(pos), self.H, self.W, len(ENSEMBLE_CHANNELS)), silt.gpu)
+        per = self.H * self.W * len(ENSEMBLE_CHANNELS) * 4
+        planes = self._planes()
+        for j0 in range(0, len(pos), _abi.SOIL_QUANTILES_MAX):
+            chunk = pos[j0:j0 + _abi.SOIL_QUANTILES_MAX]
+            _abi.check(_abi.lib().soil_erode_batch_quantiles(
+                C.byref(planes), self.B, self.H, self.W, (C.c_double * len(chunk))(*chunk), len(chunk),
+                C.c_void_p(out.ptr + j0 * per), _abi.stream()))
+        return out
+
+    def quantiles(self, q):
+        """Per cell, the quantiles `q` (one number or a sequence, each in [0, 1]) across the B models of the six
+        ENSEMBLE_CHANNELS: a silt GPU tensor of (len(q), H, W, 6) (soil_erode_batch_quantiles).  q[j] is the value
+        at fractional rank q[j] * (B - 1) of the cell's B values in the total order of the header (by bit
+        pattern: -inf < ... < -0 < +0 < ... < +inf < NaN), interpolated linearly in fp64 between the two order
+        statistics around it.  One launch per 16 quantiles whatever B is; q may be unsorted and may repeat.  An
+        empty q, a NaN or a value outside [0, 1] raises ValueError before any device work.  The batch is left as
+        it is; nothing synchronises."""
+        return self._at_positions([v * (self.B - 1) for v in self._positions("quantiles", q, "q", 1.0)])
+
+    def order_statistics(self, ranks):
+        """Per cell, the order statistics `ranks` (one integer or a sequence, each in [0, B - 1]; 0 the minimum)
+        across the B models: (len(ranks), H, W, 6), each value the bit pattern of one of the models
+        (soil_erode_batch_quantiles at exact positions).  A rank that is not an integer or lies outside
+        [0, B - 1], or no rank at all, raises ValueError before any device work.  Nothing synchronises."""
+        if isinstance(ranks, numbers.Real) and not isinstance(ranks, bool):
+            ranks = [ranks]
+        try:
+            items = list(ranks)
+        except TypeError:
+            raise ValueError("ErosionBatch.order_statistics: ranks must be an integer or a sequence of integers")
+        for r in items:
+            if not isinstance(r, numbers.Integral) or isinstance(r, bool):
+                raise ValueError("ErosionBatch.order_statistics: rank %r is not an integer" % (r,))
+        return self._at_positions(self._positions("order_statistics", [int(r) for r in items], "ranks",
+                                                  float(self.B - 1)))
+
+    def median(self):
+        """Per cell, the median across the B models, an (H, W, 6) view: position (B - 1) / 2 of
+        soil_erode_batch_quantiles (the middle model's value for odd B, the fp64 midpoint of the middle two for
+        even B).  Nothing synchronises."""
+        out = self._at_positions([(self.B - 1) / 2])
+        return silt.tensor.from_device(out.ptr, out.type, tuple(out.shape)[1:], keepalive=out)
+
+    def exceedance(self, thresholds):
+        """Per cell and channel, the share of the B models whose value exceeds `thresholds` (six numbers in the
+        order of ENSEMBLE_CHANNELS; the comparison is strict, and false with a NaN on either side): an (H, W, 6)
+        float32 silt GPU tensor written by one launch whatever B is (soil_erode_batch_exceedance).  Anything but
+        six numbers raises ValueError before any device work.  Nothing synchronises."""
+        try:
+            items = list(thresholds)
+        except TypeError:
+            raise ValueError("ErosionBatch.exceedance: thresholds must be six numbers (%s)" % ", ".join(ENSEMBLE_CHANNELS))
+        if len(items) != len(ENSEMBLE_CHANNELS) or not all(
+                isinstance(v, numbers.Real) and not isinstance(v, bool) for v in items):
+            raise ValueError("ErosionBatch.exceedance: thresholds must be six numbers (%s), got %r" % (
+                ", ".join(ENSEMBLE_CHANNELS), thresholds))
+        out = silt.tensor(silt.float32, silt.shape(self.H, self.W, len(ENSEMBLE_CHANNELS)), silt.gpu)
+        _abi.check(_abi.lib().soil_erode_batch_exceedance(
+            C.byref(self._planes()), self.B, self.H, self.W, (C.c_float * 6)(*[float(v) for v in items]), out.c_ptr,
+            _abi.stream()))
+        return out
 
     def _copy(self, name, b, model, into_batch):
         """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""

@@ -84,6 +84,7 @@ KNOBS = {
     "SOIL_ABLATE": ("particles", "-DSOIL_ABLATE builds only: bit mask of parts of the round kernel switched off (timing experiments; results wrong by construction)"),
     "SOIL_ABLATE_AFTER": ("particles", "... from the n-th launch of a kind on"),
     # ---- cells, stencils, graph
+    "SOIL_QUANTILE_PATH": ("summaries", "auto | reg | lds | bisect: the path of soil_erode_batch_quantiles (registers: B <= 64, taken unforced up to 16; LDS: B <= 256; bisection: any B; the same bytes on every path); a path forced at a B it cannot hold is refused; read per call [auto]"),
     "SOIL_CELLS_VARIANT": ("cells", "A/B variants of the fused cell kernel's launch (tools/bench_cells.py) [0]"),
     "SOIL_CELLS_NT": ("cells", "1: non-temporal accesses in the fused cell kernel (measured slower; A/B)"),
     "SOIL_CELLS_SPLIT": ("cells", "0: an eager step's cell phase as one 112-byte kernel instead of the 84-byte kernel + a zeroing pass"),
@@ -114,7 +115,8 @@ KNOBS = {
 AREAS = [("load", "Loading, devices, allocation"), ("wire", "The wire between ranks (include/soil_slab.h)"),
          ("slabs", "Slab runner (csrc/slab_runner.hip)"), ("step", "The erosion step"),
          ("particles", "Tiled particle transport (csrc/erosion_particles_tiled.hip; NAME_F / NAME_D: per kind)"),
-         ("cells", "Fused cell phase (csrc/erosion_cells.hip)"), ("stencils", "Stencil kernels (csrc/window.hpp, stencil.hip)"),
+         ("cells", "Fused cell phase (csrc/erosion_cells.hip)"),
+         ("summaries", "Summaries of a batch (csrc/erosion_quantiles.hip)"), ("stencils", "Stencil kernels (csrc/window.hpp, stencil.hip)"),
          ("graph", "Graph kernels and conditioning (csrc/graph.hip, conditioning.hip)"), ("bench", "bench.py"),
          ("tests", "Tests")]
 
