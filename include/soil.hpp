@@ -238,6 +238,48 @@ inline F slope(const F tensor, const silt::tensor_t<int> flow, const silt::vec2 
   return out;
 }
 
+// ---- the same for B models of one (H, W): (B, H, W) tensors, model-major (soil_hip.h: "flow graphs: batches
+// of models"; no counterpart in the reference).  Stream-ordered, no synchronisation.
+inline silt::tensor_t<int> direction_batch(const F height, const edge_t edge) {
+  silt::tensor_t<int> out(height.shape(), silt::GPU);
+  check(soil_direction_batch(out.data(), height.data(), height.shape()[0], height.shape()[1], height.shape()[2],
+                             edge, nullptr));
+  return out;
+}
+inline silt::tensor_t<int> steepest_batch(const F height, const edge_t edge) {
+  silt::tensor_t<int> out(height.shape(), silt::GPU);
+  check(soil_steepest_batch(out.data(), height.data(), height.shape()[0], height.shape()[1], height.shape()[2],
+                            edge, nullptr));
+  return out;
+}
+inline silt::tensor_t<int> random_weighted_batch(const F height, const edge_t edge,
+                                                 const std::vector<uint64_t>& seeds, const size_t offset,
+                                                 const float T) {
+  if (static_cast<int64_t>(seeds.size()) != height.shape()[0])
+    throw std::invalid_argument("random_weighted_batch: one seed per model");
+  silt::tensor_t<int> out(height.shape(), silt::GPU);
+  check(soil_random_weighted_batch(out.data(), height.data(), height.shape()[0], height.shape()[1],
+                                   height.shape()[2], edge, seeds.data(), offset, T, nullptr));
+  return out;
+}
+// `scales`: one pair for every model, or a pair per model
+inline F slope_batch(const F tensor, const silt::tensor_t<int> flow, const std::vector<silt::vec2>& scales) {
+  std::vector<float> pairs;
+  for (const silt::vec2& s : scales) pairs.push_back(s.x), pairs.push_back(s.y);
+  F out(tensor.shape(), silt::GPU);
+  check(soil_slope_batch(out.data(), tensor.data(), flow.data(), tensor.shape()[0], tensor.shape()[1],
+                         tensor.shape()[2], pairs.empty() ? nullptr : pairs.data(),
+                         static_cast<int64_t>(scales.size()), nullptr));
+  return out;
+}
+// `decay`: a default-constructed tensor for none (soil::accumulate), else soil::accumulate_decay
+inline F accumulate_batch(const silt::tensor_t<int> graph, const F source, const edge_t edge, const F decay = F()) {
+  F out(graph.shape(), silt::GPU);
+  check(soil_accumulate_batch(out.data(), graph.data(), source.data(), decay.data(), graph.shape()[0],
+                              graph.shape()[1], graph.shape()[2], edge, nullptr));
+  return out;
+}
+
 // ---- grad.hpp:11-17, filter.hpp:11 ------------------------------------------------------------
 inline F gradient(const F& tensor, const silt::vec2 scale) {
   F out(silt::shape(tensor.shape()[0], tensor.shape()[1], 2), silt::GPU);

@@ -860,6 +860,55 @@ int soil_fill_depressions(float* out, const float* height, int64_t H, int64_t W,
  * while no other thread is inside the library. */
 int soil_workspace_release(void);
 
+/* ------------------------------------------ flow graphs: batches of models */
+
+/* The five calls above for B models of one (H, W) in one call, in a number of launches that does not grow with B.
+ * Every tensor is model-major, as in soil_erode_step_batch: model b of a plane starts at element b * H * W.
+ *
+ * Per-model contract.  Model b's slice of every output is, bit for bit, what the single-grid call writes for
+ * model b's slices of the inputs alone — with seed = seeds[b], and with the pair scales[b] (or the one pair).
+ * A graph entry is an index WITHIN its own model (0 .. H*W-1, or -1): model b's slice of a batch graph can be
+ * handed to soil_accumulate, and a single grid's graph can be a slice of a batch.  Nothing a model holds can
+ * reach another model: a neighbour off a model's edge does not exist, and a graph entry that is not one of the
+ * cell's K neighbours inside its model is no edge (as in the single grid's donor pass).
+ *
+ * Round count.  soil_accumulate_batch runs the rounds a single model of (H, W) runs,
+ * 2 * (ceil(log2(H*W) / 2) + 1), not those of the stacked size: a graph that does not converge (a cycle) gets
+ * the values of that round count, the single grid's.
+ *
+ * The batch entries are stream-ordered and do not synchronise (soil_accumulate keeps its synchronisation); a
+ * call that finds its cached scratch too small synchronises the device before replacing it, as everywhere.
+ * Because they return with their work in flight, a host thread's calls of soil_accumulate_batch on one device share
+ * one cached scratch block (its own, not soil_accumulate's), and so do its calls of soil_random_weighted_batch and
+ * soil_slope_batch (the device copy of seeds / scales): issue such calls on ONE stream, or order the streams yourself
+ * (an event) so that the earlier call has finished before the later one starts.  Other threads have their own blocks.
+ * `seeds` (B words) and `scales` (n_scales pairs (sx, sy), n_scales == 1 or B) are HOST arrays, read before the
+ * call returns; they reach the device in at most one small stream-ordered copy.  Launches: each graph or slope
+ * entry ceil(B / 65535) kernels; soil_accumulate_batch runs in chunks of whole models — as many as keep the
+ * rounds' 32-bit offsets (K * cells * 4 < 2^32) and one donor pass (65535), SOIL_FLOW_BATCH_CELLS lowers the
+ * cells of a chunk — and per chunk one donor pass, one control kernel and the rounds, whatever B is.  Results do
+ * not depend on the chunking.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, the entry's name in soil_last_error(): a null
+ * tensor, null `seeds` or `scales`, B, H or W < 1, H * W > INT32_MAX, n_scales not 1 or B, an invalid `edge`.
+ * Without a device: SOIL_ERR_NO_DEVICE. */
+/* soil_direction for B models. */
+int soil_direction_batch(int32_t* direction, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                         void* stream);
+/* soil_steepest for B models. */
+int soil_steepest_batch(int32_t* graph, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                        void* stream);
+/* soil_random_weighted for B models: cell n of model b (n within the model) draws from the Philox block (key
+ * seeds[b]; counter {offset, n >> 2}), word n & 3. */
+int soil_random_weighted_batch(int32_t* graph, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                               const uint64_t* seeds, uint64_t offset, float T, void* stream);
+/* soil_slope for B models, model b with scales[b] or with the one pair. */
+int soil_slope_batch(float* slope, const float* tensor, const int32_t* flow, int64_t B, int64_t H, int64_t W,
+                     const float* scales, int64_t n_scales, void* stream);
+/* soil_accumulate for B models; `decay` may be NULL. */
+int soil_accumulate_batch(float* out, const int32_t* graph, const float* source, const float* decay,
+                          int64_t B, int64_t H, int64_t W, int edge, void* stream);
+
 /* ---------------------------------------------------------------- stencils */
 
 /* soil::gradient — grad.hpp:11, grad.cu:89-97 (__gradient :22-87), model.cpp:193-195.  out (H,W,2). */

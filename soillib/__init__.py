@@ -16,6 +16,8 @@ from soillib_amd.soil import (accumulate, accumulate_decay, albedo_discharge, al
                               solve_uniform, steepest, timer, transport_debris, transport_fluvial,
                               us)
 from soillib_amd.soil import particle_steps  # noqa: F401
+from soillib_amd.soil import (accumulate_batch, direction_batch, random_weighted_batch, slope_batch,  # noqa: F401
+                              steepest_batch)
 from soillib_amd.io import geotiff, geotiff_meta, mesh, tiff  # noqa: F401  (python/source/io.cpp:20-110)
 from soillib_amd.legacy import (buffer, clamp, data_t, erode, index, map_t, multiply, param_t,  # noqa: F401
                                 resize)

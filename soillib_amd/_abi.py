@@ -221,6 +221,12 @@ SIGNATURES = {
     "soil_random_weighted": (cint, [vp, vp, i64, i64, cint, u64, u64, f32, vp]),
     "soil_slope": (cint, [vp, vp, vp, i64, i64, F3, vp]),
     "soil_accumulate": (cint, [vp, vp, vp, vp, i64, i64, cint, vp]),
+    # flow graphs of B models, model-major planes; seeds and scales are host arrays
+    "soil_direction_batch": (cint, [vp, vp, i64, i64, i64, cint, vp]),
+    "soil_steepest_batch": (cint, [vp, vp, i64, i64, i64, cint, vp]),
+    "soil_random_weighted_batch": (cint, [vp, vp, i64, i64, i64, cint, C.POINTER(u64), u64, f32, vp]),
+    "soil_slope_batch": (cint, [vp, vp, vp, i64, i64, i64, F3, i64, vp]),
+    "soil_accumulate_batch": (cint, [vp, vp, vp, vp, i64, i64, i64, cint, vp]),
     "soil_workspace_release": (cint, []),
     "soil_gradient": (cint, [vp, vp, i64, i64, F3, vp]),
     "soil_negslope": (cint, [vp, vp, i64, i64, F3, vp]),

@@ -63,6 +63,8 @@ enum WorkspaceSlot {
   WS_ACCUMULATE_1 = 10,  // graph.hip: an accumulation, lane 1 (kAccSlot)
   WS_BATCH = 11,         // erosion_particles.hip: a batch's seeds or records, then its staged scratch
   WS_STATS = 12,         // erosion_stats.hip: the partial records
+  WS_FLOW_BATCH = 13,    // graph.hip: a batch entry's seeds or scale pairs
+  WS_ACCUMULATE_BATCH = 14,  // graph.hip: soil_accumulate_batch (stream-ordered: not soil_accumulate's slot)
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();
@@ -97,6 +99,10 @@ inline bool has_colour(const soil_colour_planes* C, bool bedrock = true) {
 // slot WS_BATCH (erosion_particles.hip); *models_dev valid in stream order until the slot's next use.
 int batch_models_to_device(const soil_batch_model* models, int64_t B, hipStream_t st,
                            const soil_batch_model** models_dev);
+
+// `bytes` of a host array copied to `dst` (device) in one stream-ordered copy through the same pinned staging
+// (erosion_particles.hip): the array may go as soon as the call returns.
+int batch_upload(void* dst, const void* src, size_t bytes, hipStream_t st);
 
 // One call of a batch entry point (soil_hip.h: soil_erode_step_batch, soil_particles_batch,
 // soil_erode_cells_fused_batch and their _colour, _params and _models forms), as erosion_batch.hip fills and

@@ -807,6 +807,10 @@ static int upload_seeds(void* dst, std::initializer_list<std::pair<const void*, 
   return SOIL_OK;
 }
 
+int batch_upload(void* dst, const void* src, size_t bytes, hipStream_t st) {
+  return upload_seeds(dst, {{src, bytes}}, st);
+}
+
 static_assert(sizeof(soil_batch_model) == 152 && alignof(soil_batch_model) == 8, "soil_batch_model: 152 bytes");
 static_assert(offsetof(soil_batch_model, param) == 0 && offsetof(soil_batch_model, scale) == 112 &&
                   offsetof(soil_batch_model, N) == 128 && offsetof(soil_batch_model, seed) == 136 &&

@@ -30,12 +30,49 @@ __device__ __forceinline__ float shift_len(int k) {  // __length(shift), graph.c
   return sqrtf(dx * dx + dy * dy);
 }
 
+// Which grid a work-group of a graph, slope or donor kernel works on, a compile-time choice (the batch entries,
+// soil_*_batch of soil_hip.h).  OneGrid: the one (H, W) grid of the single-grid entries.  ModelGrid: grid.z is the
+// model (the band walks of window.hpp and SOIL_ROW_LOOP take their bands from grid.y; none of the walks looks at
+// grid.z), every plane holds the models one after the other, and a kernel moves its plane pointers to its model
+// at entry — the per-cell arithmetic below that line is the single grid's, on indices within the model.  A seed
+// or a scale is then a device array with an element per model (blockIdx.z is uniform: scalar loads).
+struct BatchScale {
+  const Scale2* per_model;  // null: `one` for every model
+  Scale2 one;
+};
+struct OneGrid {
+  static constexpr bool kBatch = false;
+  using Seed = uint64_t;
+  using Scale = Scale2;
+  static __device__ __forceinline__ int64_t first_cell(int64_t, int64_t) { return 0; }
+  static __device__ __forceinline__ uint64_t seed(Seed s) { return s; }
+  static __device__ __forceinline__ Scale2 scale(const Scale& s) { return s; }
+};
+struct ModelGrid {
+  static constexpr bool kBatch = true;
+  using Seed = const uint64_t*;
+  using Scale = BatchScale;
+  static __device__ __forceinline__ int64_t first_cell(int64_t H, int64_t W) {
+    return static_cast<int64_t>(blockIdx.z) * H * W;
+  }
+  static __device__ __forceinline__ uint64_t seed(Seed s) { return s[blockIdx.z]; }
+  static __device__ __forceinline__ Scale2 scale(const Scale& s) {
+    const Scale2 v = s.per_model ? s.per_model[blockIdx.z] : s.one;
+    return Scale2{uniform(v.x), uniform(v.y)};  // (in scalar registers, as a kernel argument is)
+  }
+  static __device__ __forceinline__ float uniform(float v) {
+    return bits2f(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(f2bits(v)))));
+  }
+};
+constexpr int64_t kMaxGridZ = 65535;  // models per launch: the host moves the planes on past that many
+
 // __steepest (graph.cu:27-70) / __direction (:201-243)
-template <int K, bool STORE_K>
+template <int K, bool STORE_K, class G = OneGrid>
 __global__ void __launch_bounds__(kGBlock)
     k_steepest(int32_t* __restrict__ out, const float* __restrict__ height, int64_t H, int64_t W) {
   const int64_t y = static_cast<int64_t>(blockIdx.x) * kGBlock + threadIdx.x;
   if (y >= W) return;
+  if (G::kBatch) out += G::first_cell(H, W), height += G::first_cell(H, W);
   SOIL_ROW_LOOP(x, H) {
     const int64_t n = x * W + y;
     const float hlocal = height[n];  // :40
@@ -156,9 +193,10 @@ __device__ __forceinline__ bool steepest_group_fast(int32_t oi[4], const Walk& w
   return __ballot(tie) == 0ull;
 }
 
-template <int K, bool STORE_K, class Walk>
+template <int K, bool STORE_K, class Walk, class G = OneGrid>
 __global__ void __launch_bounds__(kWinBlock) __attribute__((amdgpu_waves_per_eu(8, 8)))
     k_steepest4(int32_t* __restrict__ out, const float* __restrict__ height, int64_t H, int64_t W) {
+  if (G::kBatch) out += G::first_cell(H, W), height += G::first_cell(H, W);
   const WinThread t = Walk::thread(H, W);
   const Recip rdiag = recip(kSqrt2);
   SOIL_WIN_WALK(Walk, w, W);
@@ -171,24 +209,29 @@ __global__ void __launch_bounds__(kWinBlock) __attribute__((amdgpu_waves_per_eu(
   }
 }
 
-template <int K, bool STORE_K, class Walk>
-void launch_steepest4_as(int32_t* out, const float* height, int64_t H, int64_t W, hipStream_t st) {
-  k_steepest4<K, STORE_K, Walk><<<Walk::grid(H, W), kWinBlock, 0, st>>>(out, height, H, W);
+// `models`: grid.z (ModelGrid; 1 for the one grid)
+inline dim3 with_models(dim3 grid, unsigned models) {
+  grid.z = models;
+  return grid;
 }
-template <int K, bool STORE_K>
-void launch_steepest4(int32_t* out, const float* height, int64_t H, int64_t W, hipStream_t st) {
+template <int K, bool STORE_K, class Walk, class G>
+void launch_steepest4_as(int32_t* out, const float* height, int64_t H, int64_t W, hipStream_t st, unsigned models) {
+  k_steepest4<K, STORE_K, Walk, G><<<with_models(Walk::grid(H, W), models), kWinBlock, 0, st>>>(out, height, H, W);
+}
+template <int K, bool STORE_K, class G = OneGrid>
+void launch_steepest4(int32_t* out, const float* height, int64_t H, int64_t W, hipStream_t st, unsigned models = 1) {
   constexpr bool kWatch = K > 4;  // the straight slopes are the differences: nothing to watch for d4
   // (steepest D8 on blocks of four rows spills its 64 registers; direction does not)
   switch (win_shape_for(STORE_K ? 4 : 0, STORE_K ? 4 : 5, H, W)) {
-    case 0: return launch_steepest4_as<K, STORE_K, RowWalkReg<kWatch>>(out, height, H, W, st);
-    case 1: return launch_steepest4_as<K, STORE_K, RowWalkLds<kWatch>>(out, height, H, W, st);
-    case 3: return launch_steepest4_as<K, STORE_K, RowWalkTall<kWatch>>(out, height, H, W, st);
-    case 4: return launch_steepest4_as<K, STORE_K, RowWalkBlock4<kWatch>>(out, height, H, W, st);
-    case 5: return launch_steepest4_as<K, STORE_K, RowWalkBlock2<kWatch>>(out, height, H, W, st);
-    case 6: return launch_steepest4_as<K, STORE_K, RowWalkShort<kWatch>>(out, height, H, W, st);
-    case 7: return launch_steepest4_as<K, STORE_K, RowWalkStack2<kWatch>>(out, height, H, W, st);
-    case 8: return launch_steepest4_as<K, STORE_K, RowWalkStack4<kWatch>>(out, height, H, W, st);
-    default: return launch_steepest4_as<K, STORE_K, RowWalkFlat<kWatch>>(out, height, H, W, st);
+    case 0: return launch_steepest4_as<K, STORE_K, RowWalkReg<kWatch>, G>(out, height, H, W, st, models);
+    case 1: return launch_steepest4_as<K, STORE_K, RowWalkLds<kWatch>, G>(out, height, H, W, st, models);
+    case 3: return launch_steepest4_as<K, STORE_K, RowWalkTall<kWatch>, G>(out, height, H, W, st, models);
+    case 4: return launch_steepest4_as<K, STORE_K, RowWalkBlock4<kWatch>, G>(out, height, H, W, st, models);
+    case 5: return launch_steepest4_as<K, STORE_K, RowWalkBlock2<kWatch>, G>(out, height, H, W, st, models);
+    case 6: return launch_steepest4_as<K, STORE_K, RowWalkShort<kWatch>, G>(out, height, H, W, st, models);
+    case 7: return launch_steepest4_as<K, STORE_K, RowWalkStack2<kWatch>, G>(out, height, H, W, st, models);
+    case 8: return launch_steepest4_as<K, STORE_K, RowWalkStack4<kWatch>, G>(out, height, H, W, st, models);
+    default: return launch_steepest4_as<K, STORE_K, RowWalkFlat<kWatch>, G>(out, height, H, W, st, models);
   }
 }
 
@@ -253,12 +296,24 @@ struct RwBatch {  // up to kRwBatch realisations per pass over the heights (soil
 };
 
 // one thread per cell (any width)
-template <int K>
+// move the graphs of a launch to the work-group's model (ModelGrid)
+template <class G>
+__device__ __forceinline__ void rw_to_model(RwBatch& b, int64_t H, int64_t W) {
+  if (G::kBatch) {
+#pragma unroll
+    for (int m = 0; m < kRwBatch; ++m) b.graph[m] += G::first_cell(H, W);
+  }
+}
+
+template <int K, class G = OneGrid>
 __global__ void __launch_bounds__(kGBlock)
     k_random_weighted(RwBatch b, const float* __restrict__ height, int64_t H, int64_t W,
-                      uint64_t seed, RwConst rc) {
+                      typename G::Seed seed_of, RwConst rc) {
   const int64_t y = static_cast<int64_t>(blockIdx.x) * kGBlock + threadIdx.x;
   if (y >= W) return;
+  const uint64_t seed = G::seed(seed_of);
+  rw_to_model<G>(b, H, W);
+  if (G::kBatch) height += G::first_cell(H, W);
   SOIL_ROW_LOOP(x, H) {
     const int64_t n = x * W + y;
     const float hlocal = height[n];  // :118
@@ -287,10 +342,13 @@ __global__ void __launch_bounds__(kGBlock)
 
 // four cells per thread, the neighbours from the thread's three-row window (window.hpp): the same
 // operations on the same values as the kernel above
-template <int K, class Walk>
+template <int K, class Walk, class G = OneGrid>
 __global__ void __launch_bounds__(kWinBlock)
-    k_random_weighted4(RwBatch b, const float* __restrict__ height, int64_t H, int64_t W, uint64_t seed,
-                       RwConst rc) {
+    k_random_weighted4(RwBatch b, const float* __restrict__ height, int64_t H, int64_t W,
+                       typename G::Seed seed_of, RwConst rc) {
+  const uint64_t seed = G::seed(seed_of);
+  rw_to_model<G>(b, H, W);
+  if (G::kBatch) height += G::first_cell(H, W);
   const WinThread t = Walk::thread(H, W);
   SOIL_WIN_WALK(Walk, w, W);
   SOIL_WIN_ROWS(x, w, height, H, W, t) {
@@ -335,21 +393,25 @@ __global__ void __launch_bounds__(kWinBlock)
   }
 }
 
-template <int K>
-static void launch_random_weighted(const RwBatch& b, const float* height, int64_t H, int64_t W, uint64_t seed,
-                                   float T, hipStream_t st) {
+// `seed`: the seed (OneGrid), or a device array with the seed of each of the launch's `models` (ModelGrid)
+template <int K, class G = OneGrid>
+static void launch_random_weighted(const RwBatch& b, const float* height, int64_t H, int64_t W,
+                                   typename G::Seed seed, float T, hipStream_t st, unsigned models = 1) {
   bool aligned = W % 4 == 0 && W >= 4 && (reinterpret_cast<uintptr_t>(height) & 15) == 0;
   for (int m = 0; m < b.n; ++m) aligned = aligned && (reinterpret_cast<uintptr_t>(b.graph[m]) & 15) == 0;
   if (aligned) {
     const int shape = win_shape_for(4, 4, H, W);
-    if (shape == 4) k_random_weighted4<K, RowWalkBlock4<false>><<<RowWalkBlock4<false>::grid(H, W), kWinBlock, 0, st>>>(b, height, H, W, seed, rw_const(T));
-    else if (shape == 5) k_random_weighted4<K, RowWalkBlock2<false>><<<RowWalkBlock2<false>::grid(H, W), kWinBlock, 0, st>>>(b, height, H, W, seed, rw_const(T));
-    else if (shape == 7) k_random_weighted4<K, RowWalkStack2<false>><<<RowWalkStack2<false>::grid(H, W), kWinBlock, 0, st>>>(b, height, H, W, seed, rw_const(T));
-    else if (shape == 8) k_random_weighted4<K, RowWalkStack4<false>><<<RowWalkStack4<false>::grid(H, W), kWinBlock, 0, st>>>(b, height, H, W, seed, rw_const(T));
-    else k_random_weighted4<K, RowWalk><<<win_grid(H, W), kWinBlock, 0, st>>>(b, height, H, W, seed, rw_const(T));
+    auto go = [&](auto kern, dim3 grid) {
+      kern<<<with_models(grid, models), kWinBlock, 0, st>>>(b, height, H, W, seed, rw_const(T));
+    };
+    if (shape == 4) go(k_random_weighted4<K, RowWalkBlock4<false>, G>, RowWalkBlock4<false>::grid(H, W));
+    else if (shape == 5) go(k_random_weighted4<K, RowWalkBlock2<false>, G>, RowWalkBlock2<false>::grid(H, W));
+    else if (shape == 7) go(k_random_weighted4<K, RowWalkStack2<false>, G>, RowWalkStack2<false>::grid(H, W));
+    else if (shape == 8) go(k_random_weighted4<K, RowWalkStack4<false>, G>, RowWalkStack4<false>::grid(H, W));
+    else go(k_random_weighted4<K, RowWalk, G>, win_grid(H, W));
   }
   else
-    k_random_weighted<K><<<grid_rows(H, W, kGBlock), kGBlock, 0, st>>>(b, height, H, W, seed, rw_const(T));
+    k_random_weighted<K, G><<<with_models(grid_rows(H, W, kGBlock), models), kGBlock, 0, st>>>(b, height, H, W, seed, rw_const(T));
 }
 
 // __slope, graph.cu:270-295.  Threads along the row, a work-group walks a band of rows: the
@@ -360,11 +422,14 @@ static void launch_random_weighted(const RwBatch& b, const float* height, int64_
 // 32-bit index arithmetic throughout (the flow graph holds int32 cell indices, so H * W < 2^31):
 // with int64 rows and columns the kernel was ~150 instructions per cell, most of them the two
 // halves of 64-bit adds, multiplies and conversions — instruction-bound at 3.5 TB/s.
+template <class G = OneGrid>
 __global__ void __launch_bounds__(kGBlock)
     k_slope(float* __restrict__ slope, const float* __restrict__ tensor,
-            const int32_t* __restrict__ flow, int32_t H, int32_t W, Scale2 s) {
+            const int32_t* __restrict__ flow, int32_t H, int32_t W, typename G::Scale scale_of) {
   const int32_t y = static_cast<int32_t>(blockIdx.x) * kGBlock + static_cast<int32_t>(threadIdx.x);
   if (y >= W) return;
+  const Scale2 s = G::scale(scale_of);
+  if (G::kBatch) slope += G::first_cell(H, W), tensor += G::first_cell(H, W), flow += G::first_cell(H, W);
   const float iy = static_cast<float>(y);
   for (int32_t band = static_cast<int32_t>(blockIdx.y); band * kRowBand < H; band += static_cast<int32_t>(gridDim.y)) {
     const int32_t x_end = (band * kRowBand + kRowBand < H) ? band * kRowBand + kRowBand : H;
@@ -398,14 +463,24 @@ __global__ void __launch_bounds__(kGBlock)
 // neighbours in every graph this library makes, and then its value is already in the thread's
 // three-row window — no gather; any other index takes the scalar kernel's general case.  16-byte
 // loads of the flow graph and the tensor, 16-byte stores.
-template <class Walk>
-__global__ void __launch_bounds__(kWinBlock)
+//
+// (The batch form, ModelGrid, of the walks that run at eight waves per SIMD — the band walk at 62 registers, blocks of
+// two rows at 64 — came out two registers dearer, at seven waves: it is held to the eight.  No spills;
+// profiles/flow_batch/kernel_resources.txt.)
+template <class Walk, class G>
+constexpr int slope4_min_waves() {
+  return G::kBatch && (std::is_same_v<Walk, RowWalk> || std::is_same_v<Walk, RowWalkBlock2<false>>) ? 8 : 1;
+}
+template <class Walk, class G = OneGrid>
+__global__ void __launch_bounds__(kWinBlock) __attribute__((amdgpu_waves_per_eu(slope4_min_waves<Walk, G>())))
     k_slope4(float* __restrict__ slope, const float* __restrict__ tensor,
-             const int32_t* __restrict__ flow, int64_t H, int64_t W, Scale2 s) {
+             const int32_t* __restrict__ flow, int64_t H, int64_t W, typename G::Scale scale_of) {
   const WinThread t = Walk::thread(H, W);
   const int32_t iW = static_cast<int32_t>(W), iH = static_cast<int32_t>(H);
   (void)iH;
   SOIL_WIN_WALK(Walk, w, W);
+  const Scale2 s = G::scale(scale_of);
+  if (G::kBatch) slope += G::first_cell(H, W), tensor += G::first_cell(H, W), flow += G::first_cell(H, W);
   SOIL_WIN_ROWS(x, w, tensor, H, W, t) {
     const int32_t n0 = static_cast<int32_t>(x * W + t.y0);
     const int4 f = *reinterpret_cast<const int4*>(flow + n0);  // :282
@@ -467,15 +542,29 @@ struct Acc {  // acc_t, graph.cu:422-427
 // asks its K neighbours n - shift[k] whether they drain into it: same slots, same
 // order, no -1 fill of the K*elem slot array, no scatter, and value = source rides
 // along.
-template <int K, bool TENSOR_DECAY>
+//
+// ModelGrid (soil_accumulate_batch): the launch's grid.z models are one donor graph of `elem` = grid.z H W cells
+// for the rounds.  `graph[d] == n` is asked on indices within the model — an entry that is not one of the cell's
+// neighbours INSIDE its model is no edge, whatever it holds —, the donor written is the index in that one graph,
+// `first + d`, and slot k of cell first + n lives at [k * elem + first + n].
+template <class G>
+__device__ __forceinline__ int64_t donor_cells(int64_t H, int64_t W) {
+  return (G::kBatch ? static_cast<int64_t>(gridDim.z) : 1) * H * W;
+}
+template <int K, bool TENSOR_DECAY, class G = OneGrid>
 __global__ void __launch_bounds__(kGBlock)
     k_donors(int32_t* __restrict__ count, int32_t* __restrict__ donor, float* __restrict__ decay,
              float* __restrict__ value, const int32_t* __restrict__ graph,
              const float* __restrict__ source, const float* __restrict__ decayIn, int64_t H,
              int64_t W) {
   const int64_t y = static_cast<int64_t>(blockIdx.x) * kGBlock + threadIdx.x;
-  const int64_t elem = H * W;
+  const int64_t elem = donor_cells<G>(H, W);
   if (y >= W) return;
+  const int32_t first = static_cast<int32_t>(G::first_cell(H, W));
+  if (G::kBatch) {
+    count += first, donor += first, value += first, graph += first, source += first;
+    if (TENSOR_DECAY) decay += first, decayIn += first;
+  }
   SOIL_ROW_LOOP(x, H) {
     const int64_t n = x * W + y;
     int c = 0;
@@ -492,7 +581,7 @@ __global__ void __launch_bounds__(kGBlock)
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       if (k < c) {
-        donor[k * elem + n] = dn[k];
+        donor[k * elem + n] = first + dn[k];
         if (TENSOR_DECAY) {  // (without a decay tensor every edge's decay is 1: no decay array at all, k_rake_compress)
           const float D = decayIn[dn[k]];
           decay[k * elem + n] = (k < 4) ? D : powf_(D, 1.414f);
@@ -506,14 +595,19 @@ __global__ void __launch_bounds__(kGBlock)
 // eight neighbours a cell asks are compile-time positions of the window, no gathers and no 64-bit
 // index arithmetic per neighbour —, count and value as 16-byte stores.  (The window moves the
 // int32 indices as float bit patterns: loads, shuffles and selects do not touch them.)
-template <int K, bool TENSOR_DECAY, class Walk>
+template <int K, bool TENSOR_DECAY, class Walk, class G = OneGrid>
 __global__ void __launch_bounds__(kWinBlock)
     k_donors4(int32_t* __restrict__ count, int32_t* __restrict__ donor, float* __restrict__ decay,
               float* __restrict__ value, const int32_t* __restrict__ graph,
               const float* __restrict__ source, const float* __restrict__ decayIn, int64_t H,
               int64_t W) {
+  const int32_t first = static_cast<int32_t>(G::first_cell(H, W));
+  if (G::kBatch) {
+    count += first, donor += first, value += first, graph += first, source += first;
+    if (TENSOR_DECAY) decay += first, decayIn += first;
+  }
   const WinThread t = Walk::thread(H, W);
-  const int64_t elem = H * W;
+  const int64_t elem = donor_cells<G>(H, W);
   const int32_t iW = static_cast<int32_t>(W);
   SOIL_WIN_WALK(Walk, w, W);
   SOIL_WIN_ROWS(x, w, reinterpret_cast<const float*>(graph), H, W, t) {
@@ -551,7 +645,7 @@ __global__ void __launch_bounds__(kWinBlock)
 #pragma unroll
         for (int k = 0; k < K; ++k) {
           if (k < ci[c]) {
-            donor[k * elem + n0 + c] = dn[c][k];
+            donor[k * elem + n0 + c] = first + dn[c][k];
             if (TENSOR_DECAY) {
               const float D = decayIn[dn[c][k]];
               decay[k * elem + n0 + c] = (k < 4) ? D : powf_(D, 1.414f);
@@ -745,10 +839,43 @@ __global__ void __launch_bounds__(kGBlock)
 constexpr int kAccLanes = 2;
 constexpr WorkspaceSlot kAccSlot[kAccLanes] = {WS_ACCUMULATE_0, WS_ACCUMULATE_1};
 
+// The donor pass (:552-556) of one grid (OneGrid, `models` 1) or of `models` models on grid.z (ModelGrid): four cells
+// per thread where the planes allow it (`wide`), else a cell per thread.
+// (round 5: blocks of rows on grids whose band walk is under 2048 work-groups, window.hpp win_shape_for —
+// 4096^2, BASELINE config 3: band walk | blocks of four | two rows 143 | 118 | 116 us per realisation)
+template <int K, class G>
+static void launch_donors(const Acc& A, const int32_t* graph, const float* source, const float* decayIn, int64_t H,
+                          int64_t W, bool wide, unsigned models, hipStream_t st) {
+  auto go = [&](auto kern, dim3 grid, int block) {
+    kern<<<with_models(grid, models), block, 0, st>>>(A.count, A.donor, A.decay, A.value, graph, source, decayIn, H, W);
+  };
+  if (!wide) {
+    if (decayIn) go(k_donors<K, true, G>, grid_rows(H, W, kGBlock), kGBlock);
+    else go(k_donors<K, false, G>, grid_rows(H, W, kGBlock), kGBlock);
+    return;
+  }
+  const int shape = win_shape_for(0, 5, H, W);
+  if (shape == 4) {
+    if (decayIn) go(k_donors4<K, true, RowWalkBlock4<false>, G>, RowWalkBlock4<false>::grid(H, W), kWinBlock);
+    else go(k_donors4<K, false, RowWalkBlock4<false>, G>, RowWalkBlock4<false>::grid(H, W), kWinBlock);
+  } else if (shape == 5) {
+    if (decayIn) go(k_donors4<K, true, RowWalkBlock2<false>, G>, RowWalkBlock2<false>::grid(H, W), kWinBlock);
+    else go(k_donors4<K, false, RowWalkBlock2<false>, G>, RowWalkBlock2<false>::grid(H, W), kWinBlock);
+  } else {
+    if (decayIn) go(k_donors4<K, true, RowWalk, G>, win_grid(H, W), kWinBlock);
+    else go(k_donors4<K, false, RowWalk, G>, win_grid(H, W), kWinBlock);
+  }
+}
+
+// One accumulation over a donor graph of `elem` cells, stream-ordered: the donor pass, the control kernel and the
+// rounds.  `models` == 0: the one (H, W) grid of soil_accumulate and soil_multiflow, elem = H W.  `models` >= 1
+// (soil_accumulate_batch, at most kMaxGridZ): that many models of (H, W), one after the other in every plane, as
+// ONE graph of elem = models H W cells whose edges stay inside their models (k_donors<.., ModelGrid>) — the
+// rounds never look at H or W.  The round count is a single model's either way.
 template <int K>
-static int accumulate_impl(float* out, const int32_t* graph, const float* source,
-                           const float* decayIn, int64_t H, int64_t W, hipStream_t st, bool sync = true, int lane = 0) {
-  const int64_t elem = H * W;
+static int rake_run(float* out, const int32_t* graph, const float* source, const float* decayIn, int64_t models,
+                    int64_t H, int64_t W, hipStream_t st, WorkspaceSlot slot) {
+  const int64_t elem = (models > 0 ? models : 1) * H * W;
   auto align = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
   const size_t b1 = align(sizeof(float) * elem), bK = align(sizeof(float) * elem * K);
   void* base = nullptr;
@@ -757,7 +884,7 @@ static int accumulate_impl(float* out, const int32_t* graph, const float* source
   // a work-group's segment of the lists of the listed rounds: its share of the cells, in whole waves
   const size_t seg = ((static_cast<size_t>(elem) + nb - 1) / nb + 255) / 256 * 256;
   const size_t bL = align(sizeof(uint32_t) * seg * nb), bF = align(sizeof(uint32_t) * nb);
-  int rc = workspace_get(kAccSlot[lane], 3 * b1 + 4 * bK + 2 * bL + 2 * bF + 256, &base);
+  int rc = workspace_get(slot, 3 * b1 + 4 * bK + 2 * bL + 2 * bF + 256, &base);
   if (rc != SOIL_OK) return rc;
   char* p = static_cast<char*>(base);
   Acc A, B;
@@ -778,34 +905,14 @@ static int accumulate_impl(float* out, const int32_t* graph, const float* source
   const bool wide = W % 4 == 0 && W >= 4 &&
                     ((reinterpret_cast<uintptr_t>(graph) | reinterpret_cast<uintptr_t>(source) |
                       reinterpret_cast<uintptr_t>(A.value) | reinterpret_cast<uintptr_t>(A.count)) & 15) == 0;
-  if (wide) {  // :552-556
-    // (round 5: blocks of rows on grids whose band walk is under 2048 work-groups, window.hpp win_shape_for —
-    // 4096^2, BASELINE config 3: band walk | blocks of four | two rows 143 | 118 | 116 us per realisation)
-    const int shape = win_shape_for(0, 5, H, W);
-    auto go = [&](auto kern, dim3 grid) {
-      kern<<<grid, kWinBlock, 0, st>>>(A.count, A.donor, A.decay, A.value, graph, source, decayIn, H, W);
-    };
-    if (shape == 4) {
-      if (decayIn) go(k_donors4<K, true, RowWalkBlock4<false>>, RowWalkBlock4<false>::grid(H, W));
-      else go(k_donors4<K, false, RowWalkBlock4<false>>, RowWalkBlock4<false>::grid(H, W));
-    } else if (shape == 5) {
-      if (decayIn) go(k_donors4<K, true, RowWalkBlock2<false>>, RowWalkBlock2<false>::grid(H, W));
-      else go(k_donors4<K, false, RowWalkBlock2<false>>, RowWalkBlock2<false>::grid(H, W));
-    } else {
-      if (decayIn) go(k_donors4<K, true, RowWalk>, win_grid(H, W));
-      else go(k_donors4<K, false, RowWalk>, win_grid(H, W));
-    }
-  }
-  else if (decayIn)
-    k_donors<K, true><<<grid_rows(H, W, kGBlock), kGBlock, 0, st>>>(A.count, A.donor, A.decay, A.value, graph, source,
-                                              decayIn, H, W);
-  else
-    k_donors<K, false><<<grid_rows(H, W, kGBlock), kGBlock, 0, st>>>(A.count, A.donor, A.decay, A.value, graph, source,
-                                               nullptr, H, W);
+  if (models > 0) launch_donors<K, ModelGrid>(A, graph, source, decayIn, H, W, wide, static_cast<unsigned>(models), st);
+  else launch_donors<K, OneGrid>(A, graph, source, decayIn, H, W, wide, 1, st);
   SOIL_LAUNCH_CHECK();
 
+  // (a batch: the rounds of ONE model of (H, W), not of the stacked size — a graph with a cycle does not
+  // converge, and its values are those of the round count)
   const int64_t iter =
-      static_cast<int64_t>(std::ceil(std::log2(static_cast<float>(elem)) / 2.0f));  // :559
+      static_cast<int64_t>(std::ceil(std::log2(static_cast<float>(H * W)) / 2.0f));  // :559
   k_rake_init<<<1, 64, 0, st>>>(flags);  // flags = {1, 0, 0} (a kernel, not a copy from the host's stack: stream-ordered)
   // (Round 4: a variant with two / four / eight cells in flight per thread and the donors' words asked
   // for in batches — three round trips per group of cells instead of four to six per cell — ran at
@@ -865,7 +972,45 @@ static int accumulate_impl(float* out, const int32_t* graph, const float* source
     }
   }
   SOIL_LAUNCH_CHECK();
+  return SOIL_OK;
+}
+
+template <int K>
+static int accumulate_impl(float* out, const int32_t* graph, const float* source,
+                           const float* decayIn, int64_t H, int64_t W, hipStream_t st, bool sync = true, int lane = 0) {
+  if (int rc = rake_run<K>(out, graph, source, decayIn, 0, H, W, st, kAccSlot[lane]); rc != SOIL_OK) return rc;
   if (sync) SOIL_HIP(hipStreamSynchronize(st));  // cudaDeviceSynchronize, graph.cu:564
+  return SOIL_OK;
+}
+
+// Models per chunk of soil_accumulate_batch: as many whole models as keep the rounds on 32-bit offsets
+// (K cells words under 4 GiB) and one donor pass (grid.z), at least one.  SOIL_FLOW_BATCH_CELLS lowers the cap on
+// the cells of a chunk (read per call: the tests reach the chunking with tiny shapes through it).
+template <int K>
+static int64_t flow_batch_models(int64_t cells_per_model) {
+  const char* const e = std::getenv("SOIL_FLOW_BATCH_CELLS");
+  const int64_t cap_env = e ? std::atoll(e) : 0ll;
+  int64_t cap = static_cast<int64_t>(((1ull << 32) / (K * sizeof(float))) - 1);
+  if (cap_env > 0 && cap_env < cap) cap = cap_env;
+  const int64_t per = cap / cells_per_model;
+  return per < 1 ? 1 : (per > kMaxGridZ ? kMaxGridZ : per);
+}
+
+// soil_accumulate_batch: chunks of whole models, each one accumulation over the chunk's cells on `st`, one after
+// the other through the same workspace — a slot of the batch entry's own: it returns with its work in flight, and
+// soil_accumulate on another stream must not find its scratch in use.  A chunk of one model takes the single grid's
+// kernels.
+template <int K>
+static int accumulate_batch_impl(float* out, const int32_t* graph, const float* source, const float* decayIn,
+                                 int64_t B, int64_t H, int64_t W, hipStream_t st) {
+  const int64_t hw = H * W, per = flow_batch_models<K>(hw);
+  for (int64_t b0 = 0; b0 < B; b0 += per) {
+    const int64_t nb = B - b0 < per ? B - b0 : per, at = b0 * hw;
+    if (int rc = rake_run<K>(out + at, graph + at, source + at, decayIn ? decayIn + at : nullptr, nb == 1 ? 0 : nb, H, W,
+                             st, WS_ACCUMULATE_BATCH);
+        rc != SOIL_OK)
+      return rc;
+  }
   return SOIL_OK;
 }
 
@@ -959,7 +1104,7 @@ int soil_slope(float* slope, const float* tensor, const int32_t* flow, int64_t H
     const dim3 grid = shape == 4 ? RowWalkBlock4<false>::grid(H, W) : (shape == 5 ? RowWalkBlock2<false>::grid(H, W) : (shape == 7 ? RowWalkStack2<false>::grid(H, W) : (shape == 8 ? RowWalkStack4<false>::grid(H, W) : win_grid(H, W))));
     k<<<grid, kWinBlock, 0, as_stream(stream)>>>(slope, tensor, flow, H, W, Scale2{scale[0], scale[1]});
   } else
-    k_slope<<<grid_rows(H, W, kGBlock), kGBlock, 0, as_stream(stream)>>>(
+    k_slope<><<<grid_rows(H, W, kGBlock), kGBlock, 0, as_stream(stream)>>>(
         slope, tensor, flow, static_cast<int32_t>(H), static_cast<int32_t>(W), Scale2{scale[0], scale[1]});
   SOIL_LAUNCH_CHECK();
   return SOIL_OK;
@@ -975,6 +1120,145 @@ int soil_accumulate(float* out, const int32_t* graph, const float* source, const
     case SOIL_D8: return accumulate_impl<8>(out, graph, source, decay, H, W, as_stream(stream));
     default: return fail(SOIL_ERR_INVALID_ARGUMENT, "invalid edge enumerator");  // graph.cu:573
   }
+}
+
+// ---- batches of models (soil_hip.h: "flow graphs: batches of models") -------------------------------------
+
+extern "C++" {
+namespace {
+
+// What every batch entry refuses before any device work, under its own name
+int check_flow_batch(const char* what, bool tensors, int64_t B, int64_t H, int64_t W, int edge = SOIL_D8) {
+  const std::string w(what);
+  SOIL_REQUIRE(tensors, w + ": null tensor");
+  SOIL_REQUIRE(B >= 1, w + ": B must be >= 1");
+  SOIL_REQUIRE(H >= 1 && W >= 1, w + ": empty grid");
+  SOIL_REQUIRE(H <= INT32_MAX / W, w + ": a model must have 1..2^31-1 cells (int32 graph)");
+  SOIL_REQUIRE(edge == SOIL_D4 || edge == SOIL_D8, w + ": invalid edge enumerator");
+  return SOIL_OK;
+}
+
+// Host words of a batch entry (B seeds, B scale pairs) on the device: one stream-ordered copy through the host
+// thread's pinned staging (erosion_particles.hip) into workspace slot WS_FLOW_BATCH, valid in stream order until
+// the slot's next use.  The caller's array may go as soon as the entry returns.
+int flow_words_to_device(const void* words, size_t bytes, hipStream_t st, const void** dev) {
+  void* base = nullptr;
+  if (int rc = workspace_get(WS_FLOW_BATCH, bytes, &base); rc != SOIL_OK) return rc;
+  if (int rc = batch_upload(base, words, bytes, st); rc != SOIL_OK) return rc;
+  *dev = base;
+  return SOIL_OK;
+}
+
+inline bool aligned16(std::initializer_list<const void*> ptrs) {
+  uintptr_t all = 0;
+  for (const void* p : ptrs) all |= reinterpret_cast<uintptr_t>(p);
+  return (all & 15) == 0;
+}
+
+// soil_direction_batch / soil_steepest_batch: a launch per kMaxGridZ models
+template <bool STORE_K>
+int steepest_batch(int32_t* out, const float* height, int64_t B, int64_t H, int64_t W, int edge, hipStream_t st) {
+  // (a model's planes start 16-byte aligned when the batch's do: W is a multiple of four)
+  const bool wide = W % 4 == 0 && W >= 4 && aligned16({out, height});
+  for (int64_t b0 = 0; b0 < B; b0 += kMaxGridZ) {
+    const unsigned nb = static_cast<unsigned>(B - b0 < kMaxGridZ ? B - b0 : kMaxGridZ);
+    int32_t* const o = out + b0 * H * W;
+    const float* const h = height + b0 * H * W;
+    const dim3 rows = with_models(grid_rows(H, W, kGBlock), nb);
+    if (edge == SOIL_D4) {
+      if (wide) launch_steepest4<4, STORE_K, ModelGrid>(o, h, H, W, st, nb);
+      else k_steepest<4, STORE_K, ModelGrid><<<rows, kGBlock, 0, st>>>(o, h, H, W);
+    } else {
+      if (wide) launch_steepest4<8, STORE_K, ModelGrid>(o, h, H, W, st, nb);
+      else k_steepest<8, STORE_K, ModelGrid><<<rows, kGBlock, 0, st>>>(o, h, H, W);
+    }
+  }
+  SOIL_LAUNCH_CHECK();
+  return SOIL_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int soil_direction_batch(int32_t* direction, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                         void* stream) {
+  SOIL_DEVICE();
+  if (int rc = check_flow_batch("direction_batch", direction && height, B, H, W, edge); rc != SOIL_OK) return rc;
+  return steepest_batch<true>(direction, height, B, H, W, edge, as_stream(stream));
+}
+
+int soil_steepest_batch(int32_t* graph, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                        void* stream) {
+  SOIL_DEVICE();
+  if (int rc = check_flow_batch("steepest_batch", graph && height, B, H, W, edge); rc != SOIL_OK) return rc;
+  return steepest_batch<false>(graph, height, B, H, W, edge, as_stream(stream));
+}
+
+int soil_random_weighted_batch(int32_t* graph, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                               const uint64_t* seeds, uint64_t offset, float T, void* stream) {
+  SOIL_DEVICE();
+  if (int rc = check_flow_batch("random_weighted_batch", graph && height, B, H, W, edge); rc != SOIL_OK) return rc;
+  SOIL_REQUIRE(seeds, "random_weighted_batch: null seeds");
+  hipStream_t st = as_stream(stream);
+  const void* dev = nullptr;
+  if (int rc = flow_words_to_device(seeds, sizeof(uint64_t) * static_cast<size_t>(B), st, &dev); rc != SOIL_OK)
+    return rc;
+  const uint64_t* const seeds_dev = static_cast<const uint64_t*>(dev);
+  for (int64_t b0 = 0; b0 < B; b0 += kMaxGridZ) {
+    const unsigned nb = static_cast<unsigned>(B - b0 < kMaxGridZ ? B - b0 : kMaxGridZ);
+    RwBatch b{};
+    b.graph[0] = graph + b0 * H * W, b.offset[0] = offset, b.n = 1;
+    if (edge == SOIL_D4) launch_random_weighted<4, ModelGrid>(b, height + b0 * H * W, H, W, seeds_dev + b0, T, st, nb);
+    else launch_random_weighted<8, ModelGrid>(b, height + b0 * H * W, H, W, seeds_dev + b0, T, st, nb);
+  }
+  SOIL_LAUNCH_CHECK();
+  return SOIL_OK;
+}
+
+int soil_slope_batch(float* slope, const float* tensor, const int32_t* flow, int64_t B, int64_t H, int64_t W,
+                     const float* scales, int64_t n_scales, void* stream) {
+  SOIL_DEVICE();
+  if (int rc = check_flow_batch("slope_batch", slope && tensor && flow, B, H, W); rc != SOIL_OK) return rc;
+  SOIL_REQUIRE(scales, "slope_batch: null scales");
+  SOIL_REQUIRE(n_scales == 1 || n_scales == B, "slope_batch: n_scales must be 1 or B");
+  hipStream_t st = as_stream(stream);
+  BatchScale sc{nullptr, Scale2{scales[0], scales[1]}};
+  if (n_scales > 1) {  // (one pair travels as a kernel argument: no copy)
+    const void* dev = nullptr;
+    if (int rc = flow_words_to_device(scales, sizeof(Scale2) * static_cast<size_t>(B), st, &dev); rc != SOIL_OK)
+      return rc;
+    sc.per_model = static_cast<const Scale2*>(dev);
+  }
+  const bool wide = W % 4 == 0 && W >= 4 && aligned16({slope, tensor, flow});
+  for (int64_t b0 = 0; b0 < B; b0 += kMaxGridZ) {
+    const unsigned nb = static_cast<unsigned>(B - b0 < kMaxGridZ ? B - b0 : kMaxGridZ);
+    const int64_t at = b0 * H * W;
+    BatchScale s = sc;
+    if (s.per_model) s.per_model += b0;
+    if (wide) {
+      const int shape = win_shape_for(5, 5, H, W);
+      auto go = [&](auto kern, dim3 grid) {
+        kern<<<with_models(grid, nb), kWinBlock, 0, st>>>(slope + at, tensor + at, flow + at, H, W, s);
+      };
+      if (shape == 4) go(k_slope4<RowWalkBlock4<false>, ModelGrid>, RowWalkBlock4<false>::grid(H, W));
+      else if (shape == 5) go(k_slope4<RowWalkBlock2<false>, ModelGrid>, RowWalkBlock2<false>::grid(H, W));
+      else if (shape == 7) go(k_slope4<RowWalkStack2<false>, ModelGrid>, RowWalkStack2<false>::grid(H, W));
+      else if (shape == 8) go(k_slope4<RowWalkStack4<false>, ModelGrid>, RowWalkStack4<false>::grid(H, W));
+      else go(k_slope4<RowWalk, ModelGrid>, win_grid(H, W));
+    } else
+      k_slope<ModelGrid><<<with_models(grid_rows(H, W, kGBlock), nb), kGBlock, 0, st>>>(
+          slope + at, tensor + at, flow + at, static_cast<int32_t>(H), static_cast<int32_t>(W), s);
+  }
+  SOIL_LAUNCH_CHECK();
+  return SOIL_OK;
+}
+
+int soil_accumulate_batch(float* out, const int32_t* graph, const float* source, const float* decay, int64_t B,
+                          int64_t H, int64_t W, int edge, void* stream) {
+  SOIL_DEVICE();
+  if (int rc = check_flow_batch("accumulate_batch", out && graph && source, B, H, W, edge); rc != SOIL_OK) return rc;
+  return edge == SOIL_D4 ? accumulate_batch_impl<4>(out, graph, source, decay, B, H, W, as_stream(stream))
+                         : accumulate_batch_impl<8>(out, graph, source, decay, B, H, W, as_stream(stream));
 }
 
 // soil_multiflow keeps kAccLanes accumulations in flight (round 6).  The realisations are independent

@@ -54,6 +54,7 @@ the same world extent: the multiscale schedule (erode coarse, resample, erode fi
 (soil_erode_batch_exceedance): the summaries of a heavy-tailed ensemble.
 """
 import ctypes as C
+import math
 import numbers
 import os
 
@@ -667,6 +668,84 @@ class ErosionBatch:
             C.byref(self._planes()), self.B, self.H, self.W, (C.c_float * 6)(*[float(v) for v in items]), out.c_ptr,
             _abi.stream()))
         return out
+
+    # ---- flow routing of every model (soil_hip.h: "flow graphs: batches of models") ----
+
+    def _edge(self, who, edge):
+        from . import soil
+        if edge is None:
+            return soil.d8
+        if isinstance(edge, bool) or edge not in (soil.d4, soil.d8):
+            raise ValueError("ErosionBatch.%s: edge must be d4 or d8, got %r" % (who, edge))
+        return int(edge)
+
+    def _flow_tensor(self, who, what, t, dtype):
+        """`t` must be a (B, H, W) silt tensor of `dtype`, or ValueError."""
+        shape = (self.B, self.H, self.W)
+        if not isinstance(t, silt.tensor) or tuple(t.shape) != shape or t.type is not dtype:
+            got = "%s %r" % (t.type.name, tuple(t.shape)) if isinstance(t, silt.tensor) else type(t).__name__
+            raise ValueError("ErosionBatch.%s: %s must be a %s tensor of shape %r, got %s" % (
+                who, what, dtype.name, shape, got))
+        return t
+
+    def flow(self, kind="steepest", edge=None, T=None, offset=0):
+        """The receiver graph of each model's `height` plane: a (B, H, W) int32 silt GPU tensor whose entries are
+        cell indices within their model (or -1), written by one launch whatever B is.  `kind`: "steepest"
+        (soil_steepest_batch), "direction" (soil_direction_batch: the neighbour's number k instead of its index)
+        or "random_weighted" (soil_random_weighted_batch: model b draws with self.seeds[b] at `offset`, and `T`,
+        the temperature, is required).  `edge` defaults to d8.  An unknown kind, a missing or non-finite T or a
+        bad edge raises ValueError before any device work.  Nothing synchronises."""
+        from . import soil
+        if kind not in ("steepest", "direction", "random_weighted"):
+            raise ValueError("ErosionBatch.flow: kind must be 'steepest', 'direction' or 'random_weighted', got %r" % (kind,))
+        e = self._edge("flow", edge)
+        if kind == "random_weighted":
+            if T is None or isinstance(T, bool) or not isinstance(T, numbers.Real) or not math.isfinite(T):
+                raise ValueError("ErosionBatch.flow: kind 'random_weighted' needs a finite temperature T, got %r" % (T,))
+            if isinstance(offset, bool) or not isinstance(offset, numbers.Integral) or offset < 0:
+                raise ValueError("ErosionBatch.flow: offset must be an integer >= 0, got %r" % (offset,))
+            return soil.random_weighted_batch(self.height, e, self.seeds, int(offset), float(T))
+        return (soil.steepest_batch if kind == "steepest" else soil.direction_batch)(self.height, e)
+
+    def drainage(self, graph=None, source=None, decay=None, edge=None):
+        """What drains through each cell of each model: `source` accumulated down `graph` (soil_accumulate_batch),
+        a (B, H, W) float32 silt GPU tensor.  `graph` defaults to flow(edge=edge); `source` to a plane of ones —
+        the number of upstream cells, the cell itself included —, `source=batch.rainfall` gives a discharge;
+        `decay`: the per-cell factors of accumulate_decay.  A tensor of the wrong shape or dtype raises ValueError
+        before any device work.  Nothing synchronises."""
+        from . import soil
+        e = self._edge("drainage", edge)
+        if graph is not None:
+            self._flow_tensor("drainage", "graph", graph, silt.int32)
+        if source is not None:
+            self._flow_tensor("drainage", "source", source, silt.float32)
+        if decay is not None:
+            self._flow_tensor("drainage", "decay", decay, silt.float32)
+        if graph is None:
+            graph = self.flow(edge=e)
+        if source is None:
+            source = silt.tensor(silt.float32, silt.shape(self.B, self.H, self.W), silt.gpu)
+            silt.set(source, 1.0)
+        return soil.accumulate_batch(graph, source, e, decay)
+
+    def flow_slope(self, graph=None):
+        """The slope of each model's `height` along `graph` (default: flow()), a (B, H, W) float32 silt GPU tensor
+        (soil_slope_batch), with the batch's one scale or model b's own (x, y) of `scales`.  A graph of the wrong
+        shape or dtype, or a wrong count of scales, raises ValueError before any device work."""
+        from . import soil
+        if graph is not None:
+            self._flow_tensor("flow_slope", "graph", graph, silt.int32)
+        if self.scales is not None:
+            try:
+                self._check_scales()
+            except ValueError as e:
+                raise ValueError("ErosionBatch.flow_slope: %s" % e)
+            scale = [[float(s[0]), float(s[1])] for s in self.scales]
+        else:
+            scale = [float(self.scale[0]), float(self.scale[1])]
+        if graph is None:
+            graph = self.flow()
+        return soil.slope_batch(self.height, graph, scale)
 
     def _copy(self, name, b, model, into_batch):
         """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""

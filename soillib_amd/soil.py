@@ -142,6 +142,91 @@ def accumulate_decay(graph, field, decay, edge_):
     return out
 
 
+# ---- the same for B models of one (H, W) in one call (soil_hip.h: "flow graphs: batches of models"; not in the
+# reference): (B, H, W) tensors, model b's slice bit for bit what the single-grid function gives for it alone; a
+# graph entry is an index within its model.  Stream-ordered, nothing synchronises.
+
+def _bhw(t, what):
+    s = tuple(t.shape) if isinstance(t, silt.tensor) else ()
+    if len(s) != 3:
+        raise ValueError("%s: expected a (B, H, W) tensor, got shape %r" % (what, s))
+    return s
+
+
+def _same(t, shape, what):
+    if not isinstance(t, silt.tensor) or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: expected a tensor of shape %r, got %r" % (
+            what, tuple(shape), tuple(t.shape) if isinstance(t, silt.tensor) else type(t).__name__))
+
+
+def direction_batch(height, edge_):
+    """soil_direction_batch: `direction` of each of the B models of a (B, H, W) height tensor."""
+    B, H, W = _bhw(height, "direction_batch: height")
+    ptr = _f(height, "height")
+    out = silt.tensor(silt.int32, silt.shape(B, H, W), silt.gpu)
+    _call("soil_direction_batch", out.c_ptr, ptr, B, H, W, edge_, _abi.stream())
+    return out
+
+
+def steepest_batch(height, edge_):
+    """soil_steepest_batch: `steepest` of each of the B models of a (B, H, W) height tensor."""
+    B, H, W = _bhw(height, "steepest_batch: height")
+    ptr = _f(height, "height")
+    out = silt.tensor(silt.int32, silt.shape(B, H, W), silt.gpu)
+    _call("soil_steepest_batch", out.c_ptr, ptr, B, H, W, edge_, _abi.stream())
+    return out
+
+
+def random_weighted_batch(height, edge_, seeds, offset, T):
+    """soil_random_weighted_batch: model b as `random_weighted(height[b], edge, seeds[b], offset, T)`."""
+    B, H, W = _bhw(height, "random_weighted_batch: height")
+    seeds = [int(v) for v in seeds]
+    if len(seeds) != B:
+        raise ValueError("random_weighted_batch: %d seeds for %d models" % (len(seeds), B))
+    ptr = _f(height, "height")
+    out = silt.tensor(silt.int32, silt.shape(B, H, W), silt.gpu)
+    _call("soil_random_weighted_batch", out.c_ptr, ptr, B, H, W, edge_, (C.c_uint64 * B)(*seeds), int(offset),
+          float(T), _abi.stream())
+    return out
+
+
+def _scale_pairs(scale, B, what):
+    """`scale` — one (sx, sy) pair or B pairs — as (C array of floats, number of pairs)."""
+    try:
+        items = list(scale)
+        pairs = [items] if len(items) == 2 and not hasattr(items[0], "__len__") else [list(p) for p in items]
+        flat = [float(v) for p in pairs for v in p]
+    except (TypeError, ValueError):
+        raise ValueError("%s: scale must be one (sx, sy) pair or %d pairs" % (what, B))
+    if any(len(p) != 2 for p in pairs) or len(pairs) not in (1, B):
+        raise ValueError("%s: scale must be one (sx, sy) pair or %d pairs, got %r" % (what, B, scale))
+    return (C.c_float * len(flat))(*flat), len(pairs)
+
+
+def slope_batch(tensor, flow, scale):
+    """soil_slope_batch: model b as `slope(tensor[b], flow[b], scale)`; `scale` is one pair or B pairs."""
+    B, H, W = _bhw(tensor, "slope_batch: tensor")
+    _same(flow, (B, H, W), "slope_batch: flow")
+    pairs, n = _scale_pairs(scale, B, "slope_batch")
+    t_ptr, f_ptr = _f(tensor, "tensor"), _gpu(flow, silt.int32, "flow")
+    out = silt.tensor(silt.float32, silt.shape(B, H, W), silt.gpu)
+    _call("soil_slope_batch", out.c_ptr, t_ptr, f_ptr, B, H, W, pairs, n, _abi.stream())
+    return out
+
+
+def accumulate_batch(graph, field, edge_, decay=None):
+    """soil_accumulate_batch: model b as `accumulate(graph[b], field[b], edge)`, with `decay` as
+    `accumulate_decay`.  Unlike those it does not synchronise."""
+    B, H, W = _bhw(graph, "accumulate_batch: graph")
+    _same(field, (B, H, W), "accumulate_batch: field")
+    if decay is not None:
+        _same(decay, (B, H, W), "accumulate_batch: decay")
+    g_ptr, f_ptr, d_ptr = _gpu(graph, silt.int32, "graph"), _f(field, "field"), _opt_f(decay, "decay")
+    out = silt.tensor(silt.float32, silt.shape(B, H, W), silt.gpu)
+    _call("soil_accumulate_batch", out.c_ptr, g_ptr, f_ptr, d_ptr, B, H, W, edge_, _abi.stream())
+    return out
+
+
 def fill_depressions(height, edge_=None):
     """Priority-flood surface of a DEM (soil_hip.h: soil_fill_depressions) — the
     conditioning step the reference leaves to pysheds (example/dem_condition.py:35-41)."""
