@@ -166,7 +166,10 @@ int soil_rng_seed(soil_rng* rng, int64_t n, uint64_t seed, uint64_t offset, void
  *                  exponential (the reference's __expf, erosion.cu:134-136,346)
  *   op 9: bits of out[i] = floor_cell(a[i]): floor as int32, saturating, NaN -> INT_MAX
  *   op 10: out[i] = sqrt_rn(a[i]), the particle step's square root; equals op 11 (sqrtf) for
- *                  a[i] >= 2^-96, +0, +inf and NaN */
+ *                  a[i] >= 2^-96, +0, +inf and NaN
+ *   op 12: out[i] = rw_exp2(a[i], b[i]) = v_exp_f32(a[i] * b[i]), the product rounded to fp32 first: the
+ *                  Gibbs weight of soil_random_weighted for a height difference a[i] and the host-made
+ *                  constant b[i] = log2(e) / (|shift| T); the kernel calls the same inline function */
 int soil_selftest_math(float* out, const float* a, const float* b, int64_t n, int op,
                        void* stream);
 
@@ -816,7 +819,11 @@ int soil_steepest(int32_t* graph, const float* height, int64_t H, int64_t W, int
 /* soil::random_weighted — graph.hpp:54, graph.cu:175-195 (__seed :97-101,
  * __random_weighted :103-173), model.cpp:173-175.  Stateless: cell n draws its one uniform in (0, 1]
  * from the Philox4x32-10 block (key seed; counter {offset, n >> 2}), word n & 3 — the reference's
- * curand_init(seed, n, offset) + one curand_uniform per cell, with one block serving four cells. */
+ * curand_init(seed, n, offset) + one curand_uniform per cell, with one block serving four cells.
+ * Temperature: T must be 0 or a normal positive float (FLT_MIN .. FLT_MAX).  T = 0, of either sign, gives the
+ * reference's graph for it, -1 in every cell (each downhill weight is +inf, or 0 for -0).  A subnormal, negative,
+ * NaN or infinite T is refused with SOIL_ERR_INVALID_ARGUMENT before anything else, with or without a device — by
+ * soil_random_weighted_batch and soil_multiflow alike. */
 int soil_random_weighted(int32_t* graph, const float* height, int64_t H, int64_t W, int edge,
                          uint64_t seed, uint64_t offset, float T, void* stream);
 /* soil::slope — graph.hpp:63, graph.cu:297-311 (__slope :270-295), model.cpp:161-163. */
@@ -891,7 +898,7 @@ int soil_workspace_release(void);
  *
  * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, the entry's name in soil_last_error(): a null
  * tensor, null `seeds` or `scales`, B, H or W < 1, H * W > INT32_MAX, n_scales not 1 or B, an invalid `edge`.
- * Without a device: SOIL_ERR_NO_DEVICE. */
+ * Without a device: SOIL_ERR_NO_DEVICE (a temperature soil_random_weighted refuses is refused first). */
 /* soil_direction for B models. */
 int soil_direction_batch(int32_t* direction, const float* height, int64_t B, int64_t H, int64_t W, int edge,
                          void* stream);

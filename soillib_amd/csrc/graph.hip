@@ -5,6 +5,7 @@
 // (graph.cu:345 uses int).  Scratch for accumulate lives in a per-device
 // workspace that is grown on demand and reused, instead of the reference's
 // eight cudaMallocs per call (graph.cu:539-550).
+#include <cfloat>
 #include <mutex>
 #include <unordered_map>
 
@@ -248,12 +249,20 @@ void launch_steepest4(int32_t* out, const float* height, int64_t H, int64_t W, h
 // per neighbour, and the inverse-CDF test `u < CDF[k] / Z` (:160) as `u Z < CDF[k]` — no division.
 // (Round 3 kept the oracle's bits here: eight software exponentials and twenty IEEE divisions per
 // cell, ~570 vector instructions, 0.98 ms at 8192^2 = 7 % of the HBM roofline.)  The oracle keeps the
-// exact statement (expf_, IEEE divisions); the parity tests count the receivers that differ, bound
-// them (a few per million) and check that each of them sits on a CDF edge
-// (tests/test_gpu_parity.py::test_random_weighted_against_the_oracle).
+// exact statement (expf_, IEEE divisions).  tests/test_gpu_random_weighted.py holds the kernel, every cell and bit
+// for bit, to a numpy restatement of rw_cdf / rw_pick below whose weights come from rw_exp2 itself
+// (soil_selftest_math op 12), and bounds the receivers that differ from the oracle's by a tolerance derived per
+// cell from the arithmetic (test_against_the_oracle_with_a_derived_tolerance); the smooth terrains at T = 10 are
+// counted in tests/test_gpu_parity.py::test_flow_maps_bit_exact (util.assert_receivers_close).
+//
+// Temperature.  T = 0 (of either sign) is a definite graph, the reference's: every downhill weight is +inf (or,
+// for -0, zero), Z is inf or 0 and every receiver -1.  A subnormal T overflows the constants where the reference's
+// dE / T may stay finite, a negative T puts the weights where v_exp_f32 and the reference's __expf flush
+// differently, and NaN / inf are no temperature: the entry points refuse all of these (rw_temperature_ok).
 struct RwConst {  // log2(e) / (|shift_k| T) for the straight and the diagonal neighbours
   float straight, diagonal;
 };
+inline bool rw_temperature_ok(float T) { return T == 0.0f || (T >= FLT_MIN && T <= FLT_MAX); }
 inline RwConst rw_const(float T) {
   const double log2e = 1.4426950408889634;
   return RwConst{static_cast<float>(log2e / static_cast<double>(T)),
@@ -269,7 +278,7 @@ __device__ __forceinline__ float rw_cdf(float CDF[K], float hlocal, const float 
   for (int k = 0; k < K; ++k) {
     const float diff = hlocal - hn[k];  // :138 (the division by |shift| is part of the constant)
     // :139 — `dE <= 0 ? 0 : exp(dE / T)`, NaN heights included (NaN <= 0 is false: the weight is NaN)
-    float P = (diff <= 0.0f) ? 0.0f : __builtin_amdgcn_exp2f(diff * (k < 4 ? rc.straight : rc.diagonal));
+    float P = (diff <= 0.0f) ? 0.0f : rw_exp2(diff, k < 4 ? rc.straight : rc.diagonal);
     if (!ok[k]) P = 0.0f;
     CDF[k] = Z + P;  // :140
     Z += P;          // :141
@@ -1076,6 +1085,7 @@ int soil_steepest(int32_t* graph, const float* height, int64_t H, int64_t W, int
 
 int soil_random_weighted(int32_t* graph, const float* height, int64_t H, int64_t W, int edge,
                          uint64_t seed, uint64_t offset, float T, void* stream) {
+  SOIL_REQUIRE(rw_temperature_ok(T), "random_weighted: T must be 0 or a normal positive float");
   SOIL_DEVICE();
   SOIL_REQUIRE(graph && height, "random_weighted: null tensor");
   SOIL_REQUIRE(H > 0 && W > 0 && H * W <= INT32_MAX,
@@ -1196,6 +1206,7 @@ int soil_steepest_batch(int32_t* graph, const float* height, int64_t B, int64_t 
 
 int soil_random_weighted_batch(int32_t* graph, const float* height, int64_t B, int64_t H, int64_t W, int edge,
                                const uint64_t* seeds, uint64_t offset, float T, void* stream) {
+  SOIL_REQUIRE(rw_temperature_ok(T), "random_weighted_batch: T must be 0 or a normal positive float");
   SOIL_DEVICE();
   if (int rc = check_flow_batch("random_weighted_batch", graph && height, B, H, W, edge); rc != SOIL_OK) return rc;
   SOIL_REQUIRE(seeds, "random_weighted_batch: null seeds");
@@ -1293,6 +1304,7 @@ static thread_local FlowLanes t_flow;
 int soil_multiflow(double* sum, const float* height, const float* source, int64_t H, int64_t W,
                    int edge, uint64_t seed, uint64_t k_first, uint64_t k_stride, uint64_t k_end,
                    uint64_t K, float T, void* stream) {
+  SOIL_REQUIRE(rw_temperature_ok(T), "multiflow: T must be 0 or a normal positive float");
   SOIL_DEVICE();
   SOIL_REQUIRE(sum && height && source, "multiflow: null tensor");
   SOIL_REQUIRE(k_stride > 0 && K > 0, "multiflow: stride and realisation count must be positive");

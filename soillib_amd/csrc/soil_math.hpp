@@ -191,6 +191,11 @@ struct QuotWatch {
 // summation order (tests/test_gpu_parity.py, _flux_close).
 __device__ __forceinline__ float att_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504f); }
 
+// The Gibbs weight of random_weighted (graph.hip: rw_cdf): 2^(diff * c), the product rounded to fp32 and then
+// v_exp_f32, with c = log2(e) / (|shift| T) made on the host.  soil_selftest_math op 12 is this function, so the
+// tests' restatement of the kernel takes its weights from the very expression the kernel evaluates.
+__device__ __forceinline__ float rw_exp2(float diff, float c) { return __builtin_amdgcn_exp2f(diff * c); }
+
 // floor(f) as an integer in one instruction (v_cvt_flr_i32_f32), saturating at the int32 range
 // — for a position inside the grid the same cell as the reference's float -> int truncation
 // (erosion_map.cu:42-47), and for one outside of it an index an unsigned comparison against the grid

@@ -693,8 +693,9 @@ class ErosionBatch:
         cell indices within their model (or -1), written by one launch whatever B is.  `kind`: "steepest"
         (soil_steepest_batch), "direction" (soil_direction_batch: the neighbour's number k instead of its index)
         or "random_weighted" (soil_random_weighted_batch: model b draws with self.seeds[b] at `offset`, and `T`,
-        the temperature, is required).  `edge` defaults to d8.  An unknown kind, a missing or non-finite T or a
-        bad edge raises ValueError before any device work.  Nothing synchronises."""
+        the temperature, is required: 0 or a normal positive float32, soil.valid_temperature).  `edge` defaults to
+        d8.  An unknown kind, a missing or refused T or a bad edge raises ValueError before any device work.  Nothing
+        synchronises."""
         from . import soil
         if kind not in ("steepest", "direction", "random_weighted"):
             raise ValueError("ErosionBatch.flow: kind must be 'steepest', 'direction' or 'random_weighted', got %r" % (kind,))
@@ -702,6 +703,8 @@ class ErosionBatch:
         if kind == "random_weighted":
             if T is None or isinstance(T, bool) or not isinstance(T, numbers.Real) or not math.isfinite(T):
                 raise ValueError("ErosionBatch.flow: kind 'random_weighted' needs a finite temperature T, got %r" % (T,))
+            if not soil.valid_temperature(T):
+                raise ValueError("ErosionBatch.flow: T must be 0 or a normal positive float32, got %r" % (T,))
             if isinstance(offset, bool) or not isinstance(offset, numbers.Integral) or offset < 0:
                 raise ValueError("ErosionBatch.flow: offset must be an integer >= 0, got %r" % (offset,))
             return soil.random_weighted_batch(self.height, e, self.seeds, int(offset), float(T))

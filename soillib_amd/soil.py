@@ -9,6 +9,7 @@ timer).  Every op forwards to the C ABI (include/soil_hip.h); tensors are
 silt::error::mismatch_host in the reference (graph.cu:75-76).
 """
 import ctypes as C
+import math
 import time
 
 import numpy as np
@@ -106,8 +107,15 @@ def steepest(height, edge_):
     return out
 
 
+def valid_temperature(T):
+    """Whether soil_random_weighted, soil_random_weighted_batch and soil_multiflow take `T` (soil_hip.h): as a
+    float32 it is 0 or a normal positive number.  They refuse anything else (ValueError here)."""
+    t = C.c_float(float(T)).value
+    return t == 0.0 or 2.0 ** -126 <= t < math.inf
+
+
 def random_weighted(height, edge_, seed, offset, T):
-    """model.cpp:173-175 -> soil::random_weighted (graph.cu:175-195)."""
+    """model.cpp:173-175 -> soil::random_weighted (graph.cu:175-195).  T: see valid_temperature."""
     H, W = _hw(height)
     out = silt.tensor(silt.int32, silt.shape(H, W), silt.gpu)
     _call("soil_random_weighted", out.c_ptr, _f(height, "height"), H, W, edge_, int(seed),

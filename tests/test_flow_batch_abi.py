@@ -213,3 +213,41 @@ def test_the_entry_points_fail_loudly_without_a_device():
     assert lib.soil_random_weighted_batch(None, None, 2, 8, 8, _abi.D8, seeds, 0, 10.0, None) == _abi.SOIL_ERR_NO_DEVICE
     assert lib.soil_slope_batch(None, None, None, 2, 8, 8, scales, 2, None) == _abi.SOIL_ERR_NO_DEVICE
     assert lib.soil_accumulate_batch(None, None, None, None, 2, 8, 8, _abi.D8, None) == _abi.SOIL_ERR_NO_DEVICE
+
+
+# ---- the temperature of random_weighted: refused before anything else, device or none (soil_hip.h) ----
+
+def _with_temperature(lib, T):
+    """(name, return code, last error) of the three entries that take a temperature, on null tensors."""
+    seeds = (C.c_uint64 * 2)(1, 2)
+    calls = {"soil_random_weighted": lambda: lib.soil_random_weighted(None, None, 8, 8, 1, 0, 0, T, None),
+             "soil_random_weighted_batch": lambda: lib.soil_random_weighted_batch(None, None, 2, 8, 8, 1, seeds, 0, T, None),
+             "soil_multiflow": lambda: lib.soil_multiflow(None, None, None, 8, 8, 1, 0, 0, 1, 2, 2, T, None)}
+    return [(name, call(), lib.soil_last_error().decode()) for name, call in calls.items()]
+
+
+@pytest.mark.parametrize("T", [-1.0, -1e-30, float("nan"), float("inf"), float("-inf"), 1e-39, -1e-45, 1e39])
+def test_a_temperature_outside_the_range_is_refused(T):
+    from soillib_amd import _abi, soil
+    assert not soil.valid_temperature(T)
+    for name, rc, msg in _with_temperature(_abi.lib(), T):
+        assert rc == _abi.SOIL_ERR_INVALID_ARGUMENT, (name, rc)
+        assert msg == "%s: T must be 0 or a normal positive float" % name[len("soil_"):], msg
+    with pytest.raises(ValueError, match=r"ErosionBatch\.flow: T must be|ErosionBatch\.flow: kind 'random_weighted' needs"):
+        _batch_without_a_device().flow(kind="random_weighted", T=T)
+
+
+@pytest.mark.parametrize("T", [0.0, -0.0, 2.0 ** -126, 10.0, 3.4028234663852886e38])
+def test_a_temperature_inside_the_range_passes_the_check(T):
+    from soillib_amd import _abi, soil
+    assert soil.valid_temperature(T)
+    for name, rc, msg in _with_temperature(_abi.lib(), T):
+        assert rc in (_abi.SOIL_ERR_NO_DEVICE, _abi.SOIL_ERR_INVALID_ARGUMENT), (name, rc)     # no device, or the null tensors
+        assert "T must be" not in msg, msg
+
+
+def test_the_header_states_the_temperature_rule():
+    text = _squash(re.sub(r"\n \* ?", "\n", _header()))
+    for phrase in ("T must be 0 or a normal positive float", "-1 in every cell",
+                   "with or without a device", "soil_random_weighted_batch and soil_multiflow alike"):
+        assert phrase in text, phrase

@@ -167,7 +167,8 @@ def test_random_weighted_receivers_at_2048(hip, oracle):
     dem_multiflow.py (heights of ~100 m, T = 10, D8), 4.2 M cells, two draws.  The receivers are equal
     but for a counted few, each of them a draw on a CDF edge (util.assert_receivers_close).
     (Widths that are not a multiple of four take the one-cell-per-thread kernel — the same operations on
-    the same values: tests/test_gpu_parity.py::test_flow_maps_bit_exact runs both.)"""
+    the same values: tests/test_gpu_random_weighted.py::test_both_kernels_on_the_same_data holds both to one
+    restatement on the same planes, and tests/test_gpu_parity.py::test_flow_maps_bit_exact runs both.)"""
     from soillib_amd import silt, soil
     from util import assert_receivers_close
     S = 2048
