@@ -63,6 +63,9 @@ def _declare(l):
     l.orc_log2f.argtypes = [C.c_float]
     l.orc_powf.restype = C.c_float
     l.orc_powf.argtypes = [C.c_float, C.c_float]
+    for f in (l.orc_fmaxf, l.orc_fminf):
+        f.restype = C.c_float
+        f.argtypes = [C.c_float, C.c_float]
     l.orc_stepsize.restype = C.c_float
     l.orc_stepsize.argtypes = [C.c_float] * 4
     l.orc_accumulate.restype = C.c_int
@@ -156,6 +159,15 @@ def powf(x, y):
     x, y = np.broadcast_arrays(np.asarray(x, np.float32), np.asarray(y, np.float32))
     return np.array([lib().orc_powf(float(a), float(b)) for a, b in zip(x.ravel(), y.ravel())],
                     np.float32).reshape(x.shape)
+
+
+def fmaxf(a, b):
+    """The cell phase's maximum (soil_oracle.c: orc_fmaxf): a NaN operand loses, -0 < +0."""
+    return np.float32(lib().orc_fmaxf(float(a), float(b)))
+
+
+def fminf(a, b):
+    return np.float32(lib().orc_fminf(float(a), float(b)))
 
 
 def philox(ctr, key):

@@ -236,6 +236,24 @@ float orc_stepsize(float px, float py, float dx, float dy) {
   return 0.5f * (tx + ty);
 }
 
+/* fmaxf / fminf as the reference's device code has them (CUDA: a NaN operand loses to the other one, and
+ * -0 orders below +0), spelt out: the C standard leaves the order of the two zeros open, and glibc returns its
+ * second operand, fmaxf(+0, -0) = -0.  The product's v_max_f32 / v_min_f32 follow the device rule.  Used
+ * throughout the cell phase (orc_glocal, orc_mass_transfer, orc_mass_creep), where a flat cell that nothing
+ * visited clamps an exact +0 against the -0 of `-0.25f * L * slope` (erosion.cu:527). */
+float orc_fmaxf(float a, float b) {
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == 0.0f && b == 0.0f) return signbit(a) ? b : a;
+  return a > b ? a : b;
+}
+float orc_fminf(float a, float b) {
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == 0.0f && b == 0.0f) return signbit(a) ? a : b;
+  return a < b ? a : b;
+}
+
 /* layers of global cell (gx, y) in a slab-local buffer; erosion_map.cu:99-105 */
 static float orc_height(const float* layers, const orc_domain* d, int64_t gx, int64_t y) {
   const int64_t i = (gx - d->x0) * d->W + y;
@@ -253,16 +271,16 @@ void orc_glocal(const float* layers, const orc_domain* d, const float scale[3], 
 
   float gxn = (h - hn0) * scale[2] / scale[0]; /* :131-133 */
   if (isnan(gxn)) gxn = exitSlope;
-  else gxn = fmaxf(gxn, 0.0f);
+  else gxn = orc_fmaxf(gxn, 0.0f);
   float gyn = (h - h0n) * scale[2] / scale[1]; /* :135-137 */
   if (isnan(gyn)) gyn = exitSlope;
-  else gyn = fmaxf(gyn, 0.0f);
+  else gyn = orc_fmaxf(gyn, 0.0f);
   float gxp = (hp0 - h) * scale[2] / scale[0]; /* :139-141 */
   if (isnan(gxp)) gxp = -exitSlope;
-  else gxp = fminf(gxp, 0.0f);
+  else gxp = orc_fminf(gxp, 0.0f);
   float gyp = (h0p - h) * scale[2] / scale[1]; /* :143-145 */
   if (isnan(gyp)) gyp = -exitSlope;
-  else gyp = fminf(gyp, 0.0f);
+  else gyp = orc_fminf(gyp, 0.0f);
 
   float gx_ = 0.0f; /* :149-155 (device abs on floats == fabsf) */
   if (fabsf(gxn) > fabsf(gx_)) gx_ = gxn;
@@ -751,21 +769,21 @@ void orc_mass_transfer(float* deltas, const float* layers, const float* upliftBa
 
       const float debrisHeight = debris[n];                                            /* :509 */
       const float excessSlope = slope - param->critSlopeBedrock;                       /* :510 */
-      const float shearLandslide = fmaxf(0.0f, kL * excessSlope);                      /* :511 */
+      const float shearLandslide = orc_fmaxf(0.0f, kL * excessSlope);                  /* :511 */
       const float shearYield = g * (debrisHeight * excessSlope - tau_y);               /* :512 */
-      const float suspendDebris = shearLandslide + kds * fmaxf(0.0f, shearYield);      /* :513 */
-      const float depositDebris = fminf(debrisHeight, fmaxf(0.0f, -kdd * shearYield)); /* :514 */
+      const float suspendDebris = shearLandslide + kds * orc_fmaxf(0.0f, shearYield);  /* :513 */
+      const float depositDebris = orc_fminf(debrisHeight, orc_fmaxf(0.0f, -kdd * shearYield)); /* :514 */
 
       float transfer = dt * (deposit - suspend + depositDebris - suspendDebris); /* :526 */
-      transfer = fmaxf(transfer, -0.25f * L * slope);                            /* :527 */
-      transfer = fminf(transfer, 0.25f * L * 0.3f);                              /* :528 */
+      transfer = orc_fmaxf(transfer, -0.25f * L * slope);                        /* :527 */
+      transfer = orc_fminf(transfer, 0.25f * L * 0.3f);                          /* :528 */
 
       const float layer_y = layers[2 * n + 1]; /* :530 */
       float dx_ = deltas[2 * n], dy_ = deltas[2 * n + 1]; /* :531 */
       dx_ += dt * uplift / scale[2];                      /* :532 */
-      dy_ += fmaxf(0.0f, transfer / scale[2]);            /* :533 */
+      dy_ += orc_fmaxf(0.0f, transfer / scale[2]);        /* :533 */
       if (transfer < 0.0f) {                              /* :535-545 */
-        const float limited = fmaxf(-layer_y * scale[2], transfer);
+        const float limited = orc_fmaxf(-layer_y * scale[2], transfer);
         dy_ += limited / scale[2];
         transfer -= limited;
         dx_ += transfer / scale[2];
@@ -779,15 +797,15 @@ void orc_mass_transfer(float* deltas, const float* layers, const float* upliftBa
         if (layer_y == 0.0f) {                               /* :558-559 */
           for (int c = 0; c < 3; ++c) albedo_surface[3 * n + c] = albedo_bedrock[3 * n + c];
         } else if (totalHeight > 0.0f && transfer > eps) { /* :560 */
-          const float wMass = fminf(massHeight / totalHeight, 1.0f); /* :562 */
-          const float wSurf = fminf(mixDepth, layer_y * scale[2]);   /* :566 */
-          const float wTrsp = fmaxf(eps, transfer);                  /* :567 */
-          const float w = fminf(wTrsp / (wTrsp + wSurf), 1.0f);      /* :568 */
+          const float wMass = orc_fminf(massHeight / totalHeight, 1.0f); /* :562 */
+          const float wSurf = orc_fminf(mixDepth, layer_y * scale[2]); /* :566 */
+          const float wTrsp = orc_fmaxf(eps, transfer);              /* :567 */
+          const float w = orc_fminf(wTrsp / (wTrsp + wSurf), 1.0f);  /* :568 */
           for (int c = 0; c < 3; ++c) {
-            const float colorTransport = fminf(
+            const float colorTransport = orc_fminf(
                 wMass * albedoFluxFluvial[3 * n + c] + (1.0f - wMass) * albedoFluxDebris[3 * n + c],
                 1.0f);                                                   /* :563 */
-            const float colorSurface = fminf(albedo_surface[3 * n + c], 1.0f); /* :564 */
+            const float colorSurface = orc_fminf(albedo_surface[3 * n + c], 1.0f); /* :564 */
             albedo_surface[3 * n + c] = w * colorTransport + (1.0f - w) * colorSurface; /* :569-570 */
           }
         }
@@ -803,7 +821,7 @@ static float orc_creep_T(float lbx, float lby, float ltx, float lty, float dx, f
   const float hb = (lbx + lby) * sz;
   const float ht = (ltx + lty) * sz;
   const float tmax = 0.5f * ((ht - hb) - critSlope * dx);
-  return fmaxf(0.0f, fminf(lty * sz, tmax));
+  return orc_fmaxf(0.0f, orc_fminf(lty * sz, tmax));
 }
 
 /* __mass_creep, erosion.cu:633-710 */

@@ -57,6 +57,8 @@ void orc_param_default(orc_param* p);
 float orc_expf(float x);
 float orc_log2f(float x);
 float orc_powf(float x, float y);
+float orc_fmaxf(float a, float b); /* the device rule: a NaN operand loses, -0 < +0 (the cell phase) */
+float orc_fminf(float a, float b);
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 uint32_t orc_rng_next(orc_rng* state, uint64_t subsequence);
 float orc_rng_uniform(orc_rng* state, uint64_t subsequence);

@@ -86,7 +86,7 @@ KNOBS = {
     # ---- cells, stencils, graph
     "SOIL_QUANTILE_PATH": ("summaries", "auto | reg | lds | bisect: the path of soil_erode_batch_quantiles (registers: B <= 64, taken unforced up to 16; LDS: B <= 256; bisection: any B; the same bytes on every path); a path forced at a B it cannot hold is refused; read per call [auto]"),
     "SOIL_CELLS_VARIANT": ("cells", "A/B variants of the fused cell kernel's launch (tools/bench_cells.py) [0]"),
-    "SOIL_CELLS_NT": ("cells", "1: non-temporal accesses in the fused cell kernel (measured slower; A/B)"),
+    "SOIL_CELLS_NT": ("cells", "1: non-temporal accesses in the one-kernel cell phase (with `SOIL_CELLS_SPLIT=0` or a re-zeroing `SOIL_CELLS_VARIANT`; the default split and `SOIL_CELLS_KEEP_FLUX` run the plain 84-byte kernel whatever it says; measured slower; A/B)"),
     "SOIL_CELLS_SPLIT": ("cells", "0: an eager step's cell phase as one 112-byte kernel instead of the 84-byte kernel + a zeroing pass"),
     "SOIL_WIN_SHAPE": ("stencils", "0..8: force the row-window walk of the four-cells-per-thread kernels (window.hpp) [per kernel and grid]"),
     "SOIL_WIN_FLAT_ORDER": ("stencils", "0: the flat window shape in natural block order instead of XCD-contiguous row ranges (A/B)"),
