@@ -280,6 +280,65 @@ inline F accumulate_batch(const silt::tensor_t<int> graph, const F source, const
   return out;
 }
 
+// ---- downstream walks (soil_hip.h: "flow graphs: downstream"; the reference's commented-out `upstream` /
+// `distance`).  `stop`: a default-constructed tensor for no pour points.  Stream-ordered, no synchronisation.
+struct flow_paths_t {
+  silt::tensor_t<int> terminal, steps;
+  F length;
+};
+inline flow_paths_t flow_paths(const silt::tensor_t<int> graph, const edge_t edge, const silt::vec2 scale,
+                               const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  flow_paths_t out{silt::tensor_t<int>(graph.shape(), silt::GPU), silt::tensor_t<int>(graph.shape(), silt::GPU),
+                   F(graph.shape(), silt::GPU)};
+  check(soil_flow_paths(out.terminal.data(), out.steps.data(), out.length.data(), graph.data(), stop.data(),
+                        graph.shape()[0], graph.shape()[1], edge, detail::s2(scale).v, nullptr));
+  return out;
+}
+inline silt::tensor_t<int> basins(const silt::tensor_t<int> graph, const edge_t edge,
+                                  const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  silt::tensor_t<int> out(graph.shape(), silt::GPU);
+  check(soil_flow_paths(out.data(), nullptr, nullptr, graph.data(), stop.data(), graph.shape()[0], graph.shape()[1],
+                        edge, nullptr, nullptr));
+  return out;
+}
+inline F flow_length(const silt::tensor_t<int> graph, const edge_t edge, const silt::vec2 scale,
+                     const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  F out(graph.shape(), silt::GPU);
+  check(soil_flow_paths(nullptr, nullptr, out.data(), graph.data(), stop.data(), graph.shape()[0], graph.shape()[1],
+                        edge, detail::s2(scale).v, nullptr));
+  return out;
+}
+// (B, H, W) tensors; `scales`: one pair for every model, or a pair per model
+inline flow_paths_t flow_paths_batch(const silt::tensor_t<int> graph, const edge_t edge,
+                                     const std::vector<silt::vec2>& scales,
+                                     const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  std::vector<float> pairs;
+  for (const silt::vec2& s : scales) pairs.push_back(s.x), pairs.push_back(s.y);
+  flow_paths_t out{silt::tensor_t<int>(graph.shape(), silt::GPU), silt::tensor_t<int>(graph.shape(), silt::GPU),
+                   F(graph.shape(), silt::GPU)};
+  check(soil_flow_paths_batch(out.terminal.data(), out.steps.data(), out.length.data(), graph.data(), stop.data(),
+                              graph.shape()[0], graph.shape()[1], graph.shape()[2], edge,
+                              pairs.empty() ? nullptr : pairs.data(), static_cast<int64_t>(scales.size()), nullptr));
+  return out;
+}
+inline silt::tensor_t<int> basins_batch(const silt::tensor_t<int> graph, const edge_t edge,
+                                        const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  silt::tensor_t<int> out(graph.shape(), silt::GPU);
+  check(soil_flow_paths_batch(out.data(), nullptr, nullptr, graph.data(), stop.data(), graph.shape()[0],
+                              graph.shape()[1], graph.shape()[2], edge, nullptr, 1, nullptr));
+  return out;
+}
+inline F flow_length_batch(const silt::tensor_t<int> graph, const edge_t edge, const std::vector<silt::vec2>& scales,
+                           const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  std::vector<float> pairs;
+  for (const silt::vec2& s : scales) pairs.push_back(s.x), pairs.push_back(s.y);
+  F out(graph.shape(), silt::GPU);
+  check(soil_flow_paths_batch(nullptr, nullptr, out.data(), graph.data(), stop.data(), graph.shape()[0],
+                              graph.shape()[1], graph.shape()[2], edge, pairs.empty() ? nullptr : pairs.data(),
+                              static_cast<int64_t>(scales.size()), nullptr));
+  return out;
+}
+
 // ---- grad.hpp:11-17, filter.hpp:11 ------------------------------------------------------------
 inline F gradient(const F& tensor, const silt::vec2 scale) {
   F out(silt::shape(tensor.shape()[0], tensor.shape()[1], 2), silt::GPU);

@@ -916,6 +916,58 @@ int soil_slope_batch(float* slope, const float* tensor, const int32_t* flow, int
 int soil_accumulate_batch(float* out, const int32_t* graph, const float* source, const float* decay,
                           int64_t B, int64_t H, int64_t W, int edge, void* stream);
 
+/* ------------------------------------------------- flow graphs: downstream */
+
+/* Where every cell of a receiver graph drains to, how many edges away that is, and how long the way is: basin
+ * labels, flow length to the outlet, and (with a stop plane) the catchment of a pour point.  The reference's binding
+ * names `upstream(tensor, index, target)` and `distance(tensor, index, target)`, commented out and without an
+ * implementation (model.cpp); the definition below is this library's.
+ *
+ * Grid (H, W), cell n = x * W + y, `edge` D4 or D8, `graph` as the calls above make it (any int32 is taken).
+ *
+ * Edge rule — the edges the donor pass of soil_accumulate accepts.  Cell n has an edge to r = graph[n] iff
+ * 0 <= r < H * W and, with (qx, qy) = (r / W, r % W): |qx - x| <= 1 and |qy - y| <= 1, not both differences zero,
+ * and for D4 not both nonzero.  Anything else is no edge and makes the cell a terminal: -1, the cell itself, a
+ * non-neighbour, a diagonal under D4, any other int32 (INT32_MIN, INT32_MAX).  A cell with stop[n] != 0 is a terminal
+ * whatever its graph entry; `stop` is an optional int32 plane of pour points.
+ *
+ * Walk.  The walk of n follows edges from n until it stands on a terminal.  terminal[n] is that cell (n itself for
+ * a terminal), steps[n] the number of edges walked = n_row (only the row changed) + n_col (only the column) + n_diag,
+ * and, in fp64 with one rounding per operation and no contraction, then one round-to-nearest conversion,
+ *     length[n] = (float)(((double)n_row * sx + (double)n_col * sy) + (double)n_diag * dd)
+ * sx, sy the floats of `scale` widened (sx belongs to a row step, as in soil_slope; the values are used as they are)
+ * and dd = sqrt(sx * sx + sy * sy), computed once on the host in double.  A cell whose walk never ends — it is on a
+ * cycle or drains into one — gets terminal = -1, steps = -1, length = NaN (quiet, 0x7fc00000).  Every cell of an
+ * acyclic graph is resolved whatever its path length, up to H * W - 1 edges: ceil(log2(H * W)) pointer-doubling
+ * rounds over 16-byte records (csrc/flow_paths.hip).
+ *
+ * Any of the three outputs may be NULL, `stop` may be NULL; `scale` / `scales` (n_scales pairs, 1 or B) are HOST
+ * arrays read before the call returns, needed only when `length` is asked for (n_scales is checked either way).
+ * Both entries are stream-ordered and do not synchronise (a call that finds its cached scratch too small
+ * synchronises the device before replacing it, as everywhere); a host thread's calls on one device share one cached
+ * scratch block of their own: issue them on ONE stream, or order the streams yourself.
+ *
+ * Batch form: model-major planes; graph, stop and terminal entries are indices WITHIN their model; model b's slice
+ * of every output is bit for bit what soil_flow_paths gives for model b's slices alone, with scales[b] or the one
+ * pair; nothing reaches another model (an entry in another model's numbering is no edge).  Chunks of whole models —
+ * as many as keep 32-bit offsets (16 bytes a cell under 4 GiB) and one init launch (65535), SOIL_FLOW_BATCH_CELLS
+ * lowers the cells of a chunk; a single model above that is a chunk of its own on 64-bit offsets — and per chunk
+ * one init launch, ceil(log2(H * W)) rounds (ONE model's count) and one final launch, whatever B is.  Results do not
+ * depend on the chunking.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): null `graph`, all three outputs null, `length` without `scale`, B, H or W < 1,
+ * H * W > INT32_MAX, n_scales not 1 or B, an invalid `edge`.  Otherwise, without a device: SOIL_ERR_NO_DEVICE. */
+int soil_flow_paths(int32_t* terminal, int32_t* steps, float* length, const int32_t* graph, const int32_t* stop,
+                    int64_t H, int64_t W, int edge, const float scale[2], void* stream);
+int soil_flow_paths_batch(int32_t* terminal, int32_t* steps, float* length, const int32_t* graph,
+                          const int32_t* stop, int64_t B, int64_t H, int64_t W, int edge, const float* scales,
+                          int64_t n_scales, void* stream);
+/* What the calling host thread's last call of soil_flow_paths or soil_flow_paths_batch did, for tests and tuning:
+ * info[0] chunks, info[1] chunks whose init pass took the 16-byte form, info[2] chunks on 64-bit offsets
+ * (SOIL_PATHS_IDX64=1 forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
+int soil_flow_paths_info(int64_t info[4]);
+
 /* ---------------------------------------------------------------- stencils */
 
 /* soil::gradient — grad.hpp:11, grad.cu:89-97 (__gradient :22-87), model.cpp:193-195.  out (H,W,2). */

@@ -18,6 +18,8 @@ from soillib_amd.soil import (accumulate, accumulate_decay, albedo_discharge, al
 from soillib_amd.soil import particle_steps  # noqa: F401
 from soillib_amd.soil import (accumulate_batch, direction_batch, random_weighted_batch, slope_batch,  # noqa: F401
                               steepest_batch)
+from soillib_amd.soil import (basins, basins_batch, flow_length, flow_length_batch, flow_paths,  # noqa: F401
+                              flow_paths_batch, watershed)
 from soillib_amd.io import geotiff, geotiff_meta, mesh, tiff  # noqa: F401  (python/source/io.cpp:20-110)
 from soillib_amd.legacy import (buffer, clamp, data_t, erode, index, map_t, multiply, param_t,  # noqa: F401
                                 resize)

@@ -227,6 +227,10 @@ SIGNATURES = {
     "soil_random_weighted_batch": (cint, [vp, vp, i64, i64, i64, cint, C.POINTER(u64), u64, f32, vp]),
     "soil_slope_batch": (cint, [vp, vp, vp, i64, i64, i64, F3, i64, vp]),
     "soil_accumulate_batch": (cint, [vp, vp, vp, vp, i64, i64, i64, cint, vp]),
+    # downstream walks: terminal / steps / length (any may be NULL), graph, stop (may be NULL); host scale pairs
+    "soil_flow_paths": (cint, [vp, vp, vp, vp, vp, i64, i64, cint, F3, vp]),
+    "soil_flow_paths_batch": (cint, [vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, vp]),
+    "soil_flow_paths_info": (cint, [C.POINTER(i64)]),
     "soil_workspace_release": (cint, []),
     "soil_gradient": (cint, [vp, vp, i64, i64, F3, vp]),
     "soil_negslope": (cint, [vp, vp, i64, i64, F3, vp]),

@@ -65,6 +65,7 @@ enum WorkspaceSlot {
   WS_STATS = 12,         // erosion_stats.hip: the partial records
   WS_FLOW_BATCH = 13,    // graph.hip: a batch entry's seeds or scale pairs
   WS_ACCUMULATE_BATCH = 14,  // graph.hip: soil_accumulate_batch (stream-ordered: not soil_accumulate's slot)
+  WS_FLOW_PATHS = 15,    // flow_paths.hip: soil_flow_paths(_batch): scale records, the two record buffers, lists
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();

@@ -750,6 +750,48 @@ class ErosionBatch:
             graph = self.flow()
         return soil.slope_batch(self.height, graph, scale)
 
+    def _path_scale(self, who):
+        """The batch's one (x, y) scale pair, or model b's own of `scales` (flow_slope's rule)."""
+        if self.scales is not None:
+            try:
+                self._check_scales()
+            except ValueError as e:
+                raise ValueError("ErosionBatch.%s: %s" % (who, e))
+            return [[float(s[0]), float(s[1])] for s in self.scales]
+        return [float(self.scale[0]), float(self.scale[1])]
+
+    def basins(self, graph=None, stop=None, edge=None):
+        """Where each cell of each model drains to along `graph` (default: flow()): a (B, H, W) int32 silt GPU tensor
+        of terminal cells, indices within their model, -1 for a cell on a cycle or draining into one
+        (soil_flow_paths_batch).  `stop`: an optional (B, H, W) int32 plane of pour points.  `edge` as in drainage():
+        the edges a walk takes, d8 by default, which covers every graph flow() makes; with d4 a diagonal entry of
+        `graph` is no edge, and the default graph is flow(edge=d4).  A tensor of the wrong shape or dtype or a bad
+        edge raises ValueError before any device work.  Nothing synchronises."""
+        from . import soil
+        e = self._edge("basins", edge)
+        if graph is not None:
+            self._flow_tensor("basins", "graph", graph, silt.int32)
+        if stop is not None:
+            self._flow_tensor("basins", "stop", stop, silt.int32)
+        if graph is None:
+            graph = self.flow(edge=e)
+        return soil.basins_batch(graph, e, stop)
+
+    def flow_length(self, graph=None, stop=None, edge=None):
+        """The length of each cell's way down `graph` (default: flow()) to its terminal, a (B, H, W) float32 silt GPU
+        tensor (soil_flow_paths_batch; NaN for a cell on a cycle or draining into one), with the batch's one scale or
+        model b's own (x, y) of `scales`, exactly as flow_slope() takes them.  `stop` and `edge` as in basins()."""
+        from . import soil
+        e = self._edge("flow_length", edge)
+        if graph is not None:
+            self._flow_tensor("flow_length", "graph", graph, silt.int32)
+        if stop is not None:
+            self._flow_tensor("flow_length", "stop", stop, silt.int32)
+        scale = self._path_scale("flow_length")
+        if graph is None:
+            graph = self.flow(edge=e)
+        return soil.flow_length_batch(graph, e, scale, stop)
+
     def _copy(self, name, b, model, into_batch):
         """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""
         t, single = getattr(self, name), getattr(model, name)

@@ -8,6 +8,7 @@ timer).  Every op forwards to the C ABI (include/soil_hip.h); tensors are
 `silt` tensors (soillib_amd.silt).  GPU ops given a CPU tensor raise, like
 silt::error::mismatch_host in the reference (graph.cu:75-76).
 """
+import contextlib
 import ctypes as C
 import math
 import time
@@ -233,6 +234,140 @@ def accumulate_batch(graph, field, edge_, decay=None):
     out = silt.tensor(silt.float32, silt.shape(B, H, W), silt.gpu)
     _call("soil_accumulate_batch", out.c_ptr, g_ptr, f_ptr, d_ptr, B, H, W, edge_, _abi.stream())
     return out
+
+
+# ---- downstream walks (soil_hip.h: "flow graphs: downstream"; the reference's commented-out `upstream` and
+# `distance`, model.cpp): where a cell drains to, how many edges away, how long the way.  Stream-ordered.
+
+def _hw2(t, what):
+    s = tuple(t.shape) if isinstance(t, silt.tensor) else ()
+    if len(s) != 2:
+        raise ValueError("%s: expected a (H, W) tensor, got shape %r" % (what, s))
+    return s
+
+
+def _int_plane(t, shape, what):
+    """`t` must be an int32 tensor of `shape`, or ValueError."""
+    _same(t, shape, what)
+    if t.type is not silt.int32:
+        raise ValueError("%s: expected an int32 tensor, got %s" % (what, t.type.name))
+
+
+def _one_pair(scale, what):
+    try:
+        pair = [float(v) for v in scale]
+    except (TypeError, ValueError):
+        raise ValueError("%s: scale must be one (sx, sy) pair, got %r" % (what, scale))
+    if len(pair) != 2:
+        raise ValueError("%s: scale must be one (sx, sy) pair, got %r" % (what, scale))
+    return (C.c_float * 2)(*pair)
+
+
+def _edge_of(edge_, what):
+    if isinstance(edge_, bool) or edge_ not in (d4, d8):
+        raise ValueError("%s: edge must be d4 or d8, got %r" % (what, edge_))
+    return int(edge_)
+
+
+def _flow_paths(who, graph, edge_, scale, stop, want):
+    """soil_flow_paths on a (H, W) graph; `want`: which of (terminal, steps, length) to make."""
+    H, W = _hw2(graph, "%s: graph" % who)
+    e = _edge_of(edge_, who)
+    _int_plane(graph, (H, W), "%s: graph" % who)
+    if stop is not None:
+        _int_plane(stop, (H, W), "%s: stop" % who)
+    pair = _one_pair(scale, who) if want[2] else None
+    g_ptr, s_ptr = _gpu(graph, silt.int32, "graph"), None if stop is None else _gpu(stop, silt.int32, "stop")
+    outs = [silt.tensor(dt, silt.shape(H, W), silt.gpu) if w else None
+            for w, dt in zip(want, (silt.int32, silt.int32, silt.float32))]
+    _call("soil_flow_paths", *[o.c_ptr if o is not None else None for o in outs], g_ptr, s_ptr, H, W, e, pair,
+          _abi.stream())
+    return tuple(outs)
+
+
+def flow_paths(graph, edge_, scale=None, stop=None):
+    """soil_flow_paths: (terminal, steps, length) of every cell's walk down `graph` — the cell it ends on, the
+    number of edges, and the way's length with the (sx, sy) of `scale` (None: no length, the third item is None).
+    `stop`: an optional int32 plane of pour points (non-zero: the walk ends here).  Cells on a cycle, or draining into
+    one, get -1 / -1 / NaN."""
+    return _flow_paths("flow_paths", graph, edge_, scale, stop, (True, True, scale is not None))
+
+
+def basins(graph, edge_, stop=None):
+    """The terminal of every cell's walk (flow_paths): cells with the same value form a basin."""
+    return _flow_paths("basins", graph, edge_, None, stop, (True, False, False))[0]
+
+
+def flow_length(graph, edge_, scale, stop=None):
+    """The length of every cell's way to its terminal (flow_paths)."""
+    return _flow_paths("flow_length", graph, edge_, scale, stop, (False, False, True))[2]
+
+
+def watershed(graph, edge_, cells):
+    """The catchment of the pour points `cells`, a list of (x, y): an int32 (H, W) mask, 1 where the cell's walk —
+    stopped at the pour points — ends on one of them, the points themselves included (the reference's commented-out
+    `upstream`)."""
+    H, W = _hw2(graph, "watershed: graph")
+    try:
+        points = [(int(x), int(y)) for x, y in cells]
+    except (TypeError, ValueError):
+        raise ValueError("watershed: cells must be a list of (x, y) pairs, got %r" % (cells,))
+    if not points or any(not (0 <= x < H and 0 <= y < W) for x, y in points):
+        raise ValueError("watershed: cells must be one or more (x, y) inside the (%d, %d) grid, got %r" % (H, W, cells))
+    _int_plane(graph, (H, W), "watershed: graph")
+    _edge_of(edge_, "watershed")
+    import torch
+    plane = np.zeros((H, W), np.int32)
+    for x, y in points:
+        plane[x, y] = 1
+    stop = silt.tensor.from_numpy(plane).gpu()
+    terminal = basins(graph, edge_, stop)
+    # a walk that ends on a pour point: its terminal carries the stop mark (unresolved cells: -1, no mark) — a gather
+    # in torch, on the stream the library's calls go to
+    with torch.cuda.stream(torch.cuda.ExternalStream(_abi._stream)) if _abi._stream else contextlib.nullcontext():
+        t, marks = terminal.view_torch().view(-1), stop.view_torch().view(-1)
+        mask = torch.where(t >= 0, marks[t.clamp(min=0).long()], torch.zeros_like(t))
+    return silt.tensor.from_torch(mask.view(H, W).contiguous())
+
+
+def _flow_paths_batch(who, graph, edge_, scale, stop, want):
+    B, H, W = _bhw(graph, "%s: graph" % who)
+    e = _edge_of(edge_, who)
+    _int_plane(graph, (B, H, W), "%s: graph" % who)
+    if stop is not None:
+        _int_plane(stop, (B, H, W), "%s: stop" % who)
+    pairs, n = _scale_pairs(scale, B, who) if want[2] else (None, 1)
+    g_ptr, s_ptr = _gpu(graph, silt.int32, "graph"), None if stop is None else _gpu(stop, silt.int32, "stop")
+    outs = [silt.tensor(dt, silt.shape(B, H, W), silt.gpu) if w else None
+            for w, dt in zip(want, (silt.int32, silt.int32, silt.float32))]
+    _call("soil_flow_paths_batch", *[o.c_ptr if o is not None else None for o in outs], g_ptr, s_ptr, B, H, W, e,
+          pairs, n, _abi.stream())
+    return tuple(outs)
+
+
+def flow_paths_batch(graph, edge_, scale=None, stop=None):
+    """soil_flow_paths_batch: model b as `flow_paths(graph[b], edge, scale, stop[b])`; `scale` is one pair or B
+    pairs (None: no length); entries of `graph`, `stop` and the terminals are indices within their model."""
+    return _flow_paths_batch("flow_paths_batch", graph, edge_, scale, stop, (True, True, scale is not None))
+
+
+def basins_batch(graph, edge_, stop=None):
+    """`basins` of each of the B models."""
+    return _flow_paths_batch("basins_batch", graph, edge_, None, stop, (True, False, False))[0]
+
+
+def flow_length_batch(graph, edge_, scale, stop=None):
+    """`flow_length` of each of the B models; `scale` is one pair or B pairs."""
+    return _flow_paths_batch("flow_length_batch", graph, edge_, scale, stop, (False, False, True))[2]
+
+
+def flow_paths_info():
+    """What this thread's last flow_paths / flow_paths_batch call did (soil_flow_paths_info): a dict with the number of
+    `chunks`, of chunks whose init pass took the 16-byte form (`vec_chunks`), of chunks on 64-bit offsets
+    (`idx64_chunks`) and the `rounds` per chunk."""
+    info = (C.c_int64 * 4)()
+    _call("soil_flow_paths_info", info)
+    return dict(zip(("chunks", "vec_chunks", "idx64_chunks", "rounds"), (int(v) for v in info)))
 
 
 def fill_depressions(height, edge_=None):
