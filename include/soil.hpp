@@ -238,6 +238,28 @@ inline F slope(const F tensor, const silt::tensor_t<int> flow, const silt::vec2 
   return out;
 }
 
+// ---- flats and filled lakes (soil_hip.h: "flow graphs: conditioning"): the distance inside a flat to the nearest
+// cell that can drain, and receivers for the terminals of `graph` that walk it down.  flat_distance synchronises.
+inline silt::tensor_t<int> flat_distance(const F height, const edge_t edge) {
+  silt::tensor_t<int> out(height.shape(), silt::GPU);
+  check(soil_flat_distance(out.data(), height.data(), height.shape()[0], height.shape()[1], edge, nullptr));
+  return out;
+}
+inline silt::tensor_t<int> flat_receivers(const silt::tensor_t<int> graph, const F height,
+                                          const silt::tensor_t<int> dist, const edge_t edge) {
+  silt::tensor_t<int> out(graph.shape(), silt::GPU);
+  check(soil_flat_receivers(out.data(), graph.data(), height.data(), dist.data(), graph.shape()[0], graph.shape()[1],
+                            edge, nullptr));
+  return out;
+}
+// `graph`: the receivers to complete (steepest, random_weighted)
+inline silt::tensor_t<int> resolve_flats(const F height, const edge_t edge, const silt::tensor_t<int> graph) {
+  return flat_receivers(graph, height, flat_distance(height, edge), edge);
+}
+inline silt::tensor_t<int> resolve_flats(const F height, const edge_t edge) {
+  return resolve_flats(height, edge, steepest(height, edge));
+}
+
 // ---- the same for B models of one (H, W): (B, H, W) tensors, model-major (soil_hip.h: "flow graphs: batches
 // of models"; no counterpart in the reference).  Stream-ordered, no synchronisation.
 inline silt::tensor_t<int> direction_batch(const F height, const edge_t edge) {

@@ -968,6 +968,61 @@ int soil_flow_paths_batch(int32_t* terminal, int32_t* steps, float* length, cons
  * (SOIL_PATHS_IDX64=1 forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
 int soil_flow_paths_info(int64_t info[4]);
 
+/* ------------------------------------------------ flow graphs: conditioning */
+
+/* Routing across flats and filled lakes.  soil_fill_depressions returns a surface on which every lake is level, and
+ * on a level surface soil_steepest and soil_random_weighted give no receiver (-1 unless a slope is positive): every
+ * cell of a filled lake is a terminal.  The two calls below give such cells receivers, as int32 indices — nothing is
+ * added to the heights.  The reference leaves this step to pysheds too (example/dem_condition.py:35-41,
+ * resolve_flats); the definition is this library's.
+ *
+ * Grid (H, W), cell n = x * W + y, `edge` D4 or D8, the neighbours in the order of the graph calls' tables
+ * (dx, dy) = (-1,0) (0,-1) (0,1) (1,0) (-1,-1) (-1,1) (1,-1) (1,1), the first four for D4.  Heights are compared as
+ * floats: -0 == +0, inf == inf, NaN equals nothing.
+ *
+ * Seed.  A non-NaN cell c is a seed if some neighbour position lies off the grid, or a neighbour is NaN (the two
+ * are the fill's outlet rule), or a neighbour in the grid is strictly lower, h[nb] < h[c].
+ *
+ * Flat distance.  dist[c] = 0 for a seed; otherwise dist[c] = 1 + min dist[nb] over the neighbours in the grid with
+ * h[nb] == h[c] and dist[nb] >= 0; dist[c] = -1 where no such chain reaches a seed (a closed depression, a single
+ * pit) and for NaN cells.  This is the shortest-path distance inside the flat.  It is the only fixed point that can
+ * be reached from "seeds 0, everything else unknown" by updates d(c) <- min(d(c), 1 + d(nb)) that only lower a value:
+ * a value is always the length of a walk from a seed, so it never falls below the distance, and where no update
+ * lowers anything any more every shortest path has been followed.  An iteration in any order therefore ends on the
+ * same integers (csrc/flats.hip: 64 x 64 tiles relaxed in LDS, launches repeated until no tile moved;
+ * SOIL_FLATS_PER_CHECK launches per look at the "changed" word).
+ *
+ * Flat receivers.  out[n] = in[n], except where in[n] < 0 and dist[n] > 0: there out[n] is the index of the first
+ * neighbour k in table order that lies in the grid, has h[nb] == h[n] and dist[nb] == dist[n] - 1.  If no neighbour
+ * qualifies (a dist that does not belong to this height), out[n] stays in[n].  out == in is allowed: a cell reads
+ * only its own graph entry.  Guarantee: if every edge of `in` goes strictly downhill (every graph soil_steepest and
+ * soil_random_weighted make), `out` is acyclic — along an edge the height never rises, and where it stays, dist
+ * falls by one.  On a surface soil_fill_depressions made, every terminal of `out` is a cell on the grid's border or
+ * beside a NaN cell.
+ *
+ * soil_flat_distance and soil_flat_distance_batch synchronise the stream before they return, as
+ * soil_fill_depressions does (the host decides after every few launches whether another is needed).
+ * soil_flat_receivers and soil_flat_receivers_batch are stream-ordered and do not synchronise.
+ *
+ * Batch form: model-major planes; entries of `in`, `out` are indices WITHIN their model; model b's slice is bit for
+ * bit what the single-grid call gives for model b's slices alone (a model's first cell is addressed in int64).  The
+ * models of a batch relax side by side: the launches of a batch are those of the model that needs most, not the sum.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): a null pointer, B, H or W < 1, H * W > INT32_MAX, an invalid `edge`.  Otherwise, without a
+ * device: SOIL_ERR_NO_DEVICE. */
+int soil_flat_distance(int32_t* dist, const float* height, int64_t H, int64_t W, int edge, void* stream);
+int soil_flat_distance_batch(int32_t* dist, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                             void* stream);
+int soil_flat_receivers(int32_t* out, const int32_t* in, const float* height, const int32_t* dist, int64_t H,
+                        int64_t W, int edge, void* stream);
+int soil_flat_receivers_batch(int32_t* out, const int32_t* in, const float* height, const int32_t* dist, int64_t B,
+                              int64_t H, int64_t W, int edge, void* stream);
+/* What the calling host thread's last call of soil_flat_distance or soil_flat_distance_batch did: info[0] relaxation
+ * launches, info[1] tiles of a model, info[2] models, info[3] looks at the "changed" word.  All zero before the
+ * first call; needs no device. */
+int soil_flat_distance_info(int64_t info[4]);
+
 /* ---------------------------------------------------------------- stencils */
 
 /* soil::gradient — grad.hpp:11, grad.cu:89-97 (__gradient :22-87), model.cpp:193-195.  out (H,W,2). */

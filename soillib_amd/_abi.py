@@ -231,6 +231,12 @@ SIGNATURES = {
     "soil_flow_paths": (cint, [vp, vp, vp, vp, vp, i64, i64, cint, F3, vp]),
     "soil_flow_paths_batch": (cint, [vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, vp]),
     "soil_flow_paths_info": (cint, [C.POINTER(i64)]),
+    # flats and filled lakes: dist / out, in, height, dist
+    "soil_flat_distance": (cint, [vp, vp, i64, i64, cint, vp]),
+    "soil_flat_distance_batch": (cint, [vp, vp, i64, i64, i64, cint, vp]),
+    "soil_flat_receivers": (cint, [vp, vp, vp, vp, i64, i64, cint, vp]),
+    "soil_flat_receivers_batch": (cint, [vp, vp, vp, vp, i64, i64, i64, cint, vp]),
+    "soil_flat_distance_info": (cint, [C.POINTER(i64)]),
     "soil_workspace_release": (cint, []),
     "soil_gradient": (cint, [vp, vp, i64, i64, F3, vp]),
     "soil_negslope": (cint, [vp, vp, i64, i64, F3, vp]),

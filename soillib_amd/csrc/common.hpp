@@ -66,6 +66,7 @@ enum WorkspaceSlot {
   WS_FLOW_BATCH = 13,    // graph.hip: a batch entry's seeds or scale pairs
   WS_ACCUMULATE_BATCH = 14,  // graph.hip: soil_accumulate_batch (stream-ordered: not soil_accumulate's slot)
   WS_FLOW_PATHS = 15,    // flow_paths.hip: soil_flow_paths(_batch): scale records, the two record buffers, lists
+  WS_FLATS = 16,         // flats.hip: soil_flat_distance(_batch): the tiles' marks, one mask byte per cell
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();

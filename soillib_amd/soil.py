@@ -380,6 +380,86 @@ def fill_depressions(height, edge_=None):
     return out
 
 
+# ---- flats and filled lakes (soil_hip.h: "flow graphs: conditioning"): on the surface fill_depressions returns every
+# lake cell is a terminal of steepest / random_weighted; these give them receivers, as indices.
+
+def _float_plane(t, shape, what):
+    _same(t, shape, what)
+    if t.type is not silt.float32:
+        raise ValueError("%s: expected a float32 tensor, got %s" % (what, t.type.name))
+
+
+def _flat_distance(who, height, edge_, dims):
+    shape = (_hw2 if dims == 2 else _bhw)(height, "%s: height" % who)
+    e = _edge_of(edge_, who)
+    _float_plane(height, shape, "%s: height" % who)
+    ptr = _f(height, "height")
+    out = silt.tensor(silt.int32, silt.shape(*shape), silt.gpu)
+    _call("soil_flat_distance" + ("" if dims == 2 else "_batch"), out.c_ptr, ptr, *shape, e, _abi.stream())
+    return out
+
+
+def _flat_receivers(who, graph, height, dist, edge_, dims):
+    shape = (_hw2 if dims == 2 else _bhw)(graph, "%s: graph" % who)
+    e = _edge_of(edge_, who)
+    _int_plane(graph, shape, "%s: graph" % who)
+    _float_plane(height, shape, "%s: height" % who)
+    _int_plane(dist, shape, "%s: dist" % who)
+    g, h, d = _gpu(graph, silt.int32, "graph"), _f(height, "height"), _gpu(dist, silt.int32, "dist")
+    out = silt.tensor(silt.int32, silt.shape(*shape), silt.gpu)
+    _call("soil_flat_receivers" + ("" if dims == 2 else "_batch"), out.c_ptr, g, h, d, *shape, e, _abi.stream())
+    return out
+
+
+def flat_distance(height, edge_):
+    """soil_flat_distance: for every cell of a (H, W) DEM the shortest way, over cells of equal height, to a cell that
+    can drain (a neighbour off the grid, NaN or strictly lower): 0 there, -1 where no such way exists and on NaN
+    cells.  int32; synchronises the stream."""
+    return _flat_distance("flat_distance", height, edge_, 2)
+
+
+def flat_receivers(graph, height, dist, edge_):
+    """soil_flat_receivers: a copy of `graph` in which every cell without a receiver (an entry < 0) and with
+    dist > 0 takes the first neighbour, in table order, of equal height and dist one less.  A strictly downhill
+    `graph` (steepest, random_weighted) stays acyclic."""
+    return _flat_receivers("flat_receivers", graph, height, dist, edge_, 2)
+
+
+def resolve_flats(height, edge_, graph=None):
+    """The receiver graph of `height` with its flats routed: flat_receivers of `graph` (None: steepest(height, edge))
+    along flat_distance(height, edge).  On a surface fill_depressions made, the only terminals left are cells on the
+    border or beside NaN cells."""
+    e = _edge_of(edge_, "resolve_flats")
+    dist = _flat_distance("resolve_flats", height, e, 2)
+    return _flat_receivers("resolve_flats", steepest(height, e) if graph is None else graph, height, dist, e, 2)
+
+
+def flat_distance_batch(height, edge_):
+    """flat_distance of each of the B models of a (B, H, W) tensor, side by side (soil_flat_distance_batch)."""
+    return _flat_distance("flat_distance_batch", height, edge_, 3)
+
+
+def flat_receivers_batch(graph, height, dist, edge_):
+    """flat_receivers of each of the B models; entries are indices within their model."""
+    return _flat_receivers("flat_receivers_batch", graph, height, dist, edge_, 3)
+
+
+def resolve_flats_batch(height, edge_, graph=None):
+    """resolve_flats of each of the B models of a (B, H, W) tensor."""
+    e = _edge_of(edge_, "resolve_flats_batch")
+    dist = _flat_distance("resolve_flats_batch", height, e, 3)
+    return _flat_receivers("resolve_flats_batch", steepest_batch(height, e) if graph is None else graph, height, dist,
+                           e, 3)
+
+
+def flat_distance_info():
+    """What this thread's last flat_distance / flat_distance_batch call did (soil_flat_distance_info): a dict with the
+    relaxation `launches`, the `tiles` of a model, the `models` and the `looks` at the "changed" word."""
+    info = (C.c_int64 * 4)()
+    _call("soil_flat_distance_info", info)
+    return dict(zip(("launches", "tiles", "models", "looks"), (int(v) for v in info)))
+
+
 def multiflow(height, source, K, T, edge_=None, seed=0, first=0, stride=1, out=None):
     """Mean of `accumulate(random_weighted(height, edge, seed, k, T), source)` over the
     realisations k = first, first+stride, ... < K, each term divided by K in float32 and
