@@ -360,6 +360,13 @@ inline F flow_length_batch(const silt::tensor_t<int> graph, const edge_t edge, c
                               static_cast<int64_t>(scales.size()), nullptr));
   return out;
 }
+// the fill of each of the B models (soil_fill_depressions_batch); synchronises, as fill_depressions does
+inline F fill_depressions_batch(const F height, const edge_t edge) {
+  F out(height.shape(), silt::GPU);
+  check(soil_fill_depressions_batch(out.data(), height.data(), height.shape()[0], height.shape()[1],
+                                    height.shape()[2], edge, nullptr));
+  return out;
+}
 
 // ---- grad.hpp:11-17, filter.hpp:11 ------------------------------------------------------------
 inline F gradient(const F& tensor, const silt::vec2 scale) {

@@ -855,6 +855,23 @@ int soil_multiflow(double* sum, const float* height, const float* source, int64_
  * level (csrc/conditioning.hip); synchronises the stream. */
 int soil_fill_depressions(float* out, const float* height, int64_t H, int64_t W, int edge,
                           void* stream);
+/* The fill of B models of one (H, W) in one call.  `height` and `out` are model-major (B, H, W) float32; model b's
+ * slice of `out` is, bit for bit, what soil_fill_depressions gives for model b's slice alone.  All models are on the
+ * same level of the pyramid at the same time: the launch grid is tiles x models (whole models per launch, at most
+ * 65535 of them; a larger batch goes in several launches side by side), one "changed" word serves the batch, and a
+ * level ends at the first look that finds no tile of any model moved — a settled model costs its tiles an early
+ * return.  The relaxation passes of a call are those of the model that needs most and do not grow with B.  Scratch:
+ * the slot of soil_fill_depressions (WS_CONDITIONING in csrc/common.hpp; both calls synchronise the stream before
+ * they return, so neither finds the other's data in use).  Refused with SOIL_ERR_INVALID_ARGUMENT before any device
+ * work, with or without a device: a null pointer, out == height, B, H or W < 1, H * W > INT32_MAX, an invalid edge. */
+int soil_fill_depressions_batch(float* out, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                                void* stream);
+/* What the calling host thread's last call of soil_fill_depressions or soil_fill_depressions_batch that got as far as
+ * its first launch did (a call that was refused, found no device or failed to get its scratch leaves the record of the
+ * call before it; one that fails later leaves what it did up to there): info[0] relaxation passes in all (one pass = every tile of every model once), info[1] levels of the
+ * pyramid, info[2] models, info[3] looks at the "changed" word, info[4 + l] passes on level l (0: the DEM itself;
+ * levels beyond the eleventh are added into info[15]).  All zero before the first call; needs no device. */
+int soil_fill_depressions_info(int64_t info[16]);
 /* Scratch memory.  The reference allocates its scratch per call (graph.cu:539-550, :182-183;
  * path.cu:195; filter.cu:77); this library keeps one cached block per host thread, device and
  * purpose (accumulate, the particle launches of either kind, fill_depressions, soil_erode) and

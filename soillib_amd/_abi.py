@@ -210,6 +210,8 @@ SIGNATURES = {
     "soil_particle_steps": (cint, [C.POINTER(u64), cint, vp]),
     "soil_ghost_extent": (cint, [vp, vp, i64, i64, i64, i64, vp]),
     "soil_fill_depressions": (cint, [vp, vp, i64, i64, cint, vp]),
+    "soil_fill_depressions_batch": (cint, [vp, vp, i64, i64, i64, cint, vp]),
+    "soil_fill_depressions_info": (cint, [C.POINTER(i64)]),
     "soil_multiflow": (cint, [vp, vp, vp, i64, i64, cint, u64, u64, u64, u64, u64, f32, vp]),
     "soil_resize": (cint, [vp, vp, i64, i64, i64, i64, cint, vp]),
     "soil_tiff_peek": (cint, [C.c_char_p, vp]),

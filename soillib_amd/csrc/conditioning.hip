@@ -38,6 +38,7 @@
 // tile (16 waves x 4 lines per direction); every tile writes its own "moved" mark (no clearing
 // pass between launches); the first launch of a level makes its start surface itself (no pass
 // over the level for it): 4.0 -> 1.7 ms at 4096^2, 8.1 -> 5.6 ms at 8192^2.
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
@@ -92,13 +93,26 @@ __device__ __forceinline__ float fill_line_pass(float z, float w, float x_in) {
 
 constexpr int kFZ = kFT + 1;  // row stride of the tile's z in LDS (column reads without conflicts)
 
-template <int K>
+// BATCH: the same for the models of a batch, model blockIdx.y of the launch.  Every plane is model-major — the DEM
+// and the surface H * W cells per model, the coarse level's surface Hc * Wc, both sets of marks tiles_h * tiles_w —
+// and every model's offset is taken in int64 (B * H * W passes 2^31 long before a model does).  One `changed` word
+// serves all models.  (One kernel template and not a shared device function: inlined from a function, the single
+// grid's instance took 70 VGPRs for its 63 and lost its second work-group per CU.)  `Hc`, the rows of the coarse
+// level, is read only with BATCH (the stride of `wc` between models); the single grid's instance ignores it.
+template <int K, bool BATCH>
 __global__ void __launch_bounds__(kFRelax)
     k_fill_relax(float* __restrict__ w, const float* __restrict__ z, int64_t H, int64_t W,
                  int tiles_w, int tiles_h, int inner_max, int* __restrict__ changed,
                  const unsigned char* __restrict__ dirty_prev,
                  unsigned char* __restrict__ dirty_next, int first,
-                 const float* __restrict__ wc, int64_t Wc) {
+                 const float* __restrict__ wc, int64_t Wc, int64_t Hc) {
+  if constexpr (BATCH) {
+    const int64_t b = blockIdx.y;
+    const int64_t cells = H * W, marks = static_cast<int64_t>(tiles_w) * tiles_h;
+    w += b * cells, z += b * cells;
+    dirty_prev += b * marks, dirty_next += b * marks;
+    if (wc) wc += b * (Hc * Wc);
+  }
   __shared__ float sw[kFH * kFH];
   __shared__ float sz[kFT * kFZ];
   __shared__ int s_flag, s_any;
@@ -256,9 +270,8 @@ __global__ void __launch_bounds__(kFRelax)
 
 
 // block maxima (NaN cells skipped: leaving an outlet out only raises the start, which stays valid)
-__global__ void __launch_bounds__(kFBlock)
-    k_fill_coarsen(float* __restrict__ zc, const float* __restrict__ z, int64_t H, int64_t W,
-                   int64_t Hc, int64_t Wc) {
+__device__ __forceinline__ void fill_coarsen_cell(float* __restrict__ zc, const float* __restrict__ z, int64_t H,
+                                                  int64_t W, int64_t Hc, int64_t Wc) {
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kFBlock + threadIdx.x;
   if (n >= Hc * Wc) return;
   const int64_t X = n / Wc, Y = n % Wc;
@@ -270,12 +283,34 @@ __global__ void __launch_bounds__(kFBlock)
     }
   zc[n] = m;
 }
+__global__ void __launch_bounds__(kFBlock)
+    k_fill_coarsen(float* __restrict__ zc, const float* __restrict__ z, int64_t H, int64_t W,
+                   int64_t Hc, int64_t Wc) {
+  fill_coarsen_cell(zc, z, H, W, Hc, Wc);
+}
+// model blockIdx.y of the launch: stacked (Hc, Wc) planes from stacked (H, W) planes
+__global__ void __launch_bounds__(kFBlock)
+    k_fill_coarsen_batch(float* __restrict__ zc, const float* __restrict__ z, int64_t H, int64_t W,
+                         int64_t Hc, int64_t Wc) {
+  const int64_t b = blockIdx.y;
+  fill_coarsen_cell(zc + b * (Hc * Wc), z + b * (H * W), H, W, Hc, Wc);
+}
 
-// one level: `out` = fill of `height` (H x W), started from the coarse surface `wc` (or +inf)
+// What the last call of soil_fill_depressions(_batch) on this host thread did (soil_fill_depressions_info)
+constexpr int kFInfoLevels = 12;  // info[4 .. 15]; deeper levels are added into the last
+struct FillInfo {
+  int64_t launches, levels, models, looks, per_level[kFInfoLevels];
+};
+static thread_local FillInfo t_fill_info{};
+
+constexpr int64_t kFModelsPerLaunch = 65535;  // a grid's y extent: a larger batch goes in chunks of whole models
+
+// one level: `out` = fill of `height` (H x W), started from the coarse surface `wc` (or +inf).  `batch`: the same
+// for B stacked planes at once, through the batch kernel (the single grid keeps its own kernel and launches).
 template <int K>
-static int fill_level(float* out, const float* height, int64_t H, int64_t W, const float* wc,
-                      int64_t Wc, unsigned char* dirty_prev, unsigned char* dirty_next, int* flag_host,
-                      int* flag_dev, hipStream_t st) {
+static int fill_level(float* out, const float* height, bool batch, int64_t B, int64_t H, int64_t W, const float* wc,
+                      int64_t Hc, int64_t Wc, size_t level, unsigned char* dirty_prev, unsigned char* dirty_next,
+                      int* flag_host, int* flag_dev, hipStream_t st) {
   const int tiles_w = static_cast<int>((W + kFT - 1) / kFT);
   const int tiles_h = static_cast<int>((H + kFT - 1) / kFT);
   const size_t ntiles = static_cast<size_t>(tiles_w) * tiles_h;
@@ -286,7 +321,7 @@ static int fill_level(float* out, const float* height, int64_t H, int64_t W, con
   // each time, and its kFT^2 cells make at most kFT / 4 stretches of 4 kFT: (4 kFT + kFT / 4) launches per tile
   // bound what any input needs.  (A serpentine corridor of pitch 2 crosses H / 2 * tiles_w seams in series, about
   // 12 000 at 1280^2, where a cap of 4 (tiles_w + tiles_h) kFT = 10 256 launches refused the DEM:
-  // tests/test_gpu_fill_oracle.py.)
+  // tests/test_gpu_fill_oracle.py.)  The models of a batch run side by side: the bound is one model's.
   const int64_t max_launches = static_cast<int64_t>(ntiles) * (4 * kFT + kFT / 4) + 16;
   // (a value below 1 or not a number would skip the launches and return the unrelaxed start)
   static const int per_check = [] {
@@ -295,36 +330,56 @@ static int fill_level(float* out, const float* height, int64_t H, int64_t W, con
     return v >= 1 ? v : 3;
   }();
   static const bool verbose = std::getenv("SOIL_FILL_VERBOSE") != nullptr;
+  const size_t slot = level < kFInfoLevels ? level : kFInfoLevels - 1;
   for (int64_t launch = 0; launch < max_launches; launch += per_check) {
     *flag_host = 0;  // the stream is idle here: the previous launches were waited for
     // several launches per look at the flag: a launch whose predecessor moved nothing costs a
     // few microseconds (every tile returns at once), a host round trip ~20
     for (int k = 0; k < per_check; ++k) {
-      k_fill_relax<K><<<static_cast<unsigned>(ntiles), kFRelax, 0, st>>>(
-          out, height, H, W, tiles_w, tiles_h, 4 * kFT, flag_dev, dirty_prev, dirty_next,
-          launch + k == 0 ? 1 : 0, wc, Wc);
+      if (!batch) {
+        k_fill_relax<K, false><<<static_cast<unsigned>(ntiles), kFRelax, 0, st>>>(
+            out, height, H, W, tiles_w, tiles_h, 4 * kFT, flag_dev, dirty_prev, dirty_next,
+            launch + k == 0 ? 1 : 0, wc, Wc, Hc);
+      } else {
+        // every model of the batch in this launch: a settled model's tiles return at once through its own marks
+        for (int64_t b0 = 0; b0 < B; b0 += kFModelsPerLaunch) {
+          const int64_t nb = B - b0 < kFModelsPerLaunch ? B - b0 : kFModelsPerLaunch;
+          const int64_t marks = b0 * static_cast<int64_t>(ntiles);
+          k_fill_relax<K, true><<<dim3(static_cast<unsigned>(ntiles), static_cast<unsigned>(nb)), kFRelax, 0, st>>>(
+              out + b0 * (H * W), height + b0 * (H * W), H, W, tiles_w, tiles_h, 4 * kFT, flag_dev,
+              dirty_prev + marks, dirty_next + marks, launch + k == 0 ? 1 : 0, wc ? wc + b0 * (Hc * Wc) : nullptr,
+              Wc, Hc);
+        }
+      }
       std::swap(dirty_prev, dirty_next);
     }
     SOIL_LAUNCH_CHECK();
     SOIL_HIP(hipStreamSynchronize(st));
-    if (verbose) std::fprintf(stderr, "[fill] %lld x %lld: launches %lld..%lld moved=%d\n", (long long)H, (long long)W, (long long)launch, (long long)launch + per_check - 1, *flag_host);
+    t_fill_info.launches += per_check, t_fill_info.per_level[slot] += per_check, t_fill_info.looks += 1;
+    if (verbose) {
+      if (batch) std::fprintf(stderr, "[fill] %lld models of ", (long long)B);
+      else std::fprintf(stderr, "[fill] ");
+      std::fprintf(stderr, "%lld x %lld: launches %lld..%lld moved=%d\n", (long long)H, (long long)W, (long long)launch, (long long)launch + per_check - 1, *flag_host);
+    }
     if (!__atomic_load_n(flag_host, __ATOMIC_ACQUIRE)) return SOIL_OK;
   }
-  return fail(SOIL_ERR_HIP, "fill_depressions: did not converge");
+  return fail(SOIL_ERR_HIP, batch ? "fill_depressions_batch: did not converge" : "fill_depressions: did not converge");
 }
 
+// `batch`: B stacked models, all on the same level of the pyramid at the same time; the level's stacked planes live
+// in the workspace (WS_CONDITIONING, shared with the single call: both synchronise before they return).
 template <int K>
-static int fill_impl(float* out, const float* height, int64_t H, int64_t W, hipStream_t st) {
+static int fill_impl(float* out, const float* height, bool batch, int64_t B, int64_t H, int64_t W, hipStream_t st) {
   // the pyramid: level 0 is the DEM itself, level l + 1 the 4x4 (kFC) block maxima of level l
   struct Level { int64_t H, W; size_t off_z, off_w; };
   std::vector<Level> lv{{H, W, 0, 0}};
   auto align = [](size_t b) { return (b + 255) & ~size_t{255}; };
   const size_t ntiles0 = static_cast<size_t>((W + kFT - 1) / kFT) * ((H + kFT - 1) / kFT);
-  const size_t b_dirty = align(ntiles0);
+  const size_t b_dirty = align(ntiles0 * static_cast<size_t>(B));  // (a coarser level has fewer tiles per model)
   size_t bytes = 256 + 2 * b_dirty;
   while (lv.back().H * lv.back().W > 4 * kFT * kFT && std::getenv("SOIL_FILL_FLAT") == nullptr) {
     const int64_t Hc = (lv.back().H + kFC - 1) / kFC, Wc = (lv.back().W + kFC - 1) / kFC;
-    const size_t b = align(sizeof(float) * Hc * Wc);
+    const size_t b = align(sizeof(float) * Hc * Wc * static_cast<size_t>(B));
     lv.push_back({Hc, Wc, bytes, bytes + b});
     bytes += 2 * b;
   }
@@ -333,7 +388,7 @@ static int fill_impl(float* out, const float* height, int64_t H, int64_t W, hipS
   char* ws = static_cast<char*>(base);
   // "some tile moved in this launch": a pinned, device-mapped word the tiles write straight
   // into (a device-to-host copy is a 25-50 us blit kernel on this stack, per launch)
-  // (one per host thread and device)
+  // (one per host thread and device; one for all the models of a batch)
   static thread_local std::map<int, std::pair<int*, int*>> t_flags;
   int dev = 0;
   SOIL_HIP(hipGetDevice(&dev));
@@ -343,19 +398,33 @@ static int fill_impl(float* out, const float* height, int64_t H, int64_t W, hipS
     SOIL_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&fl.second), fl.first, 0));
   }
   int *const t_flag = fl.first, *const t_flag_dev = fl.second;
+  // from here on the call launches: what it does is recorded (a call that failed before this leaves the last record)
+  t_fill_info = FillInfo{};
+  t_fill_info.levels = static_cast<int64_t>(lv.size()), t_fill_info.models = B;
   unsigned char* dirty_a = reinterpret_cast<unsigned char*>(ws) + 256;
   unsigned char* dirty_b = dirty_a + b_dirty;
   auto zc = [&](size_t l) { return l == 0 ? height : reinterpret_cast<const float*>(ws + lv[l].off_z); };
   auto wl = [&](size_t l) { return l == 0 ? out : reinterpret_cast<float*>(ws + lv[l].off_w); };
   for (size_t l = 1; l < lv.size(); ++l) {
-    k_fill_coarsen<<<blocks_for(lv[l].H * lv[l].W, kFBlock), kFBlock, 0, st>>>(
-        reinterpret_cast<float*>(ws + lv[l].off_z), zc(l - 1), lv[l - 1].H, lv[l - 1].W, lv[l].H, lv[l].W);
+    float* const dst = reinterpret_cast<float*>(ws + lv[l].off_z);
+    const unsigned blocks = blocks_for(lv[l].H * lv[l].W, kFBlock);
+    if (!batch) {
+      k_fill_coarsen<<<blocks, kFBlock, 0, st>>>(dst, zc(l - 1), lv[l - 1].H, lv[l - 1].W, lv[l].H, lv[l].W);
+    } else {
+      for (int64_t b0 = 0; b0 < B; b0 += kFModelsPerLaunch) {
+        const int64_t nb = B - b0 < kFModelsPerLaunch ? B - b0 : kFModelsPerLaunch;
+        k_fill_coarsen_batch<<<dim3(blocks, static_cast<unsigned>(nb)), kFBlock, 0, st>>>(
+            dst + b0 * (lv[l].H * lv[l].W), zc(l - 1) + b0 * (lv[l - 1].H * lv[l - 1].W), lv[l - 1].H, lv[l - 1].W,
+            lv[l].H, lv[l].W);
+      }
+    }
     SOIL_LAUNCH_CHECK();
   }
   for (size_t l = lv.size(); l-- > 0;) {  // coarsest first
     const bool top = l + 1 == lv.size();
-    if (int rc = fill_level<K>(wl(l), zc(l), lv[l].H, lv[l].W, top ? nullptr : wl(l + 1),
-                               top ? 0 : lv[l + 1].W, dirty_a, dirty_b, t_flag, t_flag_dev, st);
+    if (int rc = fill_level<K>(wl(l), zc(l), batch, B, lv[l].H, lv[l].W, top ? nullptr : wl(l + 1),
+                               top ? 0 : lv[l + 1].H, top ? 0 : lv[l + 1].W, l, dirty_a, dirty_b, t_flag,
+                               t_flag_dev, st);
         rc != SOIL_OK)
       return rc;
   }
@@ -374,10 +443,31 @@ int soil_fill_depressions(float* out, const float* height, int64_t H, int64_t W,
   SOIL_REQUIRE(out && height && out != height, "fill_depressions: needs distinct in and out tensors");
   SOIL_REQUIRE(H > 0 && W > 0, "fill_depressions: empty grid");
   switch (edge) {
-    case SOIL_D4: return fill_impl<4>(out, height, H, W, as_stream(stream));
-    case SOIL_D8: return fill_impl<8>(out, height, H, W, as_stream(stream));
+    case SOIL_D4: return fill_impl<4>(out, height, false, 1, H, W, as_stream(stream));
+    case SOIL_D8: return fill_impl<8>(out, height, false, 1, H, W, as_stream(stream));
     default: return fail(SOIL_ERR_INVALID_ARGUMENT, "invalid edge enumerator");
   }
+}
+
+int soil_fill_depressions_batch(float* out, const float* height, int64_t B, int64_t H, int64_t W, int edge,
+                                void* stream) {
+  SOIL_REQUIRE(out && height, "fill_depressions_batch: null tensor");
+  SOIL_REQUIRE(out != height, "fill_depressions_batch: needs distinct in and out tensors");
+  SOIL_REQUIRE(B >= 1, "fill_depressions_batch: B must be >= 1");
+  SOIL_REQUIRE(H >= 1 && W >= 1, "fill_depressions_batch: empty grid");
+  SOIL_REQUIRE(H <= INT32_MAX / W, "fill_depressions_batch: a model must have 1..2^31-1 cells");
+  SOIL_REQUIRE(edge == SOIL_D4 || edge == SOIL_D8, "fill_depressions_batch: invalid edge enumerator");
+  SOIL_DEVICE();
+  return edge == SOIL_D4 ? fill_impl<4>(out, height, true, B, H, W, as_stream(stream))
+                         : fill_impl<8>(out, height, true, B, H, W, as_stream(stream));
+}
+
+int soil_fill_depressions_info(int64_t info[16]) {
+  SOIL_REQUIRE(info, "fill_depressions_info: null info");
+  info[0] = t_fill_info.launches, info[1] = t_fill_info.levels;
+  info[2] = t_fill_info.models, info[3] = t_fill_info.looks;
+  for (int l = 0; l < kFInfoLevels; ++l) info[4 + l] = t_fill_info.per_level[l];
+  return SOIL_OK;
 }
 
 }  // extern "C"

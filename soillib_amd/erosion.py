@@ -688,6 +688,16 @@ class ErosionBatch:
                 who, what, dtype.name, shape, got))
         return t
 
+    def _check_draw(self, who, T, offset):
+        """The temperature and the offset of a random_weighted draw, or ValueError."""
+        from . import soil
+        if T is None or isinstance(T, bool) or not isinstance(T, numbers.Real) or not math.isfinite(T):
+            raise ValueError("ErosionBatch.%s: kind 'random_weighted' needs a finite temperature T, got %r" % (who, T))
+        if not soil.valid_temperature(T):
+            raise ValueError("ErosionBatch.%s: T must be 0 or a normal positive float32, got %r" % (who, T))
+        if isinstance(offset, bool) or not isinstance(offset, numbers.Integral) or offset < 0:
+            raise ValueError("ErosionBatch.%s: offset must be an integer >= 0, got %r" % (who, offset))
+
     def flow(self, kind="steepest", edge=None, T=None, offset=0):
         """The receiver graph of each model's `height` plane: a (B, H, W) int32 silt GPU tensor whose entries are
         cell indices within their model (or -1), written by one launch whatever B is.  `kind`: "steepest"
@@ -701,12 +711,7 @@ class ErosionBatch:
             raise ValueError("ErosionBatch.flow: kind must be 'steepest', 'direction' or 'random_weighted', got %r" % (kind,))
         e = self._edge("flow", edge)
         if kind == "random_weighted":
-            if T is None or isinstance(T, bool) or not isinstance(T, numbers.Real) or not math.isfinite(T):
-                raise ValueError("ErosionBatch.flow: kind 'random_weighted' needs a finite temperature T, got %r" % (T,))
-            if not soil.valid_temperature(T):
-                raise ValueError("ErosionBatch.flow: T must be 0 or a normal positive float32, got %r" % (T,))
-            if isinstance(offset, bool) or not isinstance(offset, numbers.Integral) or offset < 0:
-                raise ValueError("ErosionBatch.flow: offset must be an integer >= 0, got %r" % (offset,))
+            self._check_draw("flow", T, offset)
             return soil.random_weighted_batch(self.height, e, self.seeds, int(offset), float(T))
         return (soil.steepest_batch if kind == "steepest" else soil.direction_batch)(self.height, e)
 
@@ -791,6 +796,35 @@ class ErosionBatch:
         if graph is None:
             graph = self.flow(edge=e)
         return soil.flow_length_batch(graph, e, scale, stop)
+
+    def filled(self, edge=None):
+        """The depression-filled surface of every model's `height`: a (B, H, W) float32 silt GPU tensor, model b's
+        plane what soil.fill_depressions gives for it alone (soil_fill_depressions_batch: one call for the batch,
+        launches that do not grow with B).  `edge` defaults to d8.  Synchronises the stream."""
+        from . import soil
+        e = self._edge("filled", edge)
+        return soil.fill_depressions_batch(self.height, e)
+
+    def conditioned(self, kind="steepest", edge=None, T=None, offset=0):
+        """(filled, graph): filled() and the receiver graph of that surface with its flats and lakes routed
+        (soil.resolve_flats_batch), a (B, H, W) int32 tensor of cell indices within their model whose only terminals
+        are cells on the border or beside NaN cells.  `kind`: "steepest" or "random_weighted" — drawn on the filled
+        surface with self.seeds, `T` and `offset` checked as flow() checks them; "direction" is refused, its entries
+        are no indices.  drainage(graph=g), basins(graph=g) and flow_length(graph=g) take this graph as it is: where
+        flow() stops at every closed pit of an eroded model, every cell then drains off the grid.  A bad kind, edge,
+        T or offset raises ValueError before any device work.  Synchronises the stream."""
+        from . import soil
+        if kind not in ("steepest", "random_weighted"):
+            raise ValueError("ErosionBatch.conditioned: kind must be 'steepest' or 'random_weighted' (the entries of "
+                             "'direction' are not indices), got %r" % (kind,))
+        e = self._edge("conditioned", edge)
+        if kind == "random_weighted":
+            self._check_draw("conditioned", T, offset)
+        filled = soil.fill_depressions_batch(self.height, e)
+        graph = None
+        if kind == "random_weighted":
+            graph = soil.random_weighted_batch(filled, e, self.seeds, int(offset), float(T))
+        return filled, soil.resolve_flats_batch(filled, e, graph)
 
     def _copy(self, name, b, model, into_batch):
         """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""

@@ -460,6 +460,54 @@ def flat_distance_info():
     return dict(zip(("launches", "tiles", "models", "looks"), (int(v) for v in info)))
 
 
+# ---- the fill of a batch, and the conditioned drainage graph: fill -> steepest / random_weighted -> resolve_flats
+
+def fill_depressions_batch(height, edge_=None):
+    """fill_depressions of each of the B models of a (B, H, W) float32 tensor in one call
+    (soil_fill_depressions_batch): all models on the same pyramid level at the same time, a launch grid of tiles x
+    models, relaxation passes that do not grow with B.  Returns a new (B, H, W) tensor; synchronises the stream."""
+    shape = _bhw(height, "fill_depressions_batch: height")
+    e = _edge_of(d8 if edge_ is None else edge_, "fill_depressions_batch")
+    _float_plane(height, shape, "fill_depressions_batch: height")
+    ptr = _f(height, "height")
+    out = silt.tensor(silt.float32, silt.shape(*shape), silt.gpu)
+    _call("soil_fill_depressions_batch", out.c_ptr, ptr, *shape, e, _abi.stream())
+    return out
+
+
+def fill_info():
+    """What this thread's last fill_depressions / fill_depressions_batch call did (soil_fill_depressions_info): a dict
+    with the relaxation `launches` (passes over the batch), the pyramid's `levels`, the `models`, the `looks` at the
+    "changed" word and `per_level`, the launches of each level (0: the DEM itself)."""
+    info = (C.c_int64 * 16)()
+    _call("soil_fill_depressions_info", info)
+    v = [int(x) for x in info]
+    return {"launches": v[0], "levels": v[1], "models": v[2], "looks": v[3], "per_level": v[4:4 + min(v[1], 12)]}
+
+
+def condition(height, edge_=None):
+    """A (H, W) DEM made ready for routing: (filled, graph) with filled = fill_depressions(height, edge) and graph =
+    resolve_flats(filled, edge), the steepest graph of the filled surface with its flats and lakes routed."""
+    shape = _hw2(height, "condition: height")
+    e = _edge_of(d8 if edge_ is None else edge_, "condition")
+    _float_plane(height, shape, "condition: height")
+    filled = fill_depressions(height, e)
+    return filled, resolve_flats(filled, e)
+
+
+def condition_batch(height, edge_=None, graph=None):
+    """`condition` of each of the B models of a (B, H, W) tensor.  `graph`: the receivers to complete instead of
+    steepest_batch's — a caller who wants a random_weighted graph routed across the lakes makes it on the filled
+    surface (fill_depressions_batch) and passes it here."""
+    shape = _bhw(height, "condition_batch: height")
+    e = _edge_of(d8 if edge_ is None else edge_, "condition_batch")
+    _float_plane(height, shape, "condition_batch: height")
+    if graph is not None:
+        _int_plane(graph, shape, "condition_batch: graph")
+    filled = fill_depressions_batch(height, e)
+    return filled, resolve_flats_batch(filled, e, graph)
+
+
 def multiflow(height, source, K, T, edge_=None, seed=0, first=0, stride=1, out=None):
     """Mean of `accumulate(random_weighted(height, edge, seed, k, T), source)` over the
     realisations k = first, first+stride, ... < K, each term divided by K in float32 and
