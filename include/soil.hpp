@@ -360,6 +360,53 @@ inline F flow_length_batch(const silt::tensor_t<int> graph, const edge_t edge, c
                               static_cast<int64_t>(scales.size()), nullptr));
   return out;
 }
+
+// ---- downstream sums (soil_hip.h: "flow graphs: downstream sums"): x[n] = a[n] L(n) + b[n] x[r(n)] down a receiver
+// graph, x = t on the terminals.  `a`, `b`, `t`, `stop`: default-constructed tensors for 1, 1, 0 and no pour points;
+// `scale` null: L = 1.  Stream-ordered, no synchronisation.
+inline F downstream(const silt::tensor_t<int> graph, const edge_t edge, const F a = F(), const F b = F(),
+                    const F t = F(), const silt::vec2* scale = nullptr,
+                    const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  F out(graph.shape(), silt::GPU);
+  check(soil_downstream(out.data(), nullptr, graph.data(), a.data(), b.data(), t.data(), stop.data(),
+                        graph.shape()[0], graph.shape()[1], edge, scale ? detail::s2(*scale).v : nullptr, nullptr));
+  return out;
+}
+// (B, H, W) tensors; `scales`: none (L = 1), one pair for every model, or a pair per model
+inline F downstream_batch(const silt::tensor_t<int> graph, const edge_t edge, const F a = F(), const F b = F(),
+                          const F t = F(), const std::vector<silt::vec2>& scales = {},
+                          const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  std::vector<float> pairs;
+  for (const silt::vec2& s : scales) pairs.push_back(s.x), pairs.push_back(s.y);
+  F out(graph.shape(), silt::GPU);
+  check(soil_downstream_batch(out.data(), nullptr, graph.data(), a.data(), b.data(), t.data(), stop.data(),
+                              graph.shape()[0], graph.shape()[1], graph.shape()[2], edge,
+                              pairs.empty() ? nullptr : pairs.data(),
+                              scales.empty() ? 1 : static_cast<int64_t>(scales.size()), nullptr));
+  return out;
+}
+// One implicit stream-power step (slope exponent 1): the new heights.  `erosivity` = K A^m, made by the caller;
+// `uplift`: a default-constructed tensor for none.
+inline F stream_power(const F height, const silt::tensor_t<int> graph, const F erosivity, const edge_t edge,
+                      const silt::vec2 scale, const double dt, const F uplift = F(),
+                      const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  F out(graph.shape(), silt::GPU);
+  check(soil_stream_power(out.data(), nullptr, height.data(), graph.data(), erosivity.data(), uplift.data(),
+                          stop.data(), graph.shape()[0], graph.shape()[1], edge, detail::s2(scale).v, dt, nullptr));
+  return out;
+}
+inline F stream_power_batch(const F height, const silt::tensor_t<int> graph, const F erosivity, const edge_t edge,
+                            const std::vector<silt::vec2>& scales, const double dt, const F uplift = F(),
+                            const silt::tensor_t<int> stop = silt::tensor_t<int>()) {
+  std::vector<float> pairs;
+  for (const silt::vec2& s : scales) pairs.push_back(s.x), pairs.push_back(s.y);
+  F out(graph.shape(), silt::GPU);
+  check(soil_stream_power_batch(out.data(), nullptr, height.data(), graph.data(), erosivity.data(), uplift.data(),
+                                stop.data(), graph.shape()[0], graph.shape()[1], graph.shape()[2], edge,
+                                pairs.empty() ? nullptr : pairs.data(), static_cast<int64_t>(scales.size()), dt,
+                                nullptr));
+  return out;
+}
 // the fill of each of the B models (soil_fill_depressions_batch); synchronises, as fill_depressions does
 inline F fill_depressions_batch(const F height, const edge_t edge) {
   F out(height.shape(), silt::GPU);

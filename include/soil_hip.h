@@ -985,6 +985,88 @@ int soil_flow_paths_batch(int32_t* terminal, int32_t* steps, float* length, cons
  * (SOIL_PATHS_IDX64=1 forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
 int soil_flow_paths_info(int64_t info[4]);
 
+/* --------------------------------------------- flow graphs: downstream sums */
+
+/* A value carried DOWN a receiver graph: the linear recurrence
+ *     x[n] = t[n]                             n a terminal
+ *     x[n] = a[n] * L(n) + b[n] * x[r(n)]     n has an edge to r(n), of length L(n)
+ * chi and travel time to the outlet (sums of a per-cell weight along the way), the height of a cell's outlet (height
+ * above nearest drainage), the share of a cell's output that survives a per-cell decay on the way down, and, with
+ * coefficients made from the planes, the implicit stream-power incision step (Braun & Willett's O(N) solver, the
+ * "fastflow" of the reference's example/dem_process.py).  The reference has no such call; the definition is this
+ * library's.
+ *
+ * Grid, edge rule, `stop` and terminals are word for word those of soil_flow_paths above: cell n has an edge to
+ * r = graph[n] iff r is the index of one of its K neighbours inside the model, anything else (INT32_MIN included)
+ * makes it a terminal, and a cell with stop[n] != 0 is a terminal whatever its graph entry.
+ *
+ * soil_downstream.  `a`, `b`, `t`, `stop` and `scale` may each be NULL: a == 1, b == 1, t == 0, L == 1.  At least one
+ * of `out` (float) and `out64` (double) is non-NULL.  A cell with an edge of kind row / column / diagonal has
+ * L = sx / sy / dd, soil_flow_paths' scale: the floats of `scale` widened, dd = sqrt(sx * sx + sy * sy) made once on
+ * the host in double (the values are used as they are).  Its coefficients, in fp64:
+ *     A0 = (double)a[n] * L      one rounding; without a scale A0 = (double)a[n]
+ *     B0 = (double)b[n]
+ * A terminal has A0 = (double)t[n], B0 = 0, and is final.  Then ceil(log2(H * W)) rounds, the count for ONE model;
+ * in each a cell that is not final, with pointer p (its receiver at the start), does
+ *     A <- A + (B * A_p)         the product rounded first, then the sum
+ *     B <- B * B_p
+ *     ptr <- ptr_p
+ * every operand from the records of the round before, in fp64 with no contraction (__dmul_rn, __dadd_rn); the cell
+ * becomes final when the record it read was final, and a final record never changes again.  Result: out64[n] = A,
+ * out[n] = (float)A rounded to nearest; any NaN is written as 0x7fc00000 / 0x7ff8000000000000, and a cell that is
+ * not final after the last round — it is on a cycle or drains into one — gets that NaN too.  An acyclic graph
+ * resolves whatever its path lengths, up to H * W - 1 edges.
+ *
+ * The result is therefore one definite bit pattern, fixed by the graph and the planes alone: lists, dense rounds,
+ * offset widths, chunking and batching do not show, and b == NULL gives the bits of b == 1.0 everywhere (the kernels
+ * then keep no B: csrc/downstream.hip).  It is the value of the recurrence up to fp64 rounding in another order of
+ * association, not the serial sum's bits.
+ *
+ * soil_stream_power: the implicit step h' = (h + dt u + F h'[r]) / (1 + F), F = k dt / L, slope exponent n = 1 only
+ * (n != 1 is not an affine map, so not associative: out of scope).  The same rounds, the coefficients made in the
+ * init pass from the planes, nothing materialised in between.  For a cell with an edge of length L, each operation
+ * rounded once:
+ *     F = ((double)erosivity[n] * dt) / L
+ *     d = 1.0 + F
+ *     A0 = ((double)height[n] + dt * (double)uplift[n]) / d      (double)height[n] / d with uplift == NULL
+ *     B0 = F / d
+ * A terminal keeps (double)height[n]: it is the base level, neither lifted nor eroded.  `erosivity` is K A^m, made by
+ * the caller: the power is kept out of the kernel so that every operation in it is correctly rounded and can be
+ * restated bit for bit.  `uplift` and `stop` may be NULL.
+ *
+ * `scale` / `scales` (n_scales pairs, 1 or B) are HOST arrays read before the call returns (per-model pairs travel in
+ * one small stream-ordered copy).  The entries are stream-ordered and do not synchronise (a call that finds its cached
+ * scratch too small synchronises the device before replacing it, as everywhere); a host thread's calls on one device
+ * share one cached scratch block of their own: issue them on ONE stream, or order the streams yourself.
+ *
+ * Batch form: the conventions of soil_flow_paths_batch.  Model-major planes; graph entries are indices WITHIN their
+ * model; model b's slice of each output is bit for bit what the single call gives for model b's slices alone, with
+ * scales[b] or the one pair; nothing reaches another model.  Chunks of whole models, as many as keep 32-bit offsets
+ * and one init launch (65535), SOIL_FLOW_BATCH_CELLS lowers the cells of a chunk; a single model above that is a
+ * chunk of its own on 64-bit offsets.  Per chunk one init launch, the rounds of one model and one final launch,
+ * whatever B is.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): null `graph`, both outputs null, an output that aliases an input plane (or the other output),
+ * B, H or W < 1, H * W > INT32_MAX, n_scales not 1 or B, an invalid `edge`; for the stream-power entries in addition
+ * a null `height`, `erosivity` or `scale`, a scale entry that is not a positive finite float, a `dt` that is negative
+ * or not finite.  Otherwise, without a device: SOIL_ERR_NO_DEVICE. */
+int soil_downstream(float* out, double* out64, const int32_t* graph, const float* a, const float* b, const float* t,
+                    const int32_t* stop, int64_t H, int64_t W, int edge, const float scale[2], void* stream);
+int soil_downstream_batch(float* out, double* out64, const int32_t* graph, const float* a, const float* b,
+                          const float* t, const int32_t* stop, int64_t B, int64_t H, int64_t W, int edge,
+                          const float* scales, int64_t n_scales, void* stream);
+int soil_stream_power(float* out, double* out64, const float* height, const int32_t* graph, const float* erosivity,
+                      const float* uplift, const int32_t* stop, int64_t H, int64_t W, int edge, const float scale[2],
+                      double dt, void* stream);
+int soil_stream_power_batch(float* out, double* out64, const float* height, const int32_t* graph,
+                            const float* erosivity, const float* uplift, const int32_t* stop, int64_t B, int64_t H,
+                            int64_t W, int edge, const float* scales, int64_t n_scales, double dt, void* stream);
+/* What the calling host thread's last call of one of the four entries above did, as soil_flow_paths_info: info[0]
+ * chunks, info[1] chunks whose init pass took the 16-byte form, info[2] chunks on 64-bit offsets (SOIL_PATHS_IDX64=1
+ * forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
+int soil_downstream_info(int64_t info[4]);
+
 /* ------------------------------------------------ flow graphs: conditioning */
 
 /* Routing across flats and filled lakes.  soil_fill_depressions returns a surface on which every lake is level, and

@@ -233,6 +233,13 @@ SIGNATURES = {
     "soil_flow_paths": (cint, [vp, vp, vp, vp, vp, i64, i64, cint, F3, vp]),
     "soil_flow_paths_batch": (cint, [vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, vp]),
     "soil_flow_paths_info": (cint, [C.POINTER(i64)]),
+    # downstream sums: out / out64 (one may be NULL), graph, a / b / t / stop (each may be NULL); host scale pairs
+    "soil_downstream": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, vp]),
+    "soil_downstream_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, vp]),
+    # the implicit stream-power step: out / out64, height, graph, erosivity, uplift (may be NULL), stop (may be NULL)
+    "soil_stream_power": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double, vp]),
+    "soil_stream_power_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, C.c_double, vp]),
+    "soil_downstream_info": (cint, [C.POINTER(i64)]),
     # flats and filled lakes: dist / out, in, height, dist
     "soil_flat_distance": (cint, [vp, vp, i64, i64, cint, vp]),
     "soil_flat_distance_batch": (cint, [vp, vp, i64, i64, i64, cint, vp]),

@@ -67,6 +67,7 @@ enum WorkspaceSlot {
   WS_ACCUMULATE_BATCH = 14,  // graph.hip: soil_accumulate_batch (stream-ordered: not soil_accumulate's slot)
   WS_FLOW_PATHS = 15,    // flow_paths.hip: soil_flow_paths(_batch): scale records, the two record buffers, lists
   WS_FLATS = 16,         // flats.hip: soil_flat_distance(_batch): the tiles' marks, one mask byte per cell
+  WS_DOWNSTREAM = 17,    // downstream.hip: soil_downstream / soil_stream_power (_batch): scale records, records, B, lists
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();

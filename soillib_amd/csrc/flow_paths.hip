@@ -37,29 +37,9 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "flow_paths.hpp"  // the records' pointer word, rec_at, path_append, PathScale: shared with downstream.hip
 
 namespace soil {
-
-constexpr int kPBlock = 256;
-constexpr uint32_t kFinal = 0x80000000u;
-constexpr int64_t kPathsMaxGridZ = 65535;  // models per init / final launch, and so per chunk
-
-// A record at a 32-bit BYTE offset from a uniform base where the chunk's records are under 4 GiB (a scalar base and
-// one offset register per lane, graph.hip word_at), at a 64-bit index otherwise.
-template <typename IDX>
-__device__ __forceinline__ uint4* rec_at(uint4* base, IDX n) {
-  if constexpr (sizeof(IDX) == 4)
-    return reinterpret_cast<uint4*>(reinterpret_cast<char*>(base) + static_cast<uint32_t>(n * 16u));
-  else
-    return base + n;
-}
-template <typename IDX>
-__device__ __forceinline__ const uint4* rec_at(const uint4* base, IDX n) {
-  if constexpr (sizeof(IDX) == 4)
-    return reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(base) + static_cast<uint32_t>(n * 16u));
-  else
-    return base + n;
-}
 
 // The edge rule of soil_hip.h for cell (x, y) of a (H, W) model with graph entry g: the record of the cell, `first`
 // the model's first cell in the stacked array.  g is an edge iff it is the index of one of the cell's K neighbours
@@ -86,9 +66,6 @@ __device__ __forceinline__ uint4 path_record(int32_t g, bool stop, int64_t x, in
   }
   return rec;
 }
-
-// Control words of the dense rounds (graph.hip kRakeFlags): flags[round % 3] = "work left"
-constexpr int kPathFlags = 4;
 
 // Init: threads along the row, a work-group walks a band of rows (SOIL_ROW_LOOP), grid.z is the model.  VEC: four
 // cells per thread, the graph and the stop plane as 16-byte loads (W a multiple of four, the planes 16-byte aligned).
@@ -131,18 +108,6 @@ __device__ __forceinline__ bool path_cell(uint4* __restrict__ out, const uint4* 
   const uint4 q = *rec_at<IDX>(in, static_cast<IDX>(r.x));
   *rec_at<IDX>(out, n) = make_uint4(q.x, r.y + q.y, r.z + q.z, r.w + q.w);
   return true;
-}
-
-// graph.hip rake_append: the entries of a wave side by side in its work-group's segment, one LDS atomic per wave
-template <typename IDX>
-__device__ __forceinline__ void path_append(bool again, IDX n, uint32_t* __restrict__ segment, uint32_t* s_fill) {
-  const uint64_t m = __ballot(again);
-  if (m == 0) return;
-  const int lane = static_cast<int>(threadIdx.x & 63u), leader = __ffsll(static_cast<long long>(m)) - 1;
-  uint32_t base = 0;
-  if (lane == leader) base = atomicAdd(s_fill, static_cast<uint32_t>(__popcll(m)));
-  base = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(base), leader));
-  if (again) segment[base + static_cast<uint32_t>(__popcll(m & ((1ull << lane) - 1ull)))] = static_cast<uint32_t>(n);
 }
 
 // A dense round: a grid of a few work-groups per CU strides over the cells.  A cell that holds the bit is copied
@@ -208,15 +173,6 @@ __global__ void __launch_bounds__(kPBlock)
   if (threadIdx.x == 0) fill_out[blockIdx.x] = s_fill;
 }
 
-// The scale of a model as the final pass reads it: the floats widened, and dd = sqrt(sx sx + sy sy) made on the host
-struct PathScale {
-  double sx, sy, dd;
-};
-struct PathScales {
-  const PathScale* per_model;  // null: `one` for every model
-  PathScale one;
-};
-
 // Final: a cell per thread, grid.z is the model.  length = (float)((n_row sx + n_col sy) + n_diag dd) in fp64, one
 // rounding per operation, as soil_hip.h states it.
 __global__ void __launch_bounds__(kPBlock)
@@ -240,17 +196,6 @@ __global__ void __launch_bounds__(kPBlock)
       length[first64 + n] = resolved ? len : bits2f(0x7fc00000u);
     }
   }
-}
-
-inline PathScale path_scale(const float pair[2]) {
-  const double sx = static_cast<double>(pair[0]), sy = static_cast<double>(pair[1]);
-  return PathScale{sx, sy, std::sqrt(sx * sx + sy * sy)};  // (the squares of two floats are exact in fp64)
-}
-
-inline int ceil_log2(int64_t v) {  // ceil(log2(v)), v >= 1, in integers
-  int k = 0;
-  while ((int64_t{1} << k) < v) ++k;
-  return k;
 }
 
 // Models per chunk: as many whole models as keep the rounds on 32-bit offsets (16 bytes a cell under 4 GiB) and one
@@ -283,7 +228,6 @@ struct PathsLayout {
   size_t seg, b_rec, b_list, b_fill;
   size_t bytes() const { return 2 * b_rec + 2 * b_list + 2 * b_fill + 256; }
 };
-inline size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
 static PathsLayout paths_layout(int64_t elem) {
   static const unsigned groups_env = [] {
     const char* e = std::getenv("SOIL_PATHS_GROUPS");

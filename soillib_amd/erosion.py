@@ -797,6 +797,50 @@ class ErosionBatch:
             graph = self.flow(edge=e)
         return soil.flow_length_batch(graph, e, scale, stop)
 
+    def downstream(self, graph=None, a=None, b=None, terminal=None, stop=None, edge=None, scaled=True, double=False):
+        """A value carried down `graph` (default: flow()) in every model: x[n] = a[n] L(n) + b[n] x[r(n)], x = terminal
+        on the cells without an edge (soil_downstream_batch), a (B, H, W) float32 silt GPU tensor (float64 with
+        `double`).  `a`, `b`, `terminal`: (B, H, W) float32 tensors or None (1, 1, 0); L is the edge's length under the
+        batch's scale(s), as flow_length() takes them, or 1 with scaled=False.  `stop` and `edge` as in basins().  A
+        tensor of the wrong shape or dtype or a bad edge raises ValueError before any device work.  Nothing
+        synchronises."""
+        from . import soil
+        e = self._edge("downstream", edge)
+        if graph is not None:
+            self._flow_tensor("downstream", "graph", graph, silt.int32)
+        for name, t in (("a", a), ("b", b), ("terminal", terminal)):
+            if t is not None:
+                self._flow_tensor("downstream", name, t, silt.float32)
+        if stop is not None:
+            self._flow_tensor("downstream", "stop", stop, silt.int32)
+        scale = self._path_scale("downstream") if scaled else None
+        if graph is None:
+            graph = self.flow(edge=e)
+        return soil.downstream_batch(graph, e, a, b, terminal, scale, stop, double)
+
+    def stream_power(self, dt, K, m=0.5, kind="steepest", edge=None, T=None, offset=0, uplift=None):
+        """One implicit stream-power step (slope exponent 1) of every model, on its conditioned surface: conditioned()
+        -> drainage(graph=g) -> soil.erosivity(area, K, m) -> soil.stream_power_batch on the filled surface with the
+        batch's scale(s).  Returns the (B, H, W) float32 heights after the step; the batch's own planes are not
+        touched.  `uplift`: a (B, H, W) float32 tensor or None; `kind`, `edge`, `T`, `offset` as in conditioned().  A
+        bad argument raises ValueError before any device work.  Synchronises the stream (the fill does)."""
+        from . import soil
+        for name, v in (("dt", dt), ("K", K), ("m", m)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (name != "m" and v < 0):
+                raise ValueError("ErosionBatch.stream_power: %s must be a finite number%s, got %r" % (
+                    name, "" if name == "m" else " >= 0", v))
+        if kind not in ("steepest", "random_weighted"):
+            raise ValueError("ErosionBatch.stream_power: kind must be 'steepest' or 'random_weighted', got %r" % (kind,))
+        e = self._edge("stream_power", edge)
+        if kind == "random_weighted":
+            self._check_draw("stream_power", T, offset)
+        if uplift is not None:
+            self._flow_tensor("stream_power", "uplift", uplift, silt.float32)
+        scale = self._path_scale("stream_power")
+        filled, graph = self.conditioned(kind, e, T, offset)
+        area = self.drainage(graph=graph, edge=e)
+        return soil.stream_power_batch(filled, graph, soil.erosivity(area, K, m), e, scale, dt, uplift)
+
     def filled(self, edge=None):
         """The depression-filled surface of every model's `height`: a (B, H, W) float32 silt GPU tensor, model b's
         plane what soil.fill_depressions gives for it alone (soil_fill_depressions_batch: one call for the batch,

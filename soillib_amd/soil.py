@@ -370,6 +370,132 @@ def flow_paths_info():
     return dict(zip(("chunks", "vec_chunks", "idx64_chunks", "rounds"), (int(v) for v in info)))
 
 
+# ---- downstream sums (soil_hip.h: "flow graphs: downstream sums"): x[n] = a[n] L(n) + b[n] x[r(n)] down a receiver
+# graph, x = t on the terminals, and the implicit stream-power step, the same recurrence.  Stream-ordered.
+
+def _downstream(who, dims, graph, edge_, planes, scale, stop, double, dt=None):
+    """soil_downstream / soil_stream_power and their _batch forms: `planes` is a list of (name, tensor or None,
+    required) in the order of the C call's float planes; `dt` None: the sum, else the stream-power step.  Every check
+    comes before any device work."""
+    shape = (_hw2 if dims == 2 else _bhw)(graph, "%s: graph" % who)
+    e = _edge_of(edge_, who)
+    _int_plane(graph, shape, "%s: graph" % who)
+    for name, t, required in planes:
+        if t is None and required:
+            raise ValueError("%s: %s is required" % (who, name))
+        if t is not None:
+            _float_plane(t, shape, "%s: %s" % (who, name))
+    if stop is not None:
+        _int_plane(stop, shape, "%s: stop" % who)
+    if scale is None:
+        if dt is not None:
+            raise ValueError("%s: scale must be one (sx, sy) pair%s" % (who, "" if dims == 2 else " or B pairs"))
+        pairs, n = None, 1
+    elif dims == 2:
+        pairs, n = _one_pair(scale, who), 1
+    else:
+        pairs, n = _scale_pairs(scale, shape[0], who)
+    if dt is not None:
+        if isinstance(dt, bool) or not isinstance(dt, (int, float)) or not math.isfinite(dt) or dt < 0:
+            raise ValueError("%s: dt must be a finite number >= 0, got %r" % (who, dt))
+        if any(not (v > 0 and math.isfinite(v)) for v in pairs):
+            raise ValueError("%s: scale entries must be positive finite floats, got %r" % (who, scale))
+    g_ptr = _gpu(graph, silt.int32, "graph")
+    f_ptrs = [_opt_f(t, name) for name, t, _ in planes]
+    s_ptr = None if stop is None else _gpu(stop, silt.int32, "stop")
+    out = silt.tensor(silt.float64 if double else silt.float32, silt.shape(*shape), silt.gpu)
+    outs = (None, out.c_ptr) if double else (out.c_ptr, None)
+    tail = (pairs,) if dims == 2 else (pairs, n)
+    if dt is None:
+        _call("soil_downstream" + ("" if dims == 2 else "_batch"), *outs, g_ptr, *f_ptrs, s_ptr, *shape, e, *tail,
+              _abi.stream())
+    else:
+        _call("soil_stream_power" + ("" if dims == 2 else "_batch"), *outs, f_ptrs[0], g_ptr, *f_ptrs[1:], s_ptr, *shape,
+              e, *tail, float(dt), _abi.stream())
+    return out
+
+
+def downstream(graph, edge_, a=None, b=None, terminal=None, scale=None, stop=None, double=False):
+    """soil_downstream: x[n] = a[n] L(n) + b[n] x[r(n)] for a cell with an edge to r(n) = graph[n], x[n] = terminal[n]
+    on a cell without one (or with stop[n] != 0).  `a`, `b`, `terminal`: float32 planes or None (1, 1, 0); L: the
+    edge's length under the (sx, sy) of `scale` (None: 1).  Returns a float32 GPU tensor, float64 with `double`; NaN
+    for a cell on a cycle or draining into one.  Examples: a=None — the number of edges to the outlet, or with a
+    scale the flow length; terminal=height, a=zeros — the height of each cell's outlet; b=decay — what survives."""
+    return _downstream("downstream", 2, graph, edge_, [("a", a, False), ("b", b, False), ("terminal", terminal, False)],
+                       scale, stop, double)
+
+
+def downstream_batch(graph, edge_, a=None, b=None, terminal=None, scale=None, stop=None, double=False):
+    """`downstream` of each of the B models of (B, H, W) planes (soil_downstream_batch); `scale` is one pair or B
+    pairs; graph entries are indices within their model."""
+    return _downstream("downstream_batch", 3, graph, edge_,
+                       [("a", a, False), ("b", b, False), ("terminal", terminal, False)], scale, stop, double)
+
+
+def stream_power(height, graph, erosivity, edge_, scale, dt, uplift=None, stop=None, double=False):
+    """soil_stream_power: one implicit step of stream-power incision with slope exponent n = 1 along `graph`,
+    h'[n] = (h[n] + dt u[n] + F h'[r]) / (1 + F) with F = erosivity[n] dt / L(n); a terminal keeps its height.
+    `erosivity` is K A^m (soil.erosivity), `uplift` a float32 plane or None.  Returns the new heights, float32 (float64
+    with `double`); `height` is left as it is.  The graph should be acyclic and reach an outlet from every cell
+    (soil.condition); after a step, float32 ties can appear along edges that went strictly downhill, so the next step
+    starts again from condition()."""
+    return _downstream("stream_power", 2, graph, edge_,
+                       [("height", height, True), ("erosivity", erosivity, True), ("uplift", uplift, False)], scale, stop,
+                       double, dt)
+
+
+def stream_power_batch(height, graph, erosivity, edge_, scale, dt, uplift=None, stop=None, double=False):
+    """`stream_power` of each of the B models of (B, H, W) planes (soil_stream_power_batch); `scale` is one pair or B
+    pairs."""
+    return _downstream("stream_power_batch", 3, graph, edge_,
+                       [("height", height, True), ("erosivity", erosivity, True), ("uplift", uplift, False)], scale, stop,
+                       double, dt)
+
+
+def _on_stream():
+    """torch's current stream set to the one the library's calls go to."""
+    import torch
+    return torch.cuda.stream(torch.cuda.ExternalStream(_abi._stream)) if _abi._stream else contextlib.nullcontext()
+
+
+def erosivity(area, K, m):
+    """K * area ** m of a float32 drainage-area tensor of any shape, on the device through torch, float32: the
+    `erosivity` of stream_power.  torch's pow is not correctly rounded, so this plane is not bit-pinned; what
+    stream_power makes of a given plane is."""
+    if not isinstance(area, silt.tensor) or area.type is not silt.float32:
+        raise ValueError("erosivity: area must be a float32 silt tensor")
+    if area.host is not silt.gpu:
+        raise _abi.SoilError("mismatch_host: area must be a silt.gpu tensor")
+    with _on_stream():
+        out = area.view_torch().pow(float(m)).mul_(float(K))
+    return silt.tensor.from_torch(out.contiguous())
+
+
+def chi(graph, area, edge_, scale, theta=0.45, A0=1.0, stop=None):
+    """The chi coordinate of every cell of a (H, W) graph: the sum of (A0 / area) ** theta * L along the way to the
+    terminal, downstream(a=(A0 / area) ** theta, scale=scale).  The weights are made through torch in float32 (not
+    bit-pinned); the sum is soil_downstream's."""
+    shape = _hw2(graph, "chi: graph")
+    _float_plane(area, shape, "chi: area")
+    if area.host is not silt.gpu:
+        raise _abi.SoilError("mismatch_host: area must be a silt.gpu tensor")
+    _edge_of(edge_, "chi")
+    _one_pair(scale, "chi")
+    with _on_stream():
+        w = (float(A0) / area.view_torch()).pow_(float(theta))
+    return _downstream("chi", 2, graph, edge_, [("a", silt.tensor.from_torch(w.contiguous()), False), ("b", None, False),
+                                                ("terminal", None, False)], scale, stop, False)
+
+
+def downstream_info():
+    """What this thread's last downstream / stream_power call (or _batch form) did (soil_downstream_info): a dict with
+    the number of `chunks`, of chunks whose init pass took the 16-byte form (`vec_chunks`), of chunks on 64-bit
+    offsets (`idx64_chunks`) and the `rounds` per chunk."""
+    info = (C.c_int64 * 4)()
+    _call("soil_downstream_info", info)
+    return dict(zip(("chunks", "vec_chunks", "idx64_chunks", "rounds"), (int(v) for v in info)))
+
+
 def fill_depressions(height, edge_=None):
     """Priority-flood surface of a DEM (soil_hip.h: soil_fill_depressions) — the
     conditioning step the reference leaves to pysheds (example/dem_condition.py:35-41)."""
