@@ -21,37 +21,19 @@
 // instantiation without the plane gives the bits of b == 1.  A terminal is final with B = 0; a final record is a
 // fixed point and is copied from buffer to buffer with its B, which the cells that still point at it read.
 //
-// Everything else is flow_paths.hip's, through flow_paths.hpp: kFinal and the round count ceil(log2(H W)) of ONE
-// model, the dense round that writes down the pending cells, the listed rounds, device-side control words, chunks of
-// whole models on 32-bit byte offsets (64-bit for a single model above them), the model on grid.z in init and final.
+// Everything else is the engine of flow_paths.hpp, as flow_paths.hip's header explains it: kFinal and the round count
+// ceil(log2(H W)) of ONE model, the dense round that writes down the pending cells, the listed rounds, device-side
+// control words, chunks of whole models on 32-bit byte offsets (64-bit for a single model above them), the model on
+// grid.z in init and final.  This file has the records, the per-cell operation, init, final and the refusals.
 // A cell that never gets the bit — on a cycle, or draining into one — gets the quiet NaN.
 //
 // The result is one definite bit pattern: every operand of a round comes from the round before, every operation is
 // a single correctly rounded fp64 operation (-ffp-contract=off, and the intrinsics say so), and neither lists nor
 // offsets nor chunks change which operations a cell sees.
-#include <algorithm>
-#include <cstdlib>
-
 #include "common.hpp"
 #include "flow_paths.hpp"
 
 namespace soil {
-
-// The edge rule of soil_hip.h (flow_paths.hip path_record) for cell (x, y) with graph entry g: the kind of the edge,
-// 0 a row step, 1 a column step, 2 a diagonal, or -1 where g is no edge.
-template <int K>
-__device__ __forceinline__ int down_edge(int32_t g, int64_t x, int64_t y, int64_t H, int64_t W) {
-  const int64_t d = static_cast<int64_t>(g) - (x * W + y);
-  int kind = -1;
-#pragma unroll
-  for (int rd = -1; rd <= 1; ++rd) {
-    const int64_t cd = d - rd * W;
-    const bool ok = cd >= -1 && cd <= 1 && (rd != 0 || cd != 0) && x + rd >= 0 && x + rd < H && y + cd >= 0 &&
-                    y + cd < W && (K == 8 || rd == 0 || cd == 0);
-    if (ok) kind = rd == 0 ? 1 : (cd == 0 ? 0 : 2);
-  }
-  return kind;
-}
 
 // {ptr | kFinal, edges walked, A}.  The second word is not part of the result; it is carried (an integer add a round,
 // at most 2^31 as in flow_paths.hip) so that every word of a record read is used: the compiler narrows a 16-byte load
@@ -96,7 +78,7 @@ __device__ __forceinline__ void down_init_cell(uint4* __restrict__ rec, double* 
                                                int32_t g, bool stop, float v0, float v1, float v2, bool has2,
                                                int64_t x, int64_t y, int64_t H, int64_t W, uint32_t first,
                                                const PathScale& s, double dt) {
-  const int kind = stop ? -1 : down_edge<K>(g, x, y, H, W);
+  const int kind = stop ? -1 : edge_kind<K>(g, x, y, H, W);
   double A, B = 0.0;
   uint32_t ptr = (first + static_cast<uint32_t>(n)) | kFinal;
   if (kind < 0) {
@@ -119,7 +101,7 @@ __device__ __forceinline__ void down_init_cell(uint4* __restrict__ rec, double* 
   if constexpr (HASB) bcoef[n] = B;
 }
 
-// Init: flow_paths.hip k_paths_init — threads along the row, a band of rows per work-group, grid.z the model.  VEC:
+// Init, as k_paths_init of flow_paths.hip: threads along the row, a band of rows per work-group, grid.z the model.  VEC:
 // four cells per thread, every plane as a 16-byte load (W a multiple of four, the planes 16-byte aligned).
 template <int K, bool VEC, int MODE, bool HASB>
 __global__ void __launch_bounds__(kPBlock)
@@ -186,64 +168,23 @@ __device__ __forceinline__ bool down_cell(uint4* __restrict__ out, const uint4* 
   return true;
 }
 
-// A dense round (flow_paths.hip k_paths_round): a grid of a few work-groups per CU strides over the cells; a round
-// that wrote no new record ends the work of the dense rounds after it; `list_out`: the pending cells, work-group b
-// into segment b.
+// The dense and the listed round (flow_paths.hpp ptr_round, ptr_list) over down_cell
 template <typename IDX, bool HASB>
 __global__ void __launch_bounds__(kPBlock)
     k_down_round(uint4* __restrict__ out, const uint4* __restrict__ in, double* __restrict__ bout,
                  const double* __restrict__ bin, int64_t elem64, int* __restrict__ flags, int round,
                  uint32_t* __restrict__ list_out, uint32_t* __restrict__ fill_out, uint32_t seg) {
-  const IDX elem = static_cast<IDX>(elem64);
-  __shared__ uint32_t s_fill;
-  if (blockIdx.x == 0 && threadIdx.x == 0) flags[(round + 2) % 3] = 0;
-  if (flags[round % 3] == 0) {
-    if (list_out && threadIdx.x == 0) fill_out[blockIdx.x] = 0;
-    return;
-  }
-  if (list_out) {
-    if (threadIdx.x == 0) s_fill = 0;
-    __syncthreads();
-  }
-  uint32_t* const segment = list_out ? list_out + static_cast<size_t>(blockIdx.x) * seg : nullptr;
-  bool pending = false;
-  for (IDX n = static_cast<IDX>(blockIdx.x) * kPBlock + threadIdx.x; n < elem;
-       n += static_cast<IDX>(gridDim.x) * kPBlock) {
-    const bool again = down_cell<IDX, HASB>(out, in, bout, bin, n);
-    pending = pending || again;
-    if (list_out) path_append<IDX>(again, n, segment, &s_fill);
-  }
-  if (__any(pending) && (threadIdx.x & 63) == 0) flags[(round + 1) % 3] = 1;
-  if (list_out) {
-    __syncthreads();
-    if (threadIdx.x == 0) fill_out[blockIdx.x] = s_fill;
-  }
+  ptr_round<IDX>([=](IDX n) { return down_cell<IDX, HASB>(out, in, bout, bin, n); }, elem64, flags, round, list_out,
+                 fill_out, seg);
 }
-
-// A round over the lists (flow_paths.hip k_paths_list)
 template <typename IDX, bool HASB>
 __global__ void __launch_bounds__(kPBlock)
     k_down_list(uint4* __restrict__ out, const uint4* __restrict__ in, double* __restrict__ bout,
                 const double* __restrict__ bin, const uint32_t* __restrict__ list_in,
                 const uint32_t* __restrict__ fill_in, uint32_t* __restrict__ list_out,
                 uint32_t* __restrict__ fill_out, uint32_t seg) {
-  const uint32_t n_in = fill_in[blockIdx.x];
-  if (n_in == 0) {
-    if (threadIdx.x == 0) fill_out[blockIdx.x] = 0;
-    return;
-  }
-  __shared__ uint32_t s_fill;
-  if (threadIdx.x == 0) s_fill = 0;
-  __syncthreads();
-  const uint32_t* const mine = list_in + static_cast<size_t>(blockIdx.x) * seg;
-  uint32_t* const segment = list_out + static_cast<size_t>(blockIdx.x) * seg;
-  for (uint32_t i = threadIdx.x; i < n_in; i += kPBlock) {
-    const IDX n = static_cast<IDX>(mine[i]);
-    const bool again = down_cell<IDX, HASB>(out, in, bout, bin, n);
-    path_append<IDX>(again, n, segment, &s_fill);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) fill_out[blockIdx.x] = s_fill;
+  ptr_list<IDX>([=](IDX n) { return down_cell<IDX, HASB>(out, in, bout, bin, n); }, list_in, fill_in, list_out,
+                fill_out, seg);
 }
 
 // Final: a cell per thread, grid.z the model, no gather.  A, or the quiet NaN for any NaN and for a cell that never
@@ -261,120 +202,52 @@ __global__ void __launch_bounds__(kPBlock)
   }
 }
 
-// Models per chunk, as flow_paths.hip counts them: whole models on 32-bit offsets (16 bytes a cell under 4 GiB; B's 8
-// bytes a cell lie below that anyway) in one init launch, at least one; SOIL_FLOW_BATCH_CELLS lowers the cap.
-static int64_t down_chunk_models(int64_t cells_per_model) {
-  const char* const e = std::getenv("SOIL_FLOW_BATCH_CELLS");
-  const int64_t cap_env = e ? std::atoll(e) : 0ll;
-  int64_t cap = static_cast<int64_t>((1ull << 32) / sizeof(uint4)) - 1;
-  if (cap_env > 0 && cap_env < cap) cap = cap_env;
-  const int64_t per = cap / cells_per_model;
-  return per < 1 ? 1 : (per > kPathsMaxGridZ ? kPathsMaxGridZ : per);
-}
-
-// What the last call of one of the four entries on this host thread did (soil_downstream_info)
-struct DownInfo {
-  int64_t chunks, vec_chunks, idx64_chunks, rounds;
-};
-static thread_local DownInfo t_down_info{0, 0, 0, 0};
-
-struct DownLayout {  // the scratch of a chunk: two record buffers, two B planes (HASB), two lists, their fills, flags
-  unsigned groups;
-  size_t seg, b_rec, b_coef, b_list, b_fill;
-  size_t bytes() const { return 2 * b_rec + 2 * b_coef + 2 * b_list + 2 * b_fill + 256; }
-};
-static DownLayout down_layout(int64_t elem, bool has_b) {
-  static const unsigned groups_env = [] {
-    const char* e = std::getenv("SOIL_PATHS_GROUPS");
-    return e && std::atoi(e) > 0 ? static_cast<unsigned>(std::atoi(e)) : 256u * 32u;
-  }();
-  DownLayout L;
-  L.groups = std::min(blocks_for(elem, kPBlock), groups_env);
-  L.seg = ((static_cast<size_t>(elem) + L.groups - 1) / L.groups + 255) / 256 * 256;
-  L.b_rec = align256(sizeof(uint4) * static_cast<size_t>(elem));
-  L.b_coef = has_b ? align256(sizeof(double) * static_cast<size_t>(elem)) : 0;
-  L.b_list = align256(sizeof(uint32_t) * L.seg * L.groups);
-  L.b_fill = align256(sizeof(uint32_t) * L.groups);
-  return L;
-}
+static thread_local PtrInfo t_down_info{0, 0, 0, 0};  // soil_downstream_info
 
 struct DownOut {
   float* out;
   double* out64;
 };
 
-// One chunk of `models` models of (H, W), stream-ordered: init, the rounds of ONE model, final.
+// One chunk of `models` models (flow_paths.hpp ptr_chunk) with this file's launches; HASB: the chunk's extra planes
+// are the two B planes, 8 bytes a cell.
 template <int K, int MODE, bool HASB>
 static int down_chunk(DownOut o, const DownPlanes& in, int64_t models, int64_t H, int64_t W, const PathScales& scales,
                       char* scratch, hipStream_t st) {
-  const int64_t hw = H * W, elem = models * hw;
-  const DownLayout L = down_layout(elem, HASB);
-  char* p = scratch;
-  uint4* const rec[2] = {reinterpret_cast<uint4*>(p), reinterpret_cast<uint4*>(p + L.b_rec)};
-  p += 2 * L.b_rec;
-  double* const coef[2] = {HASB ? reinterpret_cast<double*>(p) : nullptr,
-                           HASB ? reinterpret_cast<double*>(p + L.b_coef) : nullptr};
-  p += 2 * L.b_coef;
-  uint32_t* const list[2] = {reinterpret_cast<uint32_t*>(p), reinterpret_cast<uint32_t*>(p + L.b_list)};
-  p += 2 * L.b_list;
-  uint32_t* const fill[2] = {reinterpret_cast<uint32_t*>(p), reinterpret_cast<uint32_t*>(p + L.b_fill)};
-  p += 2 * L.b_fill;
-  int* const flags = reinterpret_cast<int*>(p);
-
-  const unsigned z = static_cast<unsigned>(models);
-  const uintptr_t planes = reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.stop) |
-                           reinterpret_cast<uintptr_t>(in.p0) | reinterpret_cast<uintptr_t>(in.p1) |
-                           reinterpret_cast<uintptr_t>(in.p2);
-  const bool vec = W % 4 == 0 && (planes & 15) == 0;
-  if (vec) {
-    dim3 grid = grid_rows(H, W / 4, kPBlock);
-    grid.z = z;
-    k_down_init<K, true, MODE, HASB><<<grid, kPBlock, 0, st>>>(rec[0], coef[0], in, H, W, scales, flags);
-  } else {
-    dim3 grid = grid_rows(H, W, kPBlock);
-    grid.z = z;
-    k_down_init<K, false, MODE, HASB><<<grid, kPBlock, 0, st>>>(rec[0], coef[0], in, H, W, scales, flags);
-  }
-  SOIL_LAUNCH_CHECK();
-  t_down_info.chunks += 1;
-  t_down_info.vec_chunks += vec ? 1 : 0;
-
-  // The knobs of flow_paths.hip, read per call: SOIL_PATHS_LIST_FROM, the first round over the lists (0, or beyond
-  // the last round: dense rounds throughout), and SOIL_PATHS_IDX64=1, 64-bit offsets whatever the size.
-  const char* const e = std::getenv("SOIL_PATHS_LIST_FROM");
-  const int list_from_env = e ? std::atoi(e) : 1;
-  const int rounds = ceil_log2(hw);
-  const int list_from = (list_from_env >= 1 && list_from_env < rounds) ? list_from_env : rounds;
-  const char* const e64 = std::getenv("SOIL_PATHS_IDX64");
-  const bool idx32 = static_cast<uint64_t>(elem) * sizeof(uint4) < (1ull << 32) && !(e64 && std::atoi(e64) == 1);
-  t_down_info.idx64_chunks += idx32 ? 0 : 1;
-  t_down_info.rounds = rounds;
-  const uint32_t seg32 = static_cast<uint32_t>(L.seg);
-  for (int r = 0; r < rounds; ++r) {
-    uint4* const ro = rec[(r + 1) & 1];
-    const uint4* const ri = rec[r & 1];
-    double* const bo = coef[(r + 1) & 1];
-    const double* const bi = coef[r & 1];
-    if (r >= list_from) {
-      const uint32_t *li = list[r & 1], *fi = fill[r & 1];
-      uint32_t *lo = list[(r + 1) & 1], *fo = fill[(r + 1) & 1];
-      if (idx32) k_down_list<uint32_t, HASB><<<L.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, li, fi, lo, fo, seg32);
-      else k_down_list<int64_t, HASB><<<L.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, li, fi, lo, fo, seg32);
-      continue;
+  auto init = [&](const PtrChunk& c) {
+    const bool vec = ptr_vec_init(W, reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.stop) |
+                                         reinterpret_cast<uintptr_t>(in.p0) | reinterpret_cast<uintptr_t>(in.p1) |
+                                         reinterpret_cast<uintptr_t>(in.p2));
+    const dim3 grid = ptr_init_grid(c, H, W, vec);
+    double* const b0 = static_cast<double*>(c.extra[0]);
+    if (vec) k_down_init<K, true, MODE, HASB><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, H, W, scales, c.flags);
+    else k_down_init<K, false, MODE, HASB><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, H, W, scales, c.flags);
+    return vec;
+  };
+  auto round = [&](const PtrChunk& c, const PtrRound& q) {
+    uint4* const ro = c.rec[(q.r + 1) & 1];
+    const uint4* const ri = c.rec[q.r & 1];
+    double* const bo = static_cast<double*>(c.extra[(q.r + 1) & 1]);
+    const double* const bi = static_cast<const double*>(c.extra[q.r & 1]);
+    if (q.list_in) {
+      if (c.idx32)
+        k_down_list<uint32_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
+                                                                  q.fill_out, c.seg);
+      else
+        k_down_list<int64_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
+                                                                 q.fill_out, c.seg);
+    } else if (c.idx32) {
+      k_down_round<uint32_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
+                                                                 q.fill_out, c.seg);
+    } else {
+      k_down_round<int64_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
+                                                                q.fill_out, c.seg);
     }
-    uint32_t* const lo = list_from < rounds && r + 1 == list_from ? list[(r + 1) & 1] : nullptr;
-    uint32_t* const fo = fill[(r + 1) & 1];
-    if (idx32) k_down_round<uint32_t, HASB><<<L.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, elem, flags, r, lo, fo, seg32);
-    else k_down_round<int64_t, HASB><<<L.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, elem, flags, r, lo, fo, seg32);
-  }
-  SOIL_LAUNCH_CHECK();
-
-  const int64_t per_model = (hw + kPBlock - 1) / kPBlock;
-  const int64_t want = (8192 + models - 1) / models;
-  dim3 grid(static_cast<unsigned>(per_model < want ? per_model : want), 1, z);
-  k_down_final<<<grid, kPBlock, 0, st>>>(o.out, o.out64, rec[rounds & 1], hw);
-  SOIL_LAUNCH_CHECK();
-  return SOIL_OK;
+  };
+  auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
+    k_down_final<<<grid, kPBlock, 0, st>>>(o.out, o.out64, rec, H * W);
+  };
+  return ptr_chunk(t_down_info, models, H, W, HASB ? sizeof(double) : 0, scratch, init, round, fin);
 }
 
 // Whether [p, p + pb) and [q, q + qb) share a byte (a null pointer shares nothing)
@@ -394,11 +267,7 @@ static int check_downstream(const char* what, int mode, const void* out, const v
     SOIL_REQUIRE(in.p1, w + ": null erosivity");
     SOIL_REQUIRE(scales, w + ": the stream-power step needs a scale");
   }
-  SOIL_REQUIRE(B >= 1, w + ": B must be >= 1");
-  SOIL_REQUIRE(H >= 1 && W >= 1, w + ": empty grid");
-  SOIL_REQUIRE(H <= INT32_MAX / W, w + ": a model must have 1..2^31-1 cells (int32 graph)");
-  SOIL_REQUIRE(n_scales == 1 || n_scales == B, w + ": n_scales must be 1 or B");
-  SOIL_REQUIRE(edge == SOIL_D4 || edge == SOIL_D8, w + ": invalid edge enumerator");
+  if (int rc = check_grid_batch(w, B, H, W, edge, n_scales); rc != SOIL_OK) return rc;
   if (mode == kPower) {
     for (int64_t i = 0; i < 2 * n_scales; ++i)
       SOIL_REQUIRE(scales[i] > 0.0f && std::isfinite(scales[i]), w + ": a scale must be a positive finite float");
@@ -415,45 +284,26 @@ static int check_downstream(const char* what, int mode, const void* out, const v
   return SOIL_OK;
 }
 
-// Chunks of whole models, one after the other on `st` through one block of workspace slot WS_DOWNSTREAM (the
-// entries' own: they return with their work in flight): the B scale records first, then the chunk's scratch.
+// A call through workspace slot WS_DOWNSTREAM (flow_paths.hpp ptr_run); without a scale L == 1
 static int downstream_run(int mode, DownOut o, const DownPlanes& in, int64_t B, int64_t H, int64_t W, int edge,
                           const float* scales, int64_t n_scales, hipStream_t st) {
-  const int64_t hw = H * W, per = down_chunk_models(hw);
-  t_down_info = DownInfo{0, 0, 0, 0};
   const bool has_b = mode == kPower || in.p1 != nullptr;
-  const bool per_model = scales && n_scales > 1;
-  const size_t b_scales = per_model ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0;
-  const int64_t first_chunk = B < per ? B : per;
-  void* base = nullptr;
-  if (int rc = workspace_get(WS_DOWNSTREAM, b_scales + down_layout(first_chunk * hw, has_b).bytes(), &base);
-      rc != SOIL_OK)
-    return rc;
-  PathScales sc{nullptr, PathScale{1.0, 1.0, 1.0}};  // no scale: L == 1
-  if (scales) sc.one = path_scale(scales);
-  if (per_model) {
-    std::vector<PathScale> host(static_cast<size_t>(B));
-    for (int64_t b = 0; b < B; ++b) host[static_cast<size_t>(b)] = path_scale(scales + 2 * b);
-    if (int rc = batch_upload(base, host.data(), sizeof(PathScale) * host.size(), st); rc != SOIL_OK) return rc;
-    sc.per_model = static_cast<const PathScale*>(base);
-  }
-  char* const scratch = static_cast<char*>(base) + b_scales;
   const bool d4 = edge == SOIL_D4;
   auto go = mode == kPower ? (d4 ? down_chunk<4, kPower, true> : down_chunk<8, kPower, true>)
             : has_b        ? (d4 ? down_chunk<4, kSum, true> : down_chunk<8, kSum, true>)
                            : (d4 ? down_chunk<4, kSum, false> : down_chunk<8, kSum, false>);
-  for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int64_t nb = B - b0 < per ? B - b0 : per, at = b0 * hw;
-    PathScales s = sc;
-    if (s.per_model) s.per_model += b0;
-    const DownPlanes part{in.graph + at, in.stop ? in.stop + at : nullptr, in.p0 ? in.p0 + at : nullptr,
-                          in.p1 ? in.p1 + at : nullptr, in.p2 ? in.p2 + at : nullptr, in.dt};
-    if (int rc = go(DownOut{o.out ? o.out + at : nullptr, o.out64 ? o.out64 + at : nullptr}, part, nb, H, W, s,
-                    scratch, st);
-        rc != SOIL_OK)
-      return rc;
-  }
-  return SOIL_OK;
+  return ptr_run(WS_DOWNSTREAM, t_down_info, B, H, W, has_b ? sizeof(double) : 0, scales, n_scales,
+                 PathScale{1.0, 1.0, 1.0}, st, [&](int64_t b0, int64_t nb, const PathScales& s, char* scratch) {
+                   const int64_t at = b0 * H * W;
+                   const DownPlanes part{in.graph + at,
+                                         in.stop ? in.stop + at : nullptr,
+                                         in.p0 ? in.p0 + at : nullptr,
+                                         in.p1 ? in.p1 + at : nullptr,
+                                         in.p2 ? in.p2 + at : nullptr,
+                                         in.dt};
+                   return go(DownOut{o.out ? o.out + at : nullptr, o.out64 ? o.out64 + at : nullptr}, part, nb, H, W,
+                             s, scratch, st);
+                 });
 }
 
 }  // namespace soil
@@ -504,8 +354,7 @@ int soil_stream_power_batch(float* out, double* out64, const float* height, cons
 
 int soil_downstream_info(int64_t info[4]) {
   SOIL_REQUIRE(info, "downstream_info: null info");
-  info[0] = t_down_info.chunks, info[1] = t_down_info.vec_chunks;
-  info[2] = t_down_info.idx64_chunks, info[3] = t_down_info.rounds;
+  t_down_info.store(info);
   return SOIL_OK;
 }
 

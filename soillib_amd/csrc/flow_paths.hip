@@ -33,38 +33,22 @@
 //
 // A batch is ONE stacked array of records with pointers into that array: init takes its model from grid.z, as the
 // donor pass does, and adds the model's first cell to the receiver; the rounds never look at H, W or the model.
-#include <algorithm>
-#include <cstdlib>
-
 #include "common.hpp"
-#include "flow_paths.hpp"  // the records' pointer word, rec_at, path_append, PathScale: shared with downstream.hip
+#include "flow_paths.hpp"  // the round bodies, the edge rule and the host driver: shared with downstream.hip
 
 namespace soil {
 
-// The edge rule of soil_hip.h for cell (x, y) of a (H, W) model with graph entry g: the record of the cell, `first`
-// the model's first cell in the stacked array.  g is an edge iff it is the index of one of the cell's K neighbours
-// inside the model: of the three row steps rd the one (if any) whose column step cd = g - n - rd W lies in -1 .. 1
-// with the neighbour in the grid — at most one does, the decomposition of an index into row and column being
-// unique —, so no division is needed, and any other int32 is no edge.  64-bit differences: g may be INT32_MIN.
+// The record of cell (x, y) of a (H, W) model with graph entry g under the edge rule (edge_kind), `first` the model's
+// first cell in the stacked array.
 template <int K>
 __device__ __forceinline__ uint4 path_record(int32_t g, bool stop, int64_t x, int64_t y, int64_t H, int64_t W,
                                              uint32_t first) {
-  const int64_t n = x * W + y;
-  const int64_t d = static_cast<int64_t>(g) - n;
-  uint4 rec = make_uint4((first + static_cast<uint32_t>(n)) | kFinal, 0u, 0u, 0u);
-  if (stop) return rec;
-#pragma unroll
-  for (int rd = -1; rd <= 1; ++rd) {
-    const int64_t cd = d - rd * W;
-    const bool ok = cd >= -1 && cd <= 1 && (rd != 0 || cd != 0) && x + rd >= 0 && x + rd < H && y + cd >= 0 &&
-                    y + cd < W && (K == 8 || rd == 0 || cd == 0);
-    if (ok) {
-      const bool diag = rd != 0 && cd != 0;
-      rec = make_uint4(first + static_cast<uint32_t>(g), (rd != 0 && !diag) ? 1u : 0u, (rd == 0) ? 1u : 0u,
-                       diag ? 1u : 0u);
-    }
-  }
-  return rec;
+  const uint4 self = make_uint4((first + static_cast<uint32_t>(x * W + y)) | kFinal, 0u, 0u, 0u);
+  if (stop) return self;
+  const int kind = edge_kind<K>(g, x, y, H, W);
+  return kind < 0 ? self
+                  : make_uint4(first + static_cast<uint32_t>(g), kind == 0 ? 1u : 0u, kind == 1 ? 1u : 0u,
+                               kind == 2 ? 1u : 0u);
 }
 
 // Init: threads along the row, a work-group walks a band of rows (SOIL_ROW_LOOP), grid.z is the model.  VEC: four
@@ -110,67 +94,19 @@ __device__ __forceinline__ bool path_cell(uint4* __restrict__ out, const uint4* 
   return true;
 }
 
-// A dense round: a grid of a few work-groups per CU strides over the cells.  A cell that holds the bit is copied
-// across (a dense round keeps no word that says "final in both buffers"; the listed rounds do not come back to such
-// a cell at all), so when a dense round writes no new record every record is final in both buffers and the rounds
-// after it have nothing to do.  `list_out`: the dense round in front of the listed rounds writes down its pending
-// cells, work-group b into segment b (`seg` entries: its share of the cells).
+// The dense and the listed round (flow_paths.hpp ptr_round, ptr_list) over path_cell
 template <typename IDX>
 __global__ void __launch_bounds__(kPBlock)
     k_paths_round(uint4* __restrict__ out, const uint4* __restrict__ in, int64_t elem64, int* __restrict__ flags,
                   int round, uint32_t* __restrict__ list_out, uint32_t* __restrict__ fill_out, uint32_t seg) {
-  const IDX elem = static_cast<IDX>(elem64);
-  __shared__ uint32_t s_fill;
-  // the word round + 2 will read is cleared either way (k_rake_compress)
-  if (blockIdx.x == 0 && threadIdx.x == 0) flags[(round + 2) % 3] = 0;
-  if (flags[round % 3] == 0) {
-    if (list_out && threadIdx.x == 0) fill_out[blockIdx.x] = 0;
-    return;
-  }
-  if (list_out) {
-    if (threadIdx.x == 0) s_fill = 0;
-    __syncthreads();
-  }
-  uint32_t* const segment = list_out ? list_out + static_cast<size_t>(blockIdx.x) * seg : nullptr;
-  bool pending = false;
-  // (the trip count is uniform over the work-group but for the last trip; the ballots of path_append are per wave)
-  for (IDX n = static_cast<IDX>(blockIdx.x) * kPBlock + threadIdx.x; n < elem;
-       n += static_cast<IDX>(gridDim.x) * kPBlock) {
-    const bool again = path_cell<IDX>(out, in, n);
-    pending = pending || again;
-    if (list_out) path_append<IDX>(again, n, segment, &s_fill);
-  }
-  if (__any(pending) && (threadIdx.x & 63) == 0) flags[(round + 1) % 3] = 1;
-  if (list_out) {
-    __syncthreads();
-    if (threadIdx.x == 0) fill_out[blockIdx.x] = s_fill;
-  }
+  ptr_round<IDX>([=](IDX n) { return path_cell<IDX>(out, in, n); }, elem64, flags, round, list_out, fill_out, seg);
 }
-
-// A round over the lists: work-group b reads segment b of the lists the round before made and makes segment b of
-// the next; a work-group whose segment is empty returns at once.
 template <typename IDX>
 __global__ void __launch_bounds__(kPBlock)
     k_paths_list(uint4* __restrict__ out, const uint4* __restrict__ in, const uint32_t* __restrict__ list_in,
                  const uint32_t* __restrict__ fill_in, uint32_t* __restrict__ list_out,
                  uint32_t* __restrict__ fill_out, uint32_t seg) {
-  const uint32_t n_in = fill_in[blockIdx.x];
-  if (n_in == 0) {
-    if (threadIdx.x == 0) fill_out[blockIdx.x] = 0;
-    return;
-  }
-  __shared__ uint32_t s_fill;
-  if (threadIdx.x == 0) s_fill = 0;
-  __syncthreads();
-  const uint32_t* const mine = list_in + static_cast<size_t>(blockIdx.x) * seg;
-  uint32_t* const segment = list_out + static_cast<size_t>(blockIdx.x) * seg;
-  for (uint32_t i = threadIdx.x; i < n_in; i += kPBlock) {
-    const IDX n = static_cast<IDX>(mine[i]);
-    const bool again = path_cell<IDX>(out, in, n);
-    path_append<IDX>(again, n, segment, &s_fill);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) fill_out[blockIdx.x] = s_fill;
+  ptr_list<IDX>([=](IDX n) { return path_cell<IDX>(out, in, n); }, list_in, fill_in, list_out, fill_out, seg);
 }
 
 // Final: a cell per thread, grid.z is the model.  length = (float)((n_row sx + n_col sy) + n_diag dd) in fp64, one
@@ -198,169 +134,62 @@ __global__ void __launch_bounds__(kPBlock)
   }
 }
 
-// Models per chunk: as many whole models as keep the rounds on 32-bit offsets (16 bytes a cell under 4 GiB) and one
-// init launch (grid.z), at least one.  SOIL_FLOW_BATCH_CELLS lowers the cap on the cells of a chunk, as it does for
-// soil_accumulate_batch (read per call).
-static int64_t paths_chunk_models(int64_t cells_per_model) {
-  const char* const e = std::getenv("SOIL_FLOW_BATCH_CELLS");
-  const int64_t cap_env = e ? std::atoll(e) : 0ll;
-  int64_t cap = static_cast<int64_t>((1ull << 32) / sizeof(uint4)) - 1;
-  if (cap_env > 0 && cap_env < cap) cap = cap_env;
-  const int64_t per = cap / cells_per_model;
-  return per < 1 ? 1 : (per > kPathsMaxGridZ ? kPathsMaxGridZ : per);
-}
+static thread_local PtrInfo t_paths_info{0, 0, 0, 0};  // soil_flow_paths_info
 
-// What the last call of either entry on this host thread did (soil_flow_paths_info): the tests hold the chunking,
-// the choice of the init form and of the offsets to it.
-struct PathsInfo {
-  int64_t chunks, vec_chunks, idx64_chunks, rounds;
-};
-static thread_local PathsInfo t_paths_info{0, 0, 0, 0};
-
-struct PathsWork {  // the scratch of a chunk, carved out of the call's block
-  uint4* rec[2];
-  uint32_t* list[2];
-  uint32_t* fill[2];
-  int* flags;
-};
-struct PathsLayout {
-  unsigned groups;
-  size_t seg, b_rec, b_list, b_fill;
-  size_t bytes() const { return 2 * b_rec + 2 * b_list + 2 * b_fill + 256; }
-};
-static PathsLayout paths_layout(int64_t elem) {
-  static const unsigned groups_env = [] {
-    const char* e = std::getenv("SOIL_PATHS_GROUPS");
-    return e && std::atoi(e) > 0 ? static_cast<unsigned>(std::atoi(e)) : 256u * 32u;
-  }();
-  PathsLayout L;
-  L.groups = std::min(blocks_for(elem, kPBlock), groups_env);
-  // a work-group's segment of the lists: its share of the cells, in whole work-groups' worth of entries
-  L.seg = ((static_cast<size_t>(elem) + L.groups - 1) / L.groups + 255) / 256 * 256;
-  L.b_rec = align256(sizeof(uint4) * static_cast<size_t>(elem));
-  L.b_list = align256(sizeof(uint32_t) * L.seg * L.groups);
-  L.b_fill = align256(sizeof(uint32_t) * L.groups);
-  return L;
-}
-
-// One chunk of `models` models of (H, W), stream-ordered: init, the rounds of ONE model, final.
+// One chunk of `models` models (flow_paths.hpp ptr_chunk) with this file's launches
 template <int K>
 static int paths_chunk(int32_t* terminal, int32_t* steps, float* length, const int32_t* graph, const int32_t* stop,
-                int64_t models, int64_t H, int64_t W, const PathScales& scales, char* scratch, hipStream_t st) {
-  const int64_t hw = H * W, elem = models * hw;
-  const PathsLayout L = paths_layout(elem);
-  PathsWork w;
-  char* p = scratch;
-  w.rec[0] = reinterpret_cast<uint4*>(p), w.rec[1] = reinterpret_cast<uint4*>(p + L.b_rec), p += 2 * L.b_rec;
-  w.list[0] = reinterpret_cast<uint32_t*>(p), w.list[1] = reinterpret_cast<uint32_t*>(p + L.b_list), p += 2 * L.b_list;
-  w.fill[0] = reinterpret_cast<uint32_t*>(p), w.fill[1] = reinterpret_cast<uint32_t*>(p + L.b_fill), p += 2 * L.b_fill;
-  w.flags = reinterpret_cast<int*>(p);
-
-  const unsigned z = static_cast<unsigned>(models);
-  const bool vec = W % 4 == 0 &&
-                   ((reinterpret_cast<uintptr_t>(graph) | reinterpret_cast<uintptr_t>(stop)) & 15) == 0;
-  if (vec) {
-    dim3 grid = grid_rows(H, W / 4, kPBlock);
-    grid.z = z;
-    k_paths_init<K, true><<<grid, kPBlock, 0, st>>>(w.rec[0], graph, stop, H, W, w.flags);
-  } else {
-    dim3 grid = grid_rows(H, W, kPBlock);
-    grid.z = z;
-    k_paths_init<K, false><<<grid, kPBlock, 0, st>>>(w.rec[0], graph, stop, H, W, w.flags);
-  }
-  SOIL_LAUNCH_CHECK();
-  t_paths_info.chunks += 1;
-  t_paths_info.vec_chunks += vec ? 1 : 0;
-
-  // Rounds from `list_from` on run over the lists; the dense round in front of them makes the first lists.
-  // SOIL_PATHS_LIST_FROM: that round (0, or beyond the last round: dense rounds throughout), read per call.
-  const char* const e = std::getenv("SOIL_PATHS_LIST_FROM");
-  const int list_from_env = e ? std::atoi(e) : 1;
-  const int rounds = ceil_log2(hw);
-  const int list_from = (list_from_env >= 1 && list_from_env < rounds) ? list_from_env : rounds;
-  // SOIL_PATHS_IDX64=1 (read per call): 64-bit offsets whatever the size — the form a single model of 2^28 cells or
-  // more takes, reached by the tests at small shapes through it.
-  const char* const e64 = std::getenv("SOIL_PATHS_IDX64");
-  const bool idx32 = static_cast<uint64_t>(elem) * sizeof(uint4) < (1ull << 32) && !(e64 && std::atoi(e64) == 1);
-  t_paths_info.idx64_chunks += idx32 ? 0 : 1;
-  t_paths_info.rounds = rounds;
-  const uint32_t seg32 = static_cast<uint32_t>(L.seg);
-  for (int r = 0; r < rounds; ++r) {
-    uint4* const o = w.rec[(r + 1) & 1];
-    const uint4* const in = w.rec[r & 1];
-    if (r >= list_from) {
-      const uint32_t *li = w.list[r & 1], *fi = w.fill[r & 1];
-      uint32_t *lo = w.list[(r + 1) & 1], *fo = w.fill[(r + 1) & 1];
-      if (idx32) k_paths_list<uint32_t><<<L.groups, kPBlock, 0, st>>>(o, in, li, fi, lo, fo, seg32);
-      else k_paths_list<int64_t><<<L.groups, kPBlock, 0, st>>>(o, in, li, fi, lo, fo, seg32);
-      continue;
+                       int64_t models, int64_t H, int64_t W, const PathScales& scales, char* scratch, hipStream_t st) {
+  auto init = [&](const PtrChunk& c) {
+    const bool vec = ptr_vec_init(W, reinterpret_cast<uintptr_t>(graph) | reinterpret_cast<uintptr_t>(stop));
+    const dim3 grid = ptr_init_grid(c, H, W, vec);
+    if (vec) k_paths_init<K, true><<<grid, kPBlock, 0, st>>>(c.rec[0], graph, stop, H, W, c.flags);
+    else k_paths_init<K, false><<<grid, kPBlock, 0, st>>>(c.rec[0], graph, stop, H, W, c.flags);
+    return vec;
+  };
+  auto round = [&](const PtrChunk& c, const PtrRound& q) {
+    uint4* const o = c.rec[(q.r + 1) & 1];
+    const uint4* const in = c.rec[q.r & 1];
+    if (q.list_in) {
+      if (c.idx32)
+        k_paths_list<uint32_t><<<c.groups, kPBlock, 0, st>>>(o, in, q.list_in, q.fill_in, q.list_out, q.fill_out, c.seg);
+      else
+        k_paths_list<int64_t><<<c.groups, kPBlock, 0, st>>>(o, in, q.list_in, q.fill_in, q.list_out, q.fill_out, c.seg);
+    } else if (c.idx32) {
+      k_paths_round<uint32_t><<<c.groups, kPBlock, 0, st>>>(o, in, c.elem, c.flags, q.r, q.list_out, q.fill_out, c.seg);
+    } else {
+      k_paths_round<int64_t><<<c.groups, kPBlock, 0, st>>>(o, in, c.elem, c.flags, q.r, q.list_out, q.fill_out, c.seg);
     }
-    // (list_from == rounds: dense rounds throughout, and the last of them has nobody to make lists for)
-    uint32_t* const lo = list_from < rounds && r + 1 == list_from ? w.list[(r + 1) & 1] : nullptr;
-    uint32_t* const fo = w.fill[(r + 1) & 1];
-    if (idx32) k_paths_round<uint32_t><<<L.groups, kPBlock, 0, st>>>(o, in, elem, w.flags, r, lo, fo, seg32);
-    else k_paths_round<int64_t><<<L.groups, kPBlock, 0, st>>>(o, in, elem, w.flags, r, lo, fo, seg32);
-  }
-  SOIL_LAUNCH_CHECK();
-
-  const int64_t per_model = (hw + kPBlock - 1) / kPBlock;
-  // (a few thousand work-groups in all stride over the cells; a batch of many small models has one per model)
-  const int64_t want = (8192 + models - 1) / models;
-  dim3 grid(static_cast<unsigned>(per_model < want ? per_model : want), 1, z);
-  k_paths_final<<<grid, kPBlock, 0, st>>>(terminal, steps, length, w.rec[rounds & 1], hw, scales);
-  SOIL_LAUNCH_CHECK();
-  return SOIL_OK;
+  };
+  auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
+    k_paths_final<<<grid, kPBlock, 0, st>>>(terminal, steps, length, rec, H * W, scales);
+  };
+  return ptr_chunk(t_paths_info, models, H, W, 0, scratch, init, round, fin);
 }
 
 // What both entries refuse before any device work, under the entry's name
 static int check_flow_paths(const char* what, const void* terminal, const void* steps, const void* length,
-                     const void* graph, const void* scale, int64_t B, int64_t H, int64_t W, int edge,
-                     int64_t n_scales) {
+                            const void* graph, const void* scale, int64_t B, int64_t H, int64_t W, int edge,
+                            int64_t n_scales) {
   const std::string w(what);
   SOIL_REQUIRE(graph, w + ": null graph");
   SOIL_REQUIRE(terminal || steps || length, w + ": no output asked for (terminal, steps and length are all null)");
   SOIL_REQUIRE(!length || scale, w + ": length needs a scale");
-  SOIL_REQUIRE(B >= 1, w + ": B must be >= 1");
-  SOIL_REQUIRE(H >= 1 && W >= 1, w + ": empty grid");
-  SOIL_REQUIRE(H <= INT32_MAX / W, w + ": a model must have 1..2^31-1 cells (int32 graph)");
-  SOIL_REQUIRE(n_scales == 1 || n_scales == B, w + ": n_scales must be 1 or B");
-  SOIL_REQUIRE(edge == SOIL_D4 || edge == SOIL_D8, w + ": invalid edge enumerator");
-  return SOIL_OK;
+  return check_grid_batch(w, B, H, W, edge, n_scales);
 }
 
-// Chunks of whole models, one after the other on `st` through one block of workspace slot WS_FLOW_PATHS (the
-// entries' own: they return with their work in flight): the B scale records first, then the chunk's scratch.
+// A call through workspace slot WS_FLOW_PATHS (flow_paths.hpp ptr_run); the scales are read only for `length`
 static int flow_paths_run(int32_t* terminal, int32_t* steps, float* length, const int32_t* graph, const int32_t* stop,
-                   int64_t B, int64_t H, int64_t W, int edge, const float* scales, int64_t n_scales,
-                   hipStream_t st) {
-  const int64_t hw = H * W, per = paths_chunk_models(hw);
-  t_paths_info = PathsInfo{0, 0, 0, 0};
-  const bool per_model = length && n_scales > 1;
-  const size_t b_scales = per_model ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0;
-  const int64_t first_chunk = B < per ? B : per;
-  void* base = nullptr;
-  if (int rc = workspace_get(WS_FLOW_PATHS, b_scales + paths_layout(first_chunk * hw).bytes(), &base); rc != SOIL_OK)
-    return rc;
-  PathScales sc{nullptr, PathScale{0.0, 0.0, 0.0}};
-  if (length) sc.one = path_scale(scales);
-  if (per_model) {
-    std::vector<PathScale> host(static_cast<size_t>(B));
-    for (int64_t b = 0; b < B; ++b) host[static_cast<size_t>(b)] = path_scale(scales + 2 * b);
-    if (int rc = batch_upload(base, host.data(), sizeof(PathScale) * host.size(), st); rc != SOIL_OK) return rc;
-    sc.per_model = static_cast<const PathScale*>(base);
-  }
-  char* const scratch = static_cast<char*>(base) + b_scales;
-  for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int64_t nb = B - b0 < per ? B - b0 : per, at = b0 * hw;
-    PathScales s = sc;
-    if (s.per_model) s.per_model += b0;
-    auto go = edge == SOIL_D4 ? paths_chunk<4> : paths_chunk<8>;
-    if (int rc = go(terminal ? terminal + at : nullptr, steps ? steps + at : nullptr, length ? length + at : nullptr,
-                    graph + at, stop ? stop + at : nullptr, nb, H, W, s, scratch, st);
-        rc != SOIL_OK)
-      return rc;
-  }
-  return SOIL_OK;
+                          int64_t B, int64_t H, int64_t W, int edge, const float* scales, int64_t n_scales,
+                          hipStream_t st) {
+  auto go = edge == SOIL_D4 ? paths_chunk<4> : paths_chunk<8>;
+  return ptr_run(WS_FLOW_PATHS, t_paths_info, B, H, W, 0, length ? scales : nullptr, n_scales,
+                 PathScale{0.0, 0.0, 0.0}, st, [&](int64_t b0, int64_t nb, const PathScales& s, char* scratch) {
+                   const int64_t at = b0 * H * W;
+                   return go(terminal ? terminal + at : nullptr, steps ? steps + at : nullptr,
+                             length ? length + at : nullptr, graph + at, stop ? stop + at : nullptr, nb, H, W, s,
+                             scratch, st);
+                 });
 }
 
 }  // namespace soil
@@ -389,8 +218,7 @@ int soil_flow_paths_batch(int32_t* terminal, int32_t* steps, float* length, cons
 
 int soil_flow_paths_info(int64_t info[4]) {
   SOIL_REQUIRE(info, "flow_paths_info: null info");
-  info[0] = t_paths_info.chunks, info[1] = t_paths_info.vec_chunks;
-  info[2] = t_paths_info.idx64_chunks, info[3] = t_paths_info.rounds;
+  t_paths_info.store(info);
   return SOIL_OK;
 }
 

@@ -361,13 +361,18 @@ def flow_length_batch(graph, edge_, scale, stop=None):
     return _flow_paths_batch("flow_length_batch", graph, edge_, scale, stop, (False, False, True))[2]
 
 
+def _call_info(entry):
+    """The info record of a pointer-doubling entry (csrc/flow_paths.hpp PtrInfo) as a dict."""
+    info = (C.c_int64 * 4)()
+    _call(entry, info)
+    return dict(zip(("chunks", "vec_chunks", "idx64_chunks", "rounds"), (int(v) for v in info)))
+
+
 def flow_paths_info():
     """What this thread's last flow_paths / flow_paths_batch call did (soil_flow_paths_info): a dict with the number of
     `chunks`, of chunks whose init pass took the 16-byte form (`vec_chunks`), of chunks on 64-bit offsets
     (`idx64_chunks`) and the `rounds` per chunk."""
-    info = (C.c_int64 * 4)()
-    _call("soil_flow_paths_info", info)
-    return dict(zip(("chunks", "vec_chunks", "idx64_chunks", "rounds"), (int(v) for v in info)))
+    return _call_info("soil_flow_paths_info")
 
 
 # ---- downstream sums (soil_hip.h: "flow graphs: downstream sums"): x[n] = a[n] L(n) + b[n] x[r(n)] down a receiver
@@ -491,9 +496,7 @@ def downstream_info():
     """What this thread's last downstream / stream_power call (or _batch form) did (soil_downstream_info): a dict with
     the number of `chunks`, of chunks whose init pass took the 16-byte form (`vec_chunks`), of chunks on 64-bit
     offsets (`idx64_chunks`) and the `rounds` per chunk."""
-    info = (C.c_int64 * 4)()
-    _call("soil_downstream_info", info)
-    return dict(zip(("chunks", "vec_chunks", "idx64_chunks", "rounds"), (int(v) for v in info)))
+    return _call_info("soil_downstream_info")
 
 
 def fill_depressions(height, edge_=None):

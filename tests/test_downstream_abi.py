@@ -267,7 +267,10 @@ def test_the_surfaces():
     knobs = open(os.path.join(ROOT, "docs", "KNOBS.md")).read()
     for knob in ("SOIL_PATHS_LIST_FROM", "SOIL_PATHS_IDX64", "SOIL_FLOW_BATCH_CELLS", "SOIL_PATHS_GROUPS"):
         line = [l for l in knobs.splitlines() if l.startswith("| `%s` " % knob)]
-        assert len(line) == 1 and "soillib_amd/csrc/downstream.hip" in line[0] and "soil_downstream" in line[0], knob
+        # (read in the driver the entries share with soil_flow_paths, csrc/flow_paths.hpp)
+        assert len(line) == 1 and "soillib_amd/csrc/flow_paths.hpp" in line[0] and "soil_downstream" in line[0], knob
+    source = open(os.path.join(ROOT, "soillib_amd", "csrc", "downstream.hip")).read()
+    assert '#include "flow_paths.hpp"' in source and "ptr_run(WS_DOWNSTREAM" in source
 
 
 def test_the_call_info_needs_no_device():

@@ -462,6 +462,31 @@ def test_the_rounds_in_this_process_with_the_lists_off_and_late(hip, monkeypatch
                         assert _info() == dict(chunks=1, vec_chunks=int(W % 4 == 0), idx64_chunks=int(idx64), rounds=len(bin(H * W - 1)) - 2)
 
 
+def test_the_two_call_infos_stay_each_entry_s_own(hip, monkeypatch):
+    """One driver fills both records (csrc/flow_paths.hpp ptr_run): a flow_paths_batch call of 2 + 2 + 1 models and a
+    single-grid downstream call, in either order, leave each entry's info what its own call made it, and both calls
+    give the restatements' bits."""
+    import test_gpu_flow_paths as fp
+    graph, stop, scales, paths_want = fp._stack(5, 8, 5, D8)
+    g = _graphs(3, 5, D8)["hostile"]
+    down_want = _want(3, 5, D8, "hostile", "none", SCALES[1], 0, "sum")
+    paths_info = dict(chunks=3, vec_chunks=3, idx64_chunks=0, rounds=6)        # 80 cells a chunk; ceil(log2 40)
+    down_info = dict(chunks=1, vec_chunks=0, idx64_chunks=0, rounds=4)         # W = 5: scalar init; ceil(log2 15)
+
+    def paths():
+        monkeypatch.setenv("SOIL_FLOW_BATCH_CELLS", "80")
+        fp._same_words(fp._batch(graph, D8, scales, stop), paths_want, "5x8 x 5 in chunks of 80 cells")
+        monkeypatch.delenv("SOIL_FLOW_BATCH_CELLS")
+
+    def down():
+        _same_words(_run_mode(g, D8, _coeffs(3, 5, 0), "sum", SCALES[1], None), down_want, "hostile 3x5")
+
+    for first, second in ((paths, down), (down, paths)):
+        first()
+        second()
+        assert fp._info() == paths_info and _info() == down_info, (first.__name__, fp._info(), _info())
+
+
 # ------------------------------------------------------------------ isolation
 
 def test_a_hostile_model_between_two_benign_ones(hip):
