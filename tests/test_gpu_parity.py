@@ -702,7 +702,8 @@ def test_steepest_ties_and_near_ties(hip, oracle, kind):
         assert_bit_equal(to_np(soil.direction(gh, edge)), oracle.direction(h, edge), "direction, " + kind)
     sc = (0.4, 1.7)
     assert_bit_equal(to_np(soil.negslope(gh, sc)), oracle.negslope(h, sc), "negslope, " + kind)
-    big = (3e11, 2e-12)                         # scales at the ends of the plain range of a denominator
+    big = (3e11, 2e-12)                         # scales inside the plain range of a denominator (2^-40 .. 2^40; the ends
+                                                # themselves: tests/test_gpu_stencils_hostile.py)
     assert_bit_equal(to_np(soil.negslope(gh, big)), oracle.negslope(h, big), "negslope, " + kind)
 
 

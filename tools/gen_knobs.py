@@ -90,8 +90,8 @@ KNOBS = {
     "SOIL_CELLS_SPLIT": ("cells", "0: an eager step's cell phase as one 112-byte kernel instead of the 84-byte kernel + a zeroing pass"),
     "SOIL_WIN_SHAPE": ("stencils", "0..8: force the row-window walk of the four-cells-per-thread kernels (window.hpp) [per kernel and grid]"),
     "SOIL_WIN_FLAT_ORDER": ("stencils", "0: the flat window shape in natural block order instead of XCD-contiguous row ranges (A/B)"),
-    "SOIL_LAP2_BAND": ("stencils", "rows per band of laplacian D=2 [16]"),
-    "SOIL_NORMAL_BAND": ("stencils", "rows per band of the device normal kernel [8]"),
+    "SOIL_LAP2_BAND": ("stencils", "rows per band of laplacian D=2: 4, 8 or 16, any other value 32; read once per process [16]"),
+    "SOIL_NORMAL_BAND": ("stencils", "rows per band of the device normal kernel: 4, 8 or 16, any other value 32; read once per process [8]"),
     "SOIL_RAKE_GROUPS": ("graph", "work-groups of a rake-compress round [8192]"),
     "SOIL_RAKE_LIST_FROM": ("graph", "first rake-compress round that runs over the lists of pending cells [2; 0: dense rounds throughout]"),
     "SOIL_FLOW_BATCH_CELLS": ("graph", "cap on the cells of a chunk of soil_accumulate_batch, of soil_flow_paths_batch and of soil_downstream_batch / soil_stream_power_batch — whole models, at least one — below the default, the most that keep the rounds' 32-bit offsets [2^32 / (4 K) - 1; flow paths and downstream sums: 2^28 - 1], read per call; the tests reach the chunking with tiny shapes through it"),
