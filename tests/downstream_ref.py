@@ -139,6 +139,20 @@ def words(p):
     return p.view(np.uint32 if p.dtype == np.float32 else np.uint64)
 
 
+def same_words(got, want, what):
+    """(out, out64) of the device against the restatement's; None: not asked for."""
+    for g, w, name in zip(got, want, ("out", "out64")):
+        if g is None:
+            continue
+        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, w.dtype, g.shape, w.shape)
+        bad = words(g) != words(w)
+        if bad.any():
+            at = tuple(np.argwhere(bad)[0])
+            raise AssertionError("%s: %s differs in %d of %d cells, first at %s: %r (0x%x) against %r (0x%x)" % (
+                what, name, bad.sum(), bad.size, at, g[at], words(g)[at], w[at], words(w)[at]))
+
+
 def ulps32(x, y):
     """The distance of two float32 arrays in units in the last place, cell by cell (equal words: 0; NaN against a
     number, or two different NaN words: a huge count)."""

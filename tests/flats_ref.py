@@ -88,6 +88,17 @@ def receivers(graph, h, dist, edge):
     return out
 
 
+def same(got, want, what):
+    """Two int32 planes, cell for cell."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.dtype == want.dtype == np.int32 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
+    bad = got != want
+    if bad.any():
+        at = tuple(np.argwhere(bad)[0])
+        raise AssertionError("%s: %d of %d cells differ, first at %s: %d against %d" % (
+            what, bad.sum(), bad.size, at, got[at], want[at]))
+
+
 def interior_terminals(graph):
     """Cells without a receiver that are not on the grid's border."""
     t = np.asarray(graph) < 0

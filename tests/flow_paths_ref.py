@@ -242,3 +242,21 @@ def words(a):
     """The bit patterns of an int32 or float32 array."""
     a = np.ascontiguousarray(a)
     return a.view(np.uint32) if a.dtype == np.float32 else a.astype(np.int32).view(np.uint32)
+
+
+NAMES = ("terminal", "steps", "length")
+
+
+def same_words(got, want, what):
+    """(terminal, steps, length) of the device against a restatement's, word for word; None: not asked for."""
+    for g, w, name in zip(got, want, NAMES):
+        assert (g is None) == (w is None), (what, name)
+        if g is None:
+            continue
+        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, w.dtype, g.shape, w.shape)
+        bad = words(g) != words(w)
+        if bad.any():
+            at = tuple(np.argwhere(bad)[0])
+            raise AssertionError("%s: %s differs in %d of %d cells, first at %s: %r (0x%08x) against %r (0x%08x)" % (
+                what, name, bad.sum(), bad.size, at, g[at], words(g)[at], w[at], words(w)[at]))

@@ -8,7 +8,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _build(tmp, name="test_cpp_api"):
+def _build(tmp, name="test_cpp_api", extra=()):
+    """`extra`: further compiler flags (tests/test_gpu_cpp_ops.py: the warnings, as errors)."""
     from soillib_amd import _abi
     assert os.path.exists(_abi.LIB_PATH), "build libsoil_hip.so first"
     exe = os.path.join(str(tmp), name)
@@ -17,7 +18,7 @@ def _build(tmp, name="test_cpp_api"):
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-pthread", "-I", os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", exe,
                            "-L", libdir, "-lsoil_hip", "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath,/opt/rocm/lib"] + hip)
+                           "-Wl,-rpath,/opt/rocm/lib"] + hip + list(extra))
     return exe
 
 

@@ -47,18 +47,7 @@ DT = 3.5
 MODES = ("sum", "sum_no_b", "power")
 
 
-def _same_words(got, want, what):
-    """(out, out64) of the device against the restatement's; None: not asked for."""
-    for g, w, name in zip(got, want, ("out", "out64")):
-        if g is None:
-            continue
-        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, w.dtype, g.shape, w.shape)
-        bad = dref.words(g) != dref.words(w)
-        if bad.any():
-            at = tuple(np.argwhere(bad)[0])
-            raise AssertionError("%s: %s differs in %d of %d cells, first at %s: %r (0x%x) against %r (0x%x)" % (
-                what, name, bad.sum(), bad.size, at, g[at], dref.words(g)[at], w[at], dref.words(w)[at]))
+_same_words = dref.same_words             # (shared with tests/test_gpu_cpp_ops.py)
 
 
 def _info():

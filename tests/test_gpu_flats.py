@@ -35,14 +35,7 @@ EDGES = [D4, D8]
 PER_CHECK = int(os.environ.get("SOIL_FLATS_PER_CHECK", "3"))      # launches a look at the "changed" word (docs/KNOBS.md)
 
 
-def _same(got, want, what):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.dtype == want.dtype == np.int32 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
-    bad = got != want
-    if bad.any():
-        at = tuple(np.argwhere(bad)[0])
-        raise AssertionError("%s: %d of %d cells differ, first at %s: %d against %d" % (
-            what, bad.sum(), bad.size, at, got[at], want[at]))
+_same = ref.same                          # (shared with tests/test_gpu_cpp_ops.py)
 
 
 @functools.lru_cache(maxsize=None)

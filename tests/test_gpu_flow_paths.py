@@ -39,21 +39,8 @@ SCALAR = [(1, 1), (1, 5), (5, 1), (2, 2), (37, 53)]
 VECTOR = [(3, 4), (33, 260), (9, 1028), (256, 256)]
 BS = [1, 2, 3, 7, 64]
 SCALES = [(1.0, 1.0), (0.25, 3.0), (1e-3, 1e3)]
-NAMES = ("terminal", "steps", "length")
-
-
-def _same_words(got, want, what):
-    for g, w, name in zip(got, want, NAMES):
-        assert (g is None) == (w is None), (what, name)
-        if g is None:
-            continue
-        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, w.dtype, g.shape, w.shape)
-        bad = ref.words(g) != ref.words(w)
-        if bad.any():
-            at = tuple(np.argwhere(bad)[0])
-            raise AssertionError("%s: %s differs in %d of %d cells, first at %s: %r (0x%08x) against %r (0x%08x)" % (
-                what, name, bad.sum(), bad.size, at, g[at], ref.words(g)[at], w[at], ref.words(w)[at]))
+NAMES = ref.NAMES
+_same_words = ref.same_words              # (shared with tests/test_gpu_cpp_ops.py)
 
 
 def _info():

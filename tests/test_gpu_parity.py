@@ -14,8 +14,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from util import (assert_bit_equal, assert_receivers_close, product_param, rng_to_gpu, script_param, terrain,
-                  to_gpu, to_np)
+from util import (assert_bit_equal, assert_debris_close, assert_fluvial_close, assert_receivers_close,
+                  assert_solve_uniform_close, flux_close, product_param, rng_to_gpu, script_param, terrain, to_gpu, to_np)
 
 pytestmark = pytest.mark.gpu
 
@@ -320,19 +320,7 @@ def test_albedo_ops_bit_exact(hip, oracle):
 
 # ------------------------------------------------------- particle ops
 
-def _flux_close(got, want, what):
-    """Same trajectories, different fp32 summation order: compare against the
-    magnitude accumulated in each cell.  The absolute term covers cells of the signed (velocity)
-    planes whose deposits cancel: their rounding error goes with the magnitude of the terms — up
-    to the plane's maximum — not with the sum that is left (a lost or doubled deposit would show
-    as an error of the order of the cell's own value)."""
-    scale = np.nanmax(np.abs(want)) + 1e-30
-    np.testing.assert_allclose(got, want, rtol=2e-5, atol=4e-6 * scale, err_msg=what)
-    # the same set of visited cells.  Deposits that have decayed to the edge of the fp32 range are
-    # exempt: the oracle's expf_ flushes below e^-87, the attenuations' v_exp_f32 (att_exp,
-    # soil_math.hpp) below 2^-126 — a deposit of 1e-38 on one side, none on the other
-    assert (got[np.abs(want) > 1e-25 * scale] != 0).all(), what + ": different set of visited cells"
-    assert (np.abs(got[want == 0]) <= 1e-30 * scale).all(), what + ": different set of visited cells"
+_flux_close = flux_close                  # (tests/util.py: shared with tests/test_gpu_cpp_ops.py)
 
 
 @pytest.fixture(params=["direct", "staged", "tiled", "tiled-full", "tiled-panels", "tiled-sparse", "tiled-sparse-full"])
@@ -390,12 +378,7 @@ def test_transport_fluvial_parity(hip, oracle, particle_mode, H, W, N, which):
                            g["vf"], None, g["af"], to_gpu(asrc), grng, scale, pp)
     assert soil.particle_steps(reset=True) == steps     # same walks, step for step
     assert (to_np(grng)["offset"] == orng["offset"]).all()
-    for k in ("wf", "mf", "vf"):
-        _flux_close(to_np(g[k]), o[k], "fluvial flux " + k)
-    for k in ("wh", "m", "v"):
-        np.testing.assert_allclose(to_np(g[k]), o[k], rtol=3e-5,
-                                   atol=3e-6 * (np.nanmax(np.abs(o[k])) + 1e-30), err_msg=k)
-    np.testing.assert_allclose(to_np(g["af"]), o["af"], rtol=1e-3, atol=1e-5)
+    assert_fluvial_close({k: to_np(v) for k, v in g.items()}, o)
 
 
 @pytest.mark.parametrize("H,W,N", [(64, 64, 4096), (40, 96, 3000), (50, 33, 700), (136, 200, 20000)])
@@ -424,12 +407,7 @@ def test_transport_debris_parity(hip, oracle, particle_mode, H, W, N):
     soil.transport_debris(to_gpu(layers), g["v"], g["vf"], g["m"], g["mf"], None, g["af"],
                           to_gpu(asrc), grng, scale, pp)
     assert soil.particle_steps(reset=True) == steps
-    np.testing.assert_allclose(to_np(g["af"]), o["af"], rtol=1e-3, atol=1e-5)
-    for k in ("mf", "vf"):
-        _flux_close(to_np(g[k]), o[k], "debris flux " + k)
-    for k in ("m", "v"):
-        np.testing.assert_allclose(to_np(g[k]), o[k], rtol=3e-5,
-                                   atol=3e-6 * (np.nanmax(np.abs(o[k])) + 1e-30), err_msg=k)
+    assert_debris_close({k: to_np(v) for k, v in g.items()}, o)
 
 
 def test_particles_on_slabs_equal_whole_grid(hip, oracle, particle_mode):
@@ -734,10 +712,7 @@ def test_solve_uniform_parity(hip, oracle):
         want = oracle.solve_uniform(flow, src, decay, oracle.rng_seed(N, 1, 0), sc, N)
         got = to_np(soil.solve_uniform(to_gpu(flow), to_gpu(src), to_gpu(decay),
                                        rng_to_gpu(oracle.rng_seed(N, 1, 0)), sc, N))
-        ok = np.isfinite(want)
-        assert (np.isfinite(got) == ok).all()
-        np.testing.assert_allclose(got[ok], want[ok], rtol=5e-5,
-                                   atol=1e-6 * np.abs(want[ok]).max())
+        assert_solve_uniform_close(got, want)
 
 
 def test_noise_device_and_host_bit_exact(hip, oracle):

@@ -165,6 +165,53 @@ def assert_receivers_close(oracle, got, want, height, K, seed, offset, T, what="
         assert got[x, y] in idx + [-1] and want[x, y] in idx + [-1], what
 
 
+# ---- the particle launches and solve_uniform against the oracle (test_gpu_parity.py, test_gpu_cpp_ops.py) --------
+
+def flux_close(got, want, what):
+    """Same trajectories, different fp32 summation order: compare against the
+    magnitude accumulated in each cell.  The absolute term covers cells of the signed (velocity)
+    planes whose deposits cancel: their rounding error goes with the magnitude of the terms — up
+    to the plane's maximum — not with the sum that is left (a lost or doubled deposit would show
+    as an error of the order of the cell's own value)."""
+    scale = np.nanmax(np.abs(want)) + 1e-30
+    np.testing.assert_allclose(got, want, rtol=2e-5, atol=4e-6 * scale, err_msg=what)
+    # the same set of visited cells.  Deposits that have decayed to the edge of the fp32 range are
+    # exempt: the oracle's expf_ flushes below e^-87, the attenuations' v_exp_f32 (att_exp,
+    # soil_math.hpp) below 2^-126 — a deposit of 1e-38 on one side, none on the other
+    assert (got[np.abs(want) > 1e-25 * scale] != 0).all(), what + ": different set of visited cells"
+    assert (np.abs(got[want == 0]) <= 1e-30 * scale).all(), what + ": different set of visited cells"
+
+
+def assert_fluvial_close(got, want):
+    """The planes of a transport_fluvial launch, as numpy, against the oracle's: dicts with the flux planes wf, mf,
+    vf, the normalised planes wh, m, v and the colour flux af."""
+    for k in ("wf", "mf", "vf"):
+        flux_close(got[k], want[k], "fluvial flux " + k)
+    for k in ("wh", "m", "v"):
+        np.testing.assert_allclose(got[k], want[k], rtol=3e-5,
+                                   atol=3e-6 * (np.nanmax(np.abs(want[k])) + 1e-30), err_msg=k)
+    np.testing.assert_allclose(got["af"], want["af"], rtol=1e-3, atol=1e-5)
+
+
+def assert_debris_close(got, want):
+    """The planes of a transport_debris launch against the oracle's: the flux planes mf, vf, the normalised m, v and
+    the colour flux af."""
+    np.testing.assert_allclose(got["af"], want["af"], rtol=1e-3, atol=1e-5)
+    for k in ("mf", "vf"):
+        flux_close(got[k], want[k], "debris flux " + k)
+    for k in ("m", "v"):
+        np.testing.assert_allclose(got[k], want[k], rtol=3e-5,
+                                   atol=3e-6 * (np.nanmax(np.abs(want[k])) + 1e-30), err_msg=k)
+
+
+def assert_solve_uniform_close(got, want):
+    """solve_uniform's flux against the oracle's: the same cells finite, and those close."""
+    ok = np.isfinite(want)
+    assert (np.isfinite(got) == ok).all()
+    np.testing.assert_allclose(got[ok], want[ok], rtol=5e-5,
+                               atol=1e-6 * np.abs(want[ok]).max())
+
+
 def debris_steps_match(got, want):
     """Steps a debris launch walked against the count of a side that walks every walker to the end (the oracle,
     the direct launch shape): equal — unless this process retires spent debris walkers (soil_set_debris_retire(1);
