@@ -1067,6 +1067,81 @@ int soil_stream_power_batch(float* out, double* out64, const float* height, cons
  * forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
 int soil_downstream_info(int64_t info[4]);
 
+/* ------------------------------------------------------ hillslope diffusion */
+
+/* One implicit step of dh/dt = div(kappa grad h) + u on a grid: the hillslope half of a landscape-evolution step, beside
+ * soil_stream_power's channel half.  The reference has no such call (its example/dem_process.py carries a commented-out
+ * explicit diffuse() of laplacian + multiply + add, stable only for kappa dt / s^2 <= 1/4); the definition is this
+ * library's.
+ *
+ * The step is locally one-dimensional backward Euler: one implicit sweep along `first_axis` (0 or 1), then one along
+ * the other axis.  It is unconditionally stable and first order in time; each sweep is an M-matrix solve, so the step
+ * obeys the maximum principle (without uplift no free cell leaves the range of the non-void heights).  It is NOT
+ * Peaceman-Rachford: that scheme's explicit half steps give up positivity for second order, and at the large dt this
+ * is used with (the dt of a stream-power step) positivity is worth more than second order.
+ *
+ * Grid (H, W), cell n = x * W + y.  `scale` = (sx, sy), the spacings along axis 0 and axis 1 as in soil_flow_paths:
+ * the floats widened to double, ss = s * s made once on the host in double (ss = sx * sx for the sweep along axis 0).
+ *
+ * Cell kinds.  A cell is void if height[n] is NaN.  It is fixed if fixed[n] != 0 (`fixed` may be NULL), or if it
+ * lies on the outermost row or column and border == 1.  Any other cell is free.
+ *
+ * One sweep, for one line of cells 0 .. n-1 (a column for axis 0, a row for axis 1) with right-hand side d, in fp64:
+ * cells i and i+1 are linked iff neither is void.  The weight of the face between them is
+ *     w = (kf * dt) / ss            the product rounded, then the quotient
+ * with kf = kappa where `diffusivity` is NULL, else kf = 0.5 * ((double)k[i] + (double)k[i+1]).  Then
+ *     p_i = w_{i-1/2} if i is free and linked to i-1, else +0.0
+ *     q_i = w_{i+1/2} if i is free and linked to i+1, else +0.0
+ *     b_i = (1.0 + p_i) + q_i
+ * Forward, i ascending: if i is free and linked to i-1
+ *     den = b_i - p_i * g_{i-1},  e_i = (d_i + p_i * e_{i-1}) / den
+ * otherwise den = b_i, e_i = d_i / den; in both cases g_i = q_i / den.  Backward, i descending:
+ *     x_i = e_i + g_i * x_{i+1} if i is free and linked to i+1, else x_i = e_i
+ * Every operation is fp64, rounded once, with no contraction (__dmul_rn, __dadd_rn, __dsub_rn, __ddiv_rn; a product
+ * is rounded before the sum or difference it enters).  The selects are by predicate: a void neighbour's NaN is never
+ * multiplied by zero.
+ *
+ * The first sweep's d is (double)height[n]; on a free cell with an `uplift` plane it is
+ * (double)height[n] + dt * (double)uplift[n], soil_stream_power's expression.  The second sweep's d is the first
+ * sweep's x, unrounded.  A fixed cell therefore comes out as exactly (double)height[n] and a void cell as NaN.
+ * out64[n] = x, out[n] = (float)x rounded to nearest (at least one of the two is non-NULL); any NaN is written as
+ * 0x7fc00000 / 0x7ff8000000000000, the words soil_downstream writes.  +-inf heights and negative, zero or NaN
+ * diffusivities are used as they are and give what the arithmetic gives (dt == 0 or kappa == 0 gives the heights
+ * back, except that a free, linked cell holding -0.0 comes out as +0.0: -0.0 + 0.0 * e, and that an infinite
+ * neighbour makes 0 * inf).
+ *
+ * The result is one definite bit pattern, fixed by the planes and the arguments alone: tiling, chunking, batching,
+ * offset width and alignment do not show.
+ *
+ * `scale` / `scales` (n_scales pairs, 1 or B) are HOST arrays read before the call returns.  The entries are
+ * stream-ordered and do not synchronise (a call that finds its cached scratch too small synchronises the device
+ * before replacing it, as everywhere); a host thread's calls on one device share one cached scratch block of their
+ * own, 40 bytes a cell of a chunk (16 bytes a cell of e and g, x replacing e in place, and the transposed planes of the
+ * sweep along axis 1): issue them on ONE stream, or order the streams yourself.
+ *
+ * Batch form: the conventions of soil_stream_power_batch.  Model-major planes; model b's slice of each output is bit
+ * for bit what the single call gives for model b's slices alone, with scales[b] or the one pair; nothing reaches
+ * another model.  Chunks of whole models, at most 65535 and at most 2^28 - 1 cells, SOIL_FLOW_BATCH_CELLS lowers the
+ * cells of a chunk; a model of 2^29 cells or more runs on 64-bit offsets (SOIL_PATHS_IDX64=1 forces them).  Per chunk
+ * five launches (first_axis == 0) or four, whatever B is.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): null `height`, both outputs null, an output that aliases an input plane (or the other output),
+ * null `scale`, B, H or W < 1, H * W > INT32_MAX, n_scales not 1 or B, a scale entry that is not a positive finite
+ * float, a `dt` that is negative or not finite, a `kappa` that is negative or not finite while `diffusivity` is NULL
+ * (with a plane kappa is not read), `border` not 0 / 1, `first_axis` not 0 / 1.  Otherwise, without a device:
+ * SOIL_ERR_NO_DEVICE. */
+int soil_diffuse(float* out, double* out64, const float* height, const float* diffusivity, const float* uplift,
+                 const int32_t* fixed, int64_t H, int64_t W, const float scale[2], double kappa, double dt,
+                 int border, int first_axis, void* stream);
+int soil_diffuse_batch(float* out, double* out64, const float* height, const float* diffusivity, const float* uplift,
+                       const int32_t* fixed, int64_t B, int64_t H, int64_t W, const float* scales, int64_t n_scales,
+                       double kappa, double dt, int border, int first_axis, void* stream);
+/* What the calling host thread's last soil_diffuse or soil_diffuse_batch call did: info[0] kernel launches, info[1]
+ * chunks, info[2] chunks on 64-bit offsets, info[3] bytes of scratch the call asked for.  All zero before the first
+ * call; needs no device. */
+int soil_diffuse_info(int64_t info[4]);
+
 /* ------------------------------------------------ flow graphs: conditioning */
 
 /* Routing across flats and filled lakes.  soil_fill_depressions returns a surface on which every lake is level, and

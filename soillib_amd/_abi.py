@@ -240,6 +240,11 @@ SIGNATURES = {
     "soil_stream_power": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double, vp]),
     "soil_stream_power_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, C.c_double, vp]),
     "soil_downstream_info": (cint, [C.POINTER(i64)]),
+    # hillslope diffusion: out / out64 (one may be NULL), height, diffusivity / uplift / fixed (each may be NULL);
+    # host scale pairs, kappa, dt, border, first_axis
+    "soil_diffuse": (cint, [vp, vp, vp, vp, vp, vp, i64, i64, F3, C.c_double, C.c_double, cint, cint, vp]),
+    "soil_diffuse_batch": (cint, [vp, vp, vp, vp, vp, vp, i64, i64, i64, F3, i64, C.c_double, C.c_double, cint, cint, vp]),
+    "soil_diffuse_info": (cint, [C.POINTER(i64)]),
     # flats and filled lakes: dist / out, in, height, dist
     "soil_flat_distance": (cint, [vp, vp, i64, i64, cint, vp]),
     "soil_flat_distance_batch": (cint, [vp, vp, i64, i64, i64, cint, vp]),

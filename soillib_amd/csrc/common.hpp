@@ -68,6 +68,7 @@ enum WorkspaceSlot {
   WS_FLOW_PATHS = 15,    // flow_paths.hip: soil_flow_paths(_batch): scale records, the two record buffers, lists
   WS_FLATS = 16,         // flats.hip: soil_flat_distance(_batch): the tiles' marks, one mask byte per cell
   WS_DOWNSTREAM = 17,    // downstream.hip: soil_downstream / soil_stream_power (_batch): scale records, records, B, lists
+  WS_DIFFUSE = 18,       // diffuse.hip: soil_diffuse(_batch): scale records, the e and g planes of a chunk
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();

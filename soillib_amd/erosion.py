@@ -841,6 +841,62 @@ class ErosionBatch:
         area = self.drainage(graph=graph, edge=e)
         return soil.stream_power_batch(filled, graph, soil.erosivity(area, K, m), e, scale, dt, uplift)
 
+    def _check_diffuse(self, who, dt, kappa, diffusivity, uplift, fixed, border, first_axis):
+        """The arguments of diffuse() and of the diffusion half of evolve(), or ValueError."""
+        if isinstance(dt, bool) or not isinstance(dt, numbers.Real) or not math.isfinite(dt) or dt < 0:
+            raise ValueError("ErosionBatch.%s: dt must be a finite number >= 0, got %r" % (who, dt))
+        if (kappa is None) == (diffusivity is None):
+            raise ValueError("ErosionBatch.%s: exactly one of kappa and diffusivity must be given" % who)
+        if kappa is not None and (isinstance(kappa, bool) or not isinstance(kappa, numbers.Real)
+                                  or not math.isfinite(kappa) or kappa < 0):
+            raise ValueError("ErosionBatch.%s: kappa must be a finite number >= 0, got %r" % (who, kappa))
+        for name, t in (("diffusivity", diffusivity), ("uplift", uplift)):
+            if t is not None:
+                self._flow_tensor(who, name, t, silt.float32)
+        if fixed is not None:
+            self._flow_tensor(who, "fixed", fixed, silt.int32)
+        if border not in ("fixed", "free"):
+            raise ValueError("ErosionBatch.%s: border must be 'fixed' or 'free', got %r" % (who, border))
+        if isinstance(first_axis, bool) or first_axis not in (0, 1):
+            raise ValueError("ErosionBatch.%s: first_axis must be 0 or 1, got %r" % (who, first_axis))
+
+    def diffuse(self, dt, kappa=None, diffusivity=None, uplift=None, fixed=None, border="fixed", first_axis=0,
+                double=False):
+        """One implicit step of hillslope diffusion of every model's `height` over `dt` (soil.diffuse_batch) with the
+        batch's scale(s), as flow_length() takes them: a (B, H, W) float32 silt GPU tensor (float64 with `double`).
+        Exactly one of `kappa` (a number) and `diffusivity` (a (B, H, W) float32 tensor); `uplift`, `fixed`, `border`
+        and `first_axis` as in soil.diffuse.  The batch's own planes are not touched.  A bad argument raises
+        ValueError before any device work.  Nothing synchronises."""
+        from . import soil
+        self._check_diffuse("diffuse", dt, kappa, diffusivity, uplift, fixed, border, first_axis)
+        scale = self._path_scale("diffuse")
+        return soil.diffuse_batch(self.height, scale, dt, kappa, diffusivity, uplift, fixed, border, first_axis, double)
+
+    def evolve(self, dt, K, m=0.5, kappa=None, uplift=None, kind="steepest", edge=None, T=None, offset=0,
+               first_axis=0):
+        """One landscape-evolution step of every model, uplift + stream power + linear diffusion: stream_power(dt, K,
+        m, kind, edge, T, offset, uplift) and then soil.diffuse_batch of its result over the same `dt` with the
+        diffusivity `kappa` and border="fixed" — the outermost cells, the base level of the conditioned graph, keep
+        what the stream-power step left them.  The uplift is applied once, in the stream-power step.  Returns the
+        (B, H, W) float32 heights; the batch's own planes are not touched.  A bad argument raises ValueError before
+        any device work.  Synchronises the stream (the fill does)."""
+        from . import soil
+        self._check_diffuse("evolve", dt, kappa, None, None, None, "fixed", first_axis)
+        for name, v in (("K", K), ("m", m)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (name != "m" and v < 0):
+                raise ValueError("ErosionBatch.evolve: %s must be a finite number%s, got %r" % (
+                    name, "" if name == "m" else " >= 0", v))
+        if kind not in ("steepest", "random_weighted"):
+            raise ValueError("ErosionBatch.evolve: kind must be 'steepest' or 'random_weighted', got %r" % (kind,))
+        self._edge("evolve", edge)
+        if kind == "random_weighted":
+            self._check_draw("evolve", T, offset)
+        if uplift is not None:
+            self._flow_tensor("evolve", "uplift", uplift, silt.float32)
+        scale = self._path_scale("evolve")
+        carved = self.stream_power(dt, K, m, kind, edge, T, offset, uplift)
+        return soil.diffuse_batch(carved, scale, dt, kappa, border="fixed", first_axis=first_axis)
+
     def filled(self, edge=None):
         """The depression-filled surface of every model's `height`: a (B, H, W) float32 silt GPU tensor, model b's
         plane what soil.fill_depressions gives for it alone (soil_fill_depressions_batch: one call for the batch,

@@ -499,6 +499,72 @@ def downstream_info():
     return _call_info("soil_downstream_info")
 
 
+# ---- hillslope diffusion (soil_hip.h: "hillslope diffusion"): one implicit step of dh/dt = div(kappa grad h) + u, a
+# tridiagonal solve per grid line along one axis, then along the other.  Stream-ordered.
+
+def _diffuse(who, dims, height, scale, dt, kappa, diffusivity, uplift, fixed, border, first_axis, double):
+    """soil_diffuse and soil_diffuse_batch.  Every check comes before any device work."""
+    shape = (_hw2 if dims == 2 else _bhw)(height, "%s: height" % who)
+    _float_plane(height, shape, "%s: height" % who)
+    if (kappa is None) == (diffusivity is None):
+        raise ValueError("%s: exactly one of kappa and diffusivity must be given" % who)
+    if kappa is not None and (isinstance(kappa, bool) or not isinstance(kappa, (int, float)) or not math.isfinite(kappa)
+                              or kappa < 0):
+        raise ValueError("%s: kappa must be a finite number >= 0, got %r" % (who, kappa))
+    for name, t in (("diffusivity", diffusivity), ("uplift", uplift)):
+        if t is not None:
+            _float_plane(t, shape, "%s: %s" % (who, name))
+    if fixed is not None:
+        _int_plane(fixed, shape, "%s: fixed" % who)
+    if scale is None:
+        raise ValueError("%s: scale must be one (sx, sy) pair%s" % (who, "" if dims == 2 else " or B pairs"))
+    pairs, n = (_one_pair(scale, who), 1) if dims == 2 else _scale_pairs(scale, shape[0], who)
+    if any(not (v > 0 and math.isfinite(v)) for v in pairs):
+        raise ValueError("%s: scale entries must be positive finite floats, got %r" % (who, scale))
+    if isinstance(dt, bool) or not isinstance(dt, (int, float)) or not math.isfinite(dt) or dt < 0:
+        raise ValueError("%s: dt must be a finite number >= 0, got %r" % (who, dt))
+    if border not in ("fixed", "free"):
+        raise ValueError("%s: border must be 'fixed' or 'free', got %r" % (who, border))
+    if isinstance(first_axis, bool) or first_axis not in (0, 1):
+        raise ValueError("%s: first_axis must be 0 or 1, got %r" % (who, first_axis))
+    h_ptr = _f(height, "height")
+    k_ptr, u_ptr = _opt_f(diffusivity, "diffusivity"), _opt_f(uplift, "uplift")
+    f_ptr = None if fixed is None else _gpu(fixed, silt.int32, "fixed")
+    out = silt.tensor(silt.float64 if double else silt.float32, silt.shape(*shape), silt.gpu)
+    outs = (None, out.c_ptr) if double else (out.c_ptr, None)
+    tail = (pairs,) if dims == 2 else (pairs, n)
+    _call("soil_diffuse" + ("" if dims == 2 else "_batch"), *outs, h_ptr, k_ptr, u_ptr, f_ptr, *shape, *tail,
+          0.0 if kappa is None else float(kappa), float(dt), int(border == "fixed"), int(first_axis), _abi.stream())
+    return out
+
+
+def diffuse(height, scale, dt, kappa=None, diffusivity=None, uplift=None, fixed=None, border="fixed", first_axis=0,
+            double=False):
+    """soil_diffuse: one implicit (backward Euler, one sweep per axis) step of hillslope diffusion
+    dh/dt = div(kappa grad h) + uplift over `dt` on a (H, W) float32 height plane with the spacings (sx, sy) of
+    `scale`; stable for any dt.  Exactly one of `kappa` (a number) and `diffusivity` (a float32 plane) is given.
+    `fixed`: an int32 plane, non-zero cells keep their height; border="fixed" keeps the outermost rows and columns
+    too, "free" closes the edges (no flux: the sum is conserved).  NaN cells are voids: walls without flux, NaN in the
+    result.  `first_axis`: the axis of the first sweep.  Returns the new heights, float32 (float64 with `double`);
+    `height` is left as it is."""
+    return _diffuse("diffuse", 2, height, scale, dt, kappa, diffusivity, uplift, fixed, border, first_axis, double)
+
+
+def diffuse_batch(height, scale, dt, kappa=None, diffusivity=None, uplift=None, fixed=None, border="fixed",
+                  first_axis=0, double=False):
+    """`diffuse` of each of the B models of (B, H, W) planes (soil_diffuse_batch); `scale` is one pair or B pairs."""
+    return _diffuse("diffuse_batch", 3, height, scale, dt, kappa, diffusivity, uplift, fixed, border, first_axis,
+                    double)
+
+
+def diffuse_info():
+    """What this thread's last diffuse / diffuse_batch call did (soil_diffuse_info): a dict with the number of kernel
+    `launches`, of `chunks`, of chunks on 64-bit offsets (`idx64_chunks`) and the `scratch_bytes` it asked for."""
+    info = (C.c_int64 * 4)()
+    _call("soil_diffuse_info", info)
+    return dict(zip(("launches", "chunks", "idx64_chunks", "scratch_bytes"), (int(v) for v in info)))
+
+
 def fill_depressions(height, edge_=None):
     """Priority-flood surface of a DEM (soil_hip.h: soil_fill_depressions) — the
     conditioning step the reference leaves to pysheds (example/dem_condition.py:35-41)."""
