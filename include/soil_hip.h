@@ -1067,6 +1067,78 @@ int soil_stream_power_batch(float* out, double* out64, const float* height, cons
  * forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
 int soil_downstream_info(int64_t info[4]);
 
+/* ----------------------------------------- flow graphs: erosion-deposition */
+
+/* The stream-power step with sediment deposition: the erosion-deposition (xi-q) model of Davy & Lague in the implicit
+ * form of Yuan et al. (2019),
+ *     dh/dt = u - K A^m S + (G / A) * Qs
+ * where Qs is the net material removed from everything upstream.  It is soil_stream_power plus a deposition term fed
+ * by an upstream sum: the first call that needs both soil_accumulate (up the graph) and soil_downstream (down it).
+ * The reference has no such call (its example/dem_process.py names the steps in its comments); the definition is this
+ * library's.
+ *
+ * Grid, edge rule, terminals, `scale`, L(n) and the rounds of the records are word for word those of
+ * soil_stream_power.  There is no `stop` plane: soil_accumulate has none, and the two passes must see the same graph.
+ *
+ * All arithmetic is fp64 with one rounding per operation, in this order, with no contraction.  Per cell n that has an
+ * edge of length L:
+ *     F   = ((double)erosivity[n] * dt) / L
+ *     g   = (double)deposition[n]
+ *     d   = (1.0 + F) + g
+ *     b   = (double)height[n] + dt * (double)uplift[n]      (double)height[n] with uplift == NULL
+ *     B0  = F / d
+ * A terminal keeps (double)height[n], as in soil_stream_power.  `deposition[n]` is G * (cell area) / A[n], made by the
+ * caller as `erosivity` is, so that every operation in the kernels is correctly rounded and can be restated.
+ *
+ * The iterate starts at x^0 = b on the cells with an edge ((double)height[n] on a terminal).  For k = 1 .. iters:
+ *     q[n]  = (float)(b - x^(k-1)[n])   rounded to nearest; +0 on a terminal and wherever that float is not finite
+ *     Qs    = the bits soil_accumulate(graph, q, no decay) gives   (float32: the upstream sum, the cell itself included)
+ *     Qup   = (double)Qs[n] - (double)q[n]
+ *     A0    = (((1.0 + g) * b) + (g * Qup)) / d
+ *     x^k   = the solve x[n] = A0 + B0 * x[r(n)] down the graph, with soil_downstream's rounds, bit for bit, a NaN and
+ *             a cell that is not final after the last round kept as 0x7ff8000000000000
+ * (in iteration 1 q is +0 everywhere, and zeros accumulate to +0).  The self-implicit term: the cell's own share of Qs
+ * is taken at the new iterate, which is what (1 + g) and the + g in d are.  The plain fixed point with all of Qs from
+ * the iterate before diverges for G >= 1 at a small dt; this form contracted in every case tried.
+ * `iters` >= 1 is the caller's: a fixed count keeps the result one definite bit pattern, fixed by the graph, the
+ * planes and the arguments alone; chunking, batching, lists, offsets and alignment do not show.
+ *
+ * With `deposition` all zeros the result is the bits of soil_stream_power (stop == NULL) at any `iters`: d is 1 + F,
+ * (1.0 + 0.0) * b is b and b + 0 * Qup is b — for a finite Qup, and but for b == -0.0, which comes out as +0.0.
+ *
+ * Outputs.  At least one of `out` (float) and `out64` (double) is non-NULL: x^iters, with the NaN words of
+ * soil_downstream.  `flux` (float32, may be NULL): soil_accumulate's bits for the q made from the returned iterate,
+ * one more q pass and accumulation; at a terminal it is the sediment delivered to that base level.  `residual` (may
+ * be NULL): a device array of B doubles (one for the single call); entry b is the maximum over the cells of model b of
+ * |x^iters - x^(iters-1)|, one fp64 subtraction a cell, the cells where that is a NaN left out, 0 for a model without
+ * any other.  The maximum is taken over the words of the non-negative doubles as integers: it is exact and has one
+ * value.  Nothing synchronises; the caller reads the residual when it wants to judge convergence.  Qs is a float32
+ * sum, so the iteration has a floor: the residual stops falling at about 2^-24 of the largest Qs times g / d.
+ *
+ * The entries are stream-ordered on the caller's stream from the first launch to the last.  A host thread's calls on
+ * one device share cached scratch of their own (the records and lists of soil_stream_power, an accumulation's scratch
+ * and 16 bytes a cell for the iterate, q and Qs): issue them on ONE stream, or order the streams yourself.
+ *
+ * Batch form: the conventions of soil_stream_power_batch.  Model-major planes, 1 or B scale pairs, model b's slices
+ * bit for bit what the single call gives, chunks of whole models (SOIL_FLOW_BATCH_CELLS lowers the cells of a chunk,
+ * SOIL_PATHS_IDX64=1 forces 64-bit offsets), every iteration of a chunk before the next chunk.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): what soil_stream_power refuses, a null `deposition`, iters < 1, `flux` or `residual` aliasing an
+ * input plane, an output or each other.  Otherwise, without a device: SOIL_ERR_NO_DEVICE. */
+int soil_stream_power_deposit(float* out, double* out64, float* flux, double* residual, const float* height,
+                              const int32_t* graph, const float* erosivity, const float* deposition,
+                              const float* uplift, int64_t H, int64_t W, int edge, const float scale[2], double dt,
+                              int iters, void* stream);
+int soil_stream_power_deposit_batch(float* out, double* out64, float* flux, double* residual, const float* height,
+                                    const int32_t* graph, const float* erosivity, const float* deposition,
+                                    const float* uplift, int64_t B, int64_t H, int64_t W, int edge,
+                                    const float* scales, int64_t n_scales, double dt, int iters, void* stream);
+/* What the calling host thread's last soil_stream_power_deposit or _batch call did: info[0] kernel launches, info[1]
+ * chunks, info[2] iterations run, info[3] bytes of scratch the call asked for.  All zero before the first call; needs
+ * no device. */
+int soil_stream_power_deposit_info(int64_t info[4]);
+
 /* ------------------------------------------------------ hillslope diffusion */
 
 /* One implicit step of dh/dt = div(kappa grad h) + u on a grid: the hillslope half of a landscape-evolution step, beside

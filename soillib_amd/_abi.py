@@ -240,6 +240,12 @@ SIGNATURES = {
     "soil_stream_power": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double, vp]),
     "soil_stream_power_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, C.c_double, vp]),
     "soil_downstream_info": (cint, [C.POINTER(i64)]),
+    # the stream-power step with deposition: out / out64, flux / residual (may be NULL), height, graph, erosivity,
+    # deposition, uplift (may be NULL); host scale pairs, dt, iters
+    "soil_stream_power_deposit": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double, cint, vp]),
+    "soil_stream_power_deposit_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64,
+                                               C.c_double, cint, vp]),
+    "soil_stream_power_deposit_info": (cint, [C.POINTER(i64)]),
     # hillslope diffusion: out / out64 (one may be NULL), height, diffusivity / uplift / fixed (each may be NULL);
     # host scale pairs, kappa, dt, border, first_axis
     "soil_diffuse": (cint, [vp, vp, vp, vp, vp, vp, i64, i64, F3, C.c_double, C.c_double, cint, cint, vp]),

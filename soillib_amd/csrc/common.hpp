@@ -69,6 +69,9 @@ enum WorkspaceSlot {
   WS_FLATS = 16,         // flats.hip: soil_flat_distance(_batch): the tiles' marks, one mask byte per cell
   WS_DOWNSTREAM = 17,    // downstream.hip: soil_downstream / soil_stream_power (_batch): scale records, records, B, lists
   WS_DIFFUSE = 18,       // diffuse.hip: soil_diffuse(_batch): scale records, the e and g planes of a chunk
+  WS_DEPOSIT = 19,       // downstream.hip: soil_stream_power_deposit(_batch): scale records, records, B, lists
+  WS_DEPOSIT_RAKE = 20,  // graph.hip rake_accumulate for soil_stream_power_deposit(_batch): an accumulation's scratch
+  WS_DEPOSIT_PLANES = 21,  // downstream.hip: soil_stream_power_deposit(_batch): the iterate, q and Qs of a chunk
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();
@@ -103,6 +106,16 @@ inline bool has_colour(const soil_colour_planes* C, bool bedrock = true) {
 // slot WS_BATCH (erosion_particles.hip); *models_dev valid in stream order until the slot's next use.
 int batch_models_to_device(const soil_batch_model* models, int64_t B, hipStream_t st,
                            const soil_batch_model** models_dev);
+
+// The accumulation of soil_accumulate_batch without decay (graph.hip: the rake-compress engine as it is, chunks of
+// whole models, model b's slice the bits soil_accumulate gives for it alone), stream-ordered on `st` through workspace
+// `slot` and without the entry's checks: B models of (H, W), `edge` SOIL_D4 or SOIL_D8.  `stats` (may be null): the
+// launches are added, the bytes raised to the largest block asked for.
+struct RakeStats {
+  int64_t launches, bytes;
+};
+int rake_accumulate(float* out, const int32_t* graph, const float* source, int64_t B, int64_t H, int64_t W, int edge,
+                    hipStream_t st, WorkspaceSlot slot, RakeStats* stats);
 
 // `bytes` of a host array copied to `dst` (device) in one stream-ordered copy through the same pinned staging
 // (erosion_particles.hip): the array may go as soon as the call returns.

@@ -6,7 +6,8 @@
 // (soil_downstream / soil_downstream_batch, soil_hip.h: chi, travel time, the outlet's height, what survives a decay)
 // and the implicit stream-power step of Braun & Willett, the same recurrence with coefficients made from the planes
 // (soil_stream_power / soil_stream_power_batch).  The reference has neither; its example/dem_process.py names the
-// solver.
+// solver.  At the end of the file, the stream-power step with a deposition term (soil_stream_power_deposit /
+// soil_stream_power_deposit_batch): the same rounds inside a fixed-point iteration with graph.hip's accumulation.
 //
 // The composition of affine maps is associative, so this is the pointer doubling of flow_paths.hip with other
 // records: where that file adds three counters, a round here composes x -> A + B x with the map of the cell the
@@ -306,6 +307,329 @@ static int downstream_run(int mode, DownOut o, const DownPlanes& in, int64_t B, 
                  });
 }
 
+// ---- erosion-deposition: the stream-power step with a deposition term fed by an upstream sum -------------------
+//
+// soil_stream_power_deposit(_batch), soil_hip.h "flow graphs: erosion-deposition".  A fixed number of iterations,
+// each: q = (float)(b - x) of the iterate before (k_dep_q), Qs = its upstream sum (graph.hip's rake-compress engine
+// through rake_accumulate, as it is), the coefficients of the recurrence from the planes, Qs and q (k_dep_init), the
+// rounds above (k_down_round / k_down_list with B, untouched), and k_dep_final, which keeps the fp64 iterate in
+// scratch and on the last iteration makes the outputs and the per-model residual.  Per chunk of whole models, all on
+// the caller's stream: nothing synchronises.
+
+struct DepPlanes {
+  const int32_t* graph;
+  const float *height, *erosivity, *uplift, *deposition;
+  double dt;
+};
+// A chunk's planes between the iterations (workspace slot WS_DEPOSIT_PLANES): the iterate, q and Qs
+struct DepWork {
+  double* x;
+  float *q, *qs;
+};
+
+// b of a cell: the lifted height, soil_stream_power's expression
+__device__ __forceinline__ double dep_lifted(float h, float u, bool has_u, double dt) {
+  const double hd = static_cast<double>(h);
+  return has_u ? __dadd_rn(hd, __dmul_rn(dt, static_cast<double>(u))) : hd;
+}
+
+// One cell of the q pass.  FIRST: x^0 (b on a cell with an edge, the height on a terminal) and the +0 planes the
+// first iteration reads in place of q and Qs — zeros accumulate to +0, so that iteration has no accumulation.
+template <int K, bool FIRST>
+__device__ __forceinline__ void dep_q_cell(const DepWork& w, int64_t n, int32_t g, float h, float u, bool has_u,
+                                           int64_t x, int64_t y, int64_t H, int64_t W, double dt) {
+  const bool has_edge = edge_kind<K>(g, x, y, H, W) >= 0;
+  const double b = has_edge ? dep_lifted(h, u, has_u, dt) : static_cast<double>(h);
+  if constexpr (FIRST) {
+    w.x[n] = b;
+    w.q[n] = 0.0f;
+    w.qs[n] = 0.0f;
+  } else {
+    const float q = __double2float_rn(__dsub_rn(b, w.x[n]));
+    w.q[n] = has_edge && q - q == 0.0f ? q : 0.0f;  // (q - q: zero for a finite float, NaN otherwise)
+  }
+}
+
+// The q pass, in k_down_init's shape: threads along the row, a band of rows per work-group, grid.z the model; VEC:
+// four cells per thread on 16-byte loads and stores.
+template <int K, bool VEC, bool FIRST>
+__global__ void __launch_bounds__(kPBlock) k_dep_q(DepWork w, DepPlanes in, int64_t H, int64_t W) {
+  const int64_t y = (static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x) * (VEC ? 4 : 1);
+  if (y >= W) return;
+  const int64_t first64 = static_cast<int64_t>(blockIdx.z) * H * W;
+  w.x += first64, w.q += first64, w.qs += first64;
+  const int32_t* const graph = in.graph + first64;
+  const float* const height = in.height + first64;
+  const float* const uplift = in.uplift ? in.uplift + first64 : nullptr;
+  SOIL_ROW_LOOP(x, H) {
+    const int64_t n = x * W + y;
+    if constexpr (VEC) {
+      const int4 g = *reinterpret_cast<const int4*>(graph + n);
+      const float4 h = *reinterpret_cast<const float4*>(height + n);
+      const float4 u = uplift ? *reinterpret_cast<const float4*>(uplift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+      dep_q_cell<K, FIRST>(w, n + 0, g.x, h.x, u.x, uplift != nullptr, x, y + 0, H, W, in.dt);
+      dep_q_cell<K, FIRST>(w, n + 1, g.y, h.y, u.y, uplift != nullptr, x, y + 1, H, W, in.dt);
+      dep_q_cell<K, FIRST>(w, n + 2, g.z, h.z, u.z, uplift != nullptr, x, y + 2, H, W, in.dt);
+      dep_q_cell<K, FIRST>(w, n + 3, g.w, h.w, u.w, uplift != nullptr, x, y + 3, H, W, in.dt);
+    } else {
+      dep_q_cell<K, FIRST>(w, n, graph[n], height[n], uplift ? uplift[n] : 0.0f, uplift != nullptr, x, y, H, W, in.dt);
+    }
+  }
+}
+
+// The record of one cell of the deposit mode, and its B: soil_hip.h's operations in its order, each rounded once
+template <int K>
+__device__ __forceinline__ void dep_init_cell(uint4* __restrict__ rec, double* __restrict__ bcoef, int64_t n,
+                                              int32_t gr, float h, float e, float u, bool has_u, float dep, float qs,
+                                              float q, int64_t x, int64_t y, int64_t H, int64_t W, uint32_t first,
+                                              const PathScale& s, double dt) {
+  const int kind = edge_kind<K>(gr, x, y, H, W);
+  double A = static_cast<double>(h), B = 0.0;  // a terminal: the height of the base level
+  uint32_t ptr = (first + static_cast<uint32_t>(n)) | kFinal;
+  if (kind >= 0) {
+    ptr = first + static_cast<uint32_t>(gr);
+    const double L = kind == 0 ? s.sx : (kind == 1 ? s.sy : s.dd);
+    const double F = __ddiv_rn(__dmul_rn(static_cast<double>(e), dt), L);
+    const double g = static_cast<double>(dep);
+    const double d = __dadd_rn(__dadd_rn(1.0, F), g);
+    const double b = dep_lifted(h, u, has_u, dt);
+    const double Qup = __dsub_rn(static_cast<double>(qs), static_cast<double>(q));
+    A = __ddiv_rn(__dadd_rn(__dmul_rn(__dadd_rn(1.0, g), b), __dmul_rn(g, Qup)), d);
+    B = __ddiv_rn(F, d);
+  }
+  rec[n] = down_rec(ptr, kind < 0 ? 0u : 1u, A);
+  bcoef[n] = B;
+}
+
+// The init pass of the deposit mode, as k_down_init: seven planes, each a 16-byte load in the VEC form
+template <int K, bool VEC>
+__global__ void __launch_bounds__(kPBlock)
+    k_dep_init(uint4* __restrict__ rec, double* __restrict__ bcoef, DepPlanes in, const float* __restrict__ qs,
+               const float* __restrict__ q, int64_t H, int64_t W, PathScales scales, int* __restrict__ flags) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < kPathFlags)
+    flags[threadIdx.x] = threadIdx.x == 0 ? 1 : 0;
+  const int64_t y = (static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x) * (VEC ? 4 : 1);
+  if (y >= W) return;
+  const int64_t first64 = static_cast<int64_t>(blockIdx.z) * H * W;
+  const uint32_t first = static_cast<uint32_t>(first64);
+  const PathScale s = scales.per_model ? scales.per_model[blockIdx.z] : scales.one;
+  rec += first64, bcoef += first64, qs += first64, q += first64;
+  const int32_t* const graph = in.graph + first64;
+  const float* const height = in.height + first64;
+  const float* const erosivity = in.erosivity + first64;
+  const float* const deposition = in.deposition + first64;
+  const float* const uplift = in.uplift ? in.uplift + first64 : nullptr;
+  const bool has_u = uplift != nullptr;
+  SOIL_ROW_LOOP(x, H) {
+    const int64_t n = x * W + y;
+    if constexpr (VEC) {
+      const int4 g = *reinterpret_cast<const int4*>(graph + n);
+      const float4 h = *reinterpret_cast<const float4*>(height + n);
+      const float4 e = *reinterpret_cast<const float4*>(erosivity + n);
+      const float4 u = uplift ? *reinterpret_cast<const float4*>(uplift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 dp = *reinterpret_cast<const float4*>(deposition + n);
+      const float4 s4 = *reinterpret_cast<const float4*>(qs + n);
+      const float4 q4 = *reinterpret_cast<const float4*>(q + n);
+      dep_init_cell<K>(rec, bcoef, n + 0, g.x, h.x, e.x, u.x, has_u, dp.x, s4.x, q4.x, x, y + 0, H, W, first, s, in.dt);
+      dep_init_cell<K>(rec, bcoef, n + 1, g.y, h.y, e.y, u.y, has_u, dp.y, s4.y, q4.y, x, y + 1, H, W, first, s, in.dt);
+      dep_init_cell<K>(rec, bcoef, n + 2, g.z, h.z, e.z, u.z, has_u, dp.z, s4.z, q4.z, x, y + 2, H, W, first, s, in.dt);
+      dep_init_cell<K>(rec, bcoef, n + 3, g.w, h.w, e.w, u.w, has_u, dp.w, s4.w, q4.w, x, y + 3, H, W, first, s, in.dt);
+    } else {
+      dep_init_cell<K>(rec, bcoef, n, graph[n], height[n], erosivity[n], uplift ? uplift[n] : 0.0f, has_u,
+                       deposition[n], qs[n], q[n], x, y, H, W, first, s, in.dt);
+    }
+  }
+}
+
+// Final of an iteration, k_down_final's shape: the iterate (A, or the quiet NaN as k_down_final writes it) replaces
+// the one before in `x`; the last iteration also makes the outputs and, asked for, the residual of its model
+// (grid.z): max |x - x_before| over the cells where that is no NaN, as the largest WORD of a non-negative double — an
+// integer max through LDS and one global atomic a work-group, no floating-point atomic, any order the same bits.
+__global__ void __launch_bounds__(kPBlock)
+    k_dep_final(float* __restrict__ out, double* __restrict__ out64, double* __restrict__ x,
+                unsigned long long* __restrict__ residual, const uint4* __restrict__ rec, int64_t cells) {
+  __shared__ unsigned long long s_max;
+  if (residual) {
+    if (threadIdx.x == 0) s_max = 0ull;
+    __syncthreads();
+  }
+  const int64_t first64 = static_cast<int64_t>(blockIdx.z) * cells;
+  unsigned long long mine = 0ull;
+  for (int64_t n = static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x; n < cells;
+       n += static_cast<int64_t>(gridDim.x) * kPBlock) {
+    const uint4 r = rec[first64 + n];
+    const double A = down_a(r);
+    const bool nan = (r.x & kFinal) == 0 || A != A;
+    const double xn = nan ? __hiloint2double(0x7ff80000, 0) : A;
+    if (residual) {
+      const double diff = fabs(__dsub_rn(xn, x[first64 + n]));
+      const unsigned long long w = static_cast<unsigned long long>(__double_as_longlong(diff));
+      if (diff == diff && w > mine) mine = w;
+    }
+    x[first64 + n] = xn;
+    if (out) out[first64 + n] = nan ? bits2f(0x7fc00000u) : __double2float_rn(A);
+    if (out64) out64[first64 + n] = xn;
+  }
+  if (residual) {
+    if (mine) atomicMax(&s_max, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_max) atomicMax(residual + blockIdx.z, s_max);
+  }
+}
+
+struct DepOut {
+  float* out;
+  double* out64;
+  float* flux;
+  double* residual;
+};
+// soil_stream_power_deposit_info: launches, chunks, iterations, bytes of scratch
+struct DepInfo {
+  int64_t launches, chunks, iters, bytes;
+};
+static thread_local DepInfo t_dep_info{0, 0, 0, 0};
+
+template <int K>
+static void dep_launch_q(const DepWork& w, const DepPlanes& in, int64_t models, int64_t H, int64_t W, bool first,
+                         hipStream_t st) {
+  const bool vec = ptr_vec_init(W, reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.height) |
+                                       reinterpret_cast<uintptr_t>(in.uplift) | reinterpret_cast<uintptr_t>(w.x) |
+                                       reinterpret_cast<uintptr_t>(w.q) | reinterpret_cast<uintptr_t>(w.qs));
+  dim3 grid = grid_rows(H, vec ? W / 4 : W, kPBlock);
+  grid.z = static_cast<unsigned>(models);
+  if (vec) {
+    if (first) k_dep_q<K, true, true><<<grid, kPBlock, 0, st>>>(w, in, H, W);
+    else k_dep_q<K, true, false><<<grid, kPBlock, 0, st>>>(w, in, H, W);
+  } else {
+    if (first) k_dep_q<K, false, true><<<grid, kPBlock, 0, st>>>(w, in, H, W);
+    else k_dep_q<K, false, false><<<grid, kPBlock, 0, st>>>(w, in, H, W);
+  }
+  t_dep_info.launches += 1;
+}
+
+// One chunk of `models` models: x^0, then `iters` times q, Qs, and init / rounds / final through ptr_chunk with this
+// mode's launches, then the flux of the returned iterate.  `in`, `o` and `w` are the chunk's own.
+template <int K>
+static int dep_chunk(DepOut o, const DepPlanes& in, const DepWork& w, int iters, int64_t models, int64_t H, int64_t W,
+                     int edge, const PathScales& scales, char* scratch, RakeStats& rake, hipStream_t st) {
+  PtrInfo pinfo{0, 0, 0, 0};
+  t_dep_info.chunks += 1;
+  dep_launch_q<K>(w, in, models, H, W, true, st);
+  SOIL_LAUNCH_CHECK();
+  for (int k = 1; k <= iters; ++k) {
+    if (k > 1) {
+      dep_launch_q<K>(w, in, models, H, W, false, st);
+      SOIL_LAUNCH_CHECK();
+      if (int rc = rake_accumulate(w.qs, in.graph, w.q, models, H, W, edge, st, WS_DEPOSIT_RAKE, &rake); rc != SOIL_OK)
+        return rc;
+    }
+    const bool last = k == iters;
+    auto init = [&](const PtrChunk& c) {
+      const bool vec =
+          ptr_vec_init(W, reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.height) |
+                              reinterpret_cast<uintptr_t>(in.erosivity) | reinterpret_cast<uintptr_t>(in.uplift) |
+                              reinterpret_cast<uintptr_t>(in.deposition) | reinterpret_cast<uintptr_t>(w.qs) |
+                              reinterpret_cast<uintptr_t>(w.q));
+      const dim3 grid = ptr_init_grid(c, H, W, vec);
+      double* const b0 = static_cast<double*>(c.extra[0]);
+      if (vec) k_dep_init<K, true><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, w.qs, w.q, H, W, scales, c.flags);
+      else k_dep_init<K, false><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, w.qs, w.q, H, W, scales, c.flags);
+      return vec;
+    };
+    auto round = [&](const PtrChunk& c, const PtrRound& q) {
+      uint4* const ro = c.rec[(q.r + 1) & 1];
+      const uint4* const ri = c.rec[q.r & 1];
+      double* const bo = static_cast<double*>(c.extra[(q.r + 1) & 1]);
+      const double* const bi = static_cast<const double*>(c.extra[q.r & 1]);
+      if (q.list_in) {
+        if (c.idx32)
+          k_down_list<uint32_t, true><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
+                                                                    q.fill_out, c.seg);
+        else
+          k_down_list<int64_t, true><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
+                                                                   q.fill_out, c.seg);
+      } else if (c.idx32) {
+        k_down_round<uint32_t, true><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
+                                                                   q.fill_out, c.seg);
+      } else {
+        k_down_round<int64_t, true><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
+                                                                  q.fill_out, c.seg);
+      }
+    };
+    auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
+      k_dep_final<<<grid, kPBlock, 0, st>>>(last ? o.out : nullptr, last ? o.out64 : nullptr, w.x,
+                                            last ? reinterpret_cast<unsigned long long*>(o.residual) : nullptr, rec,
+                                            H * W);
+    };
+    if (int rc = ptr_chunk(pinfo, models, H, W, sizeof(double), scratch, init, round, fin); rc != SOIL_OK) return rc;
+    t_dep_info.launches += 2 + pinfo.rounds;
+  }
+  if (o.flux) {
+    dep_launch_q<K>(w, in, models, H, W, false, st);
+    SOIL_LAUNCH_CHECK();
+    if (int rc = rake_accumulate(o.flux, in.graph, w.q, models, H, W, edge, st, WS_DEPOSIT_RAKE, &rake); rc != SOIL_OK)
+      return rc;
+  }
+  return SOIL_OK;
+}
+
+// What the two deposit entries refuse before any device work: soil_stream_power's refusals and their own
+static int check_deposit(const char* what, const DepOut& o, const DepPlanes& in, int iters, const float* scales,
+                         int64_t B, int64_t H, int64_t W, int edge, int64_t n_scales) {
+  const std::string w(what);
+  const DownPlanes power{in.graph, nullptr, in.height, in.erosivity, in.uplift, in.dt};
+  if (int rc = check_downstream(what, kPower, o.out, o.out64, power, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
+    return rc;
+  SOIL_REQUIRE(in.deposition, w + ": null deposition");
+  SOIL_REQUIRE(iters >= 1, w + ": iters must be >= 1");
+  const int64_t hw = H * W;  // (cells counted as in check_downstream)
+  const size_t cells = static_cast<size_t>(B > (int64_t{1} << 58) / hw ? (int64_t{1} << 58) : B * hw);
+  SOIL_REQUIRE(!overlaps(o.out, 4 * cells, in.deposition, 4 * cells) &&
+                   !overlaps(o.out64, 8 * cells, in.deposition, 4 * cells),
+               w + ": an output aliases an input plane");
+  const void* const planes[] = {in.graph, in.height, in.erosivity, in.uplift, in.deposition, o.out};
+  for (const void* p : planes)
+    SOIL_REQUIRE(!overlaps(o.flux, 4 * cells, p, 4 * cells) && !overlaps(o.residual, 8 * static_cast<size_t>(B), p, 4 * cells),
+                 w + ": flux or residual aliases another plane");
+  SOIL_REQUIRE(!overlaps(o.flux, 4 * cells, o.out64, 8 * cells) &&
+                   !overlaps(o.residual, 8 * static_cast<size_t>(B), o.out64, 8 * cells) &&
+                   !overlaps(o.flux, 4 * cells, o.residual, 8 * static_cast<size_t>(B)),
+               w + ": flux or residual aliases another plane");
+  return SOIL_OK;
+}
+
+// A call: the chunks of ptr_run through slot WS_DEPOSIT, the chunk's planes in WS_DEPOSIT_PLANES beside them
+static int deposit_run(DepOut o, const DepPlanes& in, int iters, int64_t B, int64_t H, int64_t W, int edge,
+                       const float* scales, int64_t n_scales, hipStream_t st) {
+  const int64_t hw = H * W, per = ptr_chunk_models(hw), first_chunk = B < per ? B : per;
+  const size_t b_x = align256(sizeof(double) * static_cast<size_t>(first_chunk * hw));
+  const size_t b_q = align256(sizeof(float) * static_cast<size_t>(first_chunk * hw));
+  t_dep_info = DepInfo{0, 0, iters, 0};
+  void* planes = nullptr;
+  if (int rc = workspace_get(WS_DEPOSIT_PLANES, b_x + 2 * b_q, &planes); rc != SOIL_OK) return rc;
+  char* const p = static_cast<char*>(planes);
+  const DepWork w{reinterpret_cast<double*>(p), reinterpret_cast<float*>(p + b_x), reinterpret_cast<float*>(p + b_x + b_q)};
+  if (o.residual) SOIL_HIP(hipMemsetAsync(o.residual, 0, sizeof(double) * static_cast<size_t>(B), st));
+  RakeStats rake{0, 0};
+  PtrInfo pinfo{0, 0, 0, 0};
+  auto go = edge == SOIL_D4 ? dep_chunk<4> : dep_chunk<8>;
+  const int rc =
+      ptr_run(WS_DEPOSIT, pinfo, B, H, W, sizeof(double), scales, n_scales, PathScale{1.0, 1.0, 1.0}, st,
+              [&](int64_t b0, int64_t nb, const PathScales& s, char* scratch) {
+                const int64_t at = b0 * hw;
+                const DepPlanes part{in.graph + at,      in.height + at, in.erosivity + at, in.uplift ? in.uplift + at : nullptr,
+                                     in.deposition + at, in.dt};
+                const DepOut part_o{o.out ? o.out + at : nullptr, o.out64 ? o.out64 + at : nullptr,
+                                    o.flux ? o.flux + at : nullptr, o.residual ? o.residual + b0 : nullptr};
+                return go(part_o, part, w, iters, nb, H, W, edge, s, scratch, rake, st);
+              });
+  const size_t b_scales = scales && n_scales > 1 ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0;
+  t_dep_info.launches += rake.launches;
+  t_dep_info.bytes = static_cast<int64_t>(b_x + 2 * b_q + b_scales + ptr_layout(first_chunk * hw, sizeof(double)).bytes()) +
+                     rake.bytes;
+  return rc;
+}
+
 }  // namespace soil
 
 using namespace soil;
@@ -350,6 +674,35 @@ int soil_stream_power_batch(float* out, double* out64, const float* height, cons
     return rc;
   SOIL_DEVICE();
   return downstream_run(kPower, DownOut{out, out64}, in, B, H, W, edge, scales, n_scales, as_stream(stream));
+}
+
+int soil_stream_power_deposit(float* out, double* out64, float* flux, double* residual, const float* height,
+                              const int32_t* graph, const float* erosivity, const float* deposition,
+                              const float* uplift, int64_t H, int64_t W, int edge, const float scale[2], double dt,
+                              int iters, void* stream) {
+  const DepPlanes in{graph, height, erosivity, uplift, deposition, dt};
+  const DepOut o{out, out64, flux, residual};
+  if (int rc = check_deposit("stream_power_deposit", o, in, iters, scale, 1, H, W, edge, 1); rc != SOIL_OK) return rc;
+  SOIL_DEVICE();
+  return deposit_run(o, in, iters, 1, H, W, edge, scale, 1, as_stream(stream));
+}
+
+int soil_stream_power_deposit_batch(float* out, double* out64, float* flux, double* residual, const float* height,
+                                    const int32_t* graph, const float* erosivity, const float* deposition,
+                                    const float* uplift, int64_t B, int64_t H, int64_t W, int edge,
+                                    const float* scales, int64_t n_scales, double dt, int iters, void* stream) {
+  const DepPlanes in{graph, height, erosivity, uplift, deposition, dt};
+  const DepOut o{out, out64, flux, residual};
+  if (int rc = check_deposit("stream_power_deposit_batch", o, in, iters, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
+    return rc;
+  SOIL_DEVICE();
+  return deposit_run(o, in, iters, B, H, W, edge, scales, n_scales, as_stream(stream));
+}
+
+int soil_stream_power_deposit_info(int64_t info[4]) {
+  SOIL_REQUIRE(info, "stream_power_deposit_info: null info");
+  info[0] = t_dep_info.launches, info[1] = t_dep_info.chunks, info[2] = t_dep_info.iters, info[3] = t_dep_info.bytes;
+  return SOIL_OK;
 }
 
 int soil_downstream_info(int64_t info[4]) {

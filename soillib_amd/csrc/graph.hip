@@ -883,7 +883,7 @@ static void launch_donors(const Acc& A, const int32_t* graph, const float* sourc
 // rounds never look at H or W.  The round count is a single model's either way.
 template <int K>
 static int rake_run(float* out, const int32_t* graph, const float* source, const float* decayIn, int64_t models,
-                    int64_t H, int64_t W, hipStream_t st, WorkspaceSlot slot) {
+                    int64_t H, int64_t W, hipStream_t st, WorkspaceSlot slot, RakeStats* stats = nullptr) {
   const int64_t elem = (models > 0 ? models : 1) * H * W;
   auto align = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
   const size_t b1 = align(sizeof(float) * elem), bK = align(sizeof(float) * elem * K);
@@ -895,6 +895,7 @@ static int rake_run(float* out, const int32_t* graph, const float* source, const
   const size_t bL = align(sizeof(uint32_t) * seg * nb), bF = align(sizeof(uint32_t) * nb);
   int rc = workspace_get(slot, 3 * b1 + 4 * bK + 2 * bL + 2 * bF + 256, &base);
   if (rc != SOIL_OK) return rc;
+  if (stats) stats->bytes = std::max(stats->bytes, static_cast<int64_t>(3 * b1 + 4 * bK + 2 * bL + 2 * bF + 256));
   char* p = static_cast<char*>(base);
   Acc A, B;
   A.count = reinterpret_cast<int32_t*>(p); p += b1;
@@ -953,6 +954,7 @@ static int rake_run(float* out, const int32_t* graph, const float* source, const
   // The round count is the reference's: 2 (ceil(log2(HW) / 2) + 1).
   static const int list_from_env = [] { const char* e = std::getenv("SOIL_RAKE_LIST_FROM"); return e ? std::atoi(e) : 2; }();
   const int rounds = static_cast<int>(2 * (iter + 1));
+  if (stats) stats->launches += 2 + rounds;  // the donor pass, k_rake_init, the rounds
   const int list_from = (list_from_env >= 1 && list_from_env < rounds) ? list_from_env : rounds;
   const uint32_t seg32 = static_cast<uint32_t>(seg);
   for (int r = 0; r < rounds; ++r) {                                                // :560-563
@@ -1021,6 +1023,26 @@ static int accumulate_batch_impl(float* out, const int32_t* graph, const float* 
       return rc;
   }
   return SOIL_OK;
+}
+
+// rake_accumulate (common.hpp): accumulate_batch_impl without decay through the caller's slot, for an entry of another
+// file that accumulates in the middle of its own stream-ordered work (downstream.hip: soil_stream_power_deposit)
+template <int K>
+static int rake_accumulate_impl(float* out, const int32_t* graph, const float* source, int64_t B, int64_t H, int64_t W,
+                                hipStream_t st, WorkspaceSlot slot, RakeStats* stats) {
+  const int64_t hw = H * W, per = flow_batch_models<K>(hw);
+  for (int64_t b0 = 0; b0 < B; b0 += per) {
+    const int64_t nb = B - b0 < per ? B - b0 : per, at = b0 * hw;
+    if (int rc = rake_run<K>(out + at, graph + at, source + at, nullptr, nb == 1 ? 0 : nb, H, W, st, slot, stats);
+        rc != SOIL_OK)
+      return rc;
+  }
+  return SOIL_OK;
+}
+int rake_accumulate(float* out, const int32_t* graph, const float* source, int64_t B, int64_t H, int64_t W, int edge,
+                    hipStream_t st, WorkspaceSlot slot, RakeStats* stats) {
+  return edge == SOIL_D4 ? rake_accumulate_impl<4>(out, graph, source, B, H, W, st, slot, stats)
+                         : rake_accumulate_impl<8>(out, graph, source, B, H, W, st, slot, stats);
 }
 
 // sum += double(float(acc / K)): the term of example/dem_multiflow.py:49

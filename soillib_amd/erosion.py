@@ -841,6 +841,39 @@ class ErosionBatch:
         area = self.drainage(graph=graph, edge=e)
         return soil.stream_power_batch(filled, graph, soil.erosivity(area, K, m), e, scale, dt, uplift)
 
+    def stream_power_deposit(self, dt, K, m=0.5, G=1.0, iters=8, kind="steepest", edge=None, T=None, offset=0,
+                             uplift=None, flux=False, residual=False):
+        """One implicit stream-power step with sediment deposition of every model, on its conditioned surface:
+        conditioned() -> drainage(graph=g) -> soil.erosivity(area, K, m) and soil.deposition(area, G, cell) ->
+        soil.stream_power_deposit_batch with `iters` iterations and the batch's scale(s); `cell` is the product of a
+        model's scale pair.  Returns the (B, H, W) float32 heights after the step, or with `flux` / `residual` a tuple
+        with those as soil.stream_power_deposit_batch returns them; the batch's own planes are not touched.  `G`: the
+        deposition coefficient, a finite number >= 0; the rest as in stream_power().  A bad argument raises ValueError
+        before any device work.  Synchronises the stream (the fill does)."""
+        from . import soil
+        who = "stream_power_deposit"
+        for name, v in (("dt", dt), ("K", K), ("m", m), ("G", G)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (name != "m" and v < 0):
+                raise ValueError("ErosionBatch.%s: %s must be a finite number%s, got %r" % (
+                    who, name, "" if name == "m" else " >= 0", v))
+        if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= iters < 2 ** 31:
+            raise ValueError("ErosionBatch.%s: iters must be an integer >= 1, got %r" % (who, iters))
+        if kind not in ("steepest", "random_weighted"):
+            raise ValueError("ErosionBatch.%s: kind must be 'steepest' or 'random_weighted', got %r" % (who, kind))
+        e = self._edge(who, edge)
+        if kind == "random_weighted":
+            self._check_draw(who, T, offset)
+        if uplift is not None:
+            self._flow_tensor(who, "uplift", uplift, silt.float32)
+        scale = self._path_scale(who)
+        filled, graph = self.conditioned(kind, e, T, offset)
+        area = self.drainage(graph=graph, edge=e)
+        # a cell's area, model by model: float32 of the product of its pair, one value a model either way
+        pairs = scale if self.scales is not None else [scale] * self.B
+        cell = silt.tensor.from_numpy(np.array([s[0] * s[1] for s in pairs], np.float32).reshape(self.B, 1, 1)).gpu()
+        return soil.stream_power_deposit_batch(filled, graph, soil.erosivity(area, K, m), soil.deposition(area, G, cell),
+                                               e, scale, dt, uplift, int(iters), False, flux, residual)
+
     def _check_diffuse(self, who, dt, kappa, diffusivity, uplift, fixed, border, first_axis):
         """The arguments of diffuse() and of the diffusion half of evolve(), or ValueError."""
         if isinstance(dt, bool) or not isinstance(dt, numbers.Real) or not math.isfinite(dt) or dt < 0:
@@ -873,15 +906,21 @@ class ErosionBatch:
         return soil.diffuse_batch(self.height, scale, dt, kappa, diffusivity, uplift, fixed, border, first_axis, double)
 
     def evolve(self, dt, K, m=0.5, kappa=None, uplift=None, kind="steepest", edge=None, T=None, offset=0,
-               first_axis=0):
+               first_axis=0, G=None, iters=8):
         """One landscape-evolution step of every model, uplift + stream power + linear diffusion: stream_power(dt, K,
         m, kind, edge, T, offset, uplift) and then soil.diffuse_batch of its result over the same `dt` with the
         diffusivity `kappa` and border="fixed" — the outermost cells, the base level of the conditioned graph, keep
-        what the stream-power step left them.  The uplift is applied once, in the stream-power step.  Returns the
-        (B, H, W) float32 heights; the batch's own planes are not touched.  A bad argument raises ValueError before
-        any device work.  Synchronises the stream (the fill does)."""
+        what the stream-power step left them.  The uplift is applied once, in the stream-power step.  With `G` (a
+        finite number >= 0) the first half is stream_power_deposit(dt, K, m, G, iters, ...) instead: the eroded
+        material is deposited on its way down.  Returns the (B, H, W) float32 heights; the batch's own planes are not
+        touched.  A bad argument raises ValueError before any device work.  Synchronises the stream (the fill does)."""
         from . import soil
         self._check_diffuse("evolve", dt, kappa, None, None, None, "fixed", first_axis)
+        if G is not None:
+            if isinstance(G, bool) or not isinstance(G, numbers.Real) or not math.isfinite(G) or G < 0:
+                raise ValueError("ErosionBatch.evolve: G must be a finite number >= 0, got %r" % (G,))
+            if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= iters < 2 ** 31:
+                raise ValueError("ErosionBatch.evolve: iters must be an integer >= 1, got %r" % (iters,))
         for name, v in (("K", K), ("m", m)):
             if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (name != "m" and v < 0):
                 raise ValueError("ErosionBatch.evolve: %s must be a finite number%s, got %r" % (
@@ -894,7 +933,10 @@ class ErosionBatch:
         if uplift is not None:
             self._flow_tensor("evolve", "uplift", uplift, silt.float32)
         scale = self._path_scale("evolve")
-        carved = self.stream_power(dt, K, m, kind, edge, T, offset, uplift)
+        if G is None:
+            carved = self.stream_power(dt, K, m, kind, edge, T, offset, uplift)
+        else:
+            carved = self.stream_power_deposit(dt, K, m, G, iters, kind, edge, T, offset, uplift)
         return soil.diffuse_batch(carved, scale, dt, kappa, border="fixed", first_axis=first_axis)
 
     def filled(self, edge=None):

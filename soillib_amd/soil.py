@@ -492,6 +492,92 @@ def chi(graph, area, edge_, scale, theta=0.45, A0=1.0, stop=None):
                                                 ("terminal", None, False)], scale, stop, False)
 
 
+# ---- erosion-deposition (soil_hip.h: "flow graphs: erosion-deposition"): the stream-power step with a deposition
+# term fed by the upstream sum of what the step removes, a fixed number of iterations.  Stream-ordered.
+
+def _stream_power_deposit(who, dims, height, graph, erosivity, deposition, edge_, scale, dt, uplift, iters, double,
+                          flux, residual):
+    """soil_stream_power_deposit and its _batch form.  Every check comes before any device work."""
+    shape = (_hw2 if dims == 2 else _bhw)(graph, "%s: graph" % who)
+    e = _edge_of(edge_, who)
+    _int_plane(graph, shape, "%s: graph" % who)
+    planes = [("height", height, True), ("erosivity", erosivity, True), ("deposition", deposition, True),
+              ("uplift", uplift, False)]
+    for name, t, required in planes:
+        if t is None and required:
+            raise ValueError("%s: %s is required" % (who, name))
+        if t is not None:
+            _float_plane(t, shape, "%s: %s" % (who, name))
+    if scale is None:
+        raise ValueError("%s: scale must be one (sx, sy) pair%s" % (who, "" if dims == 2 else " or B pairs"))
+    pairs, n = (_one_pair(scale, who), 1) if dims == 2 else _scale_pairs(scale, shape[0], who)
+    if any(not (v > 0 and math.isfinite(v)) for v in pairs):
+        raise ValueError("%s: scale entries must be positive finite floats, got %r" % (who, scale))
+    if isinstance(dt, bool) or not isinstance(dt, (int, float)) or not math.isfinite(dt) or dt < 0:
+        raise ValueError("%s: dt must be a finite number >= 0, got %r" % (who, dt))
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters < 2 ** 31:
+        raise ValueError("%s: iters must be an integer >= 1, got %r" % (who, iters))
+    g_ptr = _gpu(graph, silt.int32, "graph")
+    h_ptr, k_ptr, d_ptr, u_ptr = (_opt_f(t, name) for name, t, _ in planes)
+    out = silt.tensor(silt.float64 if double else silt.float32, silt.shape(*shape), silt.gpu)
+    outs = (None, out.c_ptr) if double else (out.c_ptr, None)
+    f = silt.tensor(silt.float32, silt.shape(*shape), silt.gpu) if flux else None
+    r = silt.tensor(silt.float64, silt.shape(1 if dims == 2 else shape[0]), silt.gpu) if residual else None
+    tail = (pairs,) if dims == 2 else (pairs, n)
+    _call("soil_stream_power_deposit" + ("" if dims == 2 else "_batch"), *outs, None if f is None else f.c_ptr,
+          None if r is None else r.c_ptr, h_ptr, g_ptr, k_ptr, d_ptr, u_ptr, *shape, e, *tail, float(dt), int(iters),
+          _abi.stream())
+    extras = tuple(t for t in (f, r) if t is not None)
+    return (out,) + extras if extras else out
+
+
+def stream_power_deposit(height, graph, erosivity, deposition, edge_, scale, dt, uplift=None, iters=8, double=False,
+                         flux=False, residual=False):
+    """soil_stream_power_deposit: one implicit step of stream-power incision with sediment deposition (the
+    erosion-deposition model, slope exponent 1) along `graph`: stream_power's step plus (G / A) Qs, Qs the net material
+    removed upstream, by `iters` fixed-point iterations of an upstream sum and a downstream solve.  `erosivity` is
+    K A^m (soil.erosivity), `deposition` G cell / A (soil.deposition), `uplift` a float32 plane or None.  Returns the
+    new heights, float32 (float64 with `double`); with `flux` and / or `residual` a tuple (heights, flux, residual) of
+    those asked for: the float32 sediment flux through every cell (at a terminal: what reached that base level) and a
+    one-element float64 tensor, the largest change of the last iteration.  `height` is left as it is.  A zero
+    deposition plane gives stream_power's bits."""
+    return _stream_power_deposit("stream_power_deposit", 2, height, graph, erosivity, deposition, edge_, scale, dt,
+                                 uplift, iters, double, flux, residual)
+
+
+def stream_power_deposit_batch(height, graph, erosivity, deposition, edge_, scale, dt, uplift=None, iters=8,
+                               double=False, flux=False, residual=False):
+    """`stream_power_deposit` of each of the B models of (B, H, W) planes (soil_stream_power_deposit_batch); `scale`
+    is one pair or B pairs; the residual tensor has B entries."""
+    return _stream_power_deposit("stream_power_deposit_batch", 3, height, graph, erosivity, deposition, edge_, scale,
+                                 dt, uplift, iters, double, flux, residual)
+
+
+def deposition(area, G, cell=1.0):
+    """G * cell / area of a float32 drainage-area tensor, on the device through torch, float32: the `deposition` of
+    stream_power_deposit.  `cell`: the area of a cell, a number, or a tensor that broadcasts against `area` (one value
+    per model: shape (B, 1, 1)).  Not bit-pinned, as soil.erosivity is not; what stream_power_deposit makes of a
+    given plane is."""
+    if not isinstance(area, silt.tensor) or area.type is not silt.float32:
+        raise ValueError("deposition: area must be a float32 silt tensor")
+    if isinstance(G, bool) or not isinstance(G, (int, float)) or not math.isfinite(G) or G < 0:
+        raise ValueError("deposition: G must be a finite number >= 0, got %r" % (G,))
+    if area.host is not silt.gpu:
+        raise _abi.SoilError("mismatch_host: area must be a silt.gpu tensor")
+    with _on_stream():
+        c = cell.view_torch() if isinstance(cell, silt.tensor) else float(cell)
+        out = (float(G) * c / area.view_torch()).float()
+    return silt.tensor.from_torch(out.contiguous())
+
+
+def stream_power_deposit_info():
+    """What this thread's last stream_power_deposit / _batch call did (soil_stream_power_deposit_info): a dict with the
+    number of kernel `launches`, of `chunks`, the `iters` run and the `scratch_bytes` it asked for."""
+    info = (C.c_int64 * 4)()
+    _call("soil_stream_power_deposit_info", info)
+    return dict(zip(("launches", "chunks", "iters", "scratch_bytes"), (int(v) for v in info)))
+
+
 def downstream_info():
     """What this thread's last downstream / stream_power call (or _batch form) did (soil_downstream_info): a dict with
     the number of `chunks`, of chunks whose init pass took the 16-byte form (`vec_chunks`), of chunks on 64-bit
