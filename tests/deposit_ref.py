@@ -68,12 +68,14 @@ def _residual(x, before):
     return np.float64(diff.max()) if diff.size else np.float64(0.0)
 
 
-def solve_iterated(oracle, graph, edge, height, erosivity, deposition, scale, dt, uplift=None, iters=8):
+def solve_iterated(oracle, graph, edge, height, erosivity, deposition, scale, dt, uplift=None, iters=8, every=False):
+    """`every`: also `steps`, what a call with iters = 1, 2, ... returns (out, out64, flux, residual, final), from this
+    one run of the iteration."""
     graph = np.ascontiguousarray(graph, np.int32)
     H, W = graph.shape
     is_edge, h, b, g, d, B0 = coefficients(graph, edge, height, erosivity, deposition, uplift, scale, dt)
     x = np.where(is_edge, b, h)
-    residuals = []
+    residuals, steps = [], []
     for k in range(1, iters + 1):
         q = make_q(is_edge, b, x)
         Qs = oracle.accumulate(graph, q.reshape(H, W), edge).reshape(-1) if k > 1 else np.zeros(H * W, np.float32)
@@ -85,8 +87,14 @@ def solve_iterated(oracle, graph, edge, height, erosivity, deposition, scale, dt
         out, out64, final = _doubling(graph, is_edge, A0, B0, h)
         before, x = x, out64.reshape(-1).copy()
         residuals.append(_residual(x, before))
+        if every and k < iters:
+            steps.append(dict(out=out, out64=out64, flux=oracle.accumulate(graph, make_q(is_edge, b, x).reshape(H, W), edge),
+                              residual=residuals[-1], final=final))
     flux = oracle.accumulate(graph, make_q(is_edge, b, x).reshape(H, W), edge)
-    return dict(out=out, out64=out64, flux=flux, residual=residuals[-1], residuals=residuals, final=final)
+    result = dict(out=out, out64=out64, flux=flux, residual=residuals[-1], residuals=residuals, final=final)
+    if every:
+        result["steps"] = steps + [dict(out=out, out64=out64, flux=flux, residual=residuals[-1], final=final)]
+    return result
 
 
 def _doubling(graph, is_edge, A0, B0, h):

@@ -4,7 +4,8 @@ evolve(G=...)), bit for bit against solve_iterated of tests/deposit_ref.py: ever
 out (float32), out64 (float64), flux (float32) and residual (float64), the NaN words included; there is no tolerance.
 
   shapes     1x17, 17x1, 12x20 (the 16-byte init and q passes), 13x21 (the scalar ones), 48x64 (several work-groups
-             of a round); D4 and D8
+             of a round), 5x1028 and 3x261 (two work-groups along a row in the init and q passes: 257 threads a row in
+             the 16-byte form, 261 in the scalar one); D4 and D8
   graphs     every built graph of flow_paths_ref (a chain through every cell, cells with all donors, no edge at all,
              hostile entries, cycles: NaN words on a cycle and upstream of it) and downhill graphs
   inputs     with and without uplift, iters 1, 2 and 6, NaN heights as voids, dt = 0, erosivity 0
@@ -33,7 +34,7 @@ from util import product_param, script_param, terrain, to_gpu, to_np
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = [(1, 17), (17, 1), (12, 20), (13, 21), (48, 64)]
+SHAPES = [(1, 17), (17, 1), (12, 20), (13, 21), (48, 64), (5, 1028), (3, 261)]
 SCALES = [(0.3, 0.7), (1.0, 1.0), (2.5, 0.125)]
 DT = 10.0
 ALL = ("out", "out64", "flux", "residual")
@@ -288,7 +289,7 @@ def test_chunks_and_knobs(hip, tmp_path, knob):
 
 # ------------------------------------------------------------------ identities and plumbing
 
-@pytest.mark.parametrize("H,W", [(12, 20), (13, 21), (48, 64)])
+@pytest.mark.parametrize("H,W", [(12, 20), (13, 21), (48, 64), (5, 1028), (3, 261)])
 def test_a_zero_deposition_plane_gives_the_library_s_stream_power(hip, H, W):
     from soillib_amd import soil
     p = _planes(H, W, 1)
