@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "flow_host.hpp"
 
 namespace soil {
 
@@ -373,13 +374,12 @@ static int fill_impl(float* out, const float* height, bool batch, int64_t B, int
   // the pyramid: level 0 is the DEM itself, level l + 1 the 4x4 (kFC) block maxima of level l
   struct Level { int64_t H, W; size_t off_z, off_w; };
   std::vector<Level> lv{{H, W, 0, 0}};
-  auto align = [](size_t b) { return (b + 255) & ~size_t{255}; };
   const size_t ntiles0 = static_cast<size_t>((W + kFT - 1) / kFT) * ((H + kFT - 1) / kFT);
-  const size_t b_dirty = align(ntiles0 * static_cast<size_t>(B));  // (a coarser level has fewer tiles per model)
+  const size_t b_dirty = align256(ntiles0 * static_cast<size_t>(B));  // (a coarser level has fewer tiles per model)
   size_t bytes = 256 + 2 * b_dirty;
   while (lv.back().H * lv.back().W > 4 * kFT * kFT && std::getenv("SOIL_FILL_FLAT") == nullptr) {
     const int64_t Hc = (lv.back().H + kFC - 1) / kFC, Wc = (lv.back().W + kFC - 1) / kFC;
-    const size_t b = align(sizeof(float) * Hc * Wc * static_cast<size_t>(B));
+    const size_t b = align256(sizeof(float) * Hc * Wc * static_cast<size_t>(B));
     lv.push_back({Hc, Wc, bytes, bytes + b});
     bytes += 2 * b;
   }
@@ -453,10 +453,7 @@ int soil_fill_depressions_batch(float* out, const float* height, int64_t B, int6
                                 void* stream) {
   SOIL_REQUIRE(out && height, "fill_depressions_batch: null tensor");
   SOIL_REQUIRE(out != height, "fill_depressions_batch: needs distinct in and out tensors");
-  SOIL_REQUIRE(B >= 1, "fill_depressions_batch: B must be >= 1");
-  SOIL_REQUIRE(H >= 1 && W >= 1, "fill_depressions_batch: empty grid");
-  SOIL_REQUIRE(H <= INT32_MAX / W, "fill_depressions_batch: a model must have 1..2^31-1 cells");
-  SOIL_REQUIRE(edge == SOIL_D4 || edge == SOIL_D8, "fill_depressions_batch: invalid edge enumerator");
+  if (int rc = check_grid_batch("fill_depressions_batch", B, H, W, edge, 1, ""); rc != SOIL_OK) return rc;
   SOIL_DEVICE();
   return edge == SOIL_D4 ? fill_impl<4>(out, height, true, B, H, W, as_stream(stream))
                          : fill_impl<8>(out, height, true, B, H, W, as_stream(stream));

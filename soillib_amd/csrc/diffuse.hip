@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "flow_host.hpp"
 
 namespace soil {
 
@@ -324,19 +325,6 @@ struct DiffInfo {  // soil_diffuse_info
 };
 static thread_local DiffInfo t_diff_info{0, 0, 0, 0};
 
-static size_t diff_align(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-
-// Models per chunk: whole models, at most a launch's grid.y, at most 2^28 - 1 cells (4 GiB of e and g) or what
-// SOIL_FLOW_BATCH_CELLS lowers that to (read per call), at least one
-static int64_t diff_chunk_models(int64_t hw) {
-  const char* const e = std::getenv("SOIL_FLOW_BATCH_CELLS");
-  const int64_t cap_env = e ? std::atoll(e) : 0ll;
-  int64_t cap = (int64_t{1} << 28) - 1;
-  if (cap_env > 0 && cap_env < cap) cap = cap_env;
-  const int64_t per = cap / hw;
-  return per < 1 ? 1 : (per > kDiffMaxGridY ? kDiffMaxGridY : per);
-}
-
 static dim3 tr_grid(int64_t H, int64_t W, int64_t models, bool* rows_on_x) {
   const unsigned th = blocks_for(H, kTrTile), tw = blocks_for(W, kTrTile);
   *rows_on_x = th > tw;
@@ -389,11 +377,6 @@ static int diff_launch(const DiffArgs& a, const DiffScratch& w, int64_t models, 
   return 4;
 }
 
-static bool overlaps(const void* p, size_t pb, const void* q, size_t qb) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return p && q && a < b + qb && b < a + pb;
-}
-
 // What both entries refuse before any device work, under the entry's name
 static int check_diffuse(const char* what, const void* out, const void* out64, const float* height,
                          const float* diffusivity, const float* uplift, const int32_t* fixed, int64_t B, int64_t H,
@@ -403,25 +386,14 @@ static int check_diffuse(const char* what, const void* out, const void* out64, c
   SOIL_REQUIRE(height, w + ": null height");
   SOIL_REQUIRE(out || out64, w + ": no output asked for (out and out64 are both null)");
   SOIL_REQUIRE(scales, w + ": null scale");
-  SOIL_REQUIRE(B >= 1, w + ": B must be >= 1");
-  SOIL_REQUIRE(H >= 1 && W >= 1, w + ": empty grid");
-  SOIL_REQUIRE(H <= INT32_MAX / W, w + ": a model must have 1..2^31-1 cells");
-  SOIL_REQUIRE(n_scales == 1 || n_scales == B, w + ": n_scales must be 1 or B");
-  for (int64_t i = 0; i < 2 * n_scales; ++i)
-    SOIL_REQUIRE(scales[i] > 0.0f && std::isfinite(scales[i]), w + ": a scale must be a positive finite float");
-  SOIL_REQUIRE(dt >= 0.0 && std::isfinite(dt), w + ": dt must be finite and >= 0");
+  if (int rc = check_grid_batch(w, B, H, W, SOIL_D8, n_scales, ""); rc != SOIL_OK) return rc;
+  if (int rc = check_scales_positive(w, scales, n_scales); rc != SOIL_OK) return rc;
+  if (int rc = check_dt(w, dt); rc != SOIL_OK) return rc;
   SOIL_REQUIRE(diffusivity || (kappa >= 0.0 && std::isfinite(kappa)),
                w + ": kappa must be finite and >= 0 where there is no diffusivity plane");
   SOIL_REQUIRE(border == 0 || border == 1, w + ": border must be 0 or 1");
   SOIL_REQUIRE(first_axis == 0 || first_axis == 1, w + ": first_axis must be 0 or 1");
-  const int64_t hw = H * W;
-  const size_t cells = static_cast<size_t>(B > (int64_t{1} << 58) / hw ? (int64_t{1} << 58) : B * hw);
-  const void* const inputs[] = {height, diffusivity, uplift, fixed};
-  for (const void* q : inputs)
-    SOIL_REQUIRE(!overlaps(out, 4 * cells, q, 4 * cells) && !overlaps(out64, 8 * cells, q, 4 * cells),
-                 w + ": an output aliases an input plane");
-  SOIL_REQUIRE(!overlaps(out, 4 * cells, out64, 8 * cells), w + ": out and out64 overlap");
-  return SOIL_OK;
+  return check_outputs_apart(w, out, out64, plane_cells(B, H * W), {height, diffusivity, uplift, fixed});
 }
 
 static DiffScale diff_scale(const float pair[2]) {
@@ -434,31 +406,29 @@ static DiffScale diff_scale(const float pair[2]) {
 static int diffuse_run(float* out, double* out64, const float* height, const float* diffusivity, const float* uplift,
                        const int32_t* fixed, int64_t B, int64_t H, int64_t W, const float* scales, int64_t n_scales,
                        double kappa, double dt, int border, int first_axis, hipStream_t st) {
-  const int64_t hw = H * W, per = diff_chunk_models(hw);
+  // Models per chunk: whole models, at most 2^28 - 1 cells (4 GiB of e and g), at most a launch's grid.y
+  const int64_t hw = H * W, per = chunk_models((int64_t{1} << 28) - 1, hw, kDiffMaxGridY);
   const int64_t first_chunk = B < per ? B : per;
   const bool per_model = n_scales > 1;
-  const size_t b_scales = per_model ? diff_align(sizeof(DiffScale) * static_cast<size_t>(B)) : 0;
+  const size_t b_scales = per_model ? align256(sizeof(DiffScale) * static_cast<size_t>(B)) : 0;
   // 40 bytes a cell of a chunk: e / x, g and the transposed x (8 each), the transposed h, k, fixed and u (4 each)
   const size_t cells = static_cast<size_t>(first_chunk * hw);
-  const size_t b8 = diff_align(sizeof(double) * cells), b4 = diff_align(sizeof(float) * cells);
+  const size_t b8 = align256(sizeof(double) * cells), b4 = align256(sizeof(float) * cells);
   const size_t bytes = b_scales + 3 * b8 + 4 * b4;
   t_diff_info = DiffInfo{0, 0, 0, static_cast<int64_t>(bytes)};
   void* base = nullptr;
   if (int rc = workspace_get(WS_DIFFUSE, bytes, &base); rc != SOIL_OK) return rc;
   DiffScales sc{nullptr, diff_scale(scales)};
   if (per_model) {
-    std::vector<DiffScale> host(static_cast<size_t>(B));
-    for (int64_t b = 0; b < B; ++b) host[static_cast<size_t>(b)] = diff_scale(scales + 2 * b);
-    if (int rc = batch_upload(base, host.data(), sizeof(DiffScale) * host.size(), st); rc != SOIL_OK) return rc;
+    if (int rc = upload_scale_records(base, scales, B, diff_scale, st); rc != SOIL_OK) return rc;
     sc.per_model = static_cast<const DiffScale*>(base);
   }
   char* const p = static_cast<char*>(base) + b_scales;
   const DiffScratch w{reinterpret_cast<double*>(p), reinterpret_cast<double*>(p + b8), reinterpret_cast<double*>(p + 2 * b8),
                       reinterpret_cast<float*>(p + 3 * b8), reinterpret_cast<float*>(p + 3 * b8 + b4),
                       reinterpret_cast<float*>(p + 3 * b8 + 2 * b4), reinterpret_cast<int32_t*>(p + 3 * b8 + 3 * b4)};
-  // SOIL_PATHS_IDX64=1 (read per call): 64-bit offsets whatever the size, the form a model of 2^29 cells or more takes
-  const char* const e64 = std::getenv("SOIL_PATHS_IDX64");
-  const bool idx32 = static_cast<uint64_t>(hw) * sizeof(double) < (1ull << 32) && !(e64 && std::atoi(e64) == 1);
+  // (64-bit offsets: the form a model of 2^29 cells or more takes, or SOIL_PATHS_IDX64)
+  const bool idx32 = static_cast<uint64_t>(hw) * sizeof(double) < (1ull << 32) && !force_idx64();
   for (int64_t b0 = 0; b0 < B; b0 += per) {
     const int64_t nb = B - b0 < per ? B - b0 : per, at = b0 * hw;
     DiffArgs a;

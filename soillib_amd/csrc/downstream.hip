@@ -210,6 +210,29 @@ struct DownOut {
   double* out64;
 };
 
+// One round of a chunk (flow_paths.hpp ptr_chunk), dense or listed, on 32- or 64-bit offsets by the chunk
+template <bool HASB>
+static void down_launch_round(const PtrChunk& c, const PtrRound& q, hipStream_t st) {
+  uint4* const ro = c.rec[(q.r + 1) & 1];
+  const uint4* const ri = c.rec[q.r & 1];
+  double* const bo = static_cast<double*>(c.extra[(q.r + 1) & 1]);
+  const double* const bi = static_cast<const double*>(c.extra[q.r & 1]);
+  if (q.list_in) {
+    if (c.idx32)
+      k_down_list<uint32_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
+                                                                q.fill_out, c.seg);
+    else
+      k_down_list<int64_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
+                                                               q.fill_out, c.seg);
+  } else if (c.idx32) {
+    k_down_round<uint32_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
+                                                               q.fill_out, c.seg);
+  } else {
+    k_down_round<int64_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
+                                                              q.fill_out, c.seg);
+  }
+}
+
 // One chunk of `models` models (flow_paths.hpp ptr_chunk) with this file's launches; HASB: the chunk's extra planes
 // are the two B planes, 8 bytes a cell.
 template <int K, int MODE, bool HASB>
@@ -225,36 +248,11 @@ static int down_chunk(DownOut o, const DownPlanes& in, int64_t models, int64_t H
     else k_down_init<K, false, MODE, HASB><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, H, W, scales, c.flags);
     return vec;
   };
-  auto round = [&](const PtrChunk& c, const PtrRound& q) {
-    uint4* const ro = c.rec[(q.r + 1) & 1];
-    const uint4* const ri = c.rec[q.r & 1];
-    double* const bo = static_cast<double*>(c.extra[(q.r + 1) & 1]);
-    const double* const bi = static_cast<const double*>(c.extra[q.r & 1]);
-    if (q.list_in) {
-      if (c.idx32)
-        k_down_list<uint32_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
-                                                                  q.fill_out, c.seg);
-      else
-        k_down_list<int64_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
-                                                                 q.fill_out, c.seg);
-    } else if (c.idx32) {
-      k_down_round<uint32_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
-                                                                 q.fill_out, c.seg);
-    } else {
-      k_down_round<int64_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
-                                                                q.fill_out, c.seg);
-    }
-  };
+  auto round = [&](const PtrChunk& c, const PtrRound& q) { down_launch_round<HASB>(c, q, st); };
   auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
     k_down_final<<<grid, kPBlock, 0, st>>>(o.out, o.out64, rec, H * W);
   };
   return ptr_chunk(t_down_info, models, H, W, HASB ? sizeof(double) : 0, scratch, init, round, fin);
-}
-
-// Whether [p, p + pb) and [q, q + qb) share a byte (a null pointer shares nothing)
-static bool overlaps(const void* p, size_t pb, const void* q, size_t qb) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return p && q && a < b + qb && b < a + pb;
 }
 
 // What the four entries refuse before any device work, under the entry's name.  `planes`: the float inputs.
@@ -270,19 +268,10 @@ static int check_downstream(const char* what, int mode, const void* out, const v
   }
   if (int rc = check_grid_batch(w, B, H, W, edge, n_scales); rc != SOIL_OK) return rc;
   if (mode == kPower) {
-    for (int64_t i = 0; i < 2 * n_scales; ++i)
-      SOIL_REQUIRE(scales[i] > 0.0f && std::isfinite(scales[i]), w + ": a scale must be a positive finite float");
-    SOIL_REQUIRE(in.dt >= 0.0 && std::isfinite(in.dt), w + ": dt must be finite and >= 0");
+    if (int rc = check_scales_positive(w, scales, n_scales); rc != SOIL_OK) return rc;
+    if (int rc = check_dt(w, in.dt); rc != SOIL_OK) return rc;
   }
-  // (cells counted so that the byte counts below cannot wrap: a batch this large fails its allocation anyway)
-  const int64_t hw = H * W;
-  const size_t cells = static_cast<size_t>(B > (int64_t{1} << 58) / hw ? (int64_t{1} << 58) : B * hw);
-  const void* const inputs[] = {in.graph, in.stop, in.p0, in.p1, in.p2};
-  for (const void* q : inputs)
-    SOIL_REQUIRE(!overlaps(out, 4 * cells, q, 4 * cells) && !overlaps(out64, 8 * cells, q, 4 * cells),
-                 w + ": an output aliases an input plane");
-  SOIL_REQUIRE(!overlaps(out, 4 * cells, out64, 8 * cells), w + ": out and out64 overlap");
-  return SOIL_OK;
+  return check_outputs_apart(w, out, out64, plane_cells(B, H * W), {in.graph, in.stop, in.p0, in.p1, in.p2});
 }
 
 // A call through workspace slot WS_DOWNSTREAM (flow_paths.hpp ptr_run); without a scale L == 1
@@ -536,26 +525,7 @@ static int dep_chunk(DepOut o, const DepPlanes& in, const DepWork& w, int iters,
       else k_dep_init<K, false><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, w.qs, w.q, H, W, scales, c.flags);
       return vec;
     };
-    auto round = [&](const PtrChunk& c, const PtrRound& q) {
-      uint4* const ro = c.rec[(q.r + 1) & 1];
-      const uint4* const ri = c.rec[q.r & 1];
-      double* const bo = static_cast<double*>(c.extra[(q.r + 1) & 1]);
-      const double* const bi = static_cast<const double*>(c.extra[q.r & 1]);
-      if (q.list_in) {
-        if (c.idx32)
-          k_down_list<uint32_t, true><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
-                                                                    q.fill_out, c.seg);
-        else
-          k_down_list<int64_t, true><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
-                                                                   q.fill_out, c.seg);
-      } else if (c.idx32) {
-        k_down_round<uint32_t, true><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
-                                                                   q.fill_out, c.seg);
-      } else {
-        k_down_round<int64_t, true><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
-                                                                  q.fill_out, c.seg);
-      }
-    };
+    auto round = [&](const PtrChunk& c, const PtrRound& q) { down_launch_round<true>(c, q, st); };
     auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
       k_dep_final<<<grid, kPBlock, 0, st>>>(last ? o.out : nullptr, last ? o.out64 : nullptr, w.x,
                                             last ? reinterpret_cast<unsigned long long*>(o.residual) : nullptr, rec,
@@ -582,11 +552,9 @@ static int check_deposit(const char* what, const DepOut& o, const DepPlanes& in,
     return rc;
   SOIL_REQUIRE(in.deposition, w + ": null deposition");
   SOIL_REQUIRE(iters >= 1, w + ": iters must be >= 1");
-  const int64_t hw = H * W;  // (cells counted as in check_downstream)
-  const size_t cells = static_cast<size_t>(B > (int64_t{1} << 58) / hw ? (int64_t{1} << 58) : B * hw);
-  SOIL_REQUIRE(!overlaps(o.out, 4 * cells, in.deposition, 4 * cells) &&
-                   !overlaps(o.out64, 8 * cells, in.deposition, 4 * cells),
-               w + ": an output aliases an input plane");
+  const size_t cells = plane_cells(B, H * W);
+  // (out and out64 are apart: check_downstream saw to it)
+  if (int rc = check_outputs_apart(w, o.out, o.out64, cells, {in.deposition}); rc != SOIL_OK) return rc;
   const void* const planes[] = {in.graph, in.height, in.erosivity, in.uplift, in.deposition, o.out};
   for (const void* p : planes)
     SOIL_REQUIRE(!overlaps(o.flux, 4 * cells, p, 4 * cells) && !overlaps(o.residual, 8 * static_cast<size_t>(B), p, 4 * cells),

@@ -42,6 +42,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "flow_host.hpp"
 
 namespace soil {
 
@@ -269,8 +270,7 @@ static int flat_distance_run(int32_t* dist, const float* height, int64_t B, int6
   const int tiles_h = static_cast<int>((H + kLT - 1) / kLT);
   const size_t ntiles = static_cast<size_t>(tiles_w) * tiles_h;
   t_flats_info = FlatsInfo{0, static_cast<int64_t>(ntiles), B, 0};
-  auto align = [](size_t b) { return (b + 255) & ~size_t{255}; };
-  const size_t b_marks = align(ntiles * static_cast<size_t>(B));
+  const size_t b_marks = align256(ntiles * static_cast<size_t>(B));
   void* base = nullptr;
   if (int rc = workspace_get(WS_FLATS, 3 * b_marks + static_cast<size_t>(B) * H * W, &base); rc != SOIL_OK) return rc;
   unsigned char* dirty_prev = static_cast<unsigned char*>(base);
@@ -316,11 +316,7 @@ static int flat_distance_run(int32_t* dist, const float* height, int64_t B, int6
 static int check_flats(const char* what, bool pointers, int64_t B, int64_t H, int64_t W, int edge) {
   const std::string w(what);
   SOIL_REQUIRE(pointers, w + ": null tensor");
-  SOIL_REQUIRE(B >= 1, w + ": B must be >= 1");
-  SOIL_REQUIRE(H >= 1 && W >= 1, w + ": empty grid");
-  SOIL_REQUIRE(H <= INT32_MAX / W, w + ": a model must have 1..2^31-1 cells (int32 graph)");
-  SOIL_REQUIRE(edge == SOIL_D4 || edge == SOIL_D8, w + ": invalid edge enumerator");
-  return SOIL_OK;
+  return check_grid_batch(w, B, H, W, edge);
 }
 
 static int flat_receivers_run(int32_t* out, const int32_t* in, const float* height, const int32_t* dist, int64_t B,

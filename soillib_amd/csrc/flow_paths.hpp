@@ -7,8 +7,9 @@
 //           for cell n, in -> out; true where it wrote a new record".  Each file's __global__ round kernels are one
 //           statement: the body over a lambda around its path_cell / down_cell.
 //   host    models per chunk, the layout and carving of a chunk's scratch, the round plan, the chunk (init, rounds,
-//           final) and the loop over the chunks of a call (ptr_chunk, ptr_run), the call's info record, the shape
-//           refusals.  Each file hands in its launches as callables and keeps its workspace slot and info instance.
+//           final) and the loop over the chunks of a call (ptr_chunk, ptr_run), the call's info record.  Each file
+//           hands in its launches as callables and keeps its workspace slot and info instance.  The shape refusals,
+//           the chunk-size rule and the knobs read per call are flow_host.hpp's.
 //
 // The records' other words, the per-cell operation, the init and the final kernels are each file's own.
 #pragma once
@@ -16,7 +17,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "common.hpp"
+#include "flow_host.hpp"
 
 namespace soil {
 
@@ -160,8 +161,6 @@ inline int ceil_log2(int64_t v) {  // ceil(log2(v)), v >= 1, in integers
   return k;
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-
 // ---- the host driver ------------------------------------------------------------------------------------------
 
 // What the last call of an entry on this host thread did (soil_flow_paths_info, soil_downstream_info; each file has
@@ -171,26 +170,11 @@ struct PtrInfo {
   void store(int64_t info[4]) const { info[0] = chunks, info[1] = vec_chunks, info[2] = idx64_chunks, info[3] = rounds; }
 };
 
-// The shape refusals every entry shares, under the entry's name `w`, in this order
-inline int check_grid_batch(const std::string& w, int64_t B, int64_t H, int64_t W, int edge, int64_t n_scales) {
-  SOIL_REQUIRE(B >= 1, w + ": B must be >= 1");
-  SOIL_REQUIRE(H >= 1 && W >= 1, w + ": empty grid");
-  SOIL_REQUIRE(H <= INT32_MAX / W, w + ": a model must have 1..2^31-1 cells (int32 graph)");
-  SOIL_REQUIRE(n_scales == 1 || n_scales == B, w + ": n_scales must be 1 or B");
-  SOIL_REQUIRE(edge == SOIL_D4 || edge == SOIL_D8, w + ": invalid edge enumerator");
-  return SOIL_OK;
-}
-
 // Models per chunk: as many whole models as keep the rounds on 32-bit offsets (16 bytes a cell under 4 GiB; an extra
 // plane's 8 bytes a cell lie below that anyway) and one init launch (grid.z), at least one.  SOIL_FLOW_BATCH_CELLS
-// lowers the cap on the cells of a chunk, as it does for soil_accumulate_batch (read per call).
+// lowers the cap on the cells of a chunk, as it does for soil_accumulate_batch (flow_host.hpp chunk_models).
 inline int64_t ptr_chunk_models(int64_t cells_per_model) {
-  const char* const e = std::getenv("SOIL_FLOW_BATCH_CELLS");
-  const int64_t cap_env = e ? std::atoll(e) : 0ll;
-  int64_t cap = static_cast<int64_t>((1ull << 32) / sizeof(uint4)) - 1;
-  if (cap_env > 0 && cap_env < cap) cap = cap_env;
-  const int64_t per = cap / cells_per_model;
-  return per < 1 ? 1 : (per > kPathsMaxGridZ ? kPathsMaxGridZ : per);
+  return chunk_models(static_cast<int64_t>((1ull << 32) / sizeof(uint4)) - 1, cells_per_model, kPathsMaxGridZ);
 }
 
 // The scratch of a chunk of `elem` cells, in this order: two record buffers, two planes of `extra` bytes a cell
@@ -270,10 +254,8 @@ int ptr_chunk(PtrInfo& info, int64_t models, int64_t H, int64_t W, size_t extra,
   const int list_from_env = e ? std::atoi(e) : 1;
   c.rounds = ceil_log2(hw);
   const int list_from = (list_from_env >= 1 && list_from_env < c.rounds) ? list_from_env : c.rounds;
-  // SOIL_PATHS_IDX64=1 (read per call): 64-bit offsets whatever the size — the form a single model of 2^28 cells or
-  // more takes, reached by the tests at small shapes through it.
-  const char* const e64 = std::getenv("SOIL_PATHS_IDX64");
-  c.idx32 = static_cast<uint64_t>(elem) * sizeof(uint4) < (1ull << 32) && !(e64 && std::atoi(e64) == 1);
+  // (64-bit offsets: the form a single model of 2^28 cells or more takes, or SOIL_PATHS_IDX64)
+  c.idx32 = static_cast<uint64_t>(elem) * sizeof(uint4) < (1ull << 32) && !force_idx64();
 
   const bool vec = init(c);
   SOIL_LAUNCH_CHECK();
@@ -316,9 +298,7 @@ int ptr_run(WorkspaceSlot slot, PtrInfo& info, int64_t B, int64_t H, int64_t W, 
     return rc;
   PathScales sc{nullptr, scales ? path_scale(scales) : none};
   if (per_model) {
-    std::vector<PathScale> host(static_cast<size_t>(B));
-    for (int64_t b = 0; b < B; ++b) host[static_cast<size_t>(b)] = path_scale(scales + 2 * b);
-    if (int rc = batch_upload(base, host.data(), sizeof(PathScale) * host.size(), st); rc != SOIL_OK) return rc;
+    if (int rc = upload_scale_records(base, scales, B, path_scale, st); rc != SOIL_OK) return rc;
     sc.per_model = static_cast<const PathScale*>(base);
   }
   char* const scratch = static_cast<char*>(base) + b_scales;

@@ -10,6 +10,7 @@
 #include <unordered_map>
 
 #include "common.hpp"
+#include "flow_host.hpp"
 #include "window.hpp"
 
 namespace soil {
@@ -999,12 +1000,7 @@ static int accumulate_impl(float* out, const int32_t* graph, const float* source
 // the cells of a chunk (read per call: the tests reach the chunking with tiny shapes through it).
 template <int K>
 static int64_t flow_batch_models(int64_t cells_per_model) {
-  const char* const e = std::getenv("SOIL_FLOW_BATCH_CELLS");
-  const int64_t cap_env = e ? std::atoll(e) : 0ll;
-  int64_t cap = static_cast<int64_t>(((1ull << 32) / (K * sizeof(float))) - 1);
-  if (cap_env > 0 && cap_env < cap) cap = cap_env;
-  const int64_t per = cap / cells_per_model;
-  return per < 1 ? 1 : (per > kMaxGridZ ? kMaxGridZ : per);
+  return chunk_models(static_cast<int64_t>(((1ull << 32) / (K * sizeof(float))) - 1), cells_per_model, kMaxGridZ);
 }
 
 // soil_accumulate_batch: chunks of whole models, each one accumulation over the chunk's cells on `st`, one after
@@ -1163,11 +1159,7 @@ namespace {
 int check_flow_batch(const char* what, bool tensors, int64_t B, int64_t H, int64_t W, int edge = SOIL_D8) {
   const std::string w(what);
   SOIL_REQUIRE(tensors, w + ": null tensor");
-  SOIL_REQUIRE(B >= 1, w + ": B must be >= 1");
-  SOIL_REQUIRE(H >= 1 && W >= 1, w + ": empty grid");
-  SOIL_REQUIRE(H <= INT32_MAX / W, w + ": a model must have 1..2^31-1 cells (int32 graph)");
-  SOIL_REQUIRE(edge == SOIL_D4 || edge == SOIL_D8, w + ": invalid edge enumerator");
-  return SOIL_OK;
+  return check_grid_batch(w, B, H, W, edge);
 }
 
 // Host words of a batch entry (B seeds, B scale pairs) on the device: one stream-ordered copy through the host

@@ -54,13 +54,12 @@ the same world extent: the multiscale schedule (erode coarse, resample, erode fi
 (soil_erode_batch_exceedance): the summaries of a heavy-tailed ensemble.
 """
 import ctypes as C
-import math
 import numbers
 import os
 
 import numpy as np
 
-from . import _abi, silt
+from . import _abi, _check, silt
 
 # the channels of a soil_model_stats record and of the ensemble maps, in the order of include/soil_hip.h
 STAT_CHANNELS = ("bedrock", "sediment", "height", "waterHeight", "mass", "debris", "velocity.x", "velocity.y",
@@ -672,12 +671,7 @@ class ErosionBatch:
     # ---- flow routing of every model (soil_hip.h: "flow graphs: batches of models") ----
 
     def _edge(self, who, edge):
-        from . import soil
-        if edge is None:
-            return soil.d8
-        if isinstance(edge, bool) or edge not in (soil.d4, soil.d8):
-            raise ValueError("ErosionBatch.%s: edge must be d4 or d8, got %r" % (who, edge))
-        return int(edge)
+        return _check.edge("ErosionBatch.%s" % who, _abi.D8 if edge is None else edge)
 
     def _flow_tensor(self, who, what, t, dtype):
         """`t` must be a (B, H, W) silt tensor of `dtype`, or ValueError."""
@@ -688,15 +682,21 @@ class ErosionBatch:
                 who, what, dtype.name, shape, got))
         return t
 
-    def _check_draw(self, who, T, offset):
-        """The temperature and the offset of a random_weighted draw, or ValueError."""
-        from . import soil
-        if T is None or isinstance(T, bool) or not isinstance(T, numbers.Real) or not math.isfinite(T):
-            raise ValueError("ErosionBatch.%s: kind 'random_weighted' needs a finite temperature T, got %r" % (who, T))
-        if not soil.valid_temperature(T):
-            raise ValueError("ErosionBatch.%s: T must be 0 or a normal positive float32, got %r" % (who, T))
-        if isinstance(offset, bool) or not isinstance(offset, numbers.Integral) or offset < 0:
-            raise ValueError("ErosionBatch.%s: offset must be an integer >= 0, got %r" % (who, offset))
+    def _optional(self, who, dtype, **tensors):
+        """Each of `tensors` (by the argument's name) is None or a (B, H, W) tensor of `dtype`, or ValueError."""
+        for what, t in tensors.items():
+            if t is not None:
+                self._flow_tensor(who, what, t, dtype)
+
+    def _routing(self, who, kind, edge, T, offset, uplift):
+        """The arguments that stream_power(), stream_power_deposit() and evolve() route by, or ValueError: the edge
+        and the batch's path scale(s)."""
+        _check.kind("ErosionBatch.%s" % who, kind, ("steepest", "random_weighted"))
+        e = self._edge(who, edge)
+        if kind == "random_weighted":
+            _check.draw("ErosionBatch.%s" % who, T, offset)
+        self._optional(who, silt.float32, uplift=uplift)
+        return e, self._path_scale(who)
 
     def flow(self, kind="steepest", edge=None, T=None, offset=0):
         """The receiver graph of each model's `height` plane: a (B, H, W) int32 silt GPU tensor whose entries are
@@ -707,11 +707,10 @@ class ErosionBatch:
         d8.  An unknown kind, a missing or refused T or a bad edge raises ValueError before any device work.  Nothing
         synchronises."""
         from . import soil
-        if kind not in ("steepest", "direction", "random_weighted"):
-            raise ValueError("ErosionBatch.flow: kind must be 'steepest', 'direction' or 'random_weighted', got %r" % (kind,))
+        _check.kind("ErosionBatch.flow", kind, ("steepest", "direction", "random_weighted"))
         e = self._edge("flow", edge)
         if kind == "random_weighted":
-            self._check_draw("flow", T, offset)
+            _check.draw("ErosionBatch.flow", T, offset)
             return soil.random_weighted_batch(self.height, e, self.seeds, int(offset), float(T))
         return (soil.steepest_batch if kind == "steepest" else soil.direction_batch)(self.height, e)
 
@@ -723,12 +722,8 @@ class ErosionBatch:
         before any device work.  Nothing synchronises."""
         from . import soil
         e = self._edge("drainage", edge)
-        if graph is not None:
-            self._flow_tensor("drainage", "graph", graph, silt.int32)
-        if source is not None:
-            self._flow_tensor("drainage", "source", source, silt.float32)
-        if decay is not None:
-            self._flow_tensor("drainage", "decay", decay, silt.float32)
+        self._optional("drainage", silt.int32, graph=graph)
+        self._optional("drainage", silt.float32, source=source, decay=decay)
         if graph is None:
             graph = self.flow(edge=e)
         if source is None:
@@ -741,16 +736,8 @@ class ErosionBatch:
         (soil_slope_batch), with the batch's one scale or model b's own (x, y) of `scales`.  A graph of the wrong
         shape or dtype, or a wrong count of scales, raises ValueError before any device work."""
         from . import soil
-        if graph is not None:
-            self._flow_tensor("flow_slope", "graph", graph, silt.int32)
-        if self.scales is not None:
-            try:
-                self._check_scales()
-            except ValueError as e:
-                raise ValueError("ErosionBatch.flow_slope: %s" % e)
-            scale = [[float(s[0]), float(s[1])] for s in self.scales]
-        else:
-            scale = [float(self.scale[0]), float(self.scale[1])]
+        self._optional("flow_slope", silt.int32, graph=graph)
+        scale = self._path_scale("flow_slope")
         if graph is None:
             graph = self.flow()
         return soil.slope_batch(self.height, graph, scale)
@@ -774,10 +761,7 @@ class ErosionBatch:
         edge raises ValueError before any device work.  Nothing synchronises."""
         from . import soil
         e = self._edge("basins", edge)
-        if graph is not None:
-            self._flow_tensor("basins", "graph", graph, silt.int32)
-        if stop is not None:
-            self._flow_tensor("basins", "stop", stop, silt.int32)
+        self._optional("basins", silt.int32, graph=graph, stop=stop)
         if graph is None:
             graph = self.flow(edge=e)
         return soil.basins_batch(graph, e, stop)
@@ -788,10 +772,7 @@ class ErosionBatch:
         model b's own (x, y) of `scales`, exactly as flow_slope() takes them.  `stop` and `edge` as in basins()."""
         from . import soil
         e = self._edge("flow_length", edge)
-        if graph is not None:
-            self._flow_tensor("flow_length", "graph", graph, silt.int32)
-        if stop is not None:
-            self._flow_tensor("flow_length", "stop", stop, silt.int32)
+        self._optional("flow_length", silt.int32, graph=graph, stop=stop)
         scale = self._path_scale("flow_length")
         if graph is None:
             graph = self.flow(edge=e)
@@ -806,13 +787,9 @@ class ErosionBatch:
         synchronises."""
         from . import soil
         e = self._edge("downstream", edge)
-        if graph is not None:
-            self._flow_tensor("downstream", "graph", graph, silt.int32)
-        for name, t in (("a", a), ("b", b), ("terminal", terminal)):
-            if t is not None:
-                self._flow_tensor("downstream", name, t, silt.float32)
-        if stop is not None:
-            self._flow_tensor("downstream", "stop", stop, silt.int32)
+        self._optional("downstream", silt.int32, graph=graph)
+        self._optional("downstream", silt.float32, a=a, b=b, terminal=terminal)
+        self._optional("downstream", silt.int32, stop=stop)
         scale = self._path_scale("downstream") if scaled else None
         if graph is None:
             graph = self.flow(edge=e)
@@ -825,18 +802,11 @@ class ErosionBatch:
         touched.  `uplift`: a (B, H, W) float32 tensor or None; `kind`, `edge`, `T`, `offset` as in conditioned().  A
         bad argument raises ValueError before any device work.  Synchronises the stream (the fill does)."""
         from . import soil
-        for name, v in (("dt", dt), ("K", K), ("m", m)):
-            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (name != "m" and v < 0):
-                raise ValueError("ErosionBatch.stream_power: %s must be a finite number%s, got %r" % (
-                    name, "" if name == "m" else " >= 0", v))
-        if kind not in ("steepest", "random_weighted"):
-            raise ValueError("ErosionBatch.stream_power: kind must be 'steepest' or 'random_weighted', got %r" % (kind,))
-        e = self._edge("stream_power", edge)
-        if kind == "random_weighted":
-            self._check_draw("stream_power", T, offset)
-        if uplift is not None:
-            self._flow_tensor("stream_power", "uplift", uplift, silt.float32)
-        scale = self._path_scale("stream_power")
+        who = "ErosionBatch.stream_power"
+        _check.number(who, "dt", dt)
+        _check.number(who, "K", K)
+        _check.number(who, "m", m, lo=None)
+        e, scale = self._routing("stream_power", kind, edge, T, offset, uplift)
         filled, graph = self.conditioned(kind, e, T, offset)
         area = self.drainage(graph=graph, edge=e)
         return soil.stream_power_batch(filled, graph, soil.erosivity(area, K, m), e, scale, dt, uplift)
@@ -851,21 +821,13 @@ class ErosionBatch:
         deposition coefficient, a finite number >= 0; the rest as in stream_power().  A bad argument raises ValueError
         before any device work.  Synchronises the stream (the fill does)."""
         from . import soil
-        who = "stream_power_deposit"
-        for name, v in (("dt", dt), ("K", K), ("m", m), ("G", G)):
-            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (name != "m" and v < 0):
-                raise ValueError("ErosionBatch.%s: %s must be a finite number%s, got %r" % (
-                    who, name, "" if name == "m" else " >= 0", v))
-        if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= iters < 2 ** 31:
-            raise ValueError("ErosionBatch.%s: iters must be an integer >= 1, got %r" % (who, iters))
-        if kind not in ("steepest", "random_weighted"):
-            raise ValueError("ErosionBatch.%s: kind must be 'steepest' or 'random_weighted', got %r" % (who, kind))
-        e = self._edge(who, edge)
-        if kind == "random_weighted":
-            self._check_draw(who, T, offset)
-        if uplift is not None:
-            self._flow_tensor(who, "uplift", uplift, silt.float32)
-        scale = self._path_scale(who)
+        who = "ErosionBatch.stream_power_deposit"
+        _check.number(who, "dt", dt)
+        _check.number(who, "K", K)
+        _check.number(who, "m", m, lo=None)
+        _check.number(who, "G", G)
+        _check.count(who, "iters", iters)
+        e, scale = self._routing("stream_power_deposit", kind, edge, T, offset, uplift)
         filled, graph = self.conditioned(kind, e, T, offset)
         area = self.drainage(graph=graph, edge=e)
         # a cell's area, model by model: float32 of the product of its pair, one value a model either way
@@ -876,22 +838,13 @@ class ErosionBatch:
 
     def _check_diffuse(self, who, dt, kappa, diffusivity, uplift, fixed, border, first_axis):
         """The arguments of diffuse() and of the diffusion half of evolve(), or ValueError."""
-        if isinstance(dt, bool) or not isinstance(dt, numbers.Real) or not math.isfinite(dt) or dt < 0:
-            raise ValueError("ErosionBatch.%s: dt must be a finite number >= 0, got %r" % (who, dt))
-        if (kappa is None) == (diffusivity is None):
-            raise ValueError("ErosionBatch.%s: exactly one of kappa and diffusivity must be given" % who)
-        if kappa is not None and (isinstance(kappa, bool) or not isinstance(kappa, numbers.Real)
-                                  or not math.isfinite(kappa) or kappa < 0):
-            raise ValueError("ErosionBatch.%s: kappa must be a finite number >= 0, got %r" % (who, kappa))
-        for name, t in (("diffusivity", diffusivity), ("uplift", uplift)):
-            if t is not None:
-                self._flow_tensor(who, name, t, silt.float32)
-        if fixed is not None:
-            self._flow_tensor(who, "fixed", fixed, silt.int32)
-        if border not in ("fixed", "free"):
-            raise ValueError("ErosionBatch.%s: border must be 'fixed' or 'free', got %r" % (who, border))
-        if isinstance(first_axis, bool) or first_axis not in (0, 1):
-            raise ValueError("ErosionBatch.%s: first_axis must be 0 or 1, got %r" % (who, first_axis))
+        full = "ErosionBatch.%s" % who
+        _check.number(full, "dt", dt)
+        _check.kappa_or_diffusivity(full, kappa, diffusivity)
+        self._optional(who, silt.float32, diffusivity=diffusivity, uplift=uplift)
+        self._optional(who, silt.int32, fixed=fixed)
+        _check.border(full, border)
+        _check.first_axis(full, first_axis)
 
     def diffuse(self, dt, kappa=None, diffusivity=None, uplift=None, fixed=None, border="fixed", first_axis=0,
                 double=False):
@@ -915,24 +868,14 @@ class ErosionBatch:
         material is deposited on its way down.  Returns the (B, H, W) float32 heights; the batch's own planes are not
         touched.  A bad argument raises ValueError before any device work.  Synchronises the stream (the fill does)."""
         from . import soil
+        who = "ErosionBatch.evolve"
         self._check_diffuse("evolve", dt, kappa, None, None, None, "fixed", first_axis)
         if G is not None:
-            if isinstance(G, bool) or not isinstance(G, numbers.Real) or not math.isfinite(G) or G < 0:
-                raise ValueError("ErosionBatch.evolve: G must be a finite number >= 0, got %r" % (G,))
-            if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= iters < 2 ** 31:
-                raise ValueError("ErosionBatch.evolve: iters must be an integer >= 1, got %r" % (iters,))
-        for name, v in (("K", K), ("m", m)):
-            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (name != "m" and v < 0):
-                raise ValueError("ErosionBatch.evolve: %s must be a finite number%s, got %r" % (
-                    name, "" if name == "m" else " >= 0", v))
-        if kind not in ("steepest", "random_weighted"):
-            raise ValueError("ErosionBatch.evolve: kind must be 'steepest' or 'random_weighted', got %r" % (kind,))
-        self._edge("evolve", edge)
-        if kind == "random_weighted":
-            self._check_draw("evolve", T, offset)
-        if uplift is not None:
-            self._flow_tensor("evolve", "uplift", uplift, silt.float32)
-        scale = self._path_scale("evolve")
+            _check.number(who, "G", G)
+            _check.count(who, "iters", iters)
+        _check.number(who, "K", K)
+        _check.number(who, "m", m, lo=None)
+        _, scale = self._routing("evolve", kind, edge, T, offset, uplift)
         if G is None:
             carved = self.stream_power(dt, K, m, kind, edge, T, offset, uplift)
         else:
@@ -956,12 +899,11 @@ class ErosionBatch:
         flow() stops at every closed pit of an eroded model, every cell then drains off the grid.  A bad kind, edge,
         T or offset raises ValueError before any device work.  Synchronises the stream."""
         from . import soil
-        if kind not in ("steepest", "random_weighted"):
-            raise ValueError("ErosionBatch.conditioned: kind must be 'steepest' or 'random_weighted' (the entries of "
-                             "'direction' are not indices), got %r" % (kind,))
+        _check.kind("ErosionBatch.conditioned", kind, ("steepest", "random_weighted"),
+                    " (the entries of 'direction' are not indices)")
         e = self._edge("conditioned", edge)
         if kind == "random_weighted":
-            self._check_draw("conditioned", T, offset)
+            _check.draw("ErosionBatch.conditioned", T, offset)
         filled = soil.fill_depressions_batch(self.height, e)
         graph = None
         if kind == "random_weighted":

@@ -15,7 +15,8 @@ import time
 
 import numpy as np
 
-from . import _abi, silt
+from . import _abi, _check, silt
+from ._check import valid_temperature  # noqa: F401 (soil.valid_temperature)
 
 # ---------------------------------------------------------------- edge enum
 
@@ -106,13 +107,6 @@ def steepest(height, edge_):
     out = silt.tensor(silt.int32, silt.shape(H, W), silt.gpu)
     _call("soil_steepest", out.c_ptr, _f(height, "height"), H, W, edge_, _abi.stream())
     return out
-
-
-def valid_temperature(T):
-    """Whether soil_random_weighted, soil_random_weighted_batch and soil_multiflow take `T` (soil_hip.h): as a
-    float32 it is 0 or a normal positive number.  They refuse anything else (ValueError here)."""
-    t = C.c_float(float(T)).value
-    return t == 0.0 or 2.0 ** -126 <= t < math.inf
 
 
 def random_weighted(height, edge_, seed, offset, T):
@@ -263,44 +257,99 @@ def _one_pair(scale, what):
     return (C.c_float * 2)(*pair)
 
 
-def _edge_of(edge_, what):
-    if isinstance(edge_, bool) or edge_ not in (d4, d8):
-        raise ValueError("%s: edge must be d4 or d8, got %r" % (what, edge_))
-    return int(edge_)
+def _float_plane(t, shape, what):
+    _same(t, shape, what)
+    if t.type is not silt.float32:
+        raise ValueError("%s: expected a float32 tensor, got %s" % (what, t.type.name))
 
 
-def _flow_paths(who, graph, edge_, scale, stop, want):
-    """soil_flow_paths on a (H, W) graph; `want`: which of (terminal, steps, length) to make."""
-    H, W = _hw2(graph, "%s: graph" % who)
-    e = _edge_of(edge_, who)
-    _int_plane(graph, (H, W), "%s: graph" % who)
+def _opt_i(t, what):
+    return None if t is None else _gpu(t, silt.int32, what)
+
+
+def _shape(dims, t, what):
+    """The (H, W) of a grid (dims 2) or the (B, H, W) of a batch (dims 3)."""
+    return (_hw2 if dims == 2 else _bhw)(t, what)
+
+
+def _float_planes(who, shape, planes):
+    """`planes`, a list of (name, tensor or None, required), are float32 planes of `shape`."""
+    for name, t, required in planes:
+        if t is None and required:
+            raise ValueError("%s: %s is required" % (who, name))
+        if t is not None:
+            _float_plane(t, shape, "%s: %s" % (who, name))
+
+
+def _scales(who, dims, scale, B, none_ok=False):
+    """`scale` — one pair for a grid, one pair or B pairs for a batch — as (C array of floats, what the C call takes
+    for it: the array, and for a batch the number of pairs)."""
+    if scale is None and not none_ok:
+        raise ValueError("%s: scale must be one (sx, sy) pair%s" % (who, "" if dims == 2 else " or B pairs"))
+    pairs, n = (None, 1) if scale is None else (_one_pair(scale, who), 1) if dims == 2 else _scale_pairs(scale, B, who)
+    return pairs, (pairs,) if dims == 2 else (pairs, n)
+
+
+def _positive(who, pairs, scale):
+    if any(not (v > 0 and math.isfinite(v)) for v in pairs):
+        raise ValueError("%s: scale entries must be positive finite floats, got %r" % (who, scale))
+
+
+def _out_pair(shape, double):
+    """The result tensor, float64 with `double`, and the C call's (out, out64)."""
+    out = silt.tensor(silt.float64 if double else silt.float32, silt.shape(*shape), silt.gpu)
+    return out, (None, out.c_ptr) if double else (out.c_ptr, None)
+
+
+def _on_stream():
+    """torch's current stream set to the one the library's calls go to."""
+    import torch
+    return torch.cuda.stream(torch.cuda.ExternalStream(_abi._stream)) if _abi._stream else contextlib.nullcontext()
+
+
+def _call_info(entry, names=("chunks", "vec_chunks", "idx64_chunks", "rounds")):
+    """The four-word info record of `entry` as a dict; the default names are those of a pointer-doubling entry
+    (csrc/flow_paths.hpp PtrInfo)."""
+    info = (C.c_int64 * 4)()
+    _call(entry, info)
+    return dict(zip(names, (int(v) for v in info)))
+
+
+def _flow_paths(who, dims, graph, edge_, scale, stop, want):
+    """soil_flow_paths on a (H, W) graph, soil_flow_paths_batch on (B, H, W); `want`: which of (terminal, steps,
+    length) to make."""
+    shape = _shape(dims, graph, "%s: graph" % who)
+    e = _check.edge(who, edge_)
+    _int_plane(graph, shape, "%s: graph" % who)
     if stop is not None:
-        _int_plane(stop, (H, W), "%s: stop" % who)
-    pair = _one_pair(scale, who) if want[2] else None
-    g_ptr, s_ptr = _gpu(graph, silt.int32, "graph"), None if stop is None else _gpu(stop, silt.int32, "stop")
-    outs = [silt.tensor(dt, silt.shape(H, W), silt.gpu) if w else None
+        _int_plane(stop, shape, "%s: stop" % who)
+    if not want[2]:
+        tail = (None,) if dims == 2 else (None, 1)
+    else:
+        tail = (_one_pair(scale, who),) if dims == 2 else _scale_pairs(scale, shape[0], who)
+    g_ptr, s_ptr = _gpu(graph, silt.int32, "graph"), _opt_i(stop, "stop")
+    outs = [silt.tensor(dt, silt.shape(*shape), silt.gpu) if w else None
             for w, dt in zip(want, (silt.int32, silt.int32, silt.float32))]
-    _call("soil_flow_paths", *[o.c_ptr if o is not None else None for o in outs], g_ptr, s_ptr, H, W, e, pair,
-          _abi.stream())
+    _call("soil_flow_paths" + ("" if dims == 2 else "_batch"), *[o.c_ptr if o is not None else None for o in outs],
+          g_ptr, s_ptr, *shape, e, *tail, _abi.stream())
     return tuple(outs)
-
 
 def flow_paths(graph, edge_, scale=None, stop=None):
     """soil_flow_paths: (terminal, steps, length) of every cell's walk down `graph` — the cell it ends on, the
     number of edges, and the way's length with the (sx, sy) of `scale` (None: no length, the third item is None).
     `stop`: an optional int32 plane of pour points (non-zero: the walk ends here).  Cells on a cycle, or draining into
     one, get -1 / -1 / NaN."""
-    return _flow_paths("flow_paths", graph, edge_, scale, stop, (True, True, scale is not None))
+    return _flow_paths("flow_paths", 2, graph, edge_, scale, stop, (True, True, scale is not None))
 
 
 def basins(graph, edge_, stop=None):
     """The terminal of every cell's walk (flow_paths): cells with the same value form a basin."""
-    return _flow_paths("basins", graph, edge_, None, stop, (True, False, False))[0]
+    return _flow_paths("basins", 2, graph, edge_, None, stop, (True, False, False))[0]
 
 
 def flow_length(graph, edge_, scale, stop=None):
     """The length of every cell's way to its terminal (flow_paths)."""
-    return _flow_paths("flow_length", graph, edge_, scale, stop, (False, False, True))[2]
+    return _flow_paths("flow_length", 2, graph, edge_, scale, stop, (False, False, True))[2]
 
 
 def watershed(graph, edge_, cells):
@@ -315,7 +364,7 @@ def watershed(graph, edge_, cells):
     if not points or any(not (0 <= x < H and 0 <= y < W) for x, y in points):
         raise ValueError("watershed: cells must be one or more (x, y) inside the (%d, %d) grid, got %r" % (H, W, cells))
     _int_plane(graph, (H, W), "watershed: graph")
-    _edge_of(edge_, "watershed")
+    _check.edge("watershed", edge_)
     import torch
     plane = np.zeros((H, W), np.int32)
     for x, y in points:
@@ -324,48 +373,26 @@ def watershed(graph, edge_, cells):
     terminal = basins(graph, edge_, stop)
     # a walk that ends on a pour point: its terminal carries the stop mark (unresolved cells: -1, no mark) — a gather
     # in torch, on the stream the library's calls go to
-    with torch.cuda.stream(torch.cuda.ExternalStream(_abi._stream)) if _abi._stream else contextlib.nullcontext():
+    with _on_stream():
         t, marks = terminal.view_torch().view(-1), stop.view_torch().view(-1)
         mask = torch.where(t >= 0, marks[t.clamp(min=0).long()], torch.zeros_like(t))
     return silt.tensor.from_torch(mask.view(H, W).contiguous())
 
 
-def _flow_paths_batch(who, graph, edge_, scale, stop, want):
-    B, H, W = _bhw(graph, "%s: graph" % who)
-    e = _edge_of(edge_, who)
-    _int_plane(graph, (B, H, W), "%s: graph" % who)
-    if stop is not None:
-        _int_plane(stop, (B, H, W), "%s: stop" % who)
-    pairs, n = _scale_pairs(scale, B, who) if want[2] else (None, 1)
-    g_ptr, s_ptr = _gpu(graph, silt.int32, "graph"), None if stop is None else _gpu(stop, silt.int32, "stop")
-    outs = [silt.tensor(dt, silt.shape(B, H, W), silt.gpu) if w else None
-            for w, dt in zip(want, (silt.int32, silt.int32, silt.float32))]
-    _call("soil_flow_paths_batch", *[o.c_ptr if o is not None else None for o in outs], g_ptr, s_ptr, B, H, W, e,
-          pairs, n, _abi.stream())
-    return tuple(outs)
-
-
 def flow_paths_batch(graph, edge_, scale=None, stop=None):
     """soil_flow_paths_batch: model b as `flow_paths(graph[b], edge, scale, stop[b])`; `scale` is one pair or B
     pairs (None: no length); entries of `graph`, `stop` and the terminals are indices within their model."""
-    return _flow_paths_batch("flow_paths_batch", graph, edge_, scale, stop, (True, True, scale is not None))
+    return _flow_paths("flow_paths_batch", 3, graph, edge_, scale, stop, (True, True, scale is not None))
 
 
 def basins_batch(graph, edge_, stop=None):
     """`basins` of each of the B models."""
-    return _flow_paths_batch("basins_batch", graph, edge_, None, stop, (True, False, False))[0]
+    return _flow_paths("basins_batch", 3, graph, edge_, None, stop, (True, False, False))[0]
 
 
 def flow_length_batch(graph, edge_, scale, stop=None):
     """`flow_length` of each of the B models; `scale` is one pair or B pairs."""
-    return _flow_paths_batch("flow_length_batch", graph, edge_, scale, stop, (False, False, True))[2]
-
-
-def _call_info(entry):
-    """The info record of a pointer-doubling entry (csrc/flow_paths.hpp PtrInfo) as a dict."""
-    info = (C.c_int64 * 4)()
-    _call(entry, info)
-    return dict(zip(("chunks", "vec_chunks", "idx64_chunks", "rounds"), (int(v) for v in info)))
+    return _flow_paths("flow_length_batch", 3, graph, edge_, scale, stop, (False, False, True))[2]
 
 
 def flow_paths_info():
@@ -382,41 +409,26 @@ def _downstream(who, dims, graph, edge_, planes, scale, stop, double, dt=None):
     """soil_downstream / soil_stream_power and their _batch forms: `planes` is a list of (name, tensor or None,
     required) in the order of the C call's float planes; `dt` None: the sum, else the stream-power step.  Every check
     comes before any device work."""
-    shape = (_hw2 if dims == 2 else _bhw)(graph, "%s: graph" % who)
-    e = _edge_of(edge_, who)
+    shape = _shape(dims, graph, "%s: graph" % who)
+    e = _check.edge(who, edge_)
     _int_plane(graph, shape, "%s: graph" % who)
-    for name, t, required in planes:
-        if t is None and required:
-            raise ValueError("%s: %s is required" % (who, name))
-        if t is not None:
-            _float_plane(t, shape, "%s: %s" % (who, name))
+    _float_planes(who, shape, planes)
     if stop is not None:
         _int_plane(stop, shape, "%s: stop" % who)
-    if scale is None:
-        if dt is not None:
-            raise ValueError("%s: scale must be one (sx, sy) pair%s" % (who, "" if dims == 2 else " or B pairs"))
-        pairs, n = None, 1
-    elif dims == 2:
-        pairs, n = _one_pair(scale, who), 1
-    else:
-        pairs, n = _scale_pairs(scale, shape[0], who)
+    pairs, tail = _scales(who, dims, scale, shape[0], none_ok=dt is None)
     if dt is not None:
-        if isinstance(dt, bool) or not isinstance(dt, (int, float)) or not math.isfinite(dt) or dt < 0:
-            raise ValueError("%s: dt must be a finite number >= 0, got %r" % (who, dt))
-        if any(not (v > 0 and math.isfinite(v)) for v in pairs):
-            raise ValueError("%s: scale entries must be positive finite floats, got %r" % (who, scale))
+        dt = _check.number(who, "dt", dt)
+        _positive(who, pairs, scale)
     g_ptr = _gpu(graph, silt.int32, "graph")
     f_ptrs = [_opt_f(t, name) for name, t, _ in planes]
-    s_ptr = None if stop is None else _gpu(stop, silt.int32, "stop")
-    out = silt.tensor(silt.float64 if double else silt.float32, silt.shape(*shape), silt.gpu)
-    outs = (None, out.c_ptr) if double else (out.c_ptr, None)
-    tail = (pairs,) if dims == 2 else (pairs, n)
+    s_ptr = _opt_i(stop, "stop")
+    out, outs = _out_pair(shape, double)
+    batch = "" if dims == 2 else "_batch"
     if dt is None:
-        _call("soil_downstream" + ("" if dims == 2 else "_batch"), *outs, g_ptr, *f_ptrs, s_ptr, *shape, e, *tail,
-              _abi.stream())
+        _call("soil_downstream" + batch, *outs, g_ptr, *f_ptrs, s_ptr, *shape, e, *tail, _abi.stream())
     else:
-        _call("soil_stream_power" + ("" if dims == 2 else "_batch"), *outs, f_ptrs[0], g_ptr, *f_ptrs[1:], s_ptr, *shape,
-              e, *tail, float(dt), _abi.stream())
+        _call("soil_stream_power" + batch, *outs, f_ptrs[0], g_ptr, *f_ptrs[1:], s_ptr, *shape, e, *tail, dt,
+              _abi.stream())
     return out
 
 
@@ -457,12 +469,6 @@ def stream_power_batch(height, graph, erosivity, edge_, scale, dt, uplift=None, 
                        double, dt)
 
 
-def _on_stream():
-    """torch's current stream set to the one the library's calls go to."""
-    import torch
-    return torch.cuda.stream(torch.cuda.ExternalStream(_abi._stream)) if _abi._stream else contextlib.nullcontext()
-
-
 def erosivity(area, K, m):
     """K * area ** m of a float32 drainage-area tensor of any shape, on the device through torch, float32: the
     `erosivity` of stream_power.  torch's pow is not correctly rounded, so this plane is not bit-pinned; what
@@ -484,7 +490,7 @@ def chi(graph, area, edge_, scale, theta=0.45, A0=1.0, stop=None):
     _float_plane(area, shape, "chi: area")
     if area.host is not silt.gpu:
         raise _abi.SoilError("mismatch_host: area must be a silt.gpu tensor")
-    _edge_of(edge_, "chi")
+    _check.edge("chi", edge_)
     _one_pair(scale, "chi")
     with _on_stream():
         w = (float(A0) / area.view_torch()).pow_(float(theta))
@@ -498,35 +504,23 @@ def chi(graph, area, edge_, scale, theta=0.45, A0=1.0, stop=None):
 def _stream_power_deposit(who, dims, height, graph, erosivity, deposition, edge_, scale, dt, uplift, iters, double,
                           flux, residual):
     """soil_stream_power_deposit and its _batch form.  Every check comes before any device work."""
-    shape = (_hw2 if dims == 2 else _bhw)(graph, "%s: graph" % who)
-    e = _edge_of(edge_, who)
+    shape = _shape(dims, graph, "%s: graph" % who)
+    e = _check.edge(who, edge_)
     _int_plane(graph, shape, "%s: graph" % who)
     planes = [("height", height, True), ("erosivity", erosivity, True), ("deposition", deposition, True),
               ("uplift", uplift, False)]
-    for name, t, required in planes:
-        if t is None and required:
-            raise ValueError("%s: %s is required" % (who, name))
-        if t is not None:
-            _float_plane(t, shape, "%s: %s" % (who, name))
-    if scale is None:
-        raise ValueError("%s: scale must be one (sx, sy) pair%s" % (who, "" if dims == 2 else " or B pairs"))
-    pairs, n = (_one_pair(scale, who), 1) if dims == 2 else _scale_pairs(scale, shape[0], who)
-    if any(not (v > 0 and math.isfinite(v)) for v in pairs):
-        raise ValueError("%s: scale entries must be positive finite floats, got %r" % (who, scale))
-    if isinstance(dt, bool) or not isinstance(dt, (int, float)) or not math.isfinite(dt) or dt < 0:
-        raise ValueError("%s: dt must be a finite number >= 0, got %r" % (who, dt))
-    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters < 2 ** 31:
-        raise ValueError("%s: iters must be an integer >= 1, got %r" % (who, iters))
+    _float_planes(who, shape, planes)
+    pairs, tail = _scales(who, dims, scale, shape[0])
+    _positive(who, pairs, scale)
+    dt = _check.number(who, "dt", dt)
+    iters = _check.count(who, "iters", iters)
     g_ptr = _gpu(graph, silt.int32, "graph")
     h_ptr, k_ptr, d_ptr, u_ptr = (_opt_f(t, name) for name, t, _ in planes)
-    out = silt.tensor(silt.float64 if double else silt.float32, silt.shape(*shape), silt.gpu)
-    outs = (None, out.c_ptr) if double else (out.c_ptr, None)
+    out, outs = _out_pair(shape, double)
     f = silt.tensor(silt.float32, silt.shape(*shape), silt.gpu) if flux else None
     r = silt.tensor(silt.float64, silt.shape(1 if dims == 2 else shape[0]), silt.gpu) if residual else None
-    tail = (pairs,) if dims == 2 else (pairs, n)
     _call("soil_stream_power_deposit" + ("" if dims == 2 else "_batch"), *outs, None if f is None else f.c_ptr,
-          None if r is None else r.c_ptr, h_ptr, g_ptr, k_ptr, d_ptr, u_ptr, *shape, e, *tail, float(dt), int(iters),
-          _abi.stream())
+          None if r is None else r.c_ptr, h_ptr, g_ptr, k_ptr, d_ptr, u_ptr, *shape, e, *tail, dt, iters, _abi.stream())
     extras = tuple(t for t in (f, r) if t is not None)
     return (out,) + extras if extras else out
 
@@ -560,22 +554,19 @@ def deposition(area, G, cell=1.0):
     given plane is."""
     if not isinstance(area, silt.tensor) or area.type is not silt.float32:
         raise ValueError("deposition: area must be a float32 silt tensor")
-    if isinstance(G, bool) or not isinstance(G, (int, float)) or not math.isfinite(G) or G < 0:
-        raise ValueError("deposition: G must be a finite number >= 0, got %r" % (G,))
+    G = _check.number("deposition", "G", G)
     if area.host is not silt.gpu:
         raise _abi.SoilError("mismatch_host: area must be a silt.gpu tensor")
     with _on_stream():
         c = cell.view_torch() if isinstance(cell, silt.tensor) else float(cell)
-        out = (float(G) * c / area.view_torch()).float()
+        out = (G * c / area.view_torch()).float()
     return silt.tensor.from_torch(out.contiguous())
 
 
 def stream_power_deposit_info():
     """What this thread's last stream_power_deposit / _batch call did (soil_stream_power_deposit_info): a dict with the
     number of kernel `launches`, of `chunks`, the `iters` run and the `scratch_bytes` it asked for."""
-    info = (C.c_int64 * 4)()
-    _call("soil_stream_power_deposit_info", info)
-    return dict(zip(("launches", "chunks", "iters", "scratch_bytes"), (int(v) for v in info)))
+    return _call_info("soil_stream_power_deposit_info", ("launches", "chunks", "iters", "scratch_bytes"))
 
 
 def downstream_info():
@@ -590,37 +581,23 @@ def downstream_info():
 
 def _diffuse(who, dims, height, scale, dt, kappa, diffusivity, uplift, fixed, border, first_axis, double):
     """soil_diffuse and soil_diffuse_batch.  Every check comes before any device work."""
-    shape = (_hw2 if dims == 2 else _bhw)(height, "%s: height" % who)
+    shape = _shape(dims, height, "%s: height" % who)
     _float_plane(height, shape, "%s: height" % who)
-    if (kappa is None) == (diffusivity is None):
-        raise ValueError("%s: exactly one of kappa and diffusivity must be given" % who)
-    if kappa is not None and (isinstance(kappa, bool) or not isinstance(kappa, (int, float)) or not math.isfinite(kappa)
-                              or kappa < 0):
-        raise ValueError("%s: kappa must be a finite number >= 0, got %r" % (who, kappa))
-    for name, t in (("diffusivity", diffusivity), ("uplift", uplift)):
-        if t is not None:
-            _float_plane(t, shape, "%s: %s" % (who, name))
+    _check.kappa_or_diffusivity(who, kappa, diffusivity)
+    _float_planes(who, shape, [("diffusivity", diffusivity, False), ("uplift", uplift, False)])
     if fixed is not None:
         _int_plane(fixed, shape, "%s: fixed" % who)
-    if scale is None:
-        raise ValueError("%s: scale must be one (sx, sy) pair%s" % (who, "" if dims == 2 else " or B pairs"))
-    pairs, n = (_one_pair(scale, who), 1) if dims == 2 else _scale_pairs(scale, shape[0], who)
-    if any(not (v > 0 and math.isfinite(v)) for v in pairs):
-        raise ValueError("%s: scale entries must be positive finite floats, got %r" % (who, scale))
-    if isinstance(dt, bool) or not isinstance(dt, (int, float)) or not math.isfinite(dt) or dt < 0:
-        raise ValueError("%s: dt must be a finite number >= 0, got %r" % (who, dt))
-    if border not in ("fixed", "free"):
-        raise ValueError("%s: border must be 'fixed' or 'free', got %r" % (who, border))
-    if isinstance(first_axis, bool) or first_axis not in (0, 1):
-        raise ValueError("%s: first_axis must be 0 or 1, got %r" % (who, first_axis))
+    pairs, tail = _scales(who, dims, scale, shape[0])
+    _positive(who, pairs, scale)
+    dt = _check.number(who, "dt", dt)
+    border = _check.border(who, border)
+    first_axis = _check.first_axis(who, first_axis)
     h_ptr = _f(height, "height")
     k_ptr, u_ptr = _opt_f(diffusivity, "diffusivity"), _opt_f(uplift, "uplift")
-    f_ptr = None if fixed is None else _gpu(fixed, silt.int32, "fixed")
-    out = silt.tensor(silt.float64 if double else silt.float32, silt.shape(*shape), silt.gpu)
-    outs = (None, out.c_ptr) if double else (out.c_ptr, None)
-    tail = (pairs,) if dims == 2 else (pairs, n)
+    f_ptr = _opt_i(fixed, "fixed")
+    out, outs = _out_pair(shape, double)
     _call("soil_diffuse" + ("" if dims == 2 else "_batch"), *outs, h_ptr, k_ptr, u_ptr, f_ptr, *shape, *tail,
-          0.0 if kappa is None else float(kappa), float(dt), int(border == "fixed"), int(first_axis), _abi.stream())
+          0.0 if kappa is None else float(kappa), dt, border, first_axis, _abi.stream())
     return out
 
 
@@ -646,9 +623,7 @@ def diffuse_batch(height, scale, dt, kappa=None, diffusivity=None, uplift=None, 
 def diffuse_info():
     """What this thread's last diffuse / diffuse_batch call did (soil_diffuse_info): a dict with the number of kernel
     `launches`, of `chunks`, of chunks on 64-bit offsets (`idx64_chunks`) and the `scratch_bytes` it asked for."""
-    info = (C.c_int64 * 4)()
-    _call("soil_diffuse_info", info)
-    return dict(zip(("launches", "chunks", "idx64_chunks", "scratch_bytes"), (int(v) for v in info)))
+    return _call_info("soil_diffuse_info", ("launches", "chunks", "idx64_chunks", "scratch_bytes"))
 
 
 def fill_depressions(height, edge_=None):
@@ -664,15 +639,9 @@ def fill_depressions(height, edge_=None):
 # ---- flats and filled lakes (soil_hip.h: "flow graphs: conditioning"): on the surface fill_depressions returns every
 # lake cell is a terminal of steepest / random_weighted; these give them receivers, as indices.
 
-def _float_plane(t, shape, what):
-    _same(t, shape, what)
-    if t.type is not silt.float32:
-        raise ValueError("%s: expected a float32 tensor, got %s" % (what, t.type.name))
-
-
 def _flat_distance(who, height, edge_, dims):
     shape = (_hw2 if dims == 2 else _bhw)(height, "%s: height" % who)
-    e = _edge_of(edge_, who)
+    e = _check.edge(who, edge_)
     _float_plane(height, shape, "%s: height" % who)
     ptr = _f(height, "height")
     out = silt.tensor(silt.int32, silt.shape(*shape), silt.gpu)
@@ -682,7 +651,7 @@ def _flat_distance(who, height, edge_, dims):
 
 def _flat_receivers(who, graph, height, dist, edge_, dims):
     shape = (_hw2 if dims == 2 else _bhw)(graph, "%s: graph" % who)
-    e = _edge_of(edge_, who)
+    e = _check.edge(who, edge_)
     _int_plane(graph, shape, "%s: graph" % who)
     _float_plane(height, shape, "%s: height" % who)
     _int_plane(dist, shape, "%s: dist" % who)
@@ -710,7 +679,7 @@ def resolve_flats(height, edge_, graph=None):
     """The receiver graph of `height` with its flats routed: flat_receivers of `graph` (None: steepest(height, edge))
     along flat_distance(height, edge).  On a surface fill_depressions made, the only terminals left are cells on the
     border or beside NaN cells."""
-    e = _edge_of(edge_, "resolve_flats")
+    e = _check.edge("resolve_flats", edge_)
     dist = _flat_distance("resolve_flats", height, e, 2)
     return _flat_receivers("resolve_flats", steepest(height, e) if graph is None else graph, height, dist, e, 2)
 
@@ -727,7 +696,7 @@ def flat_receivers_batch(graph, height, dist, edge_):
 
 def resolve_flats_batch(height, edge_, graph=None):
     """resolve_flats of each of the B models of a (B, H, W) tensor."""
-    e = _edge_of(edge_, "resolve_flats_batch")
+    e = _check.edge("resolve_flats_batch", edge_)
     dist = _flat_distance("resolve_flats_batch", height, e, 3)
     return _flat_receivers("resolve_flats_batch", steepest_batch(height, e) if graph is None else graph, height, dist,
                            e, 3)
@@ -736,9 +705,7 @@ def resolve_flats_batch(height, edge_, graph=None):
 def flat_distance_info():
     """What this thread's last flat_distance / flat_distance_batch call did (soil_flat_distance_info): a dict with the
     relaxation `launches`, the `tiles` of a model, the `models` and the `looks` at the "changed" word."""
-    info = (C.c_int64 * 4)()
-    _call("soil_flat_distance_info", info)
-    return dict(zip(("launches", "tiles", "models", "looks"), (int(v) for v in info)))
+    return _call_info("soil_flat_distance_info", ("launches", "tiles", "models", "looks"))
 
 
 # ---- the fill of a batch, and the conditioned drainage graph: fill -> steepest / random_weighted -> resolve_flats
@@ -748,7 +715,7 @@ def fill_depressions_batch(height, edge_=None):
     (soil_fill_depressions_batch): all models on the same pyramid level at the same time, a launch grid of tiles x
     models, relaxation passes that do not grow with B.  Returns a new (B, H, W) tensor; synchronises the stream."""
     shape = _bhw(height, "fill_depressions_batch: height")
-    e = _edge_of(d8 if edge_ is None else edge_, "fill_depressions_batch")
+    e = _check.edge("fill_depressions_batch", d8 if edge_ is None else edge_)
     _float_plane(height, shape, "fill_depressions_batch: height")
     ptr = _f(height, "height")
     out = silt.tensor(silt.float32, silt.shape(*shape), silt.gpu)
@@ -770,7 +737,7 @@ def condition(height, edge_=None):
     """A (H, W) DEM made ready for routing: (filled, graph) with filled = fill_depressions(height, edge) and graph =
     resolve_flats(filled, edge), the steepest graph of the filled surface with its flats and lakes routed."""
     shape = _hw2(height, "condition: height")
-    e = _edge_of(d8 if edge_ is None else edge_, "condition")
+    e = _check.edge("condition", d8 if edge_ is None else edge_)
     _float_plane(height, shape, "condition: height")
     filled = fill_depressions(height, e)
     return filled, resolve_flats(filled, e)
@@ -781,7 +748,7 @@ def condition_batch(height, edge_=None, graph=None):
     steepest_batch's — a caller who wants a random_weighted graph routed across the lakes makes it on the filled
     surface (fill_depressions_batch) and passes it here."""
     shape = _bhw(height, "condition_batch: height")
-    e = _edge_of(d8 if edge_ is None else edge_, "condition_batch")
+    e = _check.edge("condition_batch", d8 if edge_ is None else edge_)
     _float_plane(height, shape, "condition_batch: height")
     if graph is not None:
         _int_plane(graph, shape, "condition_batch: graph")

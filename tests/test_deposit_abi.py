@@ -338,10 +338,14 @@ BATCH = [("B = 0", dict(B=0)), ("B < 0", dict(B=-3)), ("n_scales 2 of 3", dict(n
          ("n_scales 4 of 3", dict(n=4)), ("a later model's scale 0", dict(scale=_bad_scale(1, 1, 1, 1, 0, 1)))]
 
 
+def _cases(name):
+    return REFUSED + (BATCH if name.endswith("_batch") else [])
+
+
 def test_every_refusal_names_its_entry():
     from soillib_amd import _abi
     for name, call in _entries().items():
-        for what, over in REFUSED + (BATCH if name.endswith("_batch") else []):
+        for what, over in _cases(name):
             assert call(over) == _abi.SOIL_ERR_INVALID_ARGUMENT, (what, name)
             assert _abi.last_error().startswith(name + ": "), (what, name, _abi.last_error())
 
@@ -363,13 +367,13 @@ def _host(dtype, shape):
     return silt.tensor._wrap_numpy(np.zeros(shape, dtype))
 
 
-def test_the_module_functions_refuse():
+def _module_refusals():
     from soillib_amd import soil
     g2, g3 = _host(np.int32, (4, 3)), _host(np.int32, (5, 4, 3))
     f2, f3 = _host(np.float32, (4, 3)), _host(np.float32, (5, 4, 3))
     one, many = soil.stream_power_deposit, soil.stream_power_deposit_batch
     ok = (1.0, 1.0)
-    bad = [
+    return [
         (one, (f2, g3, f2, f2, soil.d8, ok, 1.0), {}, "stream_power_deposit: graph"),
         (one, (g2, g2, f2, f2, soil.d8, ok, 1.0), {}, "stream_power_deposit: height"),
         (one, (None, g2, f2, f2, soil.d8, ok, 1.0), {}, "stream_power_deposit: height is required"),
@@ -395,9 +399,40 @@ def test_the_module_functions_refuse():
         (soil.deposition, (f2, -1.0), {}, "deposition: G"),
         (soil.deposition, (f2, float("nan")), {}, "deposition: G"),
     ]
-    for fn, args, kw, match in bad:
+
+
+def test_the_module_functions_refuse():
+    for fn, args, kw, match in _module_refusals():
         with pytest.raises(ValueError, match=match):
             fn(*args, **kw)
+
+
+def test_a_numpy_scalar_is_a_number():
+    """dt as a numpy float or integer, iters as a numpy integer: past the scalar checks, refused at the device check
+    only (the tensors are host tensors).  What is no number, or out of range, is refused with the same text whatever
+    its type."""
+    from soillib_amd import _abi, soil
+    g2, g3 = _host(np.int32, (4, 3)), _host(np.int32, (5, 4, 3))
+    f2, f3 = _host(np.float32, (4, 3)), _host(np.float32, (5, 4, 3))
+    for name, fn, f, g in (("stream_power_deposit", soil.stream_power_deposit, f2, g2),
+                           ("stream_power_deposit_batch", soil.stream_power_deposit_batch, f3, g3)):
+        for dt, iters in ((np.float32(1), np.int64(2)), (np.int64(1), np.int32(2)), (1.0, np.uint8(2)), (np.float64(1), 2)):
+            with pytest.raises(_abi.SoilError, match="mismatch_host"):
+                fn(f, g, f, f, soil.d8, (1.0, 1.0), dt, iters=iters)
+        for dt in (True, "1", float("nan"), float("inf"), -1.0, np.float32("nan"), np.float32(-1), np.int64(-1)):
+            with pytest.raises(ValueError) as e:
+                fn(f, g, f, f, soil.d8, (1.0, 1.0), dt)
+            assert str(e.value) == "%s: dt must be a finite number >= 0, got %r" % (name, dt)
+        for iters in (True, "2", 2.0, np.float32(2), 0, np.int64(0), -1, 2 ** 31, np.int64(2 ** 31), float("nan")):
+            with pytest.raises(ValueError) as e:
+                fn(f, g, f, f, soil.d8, (1.0, 1.0), 1.0, iters=iters)
+            assert str(e.value) == "%s: iters must be an integer >= 1, got %r" % (name, iters)
+    with pytest.raises(_abi.SoilError, match="mismatch_host"):
+        soil.deposition(f2, np.float32(1))
+    for G in (True, "1", float("nan"), -1.0, np.float32(-1)):
+        with pytest.raises(ValueError) as e:
+            soil.deposition(f2, G)
+        assert str(e.value) == "deposition: G must be a finite number >= 0, got %r" % (G,)
 
 
 class _Untouchable:
@@ -415,8 +450,10 @@ def _batch_without_a_device(B=5, scales=None):
     return bt
 
 
-def test_the_batch_methods_refuse():
+def _batch_refusals():
+    """(method, the stub's scales, args, kw, match)."""
     good = _host(np.int32, (5, 4, 3))
+    out = []
     for args, kw in (((-1.0, 1e-4), {}), ((float("nan"), 1e-4), {}), ((1.0, -1e-4), {}), ((1.0, "k"), {}),
                      ((1.0, 1e-4), dict(m=float("inf"))), ((1.0, 1e-4), dict(G=-1.0)), ((1.0, 1e-4), dict(G=None)),
                      ((1.0, 1e-4), dict(G=float("inf"))), ((1.0, 1e-4), dict(iters=0)), ((1.0, 1e-4), dict(iters=1.5)),
@@ -424,13 +461,17 @@ def test_the_batch_methods_refuse():
                      ((1.0, 1e-4), dict(kind="random_weighted")),
                      ((1.0, 1e-4), dict(kind="random_weighted", T=1.0, offset=-1)), ((1.0, 1e-4), dict(uplift=good)),
                      ((1.0, 1e-4), dict(uplift=_host(np.float32, (5, 3, 4))))):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.stream_power_deposit"):
-            _batch_without_a_device().stream_power_deposit(*args, **kw)
-    with pytest.raises(ValueError, match=r"ErosionBatch\.stream_power_deposit"):
-        _batch_without_a_device(scales=[[1.0, 1.0, 1.0]] * 4).stream_power_deposit(1.0, 1e-4)
+        out.append(("stream_power_deposit", None, args, kw, r"ErosionBatch\.stream_power_deposit"))
+    out.append(("stream_power_deposit", [[1.0, 1.0, 1.0]] * 4, (1.0, 1e-4), {}, r"ErosionBatch\.stream_power_deposit"))
     for kw in (dict(G=-0.5), dict(G="1"), dict(G=True), dict(G=1.0, iters=0), dict(G=1.0, iters=None)):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.evolve: (G|iters)"):
-            _batch_without_a_device().evolve(1.0, 1e-4, kappa=0.1, **kw)
+        out.append(("evolve", None, (1.0, 1e-4), dict(kw, kappa=0.1), r"ErosionBatch\.evolve: (G|iters)"))
+    return out
+
+
+def test_the_batch_methods_refuse():
+    for method, scales, args, kw, match in _batch_refusals():
+        with pytest.raises(ValueError, match=match):
+            getattr(_batch_without_a_device(scales=scales), method)(*args, **kw)
 
 
 def test_evolve_without_G_builds_the_argument_list_it_builds_today(monkeypatch):

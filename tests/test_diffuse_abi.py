@@ -329,10 +329,14 @@ BATCH = [("B = 0", dict(B=0)), ("B < 0", dict(B=-3)), ("n_scales 2 of 3", dict(n
          ("n_scales 4 of 3", dict(n=4)), ("a later model's scale 0", dict(scale=_bad_scale(1, 1, 1, 1, 0, 1)))]
 
 
+def _cases(name):
+    return COMMON + (BATCH if name.endswith("_batch") else [])
+
+
 def test_every_refusal_names_its_entry():
     from soillib_amd import _abi
     for name, call in _entries().items():
-        for what, over in COMMON + (BATCH if name.endswith("_batch") else []):
+        for what, over in _cases(name):
             assert call(over) == _abi.SOIL_ERR_INVALID_ARGUMENT, (what, name)
             assert _abi.last_error().startswith(name + ": "), (what, name, _abi.last_error())
 
@@ -357,12 +361,12 @@ def _host(dtype, shape):
     return silt.tensor._wrap_numpy(np.zeros(shape, dtype))
 
 
-def test_the_module_functions_refuse():
+def _module_refusals():
     from soillib_amd import soil
     g2, g3 = _host(np.int32, (4, 3)), _host(np.int32, (5, 4, 3))
     f2, f3 = _host(np.float32, (4, 3)), _host(np.float32, (5, 4, 3))
     one = (1.0, 1.0)
-    bad = [
+    return [
         (soil.diffuse, (f3, one, 1.0), dict(kappa=1.0), r"diffuse: height: expected a \(H, W\)"),
         (soil.diffuse, (g2, one, 1.0), dict(kappa=1.0), "diffuse: height: expected a float32"),
         (soil.diffuse, (np.zeros((4, 3), np.float32), one, 1.0), dict(kappa=1.0), "diffuse: height"),
@@ -395,9 +399,31 @@ def test_the_module_functions_refuse():
         (soil.diffuse_batch, (f3, one, 1.0), dict(kappa=1.0, fixed=g2), "diffuse_batch: fixed"),
         (soil.diffuse_batch, (f3, one, 1.0), {}, "diffuse_batch: exactly one"),
     ]
-    for fn, args, kw, match in bad:
+
+
+def test_the_module_functions_refuse():
+    for fn, args, kw, match in _module_refusals():
         with pytest.raises(ValueError, match=match):
             fn(*args, **kw)
+
+
+def test_a_numpy_scalar_is_a_number():
+    """kappa and dt as numpy scalars: past the scalar checks, refused at the device check only (the tensors are host
+    tensors).  What is no finite number >= 0 is refused with the same text whatever its type."""
+    from soillib_amd import _abi, soil
+    f2, f3 = _host(np.float32, (4, 3)), _host(np.float32, (5, 4, 3))
+    for name, fn, f in (("diffuse", soil.diffuse, f2), ("diffuse_batch", soil.diffuse_batch, f3)):
+        for kappa, dt in ((np.float32(0.5), np.float32(1)), (np.int64(1), np.int64(1)), (np.float64(0.5), 1), (0.5, 1.0)):
+            with pytest.raises(_abi.SoilError, match="mismatch_host"):
+                fn(f, (1.0, 1.0), dt, kappa=kappa)
+        for bad in (True, "1", float("nan"), float("inf"), -1.0, np.float32("nan"), np.float32("inf"), np.float32(-1),
+                    np.int64(-1), np.bool_(True)):
+            with pytest.raises(ValueError) as e:
+                fn(f, (1.0, 1.0), bad, kappa=0.5)
+            assert str(e.value) == "%s: dt must be a finite number >= 0, got %r" % (name, bad)
+            with pytest.raises(ValueError) as e:
+                fn(f, (1.0, 1.0), 1.0, kappa=bad)
+            assert str(e.value) == "%s: kappa must be a finite number >= 0, got %r" % (name, bad)
 
 
 class _Untouchable:
@@ -415,21 +441,27 @@ def _batch_without_a_device(B=5, scales=None):
     return bt
 
 
-def test_the_batch_methods_refuse():
+def _batch_refusals():
+    """(method, the stub's scales, args, kw, match)."""
     mask, plane = _host(np.int32, (5, 4, 3)), _host(np.float32, (5, 4, 3))
+    out = []
     for args, kw in (((-1.0,), dict(kappa=1.0)), ((float("nan"),), dict(kappa=1.0)), ((1.0,), {}),
                      ((1.0,), dict(kappa=1.0, diffusivity=plane)), ((1.0,), dict(kappa=-1.0)), ((1.0,), dict(kappa="k")),
                      ((1.0,), dict(diffusivity=mask)), ((1.0,), dict(diffusivity=_host(np.float32, (5, 3, 4)))),
                      ((1.0,), dict(kappa=1.0, uplift=mask)), ((1.0,), dict(kappa=1.0, fixed=plane)),
                      ((1.0,), dict(kappa=1.0, border="closed")), ((1.0,), dict(kappa=1.0, first_axis=3))):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.diffuse"):
-            _batch_without_a_device().diffuse(*args, **kw)
-    with pytest.raises(ValueError, match=r"ErosionBatch\.diffuse"):
-        _batch_without_a_device(scales=[[1.0, 1.0, 1.0]] * 4).diffuse(1.0, kappa=1.0)
+        out.append(("diffuse", None, args, kw, r"ErosionBatch\.diffuse"))
+    out.append(("diffuse", [[1.0, 1.0, 1.0]] * 4, (1.0,), dict(kappa=1.0), r"ErosionBatch\.diffuse"))
     for args, kw in (((-1.0, 1e-4), dict(kappa=1.0)), ((1.0, 1e-4), {}), ((1.0, 1e-4), dict(kappa=-2.0)),
                      ((1.0, -1e-4), dict(kappa=1.0)), ((1.0, 1e-4), dict(kappa=1.0, m=float("inf"))),
                      ((1.0, 1e-4), dict(kappa=1.0, kind="direction")), ((1.0, 1e-4), dict(kappa=1.0, edge=2)),
                      ((1.0, 1e-4), dict(kappa=1.0, kind="random_weighted")), ((1.0, 1e-4), dict(kappa=1.0, uplift=mask)),
                      ((1.0, 1e-4), dict(kappa=1.0, first_axis=2))):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.evolve"):
-            _batch_without_a_device().evolve(*args, **kw)
+        out.append(("evolve", None, args, kw, r"ErosionBatch\.evolve"))
+    return out
+
+
+def test_the_batch_methods_refuse():
+    for method, scales, args, kw, match in _batch_refusals():
+        with pytest.raises(ValueError, match=match):
+            getattr(_batch_without_a_device(scales=scales), method)(*args, **kw)

@@ -265,10 +265,12 @@ def test_the_surfaces():
         assert re.search(r"inline [^;{]*\b%s\(" % name, text), name
         assert "soil_%s(" % name in text, name
     knobs = open(os.path.join(ROOT, "docs", "KNOBS.md")).read()
-    for knob in ("SOIL_PATHS_LIST_FROM", "SOIL_PATHS_IDX64", "SOIL_FLOW_BATCH_CELLS", "SOIL_PATHS_GROUPS"):
+    # (read in the driver the entries share with soil_flow_paths, csrc/flow_paths.hpp, or in the host helpers that
+    # driver shares with the other flow solvers, csrc/flow_host.hpp)
+    for knob, where in (("SOIL_PATHS_LIST_FROM", "flow_paths.hpp"), ("SOIL_PATHS_IDX64", "flow_host.hpp"),
+                        ("SOIL_FLOW_BATCH_CELLS", "flow_host.hpp"), ("SOIL_PATHS_GROUPS", "flow_paths.hpp")):
         line = [l for l in knobs.splitlines() if l.startswith("| `%s` " % knob)]
-        # (read in the driver the entries share with soil_flow_paths, csrc/flow_paths.hpp)
-        assert len(line) == 1 and "soillib_amd/csrc/flow_paths.hpp" in line[0] and "soil_downstream" in line[0], knob
+        assert len(line) == 1 and "soillib_amd/csrc/" + where in line[0] and "soil_downstream" in line[0], knob
     source = open(os.path.join(ROOT, "soillib_amd", "csrc", "downstream.hip")).read()
     assert '#include "flow_paths.hpp"' in source and "ptr_run(WS_DOWNSTREAM" in source
 
@@ -330,12 +332,15 @@ POWER = [("null height", dict(height=None)), ("null erosivity", dict(erosivity=N
 POWER_BATCH = [("a later model's scale 0", dict(scale=_bad_scale(1, 1, 1, 1, 0, 1)))]
 
 
+def _cases(name):
+    cases = COMMON + (BATCH if name.endswith("_batch") else []) + (POWER if name.startswith("stream") else [])
+    return cases + (POWER_BATCH if name == "stream_power_batch" else [])
+
+
 def test_every_refusal_names_its_entry():
     from soillib_amd import _abi
     for name, call in _entries().items():
-        cases = COMMON + (BATCH if name.endswith("_batch") else []) + (POWER if name.startswith("stream") else [])
-        cases += POWER_BATCH if name == "stream_power_batch" else []
-        for what, over in cases:
+        for what, over in _cases(name):
             assert call(over) == _abi.SOIL_ERR_INVALID_ARGUMENT, (what, name)
             assert _abi.last_error().startswith(name + ": "), (what, name, _abi.last_error())
 
@@ -361,11 +366,11 @@ def _host(dtype, shape):
     return silt.tensor._wrap_numpy(np.zeros(shape, dtype))
 
 
-def test_the_module_functions_refuse():
+def _module_refusals():
     from soillib_amd import soil
     g2, g3 = _host(np.int32, (4, 3)), _host(np.int32, (5, 4, 3))
     f2, f3 = _host(np.float32, (4, 3)), _host(np.float32, (5, 4, 3))
-    bad = [
+    return [
         (soil.downstream, (g3, soil.d8), {}, r"downstream: graph: expected a \(H, W\)"),
         (soil.downstream, (f2, soil.d8), {}, "downstream: graph: expected an int32"),
         (soil.downstream, (np.zeros((4, 3), np.int32), soil.d8), {}, "downstream: graph"),
@@ -402,9 +407,30 @@ def test_the_module_functions_refuse():
         (soil.chi, (g2, g2, soil.d8, (1.0, 1.0)), {}, "chi: area"),
         (soil.erosivity, (g2, 1.0, 0.5), {}, "erosivity: area"),
     ]
-    for fn, args, kw, match in bad:
+
+
+def test_the_module_functions_refuse():
+    for fn, args, kw, match in _module_refusals():
         with pytest.raises(ValueError, match=match):
             fn(*args, **kw)
+
+
+def test_a_numpy_scalar_is_a_number():
+    """A dt that is a numbers.Real and no bool (a numpy scalar as much as a float) passes the scalar check: with host
+    tensors the call then fails at the device check only.  What is no finite number >= 0 is refused with the same
+    text whatever its type."""
+    from soillib_amd import _abi, soil
+    g2, g3 = _host(np.int32, (4, 3)), _host(np.int32, (5, 4, 3))
+    f2, f3 = _host(np.float32, (4, 3)), _host(np.float32, (5, 4, 3))
+    for name, fn, f, g in (("stream_power", soil.stream_power, f2, g2), ("stream_power_batch", soil.stream_power_batch, f3, g3)):
+        for dt in (np.float32(1), np.int64(1), np.float64(1), 1, 1.0):
+            with pytest.raises(_abi.SoilError, match="mismatch_host"):
+                fn(f, g, f, soil.d8, (1.0, 1.0), dt)
+        for dt in (True, "1", float("nan"), float("inf"), -1.0, -1, np.float32("nan"), np.float32("inf"), np.float32(-1),
+                   np.int64(-1), np.bool_(True)):
+            with pytest.raises(ValueError) as e:
+                fn(f, g, f, soil.d8, (1.0, 1.0), dt)
+            assert str(e.value) == "%s: dt must be a finite number >= 0, got %r" % (name, dt)
 
 
 class _Untouchable:
@@ -422,19 +448,25 @@ def _batch_without_a_device(B=5, scales=None):
     return bt
 
 
-def test_the_batch_methods_refuse():
+def _batch_refusals():
+    """(method, the stub's scales, args, kw, match)."""
     good, plane = _host(np.int32, (5, 4, 3)), _host(np.float32, (5, 4, 3))
+    out = []
     for kw in (dict(graph=_host(np.int32, (5, 3, 4))), dict(graph=plane), dict(graph=good, a=good),
                dict(graph=good, b=_host(np.float32, (4, 4, 3))), dict(graph=good, terminal=3.0),
                dict(graph=good, stop=plane), dict(graph=good, edge=2), dict(edge="d4")):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.downstream"):
-            _batch_without_a_device().downstream(**kw)
-    with pytest.raises(ValueError, match=r"ErosionBatch\.downstream"):
-        _batch_without_a_device(scales=[[1.0, 1.0, 1.0]] * 4).downstream(good)
+        out.append(("downstream", None, (), kw, r"ErosionBatch\.downstream"))
+    out.append(("downstream", [[1.0, 1.0, 1.0]] * 4, (good,), {}, r"ErosionBatch\.downstream"))
     for args, kw in (((-1.0, 1e-4), {}), ((float("nan"), 1e-4), {}), ((1.0, -1e-4), {}), ((1.0, "k"), {}),
                      ((1.0, 1e-4), dict(m=float("inf"))), ((1.0, 1e-4), dict(kind="direction")),
                      ((1.0, 1e-4), dict(edge=2)), ((1.0, 1e-4), dict(kind="random_weighted")),
                      ((1.0, 1e-4), dict(kind="random_weighted", T=1.0, offset=-1)), ((1.0, 1e-4), dict(uplift=good)),
                      ((1.0, 1e-4), dict(uplift=_host(np.float32, (5, 3, 4))))):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.stream_power"):
-            _batch_without_a_device().stream_power(*args, **kw)
+        out.append(("stream_power", None, args, kw, r"ErosionBatch\.stream_power"))
+    return out
+
+
+def test_the_batch_methods_refuse():
+    for method, scales, args, kw, match in _batch_refusals():
+        with pytest.raises(ValueError, match=match):
+            getattr(_batch_without_a_device(scales=scales), method)(*args, **kw)

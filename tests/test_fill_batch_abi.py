@@ -84,16 +84,19 @@ def test_the_surfaces():
 
 # ---- refusals, without a device --------------------------------------------------------------------------------
 
+def _refused():
+    p, q = C.c_void_p(4096), C.c_void_p(8192)
+    big = 1 << 16
+    return [("null out", (None, p, 3, 4, 4, D8)), ("null height", (p, None, 3, 4, 4, D8)), ("out == height", (p, p, 3, 4, 4, D8)),
+            ("B = 0", (p, q, 0, 4, 4, D8)), ("B < 0", (p, q, -2, 4, 4, D8)), ("H = 0", (p, q, 3, 0, 4, D8)),
+            ("H < 0", (p, q, 3, -1, 4, D4)), ("W = 0", (p, q, 3, 4, 0, D8)), ("W < 0", (p, q, 3, 4, -5, D4)),
+            ("H W > INT32_MAX", (p, q, 1, big, big // 2, D8)), ("edge 2", (p, q, 3, 4, 4, 2)), ("edge -1", (p, q, 3, 4, 4, -1))]
+
+
 def test_every_refusal_names_the_entry():
     from soillib_amd import _abi
     call = _abi.lib().soil_fill_depressions_batch
-    p, q = C.c_void_p(4096), C.c_void_p(8192)
-    big = 1 << 16
-    bad = [("null out", (None, p, 3, 4, 4, D8)), ("null height", (p, None, 3, 4, 4, D8)), ("out == height", (p, p, 3, 4, 4, D8)),
-           ("B = 0", (p, q, 0, 4, 4, D8)), ("B < 0", (p, q, -2, 4, 4, D8)), ("H = 0", (p, q, 3, 0, 4, D8)),
-           ("H < 0", (p, q, 3, -1, 4, D4)), ("W = 0", (p, q, 3, 4, 0, D8)), ("W < 0", (p, q, 3, 4, -5, D4)),
-           ("H W > INT32_MAX", (p, q, 1, big, big // 2, D8)), ("edge 2", (p, q, 3, 4, 4, 2)), ("edge -1", (p, q, 3, 4, 4, -1))]
-    for what, args in bad:
+    for what, args in _refused():
         assert call(*args, None) == _abi.SOIL_ERR_INVALID_ARGUMENT, what
         assert _abi.last_error().startswith("fill_depressions_batch: "), (what, _abi.last_error())
     info = (C.c_int64 * 16)()
@@ -129,10 +132,10 @@ def no_library(monkeypatch):
     monkeypatch.setattr(_abi, "lib", refuse)
 
 
-def test_the_module_functions_refuse(no_library):
+def _module_refusals():
     from soillib_amd import soil
     h2, h3, g2, g3 = _host(np.float32, (4, 3)), _host(np.float32, (5, 4, 3)), _host(np.int32, (4, 3)), _host(np.int32, (5, 4, 3))
-    bad = [
+    return [
         (soil.fill_depressions_batch, (h2,), r"fill_depressions_batch: height: expected a \(B, H, W\)"),
         (soil.fill_depressions_batch, (g3,), "fill_depressions_batch: height: expected a float32"),
         (soil.fill_depressions_batch, (_host(np.float64, (5, 4, 3)), soil.d4), "fill_depressions_batch: height: expected a float32"),
@@ -146,24 +149,34 @@ def test_the_module_functions_refuse(no_library):
         (soil.condition_batch, (h3, soil.d8, h3), "condition_batch: graph: expected an int32"),
         (soil.condition_batch, (h3, soil.d8, _host(np.int32, (5, 4, 4))), "condition_batch: graph"),
     ]
-    for fn, args, match in bad:
+
+
+def test_the_module_functions_refuse(no_library):
+    for fn, args, match in _module_refusals():
         with pytest.raises(ValueError, match=match):
             fn(*args)
 
 
-def test_the_batch_methods_refuse(no_library):
-    """On a stub: an ErosionBatch cannot be made without a device, and the refusals touch none of its planes."""
+def _stub():
     from soillib_amd.erosion import ErosionBatch
     bt = ErosionBatch.__new__(ErosionBatch)
     bt.B, bt.H, bt.W, bt.seeds = 3, 8, 8, [1, 2, 3]
-    bad = [(dict(kind="direction"), "not indices"), (dict(kind="flow"), "kind must be"), (dict(kind=None), "kind must be"),
-           (dict(edge=2), "edge must be"), (dict(edge=True), "edge must be"),
-           (dict(kind="random_weighted"), "needs a finite temperature"), (dict(kind="random_weighted", T=float("nan")), "finite"),
-           (dict(kind="random_weighted", T=-1.0), "T must be 0 or a normal positive"),
-           (dict(kind="random_weighted", T=1e-42), "T must be 0 or a normal positive"),
-           (dict(kind="random_weighted", T=True), "finite temperature"),
-           (dict(kind="random_weighted", T=0.5, offset=-1), "offset"), (dict(kind="random_weighted", T=0.5, offset=1.5), "offset")]
-    for kwargs, match in bad:
+    return bt
+
+
+CONDITIONED = [(dict(kind="direction"), "not indices"), (dict(kind="flow"), "kind must be"), (dict(kind=None), "kind must be"),
+               (dict(edge=2), "edge must be"), (dict(edge=True), "edge must be"),
+               (dict(kind="random_weighted"), "needs a finite temperature"), (dict(kind="random_weighted", T=float("nan")), "finite"),
+               (dict(kind="random_weighted", T=-1.0), "T must be 0 or a normal positive"),
+               (dict(kind="random_weighted", T=1e-42), "T must be 0 or a normal positive"),
+               (dict(kind="random_weighted", T=True), "finite temperature"),
+               (dict(kind="random_weighted", T=0.5, offset=-1), "offset"), (dict(kind="random_weighted", T=0.5, offset=1.5), "offset")]
+
+
+def test_the_batch_methods_refuse(no_library):
+    """On a stub: an ErosionBatch cannot be made without a device, and the refusals touch none of its planes."""
+    bt = _stub()
+    for kwargs, match in CONDITIONED:
         with pytest.raises(ValueError, match="ErosionBatch.conditioned: .*%s" % match):
             bt.conditioned(**kwargs)
         if "kind" in kwargs and kwargs["kind"] == "random_weighted":       # exactly as flow() checks them

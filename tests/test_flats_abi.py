@@ -152,10 +152,10 @@ def _host(dtype, shape):
     return silt.tensor._wrap_numpy(np.zeros(shape, dtype))
 
 
-def test_the_module_functions_refuse():
+def _module_refusals():
     from soillib_amd import soil
     h2, h3, g2, g3 = _host(np.float32, (4, 3)), _host(np.float32, (5, 4, 3)), _host(np.int32, (4, 3)), _host(np.int32, (5, 4, 3))
-    bad = [
+    return [
         (soil.flat_distance, (h3, soil.d8), r"flat_distance: height: expected a \(H, W\)"),
         (soil.flat_distance, (g2, soil.d8), "flat_distance: height: expected a float32"),
         (soil.flat_distance, (h2, 2), "flat_distance: edge"),
@@ -172,7 +172,10 @@ def test_the_module_functions_refuse():
         (soil.resolve_flats, (h2, True), "resolve_flats: edge"),
         (soil.resolve_flats_batch, (h2, soil.d8), "resolve_flats_batch: height"),
     ]
-    for fn, args, match in bad:
+
+
+def test_the_module_functions_refuse():
+    for fn, args, match in _module_refusals():
         with pytest.raises(ValueError, match=match):
             fn(*args)
 

@@ -140,22 +140,25 @@ def _host_tensor(dtype, shape):
     return silt.tensor._wrap_numpy(np.zeros(shape, dtype))
 
 
-@pytest.mark.parametrize("kw", [dict(kind="steepest8"), dict(kind=None), dict(kind=1),
-                                dict(kind="random_weighted"), dict(kind="random_weighted", T=None),
-                                dict(kind="random_weighted", T=float("nan")),
-                                dict(kind="random_weighted", T=float("inf")), dict(kind="random_weighted", T="10"),
-                                dict(kind="random_weighted", T=True),
-                                dict(kind="random_weighted", T=10.0, offset=-1),
-                                dict(kind="random_weighted", T=10.0, offset=0.5),
-                                dict(edge=2), dict(edge="d8"), dict(kind="direction", edge=-1)])
+FLOW = [dict(kind="steepest8"), dict(kind=None), dict(kind=1),
+        dict(kind="random_weighted"), dict(kind="random_weighted", T=None),
+        dict(kind="random_weighted", T=float("nan")),
+        dict(kind="random_weighted", T=float("inf")), dict(kind="random_weighted", T="10"),
+        dict(kind="random_weighted", T=True),
+        dict(kind="random_weighted", T=10.0, offset=-1),
+        dict(kind="random_weighted", T=10.0, offset=0.5),
+        dict(edge=2), dict(edge="d8"), dict(kind="direction", edge=-1)]
+
+
+@pytest.mark.parametrize("kw", FLOW)
 def test_flow_refuses(kw):
     with pytest.raises(ValueError, match=r"ErosionBatch\.flow"):
         _batch_without_a_device().flow(**kw)
 
 
-def test_drainage_refuses():
+def _batch_refusals():
+    """(method, the stub's scales, args, kw, match) of drainage() and flow_slope()."""
     import numpy as np
-    bt = _batch_without_a_device()
     good_g, good_f = _host_tensor(np.int32, (5, 4, 3)), _host_tensor(np.float32, (5, 4, 3))
     bad = [dict(graph=_host_tensor(np.int32, (4, 4, 3))), dict(graph=_host_tensor(np.int32, (5, 12))),
            dict(graph=_host_tensor(np.float32, (5, 4, 3))), dict(graph=np.zeros((5, 4, 3), np.int32)),
@@ -164,41 +167,50 @@ def test_drainage_refuses():
            dict(graph=good_g, source=good_f, decay=_host_tensor(np.float32, (5, 3, 4))),
            dict(graph=good_g, source=good_f, decay=1.0),
            dict(graph=good_g, source=good_f, edge=7)]
-    for kw in bad:
-        with pytest.raises(ValueError, match=r"ErosionBatch\.drainage"):
-            bt.drainage(**kw)
+    out = [("drainage", None, (), kw, r"ErosionBatch\.drainage") for kw in bad]
+    for graph in (_host_tensor(np.int32, (5, 3, 4)), _host_tensor(np.float32, (5, 4, 3)), 3):
+        out.append(("flow_slope", None, (graph,), {}, r"ErosionBatch\.flow_slope"))
+    for scales in ([[1.0, 1.0, 1.0]] * 4, [[1.0, 1.0, 1.0]] * 6, [[1.0, 1.0]] * 5, [[1.0, 1.0, "z"]] * 5):
+        out.append(("flow_slope", scales, (good_g,), {}, r"ErosionBatch\.flow_slope"))
+    return out
+
+
+def _refuses(which):
+    cases = [c for c in _batch_refusals() if c[0] == which]
+    assert cases
+    for method, scales, args, kw, match in cases:
+        with pytest.raises(ValueError, match=match):
+            getattr(_batch_without_a_device(scales=scales), method)(*args, **kw)
+
+
+def test_drainage_refuses():
+    _refuses("drainage")
 
 
 def test_flow_slope_refuses():
-    import numpy as np
-    for graph in (_host_tensor(np.int32, (5, 3, 4)), _host_tensor(np.float32, (5, 4, 3)), 3):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.flow_slope"):
-            _batch_without_a_device().flow_slope(graph)
-    good = _host_tensor(np.int32, (5, 4, 3))
-    for scales in ([[1.0, 1.0, 1.0]] * 4, [[1.0, 1.0, 1.0]] * 6, [[1.0, 1.0]] * 5, [[1.0, 1.0, "z"]] * 5):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.flow_slope"):
-            _batch_without_a_device(scales=scales).flow_slope(good)
+    _refuses("flow_slope")
 
 
-def test_the_module_functions_refuse_wrong_counts_before_any_device_work():
+def _module_refusals():
     import numpy as np
     from soillib_amd import soil
     h = _host_tensor(np.float32, (5, 4, 3))
     g = _host_tensor(np.int32, (5, 4, 3))
-    with pytest.raises(ValueError, match="random_weighted_batch: 4 seeds for 5 models"):
-        soil.random_weighted_batch(h, soil.d8, [1, 2, 3, 4], 0, 10.0)
+    out = [(soil.random_weighted_batch, (h, soil.d8, [1, 2, 3, 4], 0, 10.0), {}, "random_weighted_batch: 4 seeds for 5 models")]
     for scale in ([1.0], [1.0, 1.0, 1.0], [[1.0, 1.0]] * 4, [[1.0, 1.0, 1.0]] * 5, 1.0, [["a", "b"]] * 5):
-        with pytest.raises(ValueError, match="slope_batch"):
-            soil.slope_batch(h, g, scale)
-    with pytest.raises(ValueError, match="slope_batch: flow"):
-        soil.slope_batch(h, _host_tensor(np.int32, (5, 3, 4)), [1.0, 1.0])
-    with pytest.raises(ValueError, match="accumulate_batch: field"):
-        soil.accumulate_batch(g, _host_tensor(np.float32, (4, 4, 3)), soil.d8)
-    with pytest.raises(ValueError, match="accumulate_batch: decay"):
-        soil.accumulate_batch(g, h, soil.d8, decay=_host_tensor(np.float32, (5, 4)))
+        out.append((soil.slope_batch, (h, g, scale), {}, "slope_batch"))
+    out += [(soil.slope_batch, (h, _host_tensor(np.int32, (5, 3, 4)), [1.0, 1.0]), {}, "slope_batch: flow"),
+            (soil.accumulate_batch, (g, _host_tensor(np.float32, (4, 4, 3)), soil.d8), {}, "accumulate_batch: field"),
+            (soil.accumulate_batch, (g, h, soil.d8), dict(decay=_host_tensor(np.float32, (5, 4))), "accumulate_batch: decay")]
     for fn in (soil.steepest_batch, soil.direction_batch):
-        with pytest.raises(ValueError, match=r"\(B, H, W\)"):
-            fn(_host_tensor(np.float32, (4, 3)), soil.d8)
+        out.append((fn, (_host_tensor(np.float32, (4, 3)), soil.d8), {}, r"\(B, H, W\)"))
+    return out
+
+
+def test_the_module_functions_refuse_wrong_counts_before_any_device_work():
+    for fn, args, kw, match in _module_refusals():
+        with pytest.raises(ValueError, match=match):
+            fn(*args, **kw)
 
 
 def test_the_entry_points_fail_loudly_without_a_device():
@@ -226,7 +238,10 @@ def _with_temperature(lib, T):
     return [(name, call(), lib.soil_last_error().decode()) for name, call in calls.items()]
 
 
-@pytest.mark.parametrize("T", [-1.0, -1e-30, float("nan"), float("inf"), float("-inf"), 1e-39, -1e-45, 1e39])
+REFUSED_T = [-1.0, -1e-30, float("nan"), float("inf"), float("-inf"), 1e-39, -1e-45, 1e39]
+
+
+@pytest.mark.parametrize("T", REFUSED_T)
 def test_a_temperature_outside_the_range_is_refused(T):
     from soillib_amd import _abi, soil
     assert not soil.valid_temperature(T)

@@ -269,10 +269,10 @@ def _host(dtype, shape):
     return silt.tensor._wrap_numpy(np.zeros(shape, dtype))
 
 
-def test_the_module_functions_refuse():
+def _module_refusals():
     from soillib_amd import soil
     g2, g3 = _host(np.int32, (4, 3)), _host(np.int32, (5, 4, 3))
-    bad = [
+    return [
         (soil.flow_paths, (g3, soil.d8), {}, r"flow_paths: graph: expected a \(H, W\)"),
         (soil.flow_paths, (_host(np.float32, (4, 3)), soil.d8), {}, "flow_paths: graph: expected an int32"),
         (soil.flow_paths, (np.zeros((4, 3), np.int32), soil.d8), {}, "flow_paths: graph"),
@@ -301,7 +301,10 @@ def test_the_module_functions_refuse():
         (soil.flow_length_batch, (g3, soil.d8, [[1.0, 1.0, 1.0]] * 5), {}, "flow_length_batch: scale"),
         (soil.flow_length_batch, (g3, soil.d8, 1.0), {}, "flow_length_batch: scale"),
     ]
-    for fn, args, kw, match in bad:
+
+
+def test_the_module_functions_refuse():
+    for fn, args, kw, match in _module_refusals():
         with pytest.raises(ValueError, match=match):
             fn(*args, **kw)
 
@@ -321,14 +324,21 @@ def _batch_without_a_device(B=5, scales=None):
     return bt
 
 
-def test_the_batch_methods_refuse():
+def _batch_refusals():
+    """(method, the stub's scales, args, kw, match)."""
     good = _host(np.int32, (5, 4, 3))
+    out = []
     for method in ("basins", "flow_length"):
         for kw in (dict(graph=_host(np.int32, (5, 3, 4))), dict(graph=_host(np.float32, (5, 4, 3))), dict(graph=3),
                    dict(graph=good, stop=_host(np.int32, (4, 4, 3))), dict(graph=good, stop=_host(np.float32, (5, 4, 3))),
                    dict(graph=good, stop=1), dict(graph=good, edge=2), dict(edge="d4")):
-            with pytest.raises(ValueError, match=r"ErosionBatch\.%s" % method):
-                getattr(_batch_without_a_device(), method)(**kw)
+            out.append((method, None, (), kw, r"ErosionBatch\.%s" % method))
     for scales in ([[1.0, 1.0, 1.0]] * 4, [[1.0, 1.0]] * 5, [[1.0, 1.0, "z"]] * 5):
-        with pytest.raises(ValueError, match=r"ErosionBatch\.flow_length"):
-            _batch_without_a_device(scales=scales).flow_length(good)
+        out.append(("flow_length", scales, (good,), {}, r"ErosionBatch\.flow_length"))
+    return out
+
+
+def test_the_batch_methods_refuse():
+    for method, scales, args, kw, match in _batch_refusals():
+        with pytest.raises(ValueError, match=match):
+            getattr(_batch_without_a_device(scales=scales), method)(*args, **kw)
