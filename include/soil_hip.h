@@ -1023,7 +1023,7 @@ int soil_flow_paths_info(int64_t info[4]);
  * association, not the serial sum's bits.
  *
  * soil_stream_power: the implicit step h' = (h + dt u + F h'[r]) / (1 + F), F = k dt / L, slope exponent n = 1 only
- * (n != 1 is not an affine map, so not associative: out of scope).  The same rounds, the coefficients made in the
+ * (n != 1 is not an affine map, so not associative: soil_stream_power_n below iterates on this solve).  The same rounds, the coefficients made in the
  * init pass from the planes, nothing materialised in between.  For a cell with an edge of length L, each operation
  * rounded once:
  *     F = ((double)erosivity[n] * dt) / L
@@ -1138,6 +1138,88 @@ int soil_stream_power_deposit_batch(float* out, double* out64, float* flux, doub
  * chunks, info[2] iterations run, info[3] bytes of scratch the call asked for.  All zero before the first call; needs
  * no device. */
 int soil_stream_power_deposit_info(int64_t info[4]);
+
+/* ------------------------------------- flow graphs: slope exponents above 1 */
+
+/* The implicit stream-power step with a slope exponent n >= 1,
+ *     dh/dt = u - K A^m S^n
+ * the general case of Braun & Willett's solver.  For n != 1 the implicit equation of a cell is not linear in the new
+ * heights, so it is no affine map and the rounds of soil_stream_power cannot compose it.  Its Newton linearisation
+ * about a given iterate is affine again,
+ *     S^n ~ (1 - n) S_j^n + n S_j^(n-1) S
+ *     h'[i] = (b + c) / (1 + F) + F / (1 + F) * h'[r],   F = n k dt S_j^(n-1) / L,   c = (n - 1) k dt S_j^n
+ * so a Newton step on the whole triangular system is one solve of soil_stream_power's rounds with other coefficients.
+ * The reference has no such call; the definition is this library's.
+ *
+ * Grid, edge rule, terminals, `stop`, `scale`, L(n), chunking, NaN words and the rounds of the records are word for
+ * word those of soil_stream_power.  `erosivity` is K A^m, made by the caller; `uplift` and `stop` may be NULL.
+ *
+ * All arithmetic is fp64 with one rounding per operation, in this order, with no contraction.
+ *     x^0 = the solve of soil_stream_power on the same arguments, in fp64: a NaN and a cell that is not final after the
+ *           last round kept as 0x7ff8000000000000
+ * For j = 1 .. iters, per cell i that has an edge to r of length L and is not stopped:
+ *     d  = x[i] - x[r]                      (x = x^(j-1), the receiver's value a gather of 8 bytes)
+ *     S  = d <= 0 ? 0.0 : d / L             (a NaN d falls through to d / L and stays NaN)
+ *     P  = n == 2 ? S : pow(S, n - 1)       (n - 1 made once on the host; pow: see below)
+ *     kd = (double)erosivity[i] * dt
+ *     F  = ((n * kd) / L) * P
+ *     c  = (kd * (n - 1)) * (P * S)
+ *     b  = (double)height[i] + dt * (double)uplift[i]      (double)height[i] with uplift == NULL
+ *     D  = 1.0 + F ;  A = (b + c) / D ;  B = F / D
+ * A terminal or stopped cell has A = (double)height[i], B = 0, and is final.  Then
+ *     x^j = the solve x[i] = A + B * x[r] down the graph, with soil_downstream's rounds, bit for bit
+ * A cell whose receiver is not below it in the iterate takes no erosion in that step: S = 0 gives F = c = 0, so
+ * x = b.  A NaN height reaches everything upstream of it, as it does at n = 1.
+ *
+ * The start is the n = 1 solve, not the old heights: the tangent of S^n at S = 0 is flat, so across a run of level
+ * cells (a filled lake) information enters one cell per iteration, and from the old heights the iteration stalls
+ * there.  From the n = 1 solve it converges in 8 to 16 iterations for K dt / L up to order 1; under a K dt / L of
+ * order 100 with n >= 2 it can still stall across a long flat, and the residual says so.  `iters`
+ * >= 1 is the caller's: a fixed count keeps the result one definite bit pattern, fixed by the graph, the planes and
+ * the arguments alone; chunking, batching, lists, offsets and alignment do not show.
+ *
+ * pow is the device library's fp64 pow behind one inline device function: deterministic, not correctly rounded.
+ * soil_selftest_math64 op 0 evaluates that very function, so a restatement that takes its powers from it is bit-exact
+ * on every path.  n == 2 needs no power: P = S.
+ *
+ * n == 1.0 runs soil_stream_power's single solve and nothing else and gives its bits; the residual is 0 and the
+ * info's iterations are 0.  n < 1 is out of scope on purpose: the per-cell function is then concave, a tangent step
+ * from above overshoots to negative slopes, where the derivative is infinite, and that needs a safeguarded solve per
+ * cell, which no affine map expresses.
+ *
+ * Outputs.  At least one of `out` (float) and `out64` (double) is non-NULL: x^iters, with the NaN words of
+ * soil_downstream.  `residual` (may be NULL): a device array of B doubles (one for the single call); entry b is the
+ * maximum over the cells of model b of |x^iters - x^(iters-1)|, one fp64 subtraction a cell, the cells where that is a
+ * NaN left out, 0 for a model without any other; taken over the words of the non-negative doubles as integers, as
+ * soil_stream_power_deposit takes it.  In every stalled case tried the residual was within a factor of about two of
+ * the true error.  Nothing synchronises.
+ *
+ * The entries are stream-ordered on the caller's stream from the first launch to the last.  A host thread's calls on
+ * one device share cached scratch of their own (the records, B planes and lists of soil_stream_power and 8 bytes a
+ * cell for the iterate): issue them on ONE stream, or order the streams yourself.
+ *
+ * Batch form: the conventions of soil_stream_power_batch.  Model-major planes, 1 or B scale pairs, model b's slices
+ * bit for bit what the single call gives, chunks of whole models (SOIL_FLOW_BATCH_CELLS lowers the cells of a chunk,
+ * SOIL_PATHS_IDX64=1 forces 64-bit offsets), every iteration of a chunk before the next chunk.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): what soil_stream_power refuses, an n that is not finite, n < 1 or n > 16, iters < 1, `residual`
+ * aliasing an input plane or an output.  Otherwise, without a device: SOIL_ERR_NO_DEVICE. */
+int soil_stream_power_n(float* out, double* out64, double* residual, const float* height, const int32_t* graph,
+                        const float* erosivity, const float* uplift, const int32_t* stop, int64_t H, int64_t W,
+                        int edge, const float scale[2], double dt, double n, int iters, void* stream);
+int soil_stream_power_n_batch(float* out, double* out64, double* residual, const float* height, const int32_t* graph,
+                              const float* erosivity, const float* uplift, const int32_t* stop, int64_t B, int64_t H,
+                              int64_t W, int edge, const float* scales, int64_t n_scales, double dt, double n,
+                              int iters, void* stream);
+/* What the calling host thread's last soil_stream_power_n or _batch call did: info[0] kernel launches, info[1]
+ * chunks, info[2] iterations run (0 for n == 1), info[3] bytes of scratch the call asked for.  All zero before the
+ * first call; needs no device. */
+int soil_stream_power_n_info(int64_t info[4]);
+/* out[i] = op(a[i], b[i]) of the fp64 device functions the kernels share with the tests' restatements, on device
+ * arrays of n doubles.  op 0: the slope power of soil_stream_power_n, pow(a, b) as its init pass evaluates it.  Any
+ * other op, or a null array, is refused with SOIL_ERR_INVALID_ARGUMENT before any device work. */
+int soil_selftest_math64(double* out, const double* a, const double* b, int64_t n, int op, void* stream);
 
 /* ------------------------------------------------------ hillslope diffusion */
 

@@ -129,6 +129,7 @@ SIGNATURES = {
     "soil_multiply_f32": (cint, [vp, f32, i64, vp]),
     "soil_rng_seed": (cint, [vp, i64, u64, u64, vp]),
     "soil_selftest_math": (cint, [vp, vp, vp, i64, cint, vp]),
+    "soil_selftest_math64": (cint, [vp, vp, vp, i64, cint, vp]),
     "soil_transport_fluvial": (cint, [vp] * 12 + [i64, i64, i64, F3, C.POINTER(Param), vp]),
     "soil_transport_debris": (cint, [vp] * 9 + [i64, i64, i64, F3, C.POINTER(Param), vp]),
     "soil_mass_transfer": (cint, [vp] * 12 + [i64, i64, F3, C.POINTER(Param), vp]),
@@ -246,6 +247,12 @@ SIGNATURES = {
     "soil_stream_power_deposit_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64,
                                                C.c_double, cint, vp]),
     "soil_stream_power_deposit_info": (cint, [C.POINTER(i64)]),
+    # the stream-power step with a slope exponent above 1: out / out64, residual (may be NULL), height, graph,
+    # erosivity, uplift (may be NULL), stop (may be NULL); host scale pairs, dt, n, iters
+    "soil_stream_power_n": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double, C.c_double, cint, vp]),
+    "soil_stream_power_n_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, C.c_double,
+                                         C.c_double, cint, vp]),
+    "soil_stream_power_n_info": (cint, [C.POINTER(i64)]),
     # hillslope diffusion: out / out64 (one may be NULL), height, diffusivity / uplift / fixed (each may be NULL);
     # host scale pairs, kappa, dt, border, first_axis
     "soil_diffuse": (cint, [vp, vp, vp, vp, vp, vp, i64, i64, F3, C.c_double, C.c_double, cint, cint, vp]),

@@ -23,6 +23,14 @@ def count(who, name, v, lo=1, below=2 ** 31):
     return int(v)
 
 
+def exponent(who, v):
+    """`v` as a float: the slope exponent of stream_power_n, a finite number in [1, 16]."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 1 or v > 16:
+        raise ValueError("%s: n must be a finite number in 1 .. 16 (a slope exponent below 1 needs a safeguarded solve "
+                         "per cell), got %r" % (who, v))
+    return float(v)
+
+
 def edge(who, v):
     if isinstance(v, bool) or v not in (_abi.D4, _abi.D8):
         raise ValueError("%s: edge must be d4 or d8, got %r" % (who, v))

@@ -7,7 +7,9 @@
 // and the implicit stream-power step of Braun & Willett, the same recurrence with coefficients made from the planes
 // (soil_stream_power / soil_stream_power_batch).  The reference has neither; its example/dem_process.py names the
 // solver.  At the end of the file, the stream-power step with a deposition term (soil_stream_power_deposit /
-// soil_stream_power_deposit_batch): the same rounds inside a fixed-point iteration with graph.hip's accumulation.
+// soil_stream_power_deposit_batch): the same rounds inside a fixed-point iteration with graph.hip's accumulation; and
+// the step with a slope exponent above 1 (soil_stream_power_n / soil_stream_power_n_batch): the same rounds inside a
+// Newton iteration, whose linearisation about an iterate is an affine recurrence again.
 //
 // The composition of affine maps is associative, so this is the pointer doubling of flow_paths.hip with other
 // records: where that file adds three counters, a round here composes x -> A + B x with the map of the cell the
@@ -598,6 +600,194 @@ static int deposit_run(DepOut o, const DepPlanes& in, int iters, int64_t B, int6
   return rc;
 }
 
+// ---- slope exponents above 1: Newton steps on the whole triangular system, each one solve of the rounds above ---
+//
+// soil_stream_power_n(_batch), soil_hip.h "flow graphs: slope exponents above 1".  x^0 is soil_stream_power's solve
+// (k_down_init<kPower>, the rounds, k_dep_final keeping the fp64 iterate); then `iters` times the coefficients of the
+// linearisation about the iterate before (k_pn_init: the receiver's value an 8-byte gather, a slope raised to a
+// power), the rounds untouched, and k_dep_final, which on the last iteration makes the outputs and the residual.  Per
+// chunk of whole models, all on the caller's stream: nothing synchronises.
+
+struct PnPlanes {
+  const int32_t* graph;
+  const int32_t* stop;
+  const float *height, *erosivity, *uplift;
+  double dt, n, n1;  // n1 = n - 1, made once on the host
+};
+
+// The record of one cell of the Newton mode, and its B: soil_hip.h's operations in its order, each rounded once.
+// `xit`: the iterate before of the cell's model, xi its value at the cell; a valid edge_kind puts gr inside the model.
+template <int K>
+__device__ __forceinline__ void pn_init_cell(uint4* __restrict__ rec, double* __restrict__ bcoef, int64_t n,
+                                             int32_t gr, bool stop, float h, float e, float u, bool has_u, double xi,
+                                             const double* __restrict__ xit, int64_t x, int64_t y, int64_t H,
+                                             int64_t W, uint32_t first, const PathScale& s, const PnPlanes& in) {
+  const int kind = stop ? -1 : edge_kind<K>(gr, x, y, H, W);
+  double A = static_cast<double>(h), B = 0.0;  // a terminal: the height of the base level
+  uint32_t ptr = (first + static_cast<uint32_t>(n)) | kFinal;
+  if (kind >= 0) {
+    ptr = first + static_cast<uint32_t>(gr);
+    const double L = kind == 0 ? s.sx : (kind == 1 ? s.sy : s.dd);
+    const double d = __dsub_rn(xi, xit[gr]);
+    const double S = d <= 0.0 ? 0.0 : __ddiv_rn(d, L);  // (a NaN d is not <= 0: it stays a NaN)
+    const double P = in.n == 2.0 ? S : sp_pow(S, in.n1);
+    const double kd = __dmul_rn(static_cast<double>(e), in.dt);
+    const double F = __dmul_rn(__ddiv_rn(__dmul_rn(in.n, kd), L), P);
+    const double c = __dmul_rn(__dmul_rn(kd, in.n1), __dmul_rn(P, S));
+    const double b = dep_lifted(h, u, has_u, in.dt);
+    const double D = __dadd_rn(1.0, F);
+    A = __ddiv_rn(__dadd_rn(b, c), D);
+    B = __ddiv_rn(F, D);
+  }
+  rec[n] = down_rec(ptr, kind < 0 ? 0u : 1u, A);
+  bcoef[n] = B;
+}
+
+// The init pass of the Newton mode, as k_dep_init: five planes and the iterate, each a 16-byte load in the VEC form
+// (the iterate two of them), and the gather of the receiver's iterate.  The gather hangs on the load of the graph
+// entry, two memory latencies in a row for every row a thread walks, so the band of rows is kPnBand, shorter than
+// kRowBand: at 256^2 sixteen rows a work-group left sixteen work-groups on the device, each waiting out thirty-two
+// latencies.
+constexpr int kPnBand = 4;
+template <int K, bool VEC>
+__global__ void __launch_bounds__(kPBlock)
+    k_pn_init(uint4* __restrict__ rec, double* __restrict__ bcoef, PnPlanes in, const double* __restrict__ xit,
+              int64_t H, int64_t W, PathScales scales, int* __restrict__ flags) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < kPathFlags)
+    flags[threadIdx.x] = threadIdx.x == 0 ? 1 : 0;
+  const int64_t y = (static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x) * (VEC ? 4 : 1);
+  if (y >= W) return;
+  const int64_t first64 = static_cast<int64_t>(blockIdx.z) * H * W;
+  const uint32_t first = static_cast<uint32_t>(first64);
+  const PathScale s = scales.per_model ? scales.per_model[blockIdx.z] : scales.one;
+  rec += first64, bcoef += first64, xit += first64;
+  const int32_t* const graph = in.graph + first64;
+  const int32_t* const stop = in.stop ? in.stop + first64 : nullptr;
+  const float* const height = in.height + first64;
+  const float* const erosivity = in.erosivity + first64;
+  const float* const uplift = in.uplift ? in.uplift + first64 : nullptr;
+  const bool has_u = uplift != nullptr;
+  for (int64_t band = blockIdx.y; band * kPnBand < H; band += gridDim.y) {
+    for (int64_t x = band * kPnBand, end = x + kPnBand < H ? x + kPnBand : H; x < end; ++x) {
+      const int64_t n = x * W + y;
+      if constexpr (VEC) {
+        const int4 g = *reinterpret_cast<const int4*>(graph + n);
+        const int4 st = stop ? *reinterpret_cast<const int4*>(stop + n) : make_int4(0, 0, 0, 0);
+        const float4 h = *reinterpret_cast<const float4*>(height + n);
+        const float4 e = *reinterpret_cast<const float4*>(erosivity + n);
+        const float4 u = uplift ? *reinterpret_cast<const float4*>(uplift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const double2 x01 = *reinterpret_cast<const double2*>(xit + n);
+        const double2 x23 = *reinterpret_cast<const double2*>(xit + n + 2);
+        pn_init_cell<K>(rec, bcoef, n + 0, g.x, st.x != 0, h.x, e.x, u.x, has_u, x01.x, xit, x, y + 0, H, W, first, s, in);
+        pn_init_cell<K>(rec, bcoef, n + 1, g.y, st.y != 0, h.y, e.y, u.y, has_u, x01.y, xit, x, y + 1, H, W, first, s, in);
+        pn_init_cell<K>(rec, bcoef, n + 2, g.z, st.z != 0, h.z, e.z, u.z, has_u, x23.x, xit, x, y + 2, H, W, first, s, in);
+        pn_init_cell<K>(rec, bcoef, n + 3, g.w, st.w != 0, h.w, e.w, u.w, has_u, x23.y, xit, x, y + 3, H, W, first, s, in);
+      } else {
+        pn_init_cell<K>(rec, bcoef, n, graph[n], stop ? stop[n] != 0 : false, height[n], erosivity[n],
+                        uplift ? uplift[n] : 0.0f, has_u, xit[n], xit, x, y, H, W, first, s, in);
+      }
+    }
+  }
+}
+
+struct PnOut {
+  float* out;
+  double* out64;
+  double* residual;
+};
+static thread_local DepInfo t_pn_info{0, 0, 0, 0};  // soil_stream_power_n_info
+
+// One chunk of `models` models: the start (soil_stream_power's init), then `iters` times k_pn_init, each with the
+// rounds and a final pass through ptr_chunk.  iters == 0 (n == 1): the start alone, with soil_stream_power's final.
+// `in`, `o` and `x` are the chunk's own.
+template <int K>
+static int pn_chunk(PnOut o, const PnPlanes& in, double* x, int iters, int64_t models, int64_t H, int64_t W,
+                    const PathScales& scales, char* scratch, hipStream_t st) {
+  PtrInfo pinfo{0, 0, 0, 0};
+  t_pn_info.chunks += 1;
+  const DownPlanes power{in.graph, in.stop, in.height, in.erosivity, in.uplift, in.dt};
+  const bool vec = ptr_vec_init(W, reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.stop) |
+                                       reinterpret_cast<uintptr_t>(in.height) |
+                                       reinterpret_cast<uintptr_t>(in.erosivity) |
+                                       reinterpret_cast<uintptr_t>(in.uplift) | reinterpret_cast<uintptr_t>(x));
+  for (int j = 0; j <= iters; ++j) {
+    const bool last = j == iters;
+    auto init = [&](const PtrChunk& c) {
+      const dim3 grid = ptr_init_grid(c, H, W, vec);
+      double* const b0 = static_cast<double*>(c.extra[0]);
+      if (j == 0) {
+        if (vec) k_down_init<K, true, kPower, true><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, power, H, W, scales, c.flags);
+        else k_down_init<K, false, kPower, true><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, power, H, W, scales, c.flags);
+      } else {
+        const int64_t bands = (H + kPnBand - 1) / kPnBand;
+        const dim3 pn_grid(grid.x, static_cast<unsigned>(bands < 65535 ? bands : 65535), grid.z);
+        if (vec) k_pn_init<K, true><<<pn_grid, kPBlock, 0, st>>>(c.rec[0], b0, in, x, H, W, scales, c.flags);
+        else k_pn_init<K, false><<<pn_grid, kPBlock, 0, st>>>(c.rec[0], b0, in, x, H, W, scales, c.flags);
+      }
+      return vec;
+    };
+    auto round = [&](const PtrChunk& c, const PtrRound& q) { down_launch_round<true>(c, q, st); };
+    auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
+      if (iters == 0)
+        k_down_final<<<grid, kPBlock, 0, st>>>(o.out, o.out64, rec, H * W);
+      else
+        k_dep_final<<<grid, kPBlock, 0, st>>>(last ? o.out : nullptr, last ? o.out64 : nullptr, x,
+                                              last ? reinterpret_cast<unsigned long long*>(o.residual) : nullptr, rec,
+                                              H * W);
+    };
+    if (int rc = ptr_chunk(pinfo, models, H, W, sizeof(double), scratch, init, round, fin); rc != SOIL_OK) return rc;
+    t_pn_info.launches += 2 + pinfo.rounds;
+  }
+  return SOIL_OK;
+}
+
+// What the two entries refuse before any device work: soil_stream_power's refusals and their own
+static int check_power_n(const char* what, const PnOut& o, const PnPlanes& in, int iters, const float* scales,
+                         int64_t B, int64_t H, int64_t W, int edge, int64_t n_scales) {
+  const std::string w(what);
+  const DownPlanes power{in.graph, in.stop, in.height, in.erosivity, in.uplift, in.dt};
+  if (int rc = check_downstream(what, kPower, o.out, o.out64, power, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
+    return rc;
+  SOIL_REQUIRE(std::isfinite(in.n) && in.n >= 1.0 && in.n <= 16.0,
+               w + ": n must be a finite slope exponent in 1 .. 16 (n < 1 makes the per-cell equation concave: it needs "
+                   "a safeguarded solve per cell, which no affine map expresses)");
+  SOIL_REQUIRE(iters >= 1, w + ": iters must be >= 1");
+  const size_t cells = plane_cells(B, H * W), b_res = 8 * static_cast<size_t>(B);
+  const void* const planes[] = {in.graph, in.stop, in.height, in.erosivity, in.uplift, o.out};
+  for (const void* p : planes)
+    SOIL_REQUIRE(!overlaps(o.residual, b_res, p, 4 * cells), w + ": residual aliases another plane");
+  SOIL_REQUIRE(!overlaps(o.residual, b_res, o.out64, 8 * cells), w + ": residual aliases another plane");
+  return SOIL_OK;
+}
+
+// A call: the chunks of ptr_run through slot WS_POWER_N, the chunk's iterate in WS_POWER_N_ITERATE beside them
+static int power_n_run(PnOut o, const PnPlanes& in, int iters, int64_t B, int64_t H, int64_t W, int edge,
+                       const float* scales, int64_t n_scales, hipStream_t st) {
+  const int64_t hw = H * W, per = ptr_chunk_models(hw), first_chunk = B < per ? B : per;
+  if (in.n == 1.0) iters = 0;  // soil_stream_power's single solve and nothing else
+  const size_t b_x = iters ? align256(sizeof(double) * static_cast<size_t>(first_chunk * hw)) : 0;
+  t_pn_info = DepInfo{0, 0, iters, 0};
+  void* x = nullptr;
+  if (b_x)
+    if (int rc = workspace_get(WS_POWER_N_ITERATE, b_x, &x); rc != SOIL_OK) return rc;
+  if (o.residual) SOIL_HIP(hipMemsetAsync(o.residual, 0, sizeof(double) * static_cast<size_t>(B), st));
+  PtrInfo pinfo{0, 0, 0, 0};
+  auto go = edge == SOIL_D4 ? pn_chunk<4> : pn_chunk<8>;
+  const int rc = ptr_run(WS_POWER_N, pinfo, B, H, W, sizeof(double), scales, n_scales, PathScale{1.0, 1.0, 1.0}, st,
+                         [&](int64_t b0, int64_t nb, const PathScales& s, char* scratch) {
+                           const int64_t at = b0 * hw;
+                           const PnPlanes part{in.graph + at, in.stop ? in.stop + at : nullptr,
+                                               in.height + at, in.erosivity + at,
+                                               in.uplift ? in.uplift + at : nullptr, in.dt, in.n, in.n1};
+                           const PnOut part_o{o.out ? o.out + at : nullptr, o.out64 ? o.out64 + at : nullptr,
+                                              o.residual ? o.residual + b0 : nullptr};
+                           return go(part_o, part, static_cast<double*>(x), iters, nb, H, W, s, scratch, st);
+                         });
+  const size_t b_scales = scales && n_scales > 1 ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0;
+  t_pn_info.bytes = static_cast<int64_t>(b_x + b_scales + ptr_layout(first_chunk * hw, sizeof(double)).bytes());
+  return rc;
+}
+
 }  // namespace soil
 
 using namespace soil;
@@ -670,6 +860,34 @@ int soil_stream_power_deposit_batch(float* out, double* out64, float* flux, doub
 int soil_stream_power_deposit_info(int64_t info[4]) {
   SOIL_REQUIRE(info, "stream_power_deposit_info: null info");
   info[0] = t_dep_info.launches, info[1] = t_dep_info.chunks, info[2] = t_dep_info.iters, info[3] = t_dep_info.bytes;
+  return SOIL_OK;
+}
+
+int soil_stream_power_n(float* out, double* out64, double* residual, const float* height, const int32_t* graph,
+                        const float* erosivity, const float* uplift, const int32_t* stop, int64_t H, int64_t W,
+                        int edge, const float scale[2], double dt, double n, int iters, void* stream) {
+  const PnPlanes in{graph, stop, height, erosivity, uplift, dt, n, n - 1.0};
+  const PnOut o{out, out64, residual};
+  if (int rc = check_power_n("stream_power_n", o, in, iters, scale, 1, H, W, edge, 1); rc != SOIL_OK) return rc;
+  SOIL_DEVICE();
+  return power_n_run(o, in, iters, 1, H, W, edge, scale, 1, as_stream(stream));
+}
+
+int soil_stream_power_n_batch(float* out, double* out64, double* residual, const float* height, const int32_t* graph,
+                              const float* erosivity, const float* uplift, const int32_t* stop, int64_t B, int64_t H,
+                              int64_t W, int edge, const float* scales, int64_t n_scales, double dt, double n,
+                              int iters, void* stream) {
+  const PnPlanes in{graph, stop, height, erosivity, uplift, dt, n, n - 1.0};
+  const PnOut o{out, out64, residual};
+  if (int rc = check_power_n("stream_power_n_batch", o, in, iters, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
+    return rc;
+  SOIL_DEVICE();
+  return power_n_run(o, in, iters, B, H, W, edge, scales, n_scales, as_stream(stream));
+}
+
+int soil_stream_power_n_info(int64_t info[4]) {
+  SOIL_REQUIRE(info, "stream_power_n_info: null info");
+  info[0] = t_pn_info.launches, info[1] = t_pn_info.chunks, info[2] = t_pn_info.iters, info[3] = t_pn_info.bytes;
   return SOIL_OK;
 }
 

@@ -223,6 +223,13 @@ __global__ void k_selftest_math(float* __restrict__ out, const float* __restrict
   out[i] = r;
 }
 
+// soil_selftest_math64: the fp64 device functions the kernels share with the tests' restatements
+__global__ void k_selftest_math64(double* __restrict__ out, const double* __restrict__ a,
+                                  const double* __restrict__ b, int64_t n) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = sp_pow(a[i], b[i]);
+}
+
 }  // namespace soil
 
 using namespace soil;
@@ -387,6 +394,16 @@ int soil_selftest_math(float* out, const float* a, const float* b, int64_t n, in
   SOIL_REQUIRE(op >= 0 && op <= 12, "selftest_math: unknown op");
   if (n <= 0) return SOIL_OK;
   k_selftest_math<<<blocks_for(n, 256), 256, 0, as_stream(stream)>>>(out, a, b, n, op);
+  SOIL_LAUNCH_CHECK();
+  return SOIL_OK;
+}
+
+int soil_selftest_math64(double* out, const double* a, const double* b, int64_t n, int op, void* stream) {
+  SOIL_REQUIRE(out && a && b, "selftest_math64: null argument");
+  SOIL_REQUIRE(op == 0, "selftest_math64: unknown op");
+  SOIL_DEVICE();
+  if (n <= 0) return SOIL_OK;
+  k_selftest_math64<<<blocks_for(n, 256), 256, 0, as_stream(stream)>>>(out, a, b, n);
   SOIL_LAUNCH_CHECK();
   return SOIL_OK;
 }

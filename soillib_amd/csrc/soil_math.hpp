@@ -196,6 +196,12 @@ __device__ __forceinline__ float att_exp(float x) { return __builtin_amdgcn_exp2
 // tests' restatement of the kernel takes its weights from the very expression the kernel evaluates.
 __device__ __forceinline__ float rw_exp2(float diff, float c) { return __builtin_amdgcn_exp2f(diff * c); }
 
+// The slope power of soil_stream_power_n (downstream.hip: pn_init_cell): S^e in fp64 through the device library's pow,
+// which is deterministic but not correctly rounded.  soil_selftest_math64 op 0 is this function, so the tests'
+// restatement of the kernel takes its powers from the very expression the kernel evaluates.  pow(+0, e > 0) is +0,
+// pow(1, e) is 1 and a NaN S stays a NaN.
+__device__ __forceinline__ double sp_pow(double S, double e) { return pow(S, e); }
+
 // floor(f) as an integer in one instruction (v_cvt_flr_i32_f32), saturating at the int32 range
 // — for a position inside the grid the same cell as the reference's float -> int truncation
 // (erosion_map.cu:42-47), and for one outside of it an index an unsigned comparison against the grid

@@ -795,21 +795,29 @@ class ErosionBatch:
             graph = self.flow(edge=e)
         return soil.downstream_batch(graph, e, a, b, terminal, scale, stop, double)
 
-    def stream_power(self, dt, K, m=0.5, kind="steepest", edge=None, T=None, offset=0, uplift=None):
-        """One implicit stream-power step (slope exponent 1) of every model, on its conditioned surface: conditioned()
-        -> drainage(graph=g) -> soil.erosivity(area, K, m) -> soil.stream_power_batch on the filled surface with the
+    def stream_power(self, dt, K, m=0.5, kind="steepest", edge=None, T=None, offset=0, uplift=None, n=1.0, iters=12,
+                     residual=False):
+        """One implicit stream-power step of every model, on its conditioned surface: conditioned() ->
+        drainage(graph=g) -> soil.erosivity(area, K, m) -> soil.stream_power_batch on the filled surface with the
         batch's scale(s).  Returns the (B, H, W) float32 heights after the step; the batch's own planes are not
-        touched.  `uplift`: a (B, H, W) float32 tensor or None; `kind`, `edge`, `T`, `offset` as in conditioned().  A
-        bad argument raises ValueError before any device work.  Synchronises the stream (the fill does)."""
+        touched.  `uplift`: a (B, H, W) float32 tensor or None; `kind`, `edge`, `T`, `offset` as in conditioned().
+        `n`: the slope exponent, 1 .. 16; with n != 1 the last link is soil.stream_power_n_batch with `iters` Newton
+        steps, and `residual` returns (heights, residual) as it does (with n == 1 the residual is a tensor of zeros).
+        A bad argument raises ValueError before any device work.  Synchronises the stream (the fill does)."""
         from . import soil
         who = "ErosionBatch.stream_power"
         _check.number(who, "dt", dt)
         _check.number(who, "K", K)
         _check.number(who, "m", m, lo=None)
+        n = _check.exponent(who, n)
+        _check.count(who, "iters", iters)
         e, scale = self._routing("stream_power", kind, edge, T, offset, uplift)
         filled, graph = self.conditioned(kind, e, T, offset)
         area = self.drainage(graph=graph, edge=e)
-        return soil.stream_power_batch(filled, graph, soil.erosivity(area, K, m), e, scale, dt, uplift)
+        if n == 1.0 and not residual:
+            return soil.stream_power_batch(filled, graph, soil.erosivity(area, K, m), e, scale, dt, uplift)
+        return soil.stream_power_n_batch(filled, graph, soil.erosivity(area, K, m), e, scale, dt, n, uplift, None,
+                                         int(iters), False, residual)
 
     def stream_power_deposit(self, dt, K, m=0.5, G=1.0, iters=8, kind="steepest", edge=None, T=None, offset=0,
                              uplift=None, flux=False, residual=False):
@@ -859,24 +867,33 @@ class ErosionBatch:
         return soil.diffuse_batch(self.height, scale, dt, kappa, diffusivity, uplift, fixed, border, first_axis, double)
 
     def evolve(self, dt, K, m=0.5, kappa=None, uplift=None, kind="steepest", edge=None, T=None, offset=0,
-               first_axis=0, G=None, iters=8):
+               first_axis=0, G=None, iters=8, n=1.0):
         """One landscape-evolution step of every model, uplift + stream power + linear diffusion: stream_power(dt, K,
         m, kind, edge, T, offset, uplift) and then soil.diffuse_batch of its result over the same `dt` with the
         diffusivity `kappa` and border="fixed" — the outermost cells, the base level of the conditioned graph, keep
         what the stream-power step left them.  The uplift is applied once, in the stream-power step.  With `G` (a
         finite number >= 0) the first half is stream_power_deposit(dt, K, m, G, iters, ...) instead: the eroded
-        material is deposited on its way down.  Returns the (B, H, W) float32 heights; the batch's own planes are not
-        touched.  A bad argument raises ValueError before any device work.  Synchronises the stream (the fill does)."""
+        material is deposited on its way down.  With `n` != 1 (a slope exponent in 1 .. 16) the first half is
+        stream_power(..., n=n, iters=iters); the deposit step stays at n = 1, so `G` together with n != 1 raises
+        ValueError.  Returns the (B, H, W) float32 heights; the batch's own planes are not touched.  A bad argument
+        raises ValueError before any device work.  Synchronises the stream (the fill does)."""
         from . import soil
         who = "ErosionBatch.evolve"
         self._check_diffuse("evolve", dt, kappa, None, None, None, "fixed", first_axis)
+        n = _check.exponent(who, n)
         if G is not None:
             _check.number(who, "G", G)
+            _check.count(who, "iters", iters)
+            if n != 1.0:
+                raise ValueError("%s: G (deposition) takes the slope exponent n = 1 only, got n = %r" % (who, n))
+        elif n != 1.0:
             _check.count(who, "iters", iters)
         _check.number(who, "K", K)
         _check.number(who, "m", m, lo=None)
         _, scale = self._routing("evolve", kind, edge, T, offset, uplift)
-        if G is None:
+        if G is None and n != 1.0:
+            carved = self.stream_power(dt, K, m, kind, edge, T, offset, uplift, n, iters)
+        elif G is None:
             carved = self.stream_power(dt, K, m, kind, edge, T, offset, uplift)
         else:
             carved = self.stream_power_deposit(dt, K, m, G, iters, kind, edge, T, offset, uplift)

@@ -450,7 +450,8 @@ def downstream_batch(graph, edge_, a=None, b=None, terminal=None, scale=None, st
 
 
 def stream_power(height, graph, erosivity, edge_, scale, dt, uplift=None, stop=None, double=False):
-    """soil_stream_power: one implicit step of stream-power incision with slope exponent n = 1 along `graph`,
+    """soil_stream_power: one implicit step of stream-power incision with slope exponent n = 1 along `graph` (any other
+    exponent in 1 .. 16: stream_power_n),
     h'[n] = (h[n] + dt u[n] + F h'[r]) / (1 + F) with F = erosivity[n] dt / L(n); a terminal keeps its height.
     `erosivity` is K A^m (soil.erosivity), `uplift` a float32 plane or None.  Returns the new heights, float32 (float64
     with `double`); `height` is left as it is.  The graph should be acyclic and reach an outlet from every cell
@@ -528,7 +529,7 @@ def _stream_power_deposit(who, dims, height, graph, erosivity, deposition, edge_
 def stream_power_deposit(height, graph, erosivity, deposition, edge_, scale, dt, uplift=None, iters=8, double=False,
                          flux=False, residual=False):
     """soil_stream_power_deposit: one implicit step of stream-power incision with sediment deposition (the
-    erosion-deposition model, slope exponent 1) along `graph`: stream_power's step plus (G / A) Qs, Qs the net material
+    erosion-deposition model; slope exponent 1 — the deposit step has no counterpart of stream_power_n yet) along `graph`: stream_power's step plus (G / A) Qs, Qs the net material
     removed upstream, by `iters` fixed-point iterations of an upstream sum and a downstream solve.  `erosivity` is
     K A^m (soil.erosivity), `deposition` G cell / A (soil.deposition), `uplift` a float32 plane or None.  Returns the
     new heights, float32 (float64 with `double`); with `flux` and / or `residual` a tuple (heights, flux, residual) of
@@ -567,6 +568,61 @@ def stream_power_deposit_info():
     """What this thread's last stream_power_deposit / _batch call did (soil_stream_power_deposit_info): a dict with the
     number of kernel `launches`, of `chunks`, the `iters` run and the `scratch_bytes` it asked for."""
     return _call_info("soil_stream_power_deposit_info", ("launches", "chunks", "iters", "scratch_bytes"))
+
+
+# ---- slope exponents above 1 (soil_hip.h: "flow graphs: slope exponents above 1"): the stream-power step as Newton
+# steps on the whole triangular system, each one solve of stream_power's rounds, from stream_power's own result.
+
+def _stream_power_n(who, dims, height, graph, erosivity, edge_, scale, dt, n, uplift, stop, iters, double, residual):
+    """soil_stream_power_n and its _batch form.  Every check comes before any device work."""
+    shape = _shape(dims, graph, "%s: graph" % who)
+    e = _check.edge(who, edge_)
+    _int_plane(graph, shape, "%s: graph" % who)
+    planes = [("height", height, True), ("erosivity", erosivity, True), ("uplift", uplift, False)]
+    _float_planes(who, shape, planes)
+    if stop is not None:
+        _int_plane(stop, shape, "%s: stop" % who)
+    pairs, tail = _scales(who, dims, scale, shape[0])
+    _positive(who, pairs, scale)
+    dt = _check.number(who, "dt", dt)
+    n = _check.exponent(who, n)
+    iters = _check.count(who, "iters", iters)
+    g_ptr = _gpu(graph, silt.int32, "graph")
+    h_ptr, k_ptr, u_ptr = (_opt_f(t, name) for name, t, _ in planes)
+    s_ptr = _opt_i(stop, "stop")
+    out, outs = _out_pair(shape, double)
+    r = silt.tensor(silt.float64, silt.shape(1 if dims == 2 else shape[0]), silt.gpu) if residual else None
+    _call("soil_stream_power_n" + ("" if dims == 2 else "_batch"), *outs, None if r is None else r.c_ptr, h_ptr, g_ptr,
+          k_ptr, u_ptr, s_ptr, *shape, e, *tail, dt, n, iters, _abi.stream())
+    return out if r is None else (out, r)
+
+
+def stream_power_n(height, graph, erosivity, edge_, scale, dt, n, uplift=None, stop=None, iters=12, double=False,
+                   residual=False):
+    """soil_stream_power_n: one implicit step of stream-power incision dh/dt = u - K A^m S^n along `graph` with a slope
+    exponent `n` in 1 .. 16: `iters` Newton steps on the whole system, each one solve of stream_power's rounds with the
+    coefficients of the linearisation about the iterate before, started from stream_power's own result (from the old
+    heights the iteration stalls across flats and filled lakes).  `erosivity` is K A^m (soil.erosivity), `uplift` and
+    `stop` as in stream_power.  Returns the new heights, float32 (float64 with `double`), or with `residual` the tuple
+    (heights, residual): a one-element float64 tensor, the largest change of the last iteration — judge convergence by
+    it; under a very large K dt the iteration crosses a flat one cell per step.  n == 1 is stream_power, bit for bit;
+    n < 1 is refused.  `height` is left as it is."""
+    return _stream_power_n("stream_power_n", 2, height, graph, erosivity, edge_, scale, dt, n, uplift, stop, iters,
+                           double, residual)
+
+
+def stream_power_n_batch(height, graph, erosivity, edge_, scale, dt, n, uplift=None, stop=None, iters=12, double=False,
+                         residual=False):
+    """`stream_power_n` of each of the B models of (B, H, W) planes (soil_stream_power_n_batch); `scale` is one pair or
+    B pairs; the residual tensor has B entries."""
+    return _stream_power_n("stream_power_n_batch", 3, height, graph, erosivity, edge_, scale, dt, n, uplift, stop, iters,
+                           double, residual)
+
+
+def stream_power_n_info():
+    """What this thread's last stream_power_n / _batch call did (soil_stream_power_n_info): a dict with the number of
+    kernel `launches`, of `chunks`, the `iters` run (0 for n == 1) and the `scratch_bytes` it asked for."""
+    return _call_info("soil_stream_power_n_info", ("launches", "chunks", "iters", "scratch_bytes"))
 
 
 def downstream_info():
