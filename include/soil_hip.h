@@ -1351,6 +1351,58 @@ int soil_flat_receivers_batch(int32_t* out, const int32_t* in, const float* heig
  * first call; needs no device. */
 int soil_flat_distance_info(int64_t info[4]);
 
+/* Threshold hillslopes: the slope-limited surface of a DEM.  No cell may stand higher above a neighbour than a
+ * critical slope times the distance allows; what stands above that surface is the excess topography, the unstable
+ * mass above a threshold angle.  Not in the reference (its particle model has one explicit creep step per erosion
+ * step, critSlopeBedrock); the definition is this library's.
+ *
+ * Grid (H, W), cell n = x * W + y, `edge` D4 or D8 with the neighbour table above.  The step length L_k toward
+ * neighbour k is the fp64 length soil_flow_paths uses for that kind of edge: sx = (double)scale[0] for a row step
+ * (dx != 0, dy == 0), sy = (double)scale[1] for a column step, sqrt(sx sx + sy sy) for a diagonal one.
+ *
+ * out = the greatest surface w <= height with
+ *        w[n] <= w[k] (+) c_k[n]    for every neighbour k of n in the grid,
+ * where c_k[n] = (float)((double)slope[n] * L_k), one fp64 product rounded once to fp32, and (+) is one fp32 addition,
+ * round to nearest, denormals kept.  slope[n] is `slope_plane[n]` if a plane is given (lithology), the scalar `slope`
+ * otherwise; the slope that binds an edge is the slope of the cell being lowered.  It is the fixed point that
+ *        w[n] <- cand   if cand < w[n],   cand = w[k] (+) c_k[n]
+ * reaches from w = height in any order of updates: the operator is monotone (round to nearest is), it only lowers
+ * values, so every chaotic iteration stays on or above the greatest fixed point below height and ends on a fixed
+ * point, that one; it ends because the floats between the least height and the heights are a finite set and c >= 0
+ * (csrc/slope_limit.hip: 64 x 64 tiles relaxed in LDS, launches repeated until no tile moved;
+ * SOIL_SLOPE_LIMIT_PER_CHECK launches per look at the "changed" word).  The rules that make it one bit pattern:
+ *   - strict <: a tie keeps the bits the cell has (a -0 that is not lowered stays -0);
+ *   - c is never -0: a product that is zero counts as +0, a scalar slope of -0 as 0;
+ *   - a NaN height is a void: never lowered, lowering nobody, NaN in the result; a position off the grid binds nothing;
+ *   - a slope_plane entry that is not >= 0 (NaN, negative) means "no limit at this cell": the cell keeps its height
+ *     and still binds its neighbours; an entry of +inf does the same by arithmetic alone (c = +inf);
+ *   - +-inf heights go through the arithmetic as they are: a -inf cell pulls every cell connected to it by finite
+ *     steps to -inf, a +inf cell comes down to its lowest neighbour plus a step;
+ *   - a slope of 0 levels every connected component to its minimum.
+ * `excess` (may be NULL): height (-) out, one fp32 subtraction, +0 where the cell was not lowered, the height's NaN
+ * on voids.
+ *
+ * Both calls synchronise the stream before they return, as soil_fill_depressions does.  Batch form: model-major
+ * planes, `scales` one pair or B pairs (host), model b's slice bit for bit what the single call gives for it alone (a
+ * model's first cell is addressed in int64).  The models relax side by side under one "changed" word: the launches of
+ * a batch are those of the model that needs most.  The batch is never cut into chunks.  The launches of a call never
+ * exceed tiles * 272 + 2 plus the launches of one look (csrc/slope_limit.hip derives it).
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): null `out` or `height`; a null scale; B, H or W < 1; H * W > INT32_MAX; n_scales not 1 or B; an
+ * invalid `edge`; an output that shares a byte with `height`, `slope_plane` or the other output; a scale that is not
+ * positive and finite; with a NULL slope_plane a `slope` that is negative or not finite (with a plane the scalar is
+ * not read).  Otherwise, without a device: SOIL_ERR_NO_DEVICE. */
+int soil_slope_limit(float* out, float* excess, const float* height, const float* slope_plane, double slope,
+                     int64_t H, int64_t W, const float scale[2], int edge, void* stream);
+int soil_slope_limit_batch(float* out, float* excess, const float* height, const float* slope_plane, double slope,
+                           int64_t B, int64_t H, int64_t W, const float* scales, int64_t n_scales, int edge,
+                           void* stream);
+/* What the calling host thread's last call of soil_slope_limit or soil_slope_limit_batch did: info[0] relaxation
+ * launches, info[1] tiles of a model, info[2] models, info[3] looks at the "changed" word.  All zero before the
+ * first call; needs no device. */
+int soil_slope_limit_info(int64_t info[4]);
+
 /* ---------------------------------------------------------------- stencils */
 
 /* soil::gradient — grad.hpp:11, grad.cu:89-97 (__gradient :22-87), model.cpp:193-195.  out (H,W,2). */

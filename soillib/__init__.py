@@ -28,6 +28,7 @@ from soillib_amd.soil import stream_power_n, stream_power_n_batch, stream_power_
 from soillib_amd.soil import diffuse, diffuse_batch, diffuse_info  # noqa: F401
 from soillib_amd.soil import (flat_distance, flat_distance_batch, flat_distance_info, flat_receivers,  # noqa: F401
                               flat_receivers_batch, resolve_flats, resolve_flats_batch)
+from soillib_amd.soil import slope_limit, slope_limit_batch, slope_limit_info  # noqa: F401
 from soillib_amd.soil import condition, condition_batch, fill_depressions_batch, fill_info  # noqa: F401
 from soillib_amd.io import geotiff, geotiff_meta, mesh, tiff  # noqa: F401  (python/source/io.cpp:20-110)
 from soillib_amd.legacy import (buffer, clamp, data_t, erode, index, map_t, multiply, param_t,  # noqa: F401

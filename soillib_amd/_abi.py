@@ -264,6 +264,10 @@ SIGNATURES = {
     "soil_flat_receivers": (cint, [vp, vp, vp, vp, i64, i64, cint, vp]),
     "soil_flat_receivers_batch": (cint, [vp, vp, vp, vp, i64, i64, i64, cint, vp]),
     "soil_flat_distance_info": (cint, [C.POINTER(i64)]),
+    # threshold hillslopes: out, excess (may be NULL), height, slope_plane (may be NULL), slope; host scale pairs
+    "soil_slope_limit": (cint, [vp, vp, vp, vp, C.c_double, i64, i64, F3, cint, vp]),
+    "soil_slope_limit_batch": (cint, [vp, vp, vp, vp, C.c_double, i64, i64, i64, F3, i64, cint, vp]),
+    "soil_slope_limit_info": (cint, [C.POINTER(i64)]),
     "soil_workspace_release": (cint, []),
     "soil_gradient": (cint, [vp, vp, i64, i64, F3, vp]),
     "soil_negslope": (cint, [vp, vp, i64, i64, F3, vp]),

@@ -74,6 +74,7 @@ enum WorkspaceSlot {
   WS_DEPOSIT_PLANES = 21,  // downstream.hip: soil_stream_power_deposit(_batch): the iterate, q and Qs of a chunk
   WS_POWER_N = 22,       // downstream.hip: soil_stream_power_n(_batch): scale records, records, B, lists
   WS_POWER_N_ITERATE = 23,  // downstream.hip: soil_stream_power_n(_batch): the fp64 iterate of a chunk, 8 bytes a cell
+  WS_SLOPE_LIMIT = 24,   // slope_limit.hip: soil_slope_limit(_batch): scale records, the tiles' marks
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();

@@ -878,8 +878,13 @@ class ErosionBatch:
         ValueError.  Returns the (B, H, W) float32 heights; the batch's own planes are not touched.  A bad argument
         raises ValueError before any device work.  Synchronises the stream (the fill does)."""
         from . import soil
-        who = "ErosionBatch.evolve"
-        self._check_diffuse("evolve", dt, kappa, None, None, None, "fixed", first_axis)
+        carved, scale = self._carved("evolve", dt, K, m, kappa, uplift, kind, edge, T, offset, first_axis, G, iters, n)
+        return soil.diffuse_batch(carved, scale, dt, kappa, border="fixed", first_axis=first_axis)
+
+    def _carved(self, name, dt, K, m, kappa, uplift, kind, edge, T, offset, first_axis, G, iters, n):
+        """The checks of evolve() under the method's `name` and its first half: (the carved surface, the scale(s))."""
+        who = "ErosionBatch.%s" % name
+        self._check_diffuse(name, dt, kappa, None, None, None, "fixed", first_axis)
         n = _check.exponent(who, n)
         if G is not None:
             _check.number(who, "G", G)
@@ -890,14 +895,50 @@ class ErosionBatch:
             _check.count(who, "iters", iters)
         _check.number(who, "K", K)
         _check.number(who, "m", m, lo=None)
-        _, scale = self._routing("evolve", kind, edge, T, offset, uplift)
+        _, scale = self._routing(name, kind, edge, T, offset, uplift)
         if G is None and n != 1.0:
             carved = self.stream_power(dt, K, m, kind, edge, T, offset, uplift, n, iters)
         elif G is None:
             carved = self.stream_power(dt, K, m, kind, edge, T, offset, uplift)
         else:
             carved = self.stream_power_deposit(dt, K, m, G, iters, kind, edge, T, offset, uplift)
-        return soil.diffuse_batch(carved, scale, dt, kappa, border="fixed", first_axis=first_axis)
+        return carved, scale
+
+    def _critical_slope(self, who, slope):
+        """`slope` of slope_limited() and evolve_limited(): a finite number >= 0 or a (B, H, W) float32 tensor."""
+        if isinstance(slope, silt.tensor):
+            return self._flow_tensor(who, "slope", slope, silt.float32)
+        return _check.number("ErosionBatch.%s" % who, "slope", slope)
+
+    def slope_limited(self, slope, edge=None, excess=False):
+        """The slope-limited surface of every model's `height` (soil.slope_limit_batch) with the batch's scale(s), as
+        diffuse() takes them: the greatest surface below the heights on which no cell stands higher above a neighbour
+        than `slope` times the distance allows — a (B, H, W) float32 silt GPU tensor, or with `excess` the tuple
+        (surface, excess), excess = height - surface, the mass above the threshold.  `slope`: a finite number >= 0 or
+        a (B, H, W) float32 tensor (an entry that is NaN or negative: no limit at that cell); `edge` defaults to d8.
+        The batch's own planes are not touched.  A bad argument raises ValueError before any device work.
+        Synchronises the stream."""
+        from . import soil
+        e = self._edge("slope_limited", edge)
+        slope = self._critical_slope("slope_limited", slope)
+        scale = self._path_scale("slope_limited")
+        return soil.slope_limit_batch(self.height, scale, slope, e, excess)
+
+    def evolve_limited(self, dt, K, critical_slope, m=0.5, kappa=None, uplift=None, kind="steepest", edge=None, T=None,
+                       offset=0, first_axis=0, G=None, iters=8, n=1.0):
+        """evolve() with threshold hillslopes: incision, then collapse to the threshold, then diffusion.  The carved
+        surface of evolve()'s first half goes through soil.slope_limit_batch with `critical_slope` (a finite number
+        >= 0 or a (B, H, W) float32 tensor, as in slope_limited()) and the step's `edge` before soil.diffuse_batch
+        relaxes it.  What collapses is removed, not deposited: slope_limited(..., excess=True) on a surface gives
+        the collapsed mass to a caller who wants to route it.  Everything else as in evolve(), whose own calls are
+        what they were."""
+        from . import soil
+        e = self._edge("evolve_limited", edge)
+        critical_slope = self._critical_slope("evolve_limited", critical_slope)
+        carved, scale = self._carved("evolve_limited", dt, K, m, kappa, uplift, kind, edge, T, offset, first_axis, G,
+                                     iters, n)
+        limited = soil.slope_limit_batch(carved, scale, critical_slope, e)
+        return soil.diffuse_batch(limited, scale, dt, kappa, border="fixed", first_axis=first_axis)
 
     def filled(self, edge=None):
         """The depression-filled surface of every model's `height`: a (B, H, W) float32 silt GPU tensor, model b's

@@ -764,6 +764,51 @@ def flat_distance_info():
     return _call_info("soil_flat_distance_info", ("launches", "tiles", "models", "looks"))
 
 
+# ---- threshold hillslopes (soil_hip.h: soil_slope_limit): the greatest surface below a DEM on which no cell stands
+# higher above a neighbour than a critical slope times the distance allows.  Synchronises the stream.
+
+def _slope_limit(who, dims, height, scale, slope, edge_, excess):
+    """soil_slope_limit and soil_slope_limit_batch.  Every check comes before any device work."""
+    shape = _shape(dims, height, "%s: height" % who)
+    _float_plane(height, shape, "%s: height" % who)
+    e = _check.edge(who, d8 if edge_ is None else edge_)
+    pairs, tail = _scales(who, dims, scale, shape[0])
+    _positive(who, pairs, scale)
+    if isinstance(slope, silt.tensor):
+        _float_plane(slope, shape, "%s: slope" % who)
+        s_ptr, s = _f(slope, "slope"), 0.0
+    else:
+        s_ptr, s = None, _check.number(who, "slope", slope)
+    h_ptr = _f(height, "height")
+    out = silt.tensor(silt.float32, silt.shape(*shape), silt.gpu)
+    ex = silt.tensor(silt.float32, silt.shape(*shape), silt.gpu) if excess else None
+    _call("soil_slope_limit" + ("" if dims == 2 else "_batch"), out.c_ptr, None if ex is None else ex.c_ptr, h_ptr,
+          s_ptr, s, *shape, *tail, e, _abi.stream())
+    return (out, ex) if excess else out
+
+
+def slope_limit(height, scale, slope, edge_=None, excess=False):
+    """soil_slope_limit: the slope-limited surface of a (H, W) float32 DEM with the spacings (sx, sy) of `scale` — the
+    greatest surface w <= height with w[n] <= w[k] + slope[n] * L_k for every neighbour k (`edge_`, d8 by default),
+    L_k the length of the step.  `slope`: a finite number >= 0, or a float32 plane of the height's shape (an entry that
+    is NaN or negative: no limit at that cell).  NaN heights are voids.  One definite bit pattern (soil_hip.h states
+    the arithmetic).  Returns the new heights, or with `excess` the tuple (heights, excess), excess = height - heights:
+    what stands above the threshold.  `height` is left as it is; synchronises the stream."""
+    return _slope_limit("slope_limit", 2, height, scale, slope, edge_, excess)
+
+
+def slope_limit_batch(height, scale, slope, edge_=None, excess=False):
+    """`slope_limit` of each of the B models of a (B, H, W) tensor, side by side (soil_slope_limit_batch): launches
+    that do not grow with B.  `scale` is one pair or B pairs; `slope` a number or a (B, H, W) float32 plane."""
+    return _slope_limit("slope_limit_batch", 3, height, scale, slope, edge_, excess)
+
+
+def slope_limit_info():
+    """What this thread's last slope_limit / slope_limit_batch call did (soil_slope_limit_info): a dict with the
+    relaxation `launches`, the `tiles` of a model, the `models` and the `looks` at the "changed" word."""
+    return _call_info("soil_slope_limit_info", ("launches", "tiles", "models", "looks"))
+
+
 # ---- the fill of a batch, and the conditioned drainage graph: fill -> steepest / random_weighted -> resolve_flats
 
 def fill_depressions_batch(height, edge_=None):

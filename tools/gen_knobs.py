@@ -103,6 +103,7 @@ KNOBS = {
     "SOIL_FILL_FLAT": ("graph", "set: fill_depressions without the coarse levels (A/B)"),
     "SOIL_FILL_VERBOSE": ("graph", "set: launches per level on stderr"),
     "SOIL_FLATS_PER_CHECK": ("graph", "relaxation launches of soil_flat_distance(_batch) between two looks at the 'changed' word [3], read per call"),
+    "SOIL_SLOPE_LIMIT_PER_CHECK": ("graph", "relaxation launches of soil_slope_limit(_batch) between two looks at the 'changed' word [3], read per call"),
     # ---- bench.py
     "SOIL_BENCH_ARITH": ("bench", "default of --particle-arith [exact]"),
     "SOIL_BENCH_GRID": ("bench", "default of --grid (strong scaling on a fixed grid) [0]"),
