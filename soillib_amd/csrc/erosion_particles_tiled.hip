@@ -529,7 +529,7 @@ __device__ __forceinline__ bool step_apply(PRec& r, const float4 q, const StepCo
     return g.alive;
   }
   const float ax = q.x + k.fx, ay = q.y + k.fy;                 // :126
-  const float w0 = quot(1.0f, g.rd), w1 = quot0(g.dL, g.rd);    // :127
+  const float w0 = recip_rn(g.rd), w1 = quot0(g.dL, g.rd);      // :127
   r.spx = w0 * r.spx + w1 * ax;
   r.spy = w0 * r.spy + w1 * ay;
   r.a1 = r.a1 * att_exp(-g.ds * k.kd);    // att_m :134

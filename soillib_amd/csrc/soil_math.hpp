@@ -111,22 +111,45 @@ SOIL_HD float powf_(float x, float y) {
 // IEEE quotients that share a denominator (device only).
 //
 // A particle step (erosion_particles_tiled.hip) divides nine (debris: eleven) times,
-// by four (five) different numbers.
-// The compiler expands every fp32 `/` into v_div_scale x2, v_rcp, a Newton step on
-// the reciprocal, three residual corrections of the quotient (the last one being
-// v_div_fmas) and v_div_fixup.  For operands in the plain range below the scale
-// instructions are the identity, v_div_fmas is a plain fma and the fix-up passes the
-// value through (ISA guide, V_DIV_SCALE/V_DIV_FMAS/V_DIV_FIXUP), so what is left is
-//      r = rcp(b); r = fma(fma(-b, r, 1), r, r)
-//      q = a * r;  q = fma(fma(-b, q, a), r, q);  q = fma(fma(-b, q, a), r, q)
-// — the same instructions on the same values, hence the same bits — and r only
-// depends on b.  recip()/quot() spell that sequence out so that r is computed once
-// per denominator.  What "plain" has to guarantee (V_DIV_SCALE): b and 1/b normal,
-// exponent(a) - exponent(b) < 96, a/b normal, exponent(a) > 23 (|a| >= 2^-103).
-// |b| in [2^-40, 2^40] with |a| in [2^-80, 2^50] does; so does any pair whose quotient
-// turns out in [2^-60, 2^90] over such a b.  a == +0 runs through the chain to the
-// correctly signed zero, -0 needs quot0().  Anything else — denormals, infinities,
-// zero or NaN denominators — has to take the written-out `/`.
+// by four (five) different numbers.  recip()/quot() compute the reciprocal once per
+// denominator and each quotient from it in three instructions:
+//      r = rcp(b); r = fma(fma(-b, r, 1), r, r)          recip(): v_rcp_f32 (1 ulp), one Newton step
+//      q = a * r;  q = fma(fma(-b, q, a), r, q)          quot():  one residual correction
+// On the plain range below, q is the correctly rounded quotient RN(a / b), which is what
+// the compiler's `/` gives as well — so the two agree to the bit.  (hipcc's own expansion
+// of `/` is this sequence between v_div_scale and v_div_fixup with a SECOND residual
+// correction; until the one-correction form was proved, quot() copied it.)
+//
+// Why the second correction does nothing.  Let q1 be the value above and suppose it is
+// RN(a / b).  Then e1 = a - b q1 is exact in fp32; a / b lies no closer than 2^-25 ulp to a
+// rounding midpoint (a - b mid is a non-zero multiple of 2^-47 for 24-bit operands in
+// [1, 2)); so |e1 r| <= (1/2 - 2^-25)(1 + 2^-24) ulp < 1/2 ulp and fma(e1, r, q1) rounds
+// back to q1.  That q1 always IS RN(a / b) with this device's v_rcp_f32 is established by
+// exhaustion, not by argument: tools/microbench/quot_exhaust.hip compares quot0(a, recip(b)),
+// the former two-correction sequence and `a / b` bit for bit on the device for every pair
+// of mantissas (2^23 x 2^23, both operands in [1, 2)) and at the corners of the exponent
+// range named below; its output is profiles/quot_one_correction/exhaust.txt, and
+// tests/test_gpu_quot_one_correction.py keeps a slice of it in the suite.  All three
+// operations are scale-invariant in the exponents as long as no intermediate leaves the
+// normal range or, for the residual, stops being exact — which is what "plain" has to
+// guarantee:
+//   * b and r ~ 1/b normal: |b| in [2^-40, 2^40] (the particle step's directions: down
+//     to 2^-60, numerators <= 1); 1 - b r is O(2^-23), never near the exponent limits;
+//   * q = a r and a / b normal and finite: |a| in [2^-80, 2^50] over such a b, or any pair
+//     whose quotient turns out in [2^-60, 2^90];
+//   * the residual a - b q exact.  With b = Mb 2^(eb-23), q = Mq 2^(eq-23) it is a multiple
+//     of u = 2^(eb+eq-46) >= 2^(ea-47) of fewer than 2^24 units (q is within an ulp of
+//     a / b), so one fp32 number as long as u >= 2^-149, the smallest denormal: ea >= -102.
+//     The smallest plain numerator is 2^-100 (a quotient of 2^-60 over 2^-40), its u
+//     2^-147; from |a| >= 2^-79 the residual is a normal number or zero.  (The library is
+//     built with fp32 denormals on — tests/test_gpu_parity.py::test_denormals_are_not_flushed —
+//     and an fma takes a denormal operand at full precision.)  The product e r inside the
+//     last fma is not rounded on its own; its size is that of an ulp of q.
+//   * nothing overflows: |b q| is within an ulp of |a| and |e r| about an ulp of q, both
+//     finite whenever a and q are; |r| <= 2^60.
+// a == +0 runs through the chain to the correctly signed zero, -0 needs quot0().
+// Anything else — denormals, infinities, zero or NaN denominators — has to take the
+// written-out `/` (v_div_scale / v_div_fixup serve those).
 struct Recip { float b, r; };
 __device__ __forceinline__ Recip recip(float b) {
   float r = __builtin_amdgcn_rcpf(b);
@@ -134,12 +157,16 @@ __device__ __forceinline__ Recip recip(float b) {
   return {b, r};
 }
 __device__ __forceinline__ float quot(float a, const Recip d) {
-  float q = a * d.r;
-  q = __builtin_fmaf(__builtin_fmaf(-d.b, q, a), d.r, q);
+  const float q = a * d.r;
   return __builtin_fmaf(__builtin_fmaf(-d.b, q, a), d.r, q);
 }
+// 1 / b = quot(1, d): with q = 1 * r = r the correction is one more Newton step on the
+// refined reciprocal.  Written out so that no product with 1 is left to the compiler.
+__device__ __forceinline__ float recip_rn(const Recip d) {
+  return __builtin_fmaf(__builtin_fmaf(-d.b, d.r, 1.0f), d.r, d.r);
+}
 // A zero numerator of either sign: the first product already is the IEEE answer (zero,
-// sign of a times sign of b); the corrections after it would turn -0 into +0.
+// sign of a times sign of b); the correction after it would turn -0 into +0.
 __device__ __forceinline__ float quot0(float a, const Recip d) {
   const float q0 = a * d.r, q = quot(a, d);
   return (a == 0.0f) ? q0 : q;
@@ -215,19 +242,20 @@ __device__ __forceinline__ int floor_cell(float f) {
 }
 __device__ __forceinline__ int nan_cell(float f, int cell) { return (f != f) ? 0 : cell; }
 
-// Correctly rounded square root for x >= 2^-96 (and +0, +inf, NaN): the compiler's own expansion of
-// sqrtf — v_sqrt_f32 (1 ulp), then the neighbours one ulp down and up are tried against the exact
-// residual x - y'*y — without its pre-scaling of arguments below 2^-96 and without the class test that
-// hands zero and infinity through (the residual tests leave those alone by themselves: they compare
-// false on NaN).  Below 2^-96 the result is merely close; the particle step only asks whether it is
-// under eps = 1e-12 there.
+// Correctly rounded square root for x >= 2^-96 (and +0, +inf, NaN) in seven instructions: y = x rsq(x)
+// (v_rsq_f32, 1 ulp) and one correction by the exact residual x - y*y times rsq(x) / 2.  That this is sqrtf
+// to the bit on every such x holds for this device's v_rsq_f32 and by exhaustion only — all 2^32 bit
+// patterns, tools/microbench/quot_exhaust.hip sqrt (profiles/quot_one_correction/exhaust.txt), and
+// tests/test_gpu_quot_one_correction.py on every mantissa at the ends of the range; with a correctly
+// rounded rsq or its neighbours the same sequence misses a few mantissas.  (Until then this was the
+// compiler's expansion of sqrtf without its scaling: v_sqrt_f32 and the neighbours one ulp down and up
+// tried against the residual, nine instructions.)  Zeros, denormals and +inf, whose rsq is infinite or
+// zero, are handed through as they are.  Below 2^-96 the result is merely close, a denormal comes back
+// unchanged; the particle step only asks whether it is under eps = 1e-12 there, and it is.
 __device__ __forceinline__ float sqrt_rn(float x) {
-  const float y = __builtin_amdgcn_sqrtf(x);
-  const float dn = bits2f(f2bits(y) - 1u), up = bits2f(f2bits(y) + 1u);
-  const float r_dn = __builtin_fmaf(-dn, y, x), r_up = __builtin_fmaf(-up, y, x);
-  float s = (r_dn <= 0.0f) ? dn : y;
-  s = (r_up > 0.0f) ? up : s;
-  return s;
+  const float r = __builtin_amdgcn_rsqf(x), y = x * r, h = 0.5f * r;
+  const float s = __builtin_fmaf(__builtin_fmaf(-y, y, x), h, y);
+  return __builtin_amdgcn_classf(x, 0x200 | 0x80 | 0x40 | 0x20 | 0x10) ? x : s;  // +inf, +-denormal, +-0
 }
 
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as
