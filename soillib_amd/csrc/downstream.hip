@@ -73,6 +73,9 @@ struct DownPlanes {
   const int32_t* stop;
   const float *p0, *p1, *p2;
   double dt;
+  DownPlanes at(int64_t off) const {  // the planes from cell `off` on: a chunk's
+    return {graph + off, soil::at(stop, off), soil::at(p0, off), soil::at(p1, off), soil::at(p2, off), dt};
+  }
 };
 
 // The record of one cell, and its B.  Each operation is rounded once, as soil_hip.h writes them down.
@@ -215,24 +218,9 @@ struct DownOut {
 // One round of a chunk (flow_paths.hpp ptr_chunk), dense or listed, on 32- or 64-bit offsets by the chunk
 template <bool HASB>
 static void down_launch_round(const PtrChunk& c, const PtrRound& q, hipStream_t st) {
-  uint4* const ro = c.rec[(q.r + 1) & 1];
-  const uint4* const ri = c.rec[q.r & 1];
-  double* const bo = static_cast<double*>(c.extra[(q.r + 1) & 1]);
-  const double* const bi = static_cast<const double*>(c.extra[q.r & 1]);
-  if (q.list_in) {
-    if (c.idx32)
-      k_down_list<uint32_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
-                                                                q.fill_out, c.seg);
-    else
-      k_down_list<int64_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, q.list_in, q.fill_in, q.list_out,
-                                                               q.fill_out, c.seg);
-  } else if (c.idx32) {
-    k_down_round<uint32_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
-                                                               q.fill_out, c.seg);
-  } else {
-    k_down_round<int64_t, HASB><<<c.groups, kPBlock, 0, st>>>(ro, ri, bo, bi, c.elem, c.flags, q.r, q.list_out,
-                                                              q.fill_out, c.seg);
-  }
+  ptr_launch_round(c, q, st, k_down_list<uint32_t, HASB>, k_down_list<int64_t, HASB>, k_down_round<uint32_t, HASB>,
+                   k_down_round<int64_t, HASB>, static_cast<double*>(c.extra[(q.r + 1) & 1]),
+                   static_cast<const double*>(c.extra[q.r & 1]));
 }
 
 // One chunk of `models` models (flow_paths.hpp ptr_chunk) with this file's launches; HASB: the chunk's extra planes
@@ -241,13 +229,9 @@ template <int K, int MODE, bool HASB>
 static int down_chunk(DownOut o, const DownPlanes& in, int64_t models, int64_t H, int64_t W, const PathScales& scales,
                       char* scratch, hipStream_t st) {
   auto init = [&](const PtrChunk& c) {
-    const bool vec = ptr_vec_init(W, reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.stop) |
-                                         reinterpret_cast<uintptr_t>(in.p0) | reinterpret_cast<uintptr_t>(in.p1) |
-                                         reinterpret_cast<uintptr_t>(in.p2));
-    const dim3 grid = ptr_init_grid(c, H, W, vec);
-    double* const b0 = static_cast<double*>(c.extra[0]);
-    if (vec) k_down_init<K, true, MODE, HASB><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, H, W, scales, c.flags);
-    else k_down_init<K, false, MODE, HASB><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, H, W, scales, c.flags);
+    const bool vec = ptr_vec_init(W, in.graph, in.stop, in.p0, in.p1, in.p2);
+    launch_vec(vec, k_down_init<K, true, MODE, HASB>, k_down_init<K, false, MODE, HASB>, ptr_init_grid(c, H, W, vec),
+               st, c.rec[0], static_cast<double*>(c.extra[0]), in, H, W, scales, c.flags);
     return vec;
   };
   auto round = [&](const PtrChunk& c, const PtrRound& q) { down_launch_round<HASB>(c, q, st); };
@@ -276,9 +260,13 @@ static int check_downstream(const char* what, int mode, const void* out, const v
   return check_outputs_apart(w, out, out64, plane_cells(B, H * W), {in.graph, in.stop, in.p0, in.p1, in.p2});
 }
 
-// A call through workspace slot WS_DOWNSTREAM (flow_paths.hpp ptr_run); without a scale L == 1
-static int downstream_run(int mode, DownOut o, const DownPlanes& in, int64_t B, int64_t H, int64_t W, int edge,
-                          const float* scales, int64_t n_scales, hipStream_t st) {
+// A call under the entry's name, through workspace slot WS_DOWNSTREAM (flow_paths.hpp ptr_run); without a scale L == 1
+static int downstream_run(const char* what, int mode, DownOut o, const DownPlanes& in, int64_t B, int64_t H, int64_t W,
+                          int edge, const float* scales, int64_t n_scales, void* stream) {
+  if (int rc = check_downstream(what, mode, o.out, o.out64, in, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
+    return rc;
+  SOIL_DEVICE();
+  const hipStream_t st = as_stream(stream);
   const bool has_b = mode == kPower || in.p1 != nullptr;
   const bool d4 = edge == SOIL_D4;
   auto go = mode == kPower ? (d4 ? down_chunk<4, kPower, true> : down_chunk<8, kPower, true>)
@@ -286,15 +274,8 @@ static int downstream_run(int mode, DownOut o, const DownPlanes& in, int64_t B, 
                            : (d4 ? down_chunk<4, kSum, false> : down_chunk<8, kSum, false>);
   return ptr_run(WS_DOWNSTREAM, t_down_info, B, H, W, has_b ? sizeof(double) : 0, scales, n_scales,
                  PathScale{1.0, 1.0, 1.0}, st, [&](int64_t b0, int64_t nb, const PathScales& s, char* scratch) {
-                   const int64_t at = b0 * H * W;
-                   const DownPlanes part{in.graph + at,
-                                         in.stop ? in.stop + at : nullptr,
-                                         in.p0 ? in.p0 + at : nullptr,
-                                         in.p1 ? in.p1 + at : nullptr,
-                                         in.p2 ? in.p2 + at : nullptr,
-                                         in.dt};
-                   return go(DownOut{o.out ? o.out + at : nullptr, o.out64 ? o.out64 + at : nullptr}, part, nb, H, W,
-                             s, scratch, st);
+                   const int64_t off = b0 * H * W;
+                   return go(DownOut{at(o.out, off), at(o.out64, off)}, in.at(off), nb, H, W, s, scratch, st);
                  });
 }
 
@@ -311,6 +292,9 @@ struct DepPlanes {
   const int32_t* graph;
   const float *height, *erosivity, *uplift, *deposition;
   double dt;
+  DepPlanes at(int64_t off) const {
+    return {graph + off, height + off, erosivity + off, soil::at(uplift, off), deposition + off, dt};
+  }
 };
 // A chunk's planes between the iterations (workspace slot WS_DEPOSIT_PLANES): the iterate, q and Qs
 struct DepWork {
@@ -468,11 +452,15 @@ __global__ void __launch_bounds__(kPBlock)
   }
 }
 
-struct DepOut {
+// The outputs of an iterated step, each may be null; `flux` is the deposit step's alone
+struct StepOut {
   float* out;
   double* out64;
   float* flux;
-  double* residual;
+  double* residual;  // a word a model
+  StepOut at(int64_t off, int64_t b0) const {
+    return {soil::at(out, off), soil::at(out64, off), soil::at(flux, off), soil::at(residual, b0)};
+  }
 };
 // soil_stream_power_deposit_info: launches, chunks, iterations, bytes of scratch
 struct DepInfo {
@@ -480,33 +468,48 @@ struct DepInfo {
 };
 static thread_local DepInfo t_dep_info{0, 0, 0, 0};
 
+// One solve of an iterated step over a chunk (flow_paths.hpp ptr_chunk): `init` makes the records and B from the
+// iterate before, the rounds are the recurrence's with B, and k_dep_final leaves the new iterate in `x`.  `o`: the
+// outputs on the step's last pass, nothing before it.  Adds what it launched to `launches`.
+template <typename Init>
+static int solve_pass(int64_t& launches, int64_t models, int64_t H, int64_t W, char* scratch, hipStream_t st, Init init,
+                      double* x, const StepOut& o) {
+  PtrInfo pinfo{0, 0, 0, 0};
+  auto round = [&](const PtrChunk& c, const PtrRound& q) { down_launch_round<true>(c, q, st); };
+  auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
+    k_dep_final<<<grid, kPBlock, 0, st>>>(o.out, o.out64, x, reinterpret_cast<unsigned long long*>(o.residual), rec,
+                                          H * W);
+  };
+  if (int rc = ptr_chunk(pinfo, models, H, W, sizeof(double), scratch, init, round, fin); rc != SOIL_OK) return rc;
+  launches += 2 + pinfo.rounds;
+  return SOIL_OK;
+}
+
 template <int K>
 static void dep_launch_q(const DepWork& w, const DepPlanes& in, int64_t models, int64_t H, int64_t W, bool first,
                          hipStream_t st) {
-  const bool vec = ptr_vec_init(W, reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.height) |
-                                       reinterpret_cast<uintptr_t>(in.uplift) | reinterpret_cast<uintptr_t>(w.x) |
-                                       reinterpret_cast<uintptr_t>(w.q) | reinterpret_cast<uintptr_t>(w.qs));
+  const bool vec = ptr_vec_init(W, in.graph, in.height, in.uplift, w.x, w.q, w.qs);
   dim3 grid = grid_rows(H, vec ? W / 4 : W, kPBlock);
   grid.z = static_cast<unsigned>(models);
-  if (vec) {
-    if (first) k_dep_q<K, true, true><<<grid, kPBlock, 0, st>>>(w, in, H, W);
-    else k_dep_q<K, true, false><<<grid, kPBlock, 0, st>>>(w, in, H, W);
-  } else {
-    if (first) k_dep_q<K, false, true><<<grid, kPBlock, 0, st>>>(w, in, H, W);
-    else k_dep_q<K, false, false><<<grid, kPBlock, 0, st>>>(w, in, H, W);
-  }
+  if (first) launch_vec(vec, k_dep_q<K, true, true>, k_dep_q<K, false, true>, grid, st, w, in, H, W);
+  else launch_vec(vec, k_dep_q<K, true, false>, k_dep_q<K, false, false>, grid, st, w, in, H, W);
   t_dep_info.launches += 1;
 }
 
-// One chunk of `models` models: x^0, then `iters` times q, Qs, and init / rounds / final through ptr_chunk with this
-// mode's launches, then the flux of the returned iterate.  `in`, `o` and `w` are the chunk's own.
+// One chunk of `models` models: x^0, then `iters` times q, Qs and a solve pass from them, then the flux of the
+// returned iterate.  `in`, `o` and `w` are the chunk's own.
 template <int K>
-static int dep_chunk(DepOut o, const DepPlanes& in, const DepWork& w, int iters, int64_t models, int64_t H, int64_t W,
+static int dep_chunk(StepOut o, const DepPlanes& in, const DepWork& w, int iters, int64_t models, int64_t H, int64_t W,
                      int edge, const PathScales& scales, char* scratch, RakeStats& rake, hipStream_t st) {
-  PtrInfo pinfo{0, 0, 0, 0};
   t_dep_info.chunks += 1;
   dep_launch_q<K>(w, in, models, H, W, true, st);
   SOIL_LAUNCH_CHECK();
+  auto init = [&](const PtrChunk& c) {
+    const bool vec = ptr_vec_init(W, in.graph, in.height, in.erosivity, in.uplift, in.deposition, w.qs, w.q);
+    launch_vec(vec, k_dep_init<K, true>, k_dep_init<K, false>, ptr_init_grid(c, H, W, vec), st, c.rec[0],
+               static_cast<double*>(c.extra[0]), in, w.qs, w.q, H, W, scales, c.flags);
+    return vec;
+  };
   for (int k = 1; k <= iters; ++k) {
     if (k > 1) {
       dep_launch_q<K>(w, in, models, H, W, false, st);
@@ -514,27 +517,9 @@ static int dep_chunk(DepOut o, const DepPlanes& in, const DepWork& w, int iters,
       if (int rc = rake_accumulate(w.qs, in.graph, w.q, models, H, W, edge, st, WS_DEPOSIT_RAKE, &rake); rc != SOIL_OK)
         return rc;
     }
-    const bool last = k == iters;
-    auto init = [&](const PtrChunk& c) {
-      const bool vec =
-          ptr_vec_init(W, reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.height) |
-                              reinterpret_cast<uintptr_t>(in.erosivity) | reinterpret_cast<uintptr_t>(in.uplift) |
-                              reinterpret_cast<uintptr_t>(in.deposition) | reinterpret_cast<uintptr_t>(w.qs) |
-                              reinterpret_cast<uintptr_t>(w.q));
-      const dim3 grid = ptr_init_grid(c, H, W, vec);
-      double* const b0 = static_cast<double*>(c.extra[0]);
-      if (vec) k_dep_init<K, true><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, w.qs, w.q, H, W, scales, c.flags);
-      else k_dep_init<K, false><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, in, w.qs, w.q, H, W, scales, c.flags);
-      return vec;
-    };
-    auto round = [&](const PtrChunk& c, const PtrRound& q) { down_launch_round<true>(c, q, st); };
-    auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
-      k_dep_final<<<grid, kPBlock, 0, st>>>(last ? o.out : nullptr, last ? o.out64 : nullptr, w.x,
-                                            last ? reinterpret_cast<unsigned long long*>(o.residual) : nullptr, rec,
-                                            H * W);
-    };
-    if (int rc = ptr_chunk(pinfo, models, H, W, sizeof(double), scratch, init, round, fin); rc != SOIL_OK) return rc;
-    t_dep_info.launches += 2 + pinfo.rounds;
+    if (int rc = solve_pass(t_dep_info.launches, models, H, W, scratch, st, init, w.x, k == iters ? o : StepOut{});
+        rc != SOIL_OK)
+      return rc;
   }
   if (o.flux) {
     dep_launch_q<K>(w, in, models, H, W, false, st);
@@ -545,8 +530,21 @@ static int dep_chunk(DepOut o, const DepPlanes& in, const DepWork& w, int iters,
   return SOIL_OK;
 }
 
+// Neither the flux (4 bytes a cell) nor the residual (8 bytes a model) shares a byte with one of `planes` (4 bytes a
+// cell), with out64 or with the other; `msg` names the two an entry has
+static int check_side_outputs_apart(const std::string& msg, const StepOut& o, int64_t B, size_t cells,
+                                    std::initializer_list<const void*> planes) {
+  const size_t b_res = 8 * static_cast<size_t>(B);
+  for (const void* p : planes)
+    SOIL_REQUIRE(!overlaps(o.flux, 4 * cells, p, 4 * cells) && !overlaps(o.residual, b_res, p, 4 * cells), msg);
+  SOIL_REQUIRE(!overlaps(o.flux, 4 * cells, o.out64, 8 * cells) && !overlaps(o.residual, b_res, o.out64, 8 * cells) &&
+                   !overlaps(o.flux, 4 * cells, o.residual, b_res),
+               msg);
+  return SOIL_OK;
+}
+
 // What the two deposit entries refuse before any device work: soil_stream_power's refusals and their own
-static int check_deposit(const char* what, const DepOut& o, const DepPlanes& in, int iters, const float* scales,
+static int check_deposit(const char* what, const StepOut& o, const DepPlanes& in, int iters, const float* scales,
                          int64_t B, int64_t H, int64_t W, int edge, int64_t n_scales) {
   const std::string w(what);
   const DownPlanes power{in.graph, nullptr, in.height, in.erosivity, in.uplift, in.dt};
@@ -557,46 +555,54 @@ static int check_deposit(const char* what, const DepOut& o, const DepPlanes& in,
   const size_t cells = plane_cells(B, H * W);
   // (out and out64 are apart: check_downstream saw to it)
   if (int rc = check_outputs_apart(w, o.out, o.out64, cells, {in.deposition}); rc != SOIL_OK) return rc;
-  const void* const planes[] = {in.graph, in.height, in.erosivity, in.uplift, in.deposition, o.out};
-  for (const void* p : planes)
-    SOIL_REQUIRE(!overlaps(o.flux, 4 * cells, p, 4 * cells) && !overlaps(o.residual, 8 * static_cast<size_t>(B), p, 4 * cells),
-                 w + ": flux or residual aliases another plane");
-  SOIL_REQUIRE(!overlaps(o.flux, 4 * cells, o.out64, 8 * cells) &&
-                   !overlaps(o.residual, 8 * static_cast<size_t>(B), o.out64, 8 * cells) &&
-                   !overlaps(o.flux, 4 * cells, o.residual, 8 * static_cast<size_t>(B)),
-               w + ": flux or residual aliases another plane");
+  return check_side_outputs_apart(w + ": flux or residual aliases another plane", o, B, cells,
+                                  {in.graph, in.height, in.erosivity, in.uplift, in.deposition, o.out});
+}
+
+// What the two iterated drivers set up before ptr_run: the planes a chunk keeps between its passes (`side`: the bytes
+// a cell of each, 0 for none; sized for the call's first chunk, each padded to 256 bytes) in workspace `slot`, the
+// residual cleared in stream order, and the bytes of scratch of the call, those planes and ptr_run's block
+struct IterSetup {
+  char* plane[3];
+  int64_t bytes;
+};
+static int iter_setup(IterSetup& s, WorkspaceSlot slot, const size_t (&side)[3], double* residual, int64_t B, int64_t H,
+                      int64_t W, const float* scales, int64_t n_scales, hipStream_t st) {
+  const PtrBlock blk = ptr_block(B, H * W, sizeof(double), scales, n_scales);
+  size_t total = 0, off[3];
+  for (int i = 0; i < 3; ++i) off[i] = total, total += align256(side[i] * static_cast<size_t>(blk.cells));
+  void* base = nullptr;
+  if (total)
+    if (int rc = workspace_get(slot, total, &base); rc != SOIL_OK) return rc;
+  for (int i = 0; i < 3; ++i) s.plane[i] = static_cast<char*>(base) + off[i];
+  if (residual) SOIL_HIP(hipMemsetAsync(residual, 0, sizeof(double) * static_cast<size_t>(B), st));
+  s.bytes = static_cast<int64_t>(total + blk.b_scales + blk.b_chunk);
   return SOIL_OK;
 }
 
-// A call: the chunks of ptr_run through slot WS_DEPOSIT, the chunk's planes in WS_DEPOSIT_PLANES beside them
-static int deposit_run(DepOut o, const DepPlanes& in, int iters, int64_t B, int64_t H, int64_t W, int edge,
-                       const float* scales, int64_t n_scales, hipStream_t st) {
-  const int64_t hw = H * W, per = ptr_chunk_models(hw), first_chunk = B < per ? B : per;
-  const size_t b_x = align256(sizeof(double) * static_cast<size_t>(first_chunk * hw));
-  const size_t b_q = align256(sizeof(float) * static_cast<size_t>(first_chunk * hw));
+// A call, under the entry's name: the chunks of ptr_run through slot WS_DEPOSIT, the chunk's planes in
+// WS_DEPOSIT_PLANES beside them
+static int deposit_run(const char* what, StepOut o, const DepPlanes& in, int iters, int64_t B, int64_t H, int64_t W,
+                       int edge, const float* scales, int64_t n_scales, void* stream) {
+  if (int rc = check_deposit(what, o, in, iters, scales, B, H, W, edge, n_scales); rc != SOIL_OK) return rc;
+  SOIL_DEVICE();
+  const hipStream_t st = as_stream(stream);
   t_dep_info = DepInfo{0, 0, iters, 0};
-  void* planes = nullptr;
-  if (int rc = workspace_get(WS_DEPOSIT_PLANES, b_x + 2 * b_q, &planes); rc != SOIL_OK) return rc;
-  char* const p = static_cast<char*>(planes);
-  const DepWork w{reinterpret_cast<double*>(p), reinterpret_cast<float*>(p + b_x), reinterpret_cast<float*>(p + b_x + b_q)};
-  if (o.residual) SOIL_HIP(hipMemsetAsync(o.residual, 0, sizeof(double) * static_cast<size_t>(B), st));
+  IterSetup s;
+  if (int rc = iter_setup(s, WS_DEPOSIT_PLANES, {8, 4, 4}, o.residual, B, H, W, scales, n_scales, st); rc != SOIL_OK)
+    return rc;
+  const DepWork w{reinterpret_cast<double*>(s.plane[0]), reinterpret_cast<float*>(s.plane[1]),
+                  reinterpret_cast<float*>(s.plane[2])};
   RakeStats rake{0, 0};
   PtrInfo pinfo{0, 0, 0, 0};
   auto go = edge == SOIL_D4 ? dep_chunk<4> : dep_chunk<8>;
-  const int rc =
-      ptr_run(WS_DEPOSIT, pinfo, B, H, W, sizeof(double), scales, n_scales, PathScale{1.0, 1.0, 1.0}, st,
-              [&](int64_t b0, int64_t nb, const PathScales& s, char* scratch) {
-                const int64_t at = b0 * hw;
-                const DepPlanes part{in.graph + at,      in.height + at, in.erosivity + at, in.uplift ? in.uplift + at : nullptr,
-                                     in.deposition + at, in.dt};
-                const DepOut part_o{o.out ? o.out + at : nullptr, o.out64 ? o.out64 + at : nullptr,
-                                    o.flux ? o.flux + at : nullptr, o.residual ? o.residual + b0 : nullptr};
-                return go(part_o, part, w, iters, nb, H, W, edge, s, scratch, rake, st);
-              });
-  const size_t b_scales = scales && n_scales > 1 ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0;
+  const int rc = ptr_run(WS_DEPOSIT, pinfo, B, H, W, sizeof(double), scales, n_scales, PathScale{1.0, 1.0, 1.0}, st,
+                         [&](int64_t b0, int64_t nb, const PathScales& sc, char* scratch) {
+                           const int64_t off = b0 * H * W;
+                           return go(o.at(off, b0), in.at(off), w, iters, nb, H, W, edge, sc, scratch, rake, st);
+                         });
   t_dep_info.launches += rake.launches;
-  t_dep_info.bytes = static_cast<int64_t>(b_x + 2 * b_q + b_scales + ptr_layout(first_chunk * hw, sizeof(double)).bytes()) +
-                     rake.bytes;
+  t_dep_info.bytes = s.bytes + rake.bytes;
   return rc;
 }
 
@@ -613,6 +619,9 @@ struct PnPlanes {
   const int32_t* stop;
   const float *height, *erosivity, *uplift;
   double dt, n, n1;  // n1 = n - 1, made once on the host
+  PnPlanes at(int64_t off) const {
+    return {graph + off, soil::at(stop, off), height + off, erosivity + off, soil::at(uplift, off), dt, n, n1};
+  }
 };
 
 // The record of one cell of the Newton mode, and its B: soil_hip.h's operations in its order, each rounded once.
@@ -690,59 +699,50 @@ __global__ void __launch_bounds__(kPBlock)
   }
 }
 
-struct PnOut {
-  float* out;
-  double* out64;
-  double* residual;
-};
 static thread_local DepInfo t_pn_info{0, 0, 0, 0};  // soil_stream_power_n_info
 
-// One chunk of `models` models: the start (soil_stream_power's init), then `iters` times k_pn_init, each with the
-// rounds and a final pass through ptr_chunk.  iters == 0 (n == 1): the start alone, with soil_stream_power's final.
-// `in`, `o` and `x` are the chunk's own.
+// One chunk of `models` models: the start (soil_stream_power's init), then `iters` times k_pn_init, each a solve
+// pass.  iters == 0 (n == 1): the start alone, with soil_stream_power's final.  `in`, `o` and `x` are the chunk's own.
 template <int K>
-static int pn_chunk(PnOut o, const PnPlanes& in, double* x, int iters, int64_t models, int64_t H, int64_t W,
+static int pn_chunk(StepOut o, const PnPlanes& in, double* x, int iters, int64_t models, int64_t H, int64_t W,
                     const PathScales& scales, char* scratch, hipStream_t st) {
-  PtrInfo pinfo{0, 0, 0, 0};
   t_pn_info.chunks += 1;
   const DownPlanes power{in.graph, in.stop, in.height, in.erosivity, in.uplift, in.dt};
-  const bool vec = ptr_vec_init(W, reinterpret_cast<uintptr_t>(in.graph) | reinterpret_cast<uintptr_t>(in.stop) |
-                                       reinterpret_cast<uintptr_t>(in.height) |
-                                       reinterpret_cast<uintptr_t>(in.erosivity) |
-                                       reinterpret_cast<uintptr_t>(in.uplift) | reinterpret_cast<uintptr_t>(x));
-  for (int j = 0; j <= iters; ++j) {
-    const bool last = j == iters;
-    auto init = [&](const PtrChunk& c) {
-      const dim3 grid = ptr_init_grid(c, H, W, vec);
-      double* const b0 = static_cast<double*>(c.extra[0]);
-      if (j == 0) {
-        if (vec) k_down_init<K, true, kPower, true><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, power, H, W, scales, c.flags);
-        else k_down_init<K, false, kPower, true><<<grid, kPBlock, 0, st>>>(c.rec[0], b0, power, H, W, scales, c.flags);
-      } else {
-        const int64_t bands = (H + kPnBand - 1) / kPnBand;
-        const dim3 pn_grid(grid.x, static_cast<unsigned>(bands < 65535 ? bands : 65535), grid.z);
-        if (vec) k_pn_init<K, true><<<pn_grid, kPBlock, 0, st>>>(c.rec[0], b0, in, x, H, W, scales, c.flags);
-        else k_pn_init<K, false><<<pn_grid, kPBlock, 0, st>>>(c.rec[0], b0, in, x, H, W, scales, c.flags);
-      }
-      return vec;
-    };
+  const bool vec = ptr_vec_init(W, in.graph, in.stop, in.height, in.erosivity, in.uplift, x);
+  auto start = [&](const PtrChunk& c) {
+    launch_vec(vec, k_down_init<K, true, kPower, true>, k_down_init<K, false, kPower, true>,
+               ptr_init_grid(c, H, W, vec), st, c.rec[0], static_cast<double*>(c.extra[0]), power, H, W, scales,
+               c.flags);
+    return vec;
+  };
+  auto init = [&](const PtrChunk& c) {
+    const dim3 grid = ptr_init_grid(c, H, W, vec);
+    const int64_t bands = (H + kPnBand - 1) / kPnBand;
+    launch_vec(vec, k_pn_init<K, true>, k_pn_init<K, false>,
+               dim3(grid.x, static_cast<unsigned>(bands < 65535 ? bands : 65535), grid.z), st, c.rec[0],
+               static_cast<double*>(c.extra[0]), in, x, H, W, scales, c.flags);
+    return vec;
+  };
+  if (iters == 0) {
+    PtrInfo pinfo{0, 0, 0, 0};
     auto round = [&](const PtrChunk& c, const PtrRound& q) { down_launch_round<true>(c, q, st); };
     auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
-      if (iters == 0)
-        k_down_final<<<grid, kPBlock, 0, st>>>(o.out, o.out64, rec, H * W);
-      else
-        k_dep_final<<<grid, kPBlock, 0, st>>>(last ? o.out : nullptr, last ? o.out64 : nullptr, x,
-                                              last ? reinterpret_cast<unsigned long long*>(o.residual) : nullptr, rec,
-                                              H * W);
+      k_down_final<<<grid, kPBlock, 0, st>>>(o.out, o.out64, rec, H * W);
     };
-    if (int rc = ptr_chunk(pinfo, models, H, W, sizeof(double), scratch, init, round, fin); rc != SOIL_OK) return rc;
+    if (int rc = ptr_chunk(pinfo, models, H, W, sizeof(double), scratch, start, round, fin); rc != SOIL_OK) return rc;
     t_pn_info.launches += 2 + pinfo.rounds;
+    return SOIL_OK;
   }
+  if (int rc = solve_pass(t_pn_info.launches, models, H, W, scratch, st, start, x, StepOut{}); rc != SOIL_OK) return rc;
+  for (int j = 1; j <= iters; ++j)
+    if (int rc = solve_pass(t_pn_info.launches, models, H, W, scratch, st, init, x, j == iters ? o : StepOut{});
+        rc != SOIL_OK)
+      return rc;
   return SOIL_OK;
 }
 
 // What the two entries refuse before any device work: soil_stream_power's refusals and their own
-static int check_power_n(const char* what, const PnOut& o, const PnPlanes& in, int iters, const float* scales,
+static int check_power_n(const char* what, const StepOut& o, const PnPlanes& in, int iters, const float* scales,
                          int64_t B, int64_t H, int64_t W, int edge, int64_t n_scales) {
   const std::string w(what);
   const DownPlanes power{in.graph, in.stop, in.height, in.erosivity, in.uplift, in.dt};
@@ -752,39 +752,33 @@ static int check_power_n(const char* what, const PnOut& o, const PnPlanes& in, i
                w + ": n must be a finite slope exponent in 1 .. 16 (n < 1 makes the per-cell equation concave: it needs "
                    "a safeguarded solve per cell, which no affine map expresses)");
   SOIL_REQUIRE(iters >= 1, w + ": iters must be >= 1");
-  const size_t cells = plane_cells(B, H * W), b_res = 8 * static_cast<size_t>(B);
-  const void* const planes[] = {in.graph, in.stop, in.height, in.erosivity, in.uplift, o.out};
-  for (const void* p : planes)
-    SOIL_REQUIRE(!overlaps(o.residual, b_res, p, 4 * cells), w + ": residual aliases another plane");
-  SOIL_REQUIRE(!overlaps(o.residual, b_res, o.out64, 8 * cells), w + ": residual aliases another plane");
-  return SOIL_OK;
+  return check_side_outputs_apart(w + ": residual aliases another plane", o, B, plane_cells(B, H * W),
+                                  {in.graph, in.stop, in.height, in.erosivity, in.uplift, o.out});
 }
 
-// A call: the chunks of ptr_run through slot WS_POWER_N, the chunk's iterate in WS_POWER_N_ITERATE beside them
-static int power_n_run(PnOut o, const PnPlanes& in, int iters, int64_t B, int64_t H, int64_t W, int edge,
-                       const float* scales, int64_t n_scales, hipStream_t st) {
-  const int64_t hw = H * W, per = ptr_chunk_models(hw), first_chunk = B < per ? B : per;
+// A call, under the entry's name: the chunks of ptr_run through slot WS_POWER_N, the chunk's iterate in
+// WS_POWER_N_ITERATE beside them
+static int power_n_run(const char* what, StepOut o, const PnPlanes& in, int iters, int64_t B, int64_t H, int64_t W,
+                       int edge, const float* scales, int64_t n_scales, void* stream) {
+  if (int rc = check_power_n(what, o, in, iters, scales, B, H, W, edge, n_scales); rc != SOIL_OK) return rc;
+  SOIL_DEVICE();
+  const hipStream_t st = as_stream(stream);
   if (in.n == 1.0) iters = 0;  // soil_stream_power's single solve and nothing else
-  const size_t b_x = iters ? align256(sizeof(double) * static_cast<size_t>(first_chunk * hw)) : 0;
   t_pn_info = DepInfo{0, 0, iters, 0};
-  void* x = nullptr;
-  if (b_x)
-    if (int rc = workspace_get(WS_POWER_N_ITERATE, b_x, &x); rc != SOIL_OK) return rc;
-  if (o.residual) SOIL_HIP(hipMemsetAsync(o.residual, 0, sizeof(double) * static_cast<size_t>(B), st));
+  IterSetup s;
+  if (int rc = iter_setup(s, WS_POWER_N_ITERATE, {iters ? sizeof(double) : 0, 0, 0}, o.residual, B, H, W, scales,
+                          n_scales, st);
+      rc != SOIL_OK)
+    return rc;
+  double* const x = reinterpret_cast<double*>(s.plane[0]);  // (null with iters == 0)
   PtrInfo pinfo{0, 0, 0, 0};
   auto go = edge == SOIL_D4 ? pn_chunk<4> : pn_chunk<8>;
   const int rc = ptr_run(WS_POWER_N, pinfo, B, H, W, sizeof(double), scales, n_scales, PathScale{1.0, 1.0, 1.0}, st,
-                         [&](int64_t b0, int64_t nb, const PathScales& s, char* scratch) {
-                           const int64_t at = b0 * hw;
-                           const PnPlanes part{in.graph + at, in.stop ? in.stop + at : nullptr,
-                                               in.height + at, in.erosivity + at,
-                                               in.uplift ? in.uplift + at : nullptr, in.dt, in.n, in.n1};
-                           const PnOut part_o{o.out ? o.out + at : nullptr, o.out64 ? o.out64 + at : nullptr,
-                                              o.residual ? o.residual + b0 : nullptr};
-                           return go(part_o, part, static_cast<double*>(x), iters, nb, H, W, s, scratch, st);
+                         [&](int64_t b0, int64_t nb, const PathScales& sc, char* scratch) {
+                           const int64_t off = b0 * H * W;
+                           return go(o.at(off, b0), in.at(off), x, iters, nb, H, W, sc, scratch, st);
                          });
-  const size_t b_scales = scales && n_scales > 1 ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0;
-  t_pn_info.bytes = static_cast<int64_t>(b_x + b_scales + ptr_layout(first_chunk * hw, sizeof(double)).bytes());
+  t_pn_info.bytes = s.bytes;
   return rc;
 }
 
@@ -794,67 +788,50 @@ using namespace soil;
 
 extern "C" {
 
+// (each grid entry is its batch twin's call with B = 1 and one scale pair, under its own name)
+
 int soil_downstream(float* out, double* out64, const int32_t* graph, const float* a, const float* b, const float* t,
                     const int32_t* stop, int64_t H, int64_t W, int edge, const float scale[2], void* stream) {
-  const DownPlanes in{graph, stop, a, b, t, 0.0};
-  if (int rc = check_downstream("downstream", kSum, out, out64, in, scale, 1, H, W, edge, 1); rc != SOIL_OK) return rc;
-  SOIL_DEVICE();
-  return downstream_run(kSum, DownOut{out, out64}, in, 1, H, W, edge, scale, 1, as_stream(stream));
+  return downstream_run("downstream", kSum, DownOut{out, out64}, DownPlanes{graph, stop, a, b, t, 0.0}, 1, H, W, edge,
+                        scale, 1, stream);
 }
 
 int soil_downstream_batch(float* out, double* out64, const int32_t* graph, const float* a, const float* b,
                           const float* t, const int32_t* stop, int64_t B, int64_t H, int64_t W, int edge,
                           const float* scales, int64_t n_scales, void* stream) {
-  const DownPlanes in{graph, stop, a, b, t, 0.0};
-  if (int rc = check_downstream("downstream_batch", kSum, out, out64, in, scales, B, H, W, edge, n_scales);
-      rc != SOIL_OK)
-    return rc;
-  SOIL_DEVICE();
-  return downstream_run(kSum, DownOut{out, out64}, in, B, H, W, edge, scales, n_scales, as_stream(stream));
+  return downstream_run("downstream_batch", kSum, DownOut{out, out64}, DownPlanes{graph, stop, a, b, t, 0.0}, B, H, W,
+                        edge, scales, n_scales, stream);
 }
 
 int soil_stream_power(float* out, double* out64, const float* height, const int32_t* graph, const float* erosivity,
                       const float* uplift, const int32_t* stop, int64_t H, int64_t W, int edge, const float scale[2],
                       double dt, void* stream) {
-  const DownPlanes in{graph, stop, height, erosivity, uplift, dt};
-  if (int rc = check_downstream("stream_power", kPower, out, out64, in, scale, 1, H, W, edge, 1); rc != SOIL_OK)
-    return rc;
-  SOIL_DEVICE();
-  return downstream_run(kPower, DownOut{out, out64}, in, 1, H, W, edge, scale, 1, as_stream(stream));
+  return downstream_run("stream_power", kPower, DownOut{out, out64}, DownPlanes{graph, stop, height, erosivity, uplift, dt},
+                        1, H, W, edge, scale, 1, stream);
 }
 
 int soil_stream_power_batch(float* out, double* out64, const float* height, const int32_t* graph,
                             const float* erosivity, const float* uplift, const int32_t* stop, int64_t B, int64_t H,
                             int64_t W, int edge, const float* scales, int64_t n_scales, double dt, void* stream) {
-  const DownPlanes in{graph, stop, height, erosivity, uplift, dt};
-  if (int rc = check_downstream("stream_power_batch", kPower, out, out64, in, scales, B, H, W, edge, n_scales);
-      rc != SOIL_OK)
-    return rc;
-  SOIL_DEVICE();
-  return downstream_run(kPower, DownOut{out, out64}, in, B, H, W, edge, scales, n_scales, as_stream(stream));
+  return downstream_run("stream_power_batch", kPower, DownOut{out, out64},
+                        DownPlanes{graph, stop, height, erosivity, uplift, dt}, B, H, W, edge, scales, n_scales, stream);
 }
 
 int soil_stream_power_deposit(float* out, double* out64, float* flux, double* residual, const float* height,
                               const int32_t* graph, const float* erosivity, const float* deposition,
                               const float* uplift, int64_t H, int64_t W, int edge, const float scale[2], double dt,
                               int iters, void* stream) {
-  const DepPlanes in{graph, height, erosivity, uplift, deposition, dt};
-  const DepOut o{out, out64, flux, residual};
-  if (int rc = check_deposit("stream_power_deposit", o, in, iters, scale, 1, H, W, edge, 1); rc != SOIL_OK) return rc;
-  SOIL_DEVICE();
-  return deposit_run(o, in, iters, 1, H, W, edge, scale, 1, as_stream(stream));
+  return deposit_run("stream_power_deposit", StepOut{out, out64, flux, residual},
+                     DepPlanes{graph, height, erosivity, uplift, deposition, dt}, iters, 1, H, W, edge, scale, 1, stream);
 }
 
 int soil_stream_power_deposit_batch(float* out, double* out64, float* flux, double* residual, const float* height,
                                     const int32_t* graph, const float* erosivity, const float* deposition,
                                     const float* uplift, int64_t B, int64_t H, int64_t W, int edge,
                                     const float* scales, int64_t n_scales, double dt, int iters, void* stream) {
-  const DepPlanes in{graph, height, erosivity, uplift, deposition, dt};
-  const DepOut o{out, out64, flux, residual};
-  if (int rc = check_deposit("stream_power_deposit_batch", o, in, iters, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
-    return rc;
-  SOIL_DEVICE();
-  return deposit_run(o, in, iters, B, H, W, edge, scales, n_scales, as_stream(stream));
+  return deposit_run("stream_power_deposit_batch", StepOut{out, out64, flux, residual},
+                     DepPlanes{graph, height, erosivity, uplift, deposition, dt}, iters, B, H, W, edge, scales, n_scales,
+                     stream);
 }
 
 int soil_stream_power_deposit_info(int64_t info[4]) {
@@ -866,23 +843,18 @@ int soil_stream_power_deposit_info(int64_t info[4]) {
 int soil_stream_power_n(float* out, double* out64, double* residual, const float* height, const int32_t* graph,
                         const float* erosivity, const float* uplift, const int32_t* stop, int64_t H, int64_t W,
                         int edge, const float scale[2], double dt, double n, int iters, void* stream) {
-  const PnPlanes in{graph, stop, height, erosivity, uplift, dt, n, n - 1.0};
-  const PnOut o{out, out64, residual};
-  if (int rc = check_power_n("stream_power_n", o, in, iters, scale, 1, H, W, edge, 1); rc != SOIL_OK) return rc;
-  SOIL_DEVICE();
-  return power_n_run(o, in, iters, 1, H, W, edge, scale, 1, as_stream(stream));
+  return power_n_run("stream_power_n", StepOut{out, out64, nullptr, residual},
+                     PnPlanes{graph, stop, height, erosivity, uplift, dt, n, n - 1.0}, iters, 1, H, W, edge, scale, 1,
+                     stream);
 }
 
 int soil_stream_power_n_batch(float* out, double* out64, double* residual, const float* height, const int32_t* graph,
                               const float* erosivity, const float* uplift, const int32_t* stop, int64_t B, int64_t H,
                               int64_t W, int edge, const float* scales, int64_t n_scales, double dt, double n,
                               int iters, void* stream) {
-  const PnPlanes in{graph, stop, height, erosivity, uplift, dt, n, n - 1.0};
-  const PnOut o{out, out64, residual};
-  if (int rc = check_power_n("stream_power_n_batch", o, in, iters, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
-    return rc;
-  SOIL_DEVICE();
-  return power_n_run(o, in, iters, B, H, W, edge, scales, n_scales, as_stream(stream));
+  return power_n_run("stream_power_n_batch", StepOut{out, out64, nullptr, residual},
+                     PnPlanes{graph, stop, height, erosivity, uplift, dt, n, n - 1.0}, iters, B, H, W, edge, scales,
+                     n_scales, stream);
 }
 
 int soil_stream_power_n_info(int64_t info[4]) {

@@ -141,25 +141,14 @@ template <int K>
 static int paths_chunk(int32_t* terminal, int32_t* steps, float* length, const int32_t* graph, const int32_t* stop,
                        int64_t models, int64_t H, int64_t W, const PathScales& scales, char* scratch, hipStream_t st) {
   auto init = [&](const PtrChunk& c) {
-    const bool vec = ptr_vec_init(W, reinterpret_cast<uintptr_t>(graph) | reinterpret_cast<uintptr_t>(stop));
-    const dim3 grid = ptr_init_grid(c, H, W, vec);
-    if (vec) k_paths_init<K, true><<<grid, kPBlock, 0, st>>>(c.rec[0], graph, stop, H, W, c.flags);
-    else k_paths_init<K, false><<<grid, kPBlock, 0, st>>>(c.rec[0], graph, stop, H, W, c.flags);
+    const bool vec = ptr_vec_init(W, graph, stop);
+    launch_vec(vec, k_paths_init<K, true>, k_paths_init<K, false>, ptr_init_grid(c, H, W, vec), st, c.rec[0], graph,
+               stop, H, W, c.flags);
     return vec;
   };
   auto round = [&](const PtrChunk& c, const PtrRound& q) {
-    uint4* const o = c.rec[(q.r + 1) & 1];
-    const uint4* const in = c.rec[q.r & 1];
-    if (q.list_in) {
-      if (c.idx32)
-        k_paths_list<uint32_t><<<c.groups, kPBlock, 0, st>>>(o, in, q.list_in, q.fill_in, q.list_out, q.fill_out, c.seg);
-      else
-        k_paths_list<int64_t><<<c.groups, kPBlock, 0, st>>>(o, in, q.list_in, q.fill_in, q.list_out, q.fill_out, c.seg);
-    } else if (c.idx32) {
-      k_paths_round<uint32_t><<<c.groups, kPBlock, 0, st>>>(o, in, c.elem, c.flags, q.r, q.list_out, q.fill_out, c.seg);
-    } else {
-      k_paths_round<int64_t><<<c.groups, kPBlock, 0, st>>>(o, in, c.elem, c.flags, q.r, q.list_out, q.fill_out, c.seg);
-    }
+    ptr_launch_round(c, q, st, k_paths_list<uint32_t>, k_paths_list<int64_t>, k_paths_round<uint32_t>,
+                     k_paths_round<int64_t>);
   };
   auto fin = [&](const PtrChunk&, dim3 grid, const uint4* rec) {
     k_paths_final<<<grid, kPBlock, 0, st>>>(terminal, steps, length, rec, H * W, scales);
@@ -178,17 +167,21 @@ static int check_flow_paths(const char* what, const void* terminal, const void* 
   return check_grid_batch(w, B, H, W, edge, n_scales);
 }
 
-// A call through workspace slot WS_FLOW_PATHS (flow_paths.hpp ptr_run); the scales are read only for `length`
-static int flow_paths_run(int32_t* terminal, int32_t* steps, float* length, const int32_t* graph, const int32_t* stop,
-                          int64_t B, int64_t H, int64_t W, int edge, const float* scales, int64_t n_scales,
-                          hipStream_t st) {
+// A call, under the entry's name, through workspace slot WS_FLOW_PATHS (flow_paths.hpp ptr_run); the scales are read
+// only for `length`
+static int flow_paths_run(const char* what, int32_t* terminal, int32_t* steps, float* length, const int32_t* graph,
+                          const int32_t* stop, int64_t B, int64_t H, int64_t W, int edge, const float* scales,
+                          int64_t n_scales, void* stream) {
+  if (int rc = check_flow_paths(what, terminal, steps, length, graph, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
+    return rc;
+  SOIL_DEVICE();
+  const hipStream_t st = as_stream(stream);
   auto go = edge == SOIL_D4 ? paths_chunk<4> : paths_chunk<8>;
   return ptr_run(WS_FLOW_PATHS, t_paths_info, B, H, W, 0, length ? scales : nullptr, n_scales,
                  PathScale{0.0, 0.0, 0.0}, st, [&](int64_t b0, int64_t nb, const PathScales& s, char* scratch) {
-                   const int64_t at = b0 * H * W;
-                   return go(terminal ? terminal + at : nullptr, steps ? steps + at : nullptr,
-                             length ? length + at : nullptr, graph + at, stop ? stop + at : nullptr, nb, H, W, s,
-                             scratch, st);
+                   const int64_t off = b0 * H * W;
+                   return go(at(terminal, off), at(steps, off), at(length, off), graph + off, at(stop, off), nb, H, W,
+                             s, scratch, st);
                  });
 }
 
@@ -200,20 +193,14 @@ extern "C" {
 
 int soil_flow_paths(int32_t* terminal, int32_t* steps, float* length, const int32_t* graph, const int32_t* stop,
                     int64_t H, int64_t W, int edge, const float scale[2], void* stream) {
-  if (int rc = check_flow_paths("flow_paths", terminal, steps, length, graph, scale, 1, H, W, edge, 1); rc != SOIL_OK)
-    return rc;
-  SOIL_DEVICE();
-  return flow_paths_run(terminal, steps, length, graph, stop, 1, H, W, edge, scale, 1, as_stream(stream));
+  return flow_paths_run("flow_paths", terminal, steps, length, graph, stop, 1, H, W, edge, scale, 1, stream);
 }
 
 int soil_flow_paths_batch(int32_t* terminal, int32_t* steps, float* length, const int32_t* graph,
                           const int32_t* stop, int64_t B, int64_t H, int64_t W, int edge, const float* scales,
                           int64_t n_scales, void* stream) {
-  if (int rc = check_flow_paths("flow_paths_batch", terminal, steps, length, graph, scales, B, H, W, edge, n_scales);
-      rc != SOIL_OK)
-    return rc;
-  SOIL_DEVICE();
-  return flow_paths_run(terminal, steps, length, graph, stop, B, H, W, edge, scales, n_scales, as_stream(stream));
+  return flow_paths_run("flow_paths_batch", terminal, steps, length, graph, stop, B, H, W, edge, scales, n_scales,
+                        stream);
 }
 
 int soil_flow_paths_info(int64_t info[4]) {

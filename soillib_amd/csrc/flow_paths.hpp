@@ -221,13 +221,39 @@ struct PtrRound {
   uint32_t *list_out, *fill_out;
 };
 
+// A plane from cell `off` on — a chunk's part of a batch's plane —, null for a plane that is not given
+template <typename T>
+T* at(T* p, int64_t off) { return p ? p + off : nullptr; }
+
 // The init form: four cells per thread where W is a multiple of four and every plane (the OR of their addresses) is
 // 16-byte aligned; the grid of either form
 inline bool ptr_vec_init(int64_t W, uintptr_t planes) { return W % 4 == 0 && (planes & 15) == 0; }
+template <typename... P>
+bool ptr_vec_init(int64_t W, const P*... planes) { return ptr_vec_init(W, (reinterpret_cast<uintptr_t>(planes) | ...)); }
 inline dim3 ptr_init_grid(const PtrChunk& c, int64_t H, int64_t W, bool vec) {
   dim3 grid = grid_rows(H, vec ? W / 4 : W, kPBlock);
   grid.z = c.z;
   return grid;
+}
+// An init-shaped kernel in its 16-byte form or its scalar one (two instantiations of one signature), same arguments
+template <typename Kernel, typename... Args>
+void launch_vec(bool vec, Kernel* k_vec, Kernel* k_scalar, dim3 grid, hipStream_t st, Args... args) {
+  (vec ? k_vec : k_scalar)<<<grid, kPBlock, 0, st>>>(args...);
+}
+
+// One round of a chunk, dense or listed, on 32- or 64-bit offsets by the chunk: the file's four round kernels, and
+// `planes`, what its kernels take between the two record buffers and the engine's own arguments (downstream.hip's B)
+template <typename List, typename Round, typename... Planes>
+void ptr_launch_round(const PtrChunk& c, const PtrRound& q, hipStream_t st, List* list32, List* list64, Round* round32,
+                      Round* round64, Planes... planes) {
+  uint4* const out = c.rec[(q.r + 1) & 1];
+  const uint4* const in = c.rec[q.r & 1];
+  if (q.list_in)
+    (c.idx32 ? list32 : list64)<<<c.groups, kPBlock, 0, st>>>(out, in, planes..., q.list_in, q.fill_in, q.list_out,
+                                                              q.fill_out, c.seg);
+  else
+    (c.idx32 ? round32 : round64)<<<c.groups, kPBlock, 0, st>>>(out, in, planes..., c.elem, c.flags, q.r, q.list_out,
+                                                                q.fill_out, c.seg);
 }
 
 // One chunk of `models` models of (H, W), stream-ordered: init, the rounds of ONE model, final.
@@ -285,17 +311,26 @@ int ptr_chunk(PtrInfo& info, int64_t models, int64_t H, int64_t W, size_t extra,
 // A call: chunks of whole models, one after the other on `st` through one block of workspace `slot` (the entries'
 // own: they return with their work in flight): the B scale records first (`scales` with n_scales > 1; null: `none`
 // for every model), then the chunk's scratch.  chunk(b0, nb, scales of the chunk, scratch) runs models b0 .. b0 + nb.
+// PtrBlock: the models of a chunk, the cells of the first chunk, the largest, and the two parts of the block in bytes;
+// a driver that keeps planes of its own beside the block (downstream.hip iter_setup) sizes them by it.
+struct PtrBlock {
+  int64_t per, cells;
+  size_t b_scales, b_chunk;
+};
+inline PtrBlock ptr_block(int64_t B, int64_t hw, size_t extra, const float* scales, int64_t n_scales) {
+  const int64_t per = ptr_chunk_models(hw), cells = (B < per ? B : per) * hw;
+  const bool per_model = scales && n_scales > 1;
+  return PtrBlock{per, cells, per_model ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0,
+                  ptr_layout(cells, extra).bytes()};
+}
 template <typename Chunk>
 int ptr_run(WorkspaceSlot slot, PtrInfo& info, int64_t B, int64_t H, int64_t W, size_t extra, const float* scales,
             int64_t n_scales, PathScale none, hipStream_t st, Chunk chunk) {
-  const int64_t hw = H * W, per = ptr_chunk_models(hw);
+  const auto [per, cells, b_scales, b_chunk] = ptr_block(B, H * W, extra, scales, n_scales);
   info = PtrInfo{0, 0, 0, 0};
-  const bool per_model = scales && n_scales > 1;
-  const size_t b_scales = per_model ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0;
-  const int64_t first_chunk = B < per ? B : per;
+  const bool per_model = b_scales != 0;
   void* base = nullptr;
-  if (int rc = workspace_get(slot, b_scales + ptr_layout(first_chunk * hw, extra).bytes(), &base); rc != SOIL_OK)
-    return rc;
+  if (int rc = workspace_get(slot, b_scales + b_chunk, &base); rc != SOIL_OK) return rc;
   PathScales sc{nullptr, scales ? path_scale(scales) : none};
   if (per_model) {
     if (int rc = upload_scale_records(base, scales, B, path_scale, st); rc != SOIL_OK) return rc;

@@ -254,14 +254,40 @@ def _child_main(path):
                     out[key + k] = v
                 i = _info()
                 out[key + "info"] = np.array([i["chunks"], i["iters"], i["launches"]])
+    _child_optional()
     np.savez(path, **out)
+
+
+# (H, W, SOIL_FLOW_BATCH_CELLS): B = 5 as 2 + 2 + 1 models, the 16-byte passes and the scalar ones
+OPTIONAL_SHAPES = [(8, 12, 192), (8, 10, 160)]
+OPTIONAL_NULLS = [(), ("uplift", "out64", "flux"), ("out", "residual")]
+
+
+def _child_optional():
+    """The uplift and every output given and NULL over three chunks: from the second chunk on a plane is the chunk's
+    part of it, and one that is not given must stay not given.  The words of the five single-grid calls; raises."""
+    for H, W, cells in OPTIONAL_SHAPES:
+        graph, planes, scales, _ = _stack(H, W, 5, D8, 2)
+        shrink = np.float32([1.0, 0.9, 0.8, 0.7, 0.6])[:, None, None]              # no two models share a plane
+        planes = {k: v * shrink for k, v in planes.items()}
+        for null in OPTIONAL_NULLS:
+            kw = dict(uplift="uplift" not in null, want=tuple(k for k in ALL if k not in null))
+            os.environ["SOIL_FLOW_BATCH_CELLS"] = str(cells)
+            got = _run_stack(graph, planes, scales, D8, 2, **kw)
+            assert _info()["chunks"] == 3 and sorted(got) == sorted(kw["want"]), (H, W, null, _info(), sorted(got))
+            del os.environ["SOIL_FLOW_BATCH_CELLS"]
+            for b in range(5):
+                one = _run_stack(graph[b], {k: v[b] for k, v in planes.items()}, scales[b], D8, 2, **kw)
+                dep.same_words({k: v[b] for k, v in got.items()}, one, "%dx%d without %s, model %d" % (H, W, null, b))
 
 
 @pytest.mark.parametrize("knob", [None, "idx64", "paths_0", "paths_1", "rake_0", "rake_1"])
 def test_chunks_and_knobs(hip, tmp_path, knob):
     """A 5-model batch in a child process, whole and in chunks of 2 + 2 + 1 and of one model (SOIL_FLOW_BATCH_CELLS):
     by default, under SOIL_PATHS_IDX64 = 1, and with the listed rounds of either engine off (0) and from the first
-    round they can start at (1): SOIL_PATHS_LIST_FROM, SOIL_RAKE_LIST_FROM.  The restatement's words every time."""
+    round they can start at (1): SOIL_PATHS_LIST_FROM, SOIL_RAKE_LIST_FROM.  The restatement's words every time.  The
+    child also holds the uplift and each output, given and NULL over three chunks, to the single-grid calls
+    (_child_optional)."""
     path = str(tmp_path / "chunks.npz")
     env = dict(os.environ)
     for name in ("SOIL_FLOW_BATCH_CELLS", "SOIL_PATHS_LIST_FROM", "SOIL_PATHS_IDX64", "SOIL_RAKE_LIST_FROM"):

@@ -398,7 +398,39 @@ def _child_main(path):
                     out[key + "_out"], out[key + "_out64"] = _run_mode(graph, edge, planes, mode, scales, stop)
                     i = _info()
                     out[key + "_info"] = np.array([i["chunks"], i["vec_chunks"], i["idx64_chunks"]])
+    _child_optional()
     np.savez(path, **out)
+
+
+# (H, W, SOIL_FLOW_BATCH_CELLS): B = 5 as 2 + 2 + 1 models, the 16-byte init and the scalar one
+OPTIONAL_SHAPES = [(8, 12, 192), (8, 10, 160)]
+OPTIONAL_NULLS = {"sum": [(), ("a", "t", "stop", "out64"), ("b", "out")],
+                  "power": [(), ("uplift", "stop", "out64"), ("out",)]}
+
+
+def _child_optional():
+    """Every optional argument given and NULL over three chunks: from the second chunk on a plane is the chunk's part
+    of it, and a plane that is not given must stay not given.  The words of the five single-grid calls; raises."""
+    for H, W, cells in OPTIONAL_SHAPES:
+        for mode, nulls in OPTIONAL_NULLS.items():
+            graph, stop, scales, planes, _ = _stack(H, W, 5, D8, mode)
+            shrink = np.float32([1.0, 0.9, 0.8, 0.7, 0.6])[:, None, None]          # no two models share a plane
+            planes = {k: v * shrink for k, v in planes.items()}
+            for null in nulls:
+                p = {k: None if k in null else v for k, v in planes.items()}
+                s = None if "stop" in null else stop
+                outs = ("out" not in null, "out64" not in null)
+                os.environ["SOIL_FLOW_BATCH_CELLS"] = str(cells)
+                got = _run_mode(graph, D8, p, mode, scales, s, outs)
+                i = _info()
+                assert (i["chunks"], i["vec_chunks"]) == (3, 3 if W % 4 == 0 else 0), (H, W, mode, null, i)
+                del os.environ["SOIL_FLOW_BATCH_CELLS"]
+                for b in range(5):
+                    one = _run_mode(graph[b], D8, {k: None if v is None else v[b] for k, v in p.items()}, mode,
+                                    scales[b], None if s is None else s[b], outs)
+                    assert [g is None for g in got] == [o is None for o in one] == [not o for o in outs]
+                    _same_words([None if g is None else g[b] for g in got], one,
+                                "%dx%d %s without %s, model %d" % (H, W, mode, null, b))
 
 
 @pytest.mark.parametrize("knob", [None, "0", "1", "3", "idx64"])
@@ -406,7 +438,8 @@ def test_chunks(hip, tmp_path, knob):
     """Chunks of 2 + 2 + 1 models and of one model (SOIL_FLOW_BATCH_CELLS) in a child process: by default, with the
     listed rounds off (SOIL_PATHS_LIST_FROM = 0), from round 1 and from the later round 3, and ("idx64") under
     SOIL_PATHS_IDX64 = 1, the 64-bit offsets of a model of 2^28 cells or more.  The restatement's bits whatever the
-    chunking; the child reports what each call did (soil_downstream_info)."""
+    chunking; the child reports what each call did (soil_downstream_info).  The child also holds a, b, t, stop, uplift
+    and either output, given and NULL over three chunks, to the single-grid calls (_child_optional)."""
     path = str(tmp_path / "chunks.npz")
     env = dict(os.environ)
     for name in ("SOIL_FLOW_BATCH_CELLS", "SOIL_PATHS_LIST_FROM", "SOIL_PATHS_IDX64"):

@@ -313,7 +313,41 @@ def _child_main(path):
                     out["%dx%d_m%d_e%d_%s" % (H, W, models, edge, name)] = plane
                 i = _info()
                 out["%dx%d_m%d_e%d_info" % (H, W, models, edge)] = np.array([i["chunks"], i["vec_chunks"], i["idx64_chunks"]])
+    _child_optional()
     np.savez(path, **out)
+
+
+# (H, W, SOIL_FLOW_BATCH_CELLS): B = 5 as 2 + 2 + 1 models, the 16-byte init and the scalar one
+OPTIONAL_SHAPES = [(8, 12, 192), (8, 10, 160)]
+OPTIONAL_ASKS = [((True, True, True), True), ((True, False, False), False), ((False, True, False), True),
+                 ((False, False, True), False)]                  # (terminal, steps, length), the stop plane
+
+
+def _child_optional():
+    """The stop plane and each output given and NULL over three chunks: from the second chunk on a plane is the
+    chunk's part of it, and one that is not given must stay not given.  The words of the five single-grid calls;
+    raises."""
+    from soillib_amd import _abi, silt
+    lib = _abi.lib()
+    dts = (silt.int32, silt.int32, silt.float32)
+    ptr = lambda t: None if t is None else t.c_ptr
+    for H, W, cells in OPTIONAL_SHAPES:
+        graph, stop, scales, _ = _stack(H, W, 5, D8)
+        for ask, with_stop in OPTIONAL_ASKS:
+            gg, gs = to_gpu(graph), to_gpu(stop) if with_stop else None
+            pairs = (C.c_float * 10)(*[v for s in scales for v in s]) if ask[2] else None
+            outs = [silt.tensor(dt, silt.shape(5, H, W), silt.gpu) if a else None for a, dt in zip(ask, dts)]
+            os.environ["SOIL_FLOW_BATCH_CELLS"] = str(cells)
+            _abi.check(lib.soil_flow_paths_batch(*[ptr(o) for o in outs], gg.c_ptr, ptr(gs), 5, H, W, D8, pairs,
+                                                 5 if ask[2] else 1, _abi.stream()))
+            i = _info()
+            assert (i["chunks"], i["vec_chunks"]) == (3, 3 if W % 4 == 0 else 0), (H, W, ask, with_stop, i)
+            del os.environ["SOIL_FLOW_BATCH_CELLS"]
+            got = _np3(outs)
+            for b in range(5):
+                one = _single(graph[b], D8, scales[b], stop[b] if with_stop else None)
+                _same_words([None if g is None else g[b] for g in got], [w if a else None for a, w in zip(ask, one)],
+                            "%dx%d outputs %r, stop %r, model %d" % (H, W, ask, with_stop, b))
 
 
 @pytest.mark.parametrize("list_from", [None, "0", "1", "idx64"])
@@ -322,7 +356,9 @@ def test_chunks(hip, tmp_path, list_from):
     listed rounds off (SOIL_PATHS_LIST_FROM = 0) and forced on from round 1: the restatement's results, whatever the
     chunking.  (Later first rounds: test_the_rounds_in_this_process_with_the_lists_off_and_late.)  "idx64": the
     same under SOIL_PATHS_IDX64 = 1, the 64-bit offsets of a model of 2^28 cells or more.  The child reports what each
-    call did (soil_flow_paths_info): 3 and 5 chunks, the 16-byte form at (33, 260) alone, the offsets asked for."""
+    call did (soil_flow_paths_info): 3 and 5 chunks, the 16-byte form at (33, 260) alone, the offsets asked for.  The
+    child also holds the stop plane and each output, given and NULL over three chunks, to the single-grid calls
+    (_child_optional)."""
     path = str(tmp_path / "chunks.npz")
     env = dict(os.environ)
     env.pop("SOIL_FLOW_BATCH_CELLS", None)

@@ -352,13 +352,42 @@ def _child_main(path):
                     out[key + "want_" + k] = want[k]
                 i = _info()
                 out[key + "info"] = np.array([i["chunks"], i["iters"], i["launches"]])
+    _child_optional()
     np.savez(path, **out)
+
+
+# (H, W, SOIL_FLOW_BATCH_CELLS): B = 5 as 2 + 2 + 1 models, the 16-byte init passes and the scalar ones
+OPTIONAL_SHAPES = [(8, 12, 192), (8, 10, 160)]
+OPTIONAL_NULLS = [(), ("uplift", "stop", "out64"), ("out", "residual")]
+
+
+def _child_optional():
+    """The uplift, the stop plane and every output given and NULL over three chunks: from the second chunk on a plane
+    is the chunk's part of it, and one that is not given must stay not given.  Five models that differ in every plane;
+    the words of the five single-grid calls; raises."""
+    n, iters = 2.5, 2
+    for H, W, cells in OPTIONAL_SHAPES:
+        built = dict(ref.built_graphs(H, W, D8))
+        cfg = [(("serpentine", "hostile")[b % 2], b) for b in range(5)]
+        graph = np.stack([built[g] for g, _ in cfg])
+        planes = {k: np.stack([_planes(H, W, D8, g, d)[k] for g, d in cfg]) for k in ("height", "erosivity", "uplift", "stop")}
+        scales = [SCALES[b % 3] for b in range(5)]
+        for null in OPTIONAL_NULLS:
+            kw = dict(uplift="uplift" not in null, stop="stop" not in null, want=tuple(k for k in ALL if k not in null))
+            os.environ["SOIL_FLOW_BATCH_CELLS"] = str(cells)
+            got = _run_stack(graph, planes, scales, D8, n, iters, **kw)
+            assert _info()["chunks"] == 3 and sorted(got) == sorted(kw["want"]), (H, W, null, _info(), sorted(got))
+            del os.environ["SOIL_FLOW_BATCH_CELLS"]
+            for b in range(5):
+                one = _run_stack(graph[b], {k: v[b] for k, v in planes.items()}, scales[b], D8, n, iters, **kw)
+                pn.same_words({k: v[b] for k, v in got.items()}, one, "%dx%d without %s, model %d" % (H, W, null, b))
 
 
 def test_chunking_does_not_show(hip, tmp_path):
     """A 5-model batch in one child process under SOIL_PATHS_GROUPS = 3 (read once per process: three work-groups a
     round, several trips each), whole and in chunks of 2 + 2 + 1 models (SOIL_FLOW_BATCH_CELLS): the restatement's
-    words every time, and a chunk's launches do not depend on its models."""
+    words every time, and a chunk's launches do not depend on its models.  The child also holds the uplift, the stop
+    plane and each output, given and NULL over three chunks, to the single-grid calls (_child_optional)."""
     path = str(tmp_path / "chunks.npz")
     env = dict(os.environ)
     for name in ("SOIL_FLOW_BATCH_CELLS", "SOIL_PATHS_LIST_FROM", "SOIL_PATHS_IDX64"):
