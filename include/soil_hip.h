@@ -1117,7 +1117,8 @@ int soil_downstream_info(int64_t info[4]);
  *
  * The entries are stream-ordered on the caller's stream from the first launch to the last.  A host thread's calls on
  * one device share cached scratch of their own (the records and lists of soil_stream_power, an accumulation's scratch
- * and 16 bytes a cell for the iterate, q and Qs): issue them on ONE stream, or order the streams yourself.
+ * and 16 bytes a cell for the iterate, q and Qs): issue them on ONE stream, or order the streams yourself.  That
+ * scratch is shared with soil_stream_power_deposit_n and its _batch form (below): the rule holds across both families.
  *
  * Batch form: the conventions of soil_stream_power_batch.  Model-major planes, 1 or B scale pairs, model b's slices
  * bit for bit what the single call gives, chunks of whole models (SOIL_FLOW_BATCH_CELLS lowers the cells of a chunk,
@@ -1220,6 +1221,78 @@ int soil_stream_power_n_info(int64_t info[4]);
  * arrays of n doubles.  op 0: the slope power of soil_stream_power_n, pow(a, b) as its init pass evaluates it.  Any
  * other op, or a null array, is refused with SOIL_ERR_INVALID_ARGUMENT before any device work. */
 int soil_selftest_math64(double* out, const double* a, const double* b, int64_t n, int op, void* stream);
+
+/* ------------- flow graphs: erosion-deposition at slope exponents above 1 */
+
+/* The stream-power step with sediment deposition and a slope exponent n >= 1,
+ *     dh/dt = u - K A^m S^n + (G / A) * Qs
+ * soil_stream_power_deposit and soil_stream_power_n in one step.  It is the Newton linearisation of the latter,
+ *     S^n ~ (1 - n) S_j^n + n S_j^(n-1) S
+ * put into the self-implicit equation of the former, x - b = -k dt S^n + g (Qup + b - x): one iteration renews the
+ * tangent and the upstream sum together.  The reference has no such call; the definition is this library's.
+ *
+ * Grid, edge rule, terminals, `scale`, L(n), NaN words, chunking, the q pass, the accumulation and the rounds of the
+ * records are word for word those of soil_stream_power_deposit.  There is no `stop` plane, as there.  The slope and
+ * the power are soil_stream_power_n's, the n == 2 shortcut and the one inline pow that soil_selftest_math64 op 0
+ * returns included.
+ *
+ * All arithmetic is fp64 with one rounding per operation, in this order, with no contraction.
+ *     x^0 = the solve of soil_stream_power on the same arguments with stop == NULL, in fp64: soil_stream_power_n's
+ *           start, for its reason (a filled lake)
+ * For j = 1 .. iters, with x = x^(j-1), per cell i that has an edge to r of length L:
+ *     q[i] = (float)(b - x[i])               rounded to nearest; +0 on a terminal and wherever that float is not finite
+ *     Qs   = the bits soil_accumulate(graph, q, no decay) gives      (float32)
+ *     Qup  = (double)Qs[i] - (double)q[i]
+ *     d    = x[i] - x[r]                     (the receiver's value a gather of 8 bytes)
+ *     S    = d <= 0 ? 0.0 : d / L            (a NaN d falls through to d / L and stays NaN)
+ *     P    = n == 2 ? S : pow(S, n - 1)      (n - 1 made once on the host)
+ *     kd   = (double)erosivity[i] * dt
+ *     F    = ((n * kd) / L) * P
+ *     c    = (kd * (n - 1)) * (P * S)
+ *     g    = (double)deposition[i]
+ *     b    = (double)height[i] + dt * (double)uplift[i]      (double)height[i] with uplift == NULL
+ *     D    = (1.0 + F) + g
+ *     A    = ((((1.0 + g) * b) + (g * Qup)) + c) / D ;   B = F / D
+ *     x^j  = the solve x[i] = A + B * x[r] down the graph, with soil_downstream's rounds, bit for bit
+ * A terminal has A = (double)height[i], B = 0, and is final.  Unlike the deposit step's first iteration, iteration 1
+ * here has its q pass and accumulation: x^0 is not b.
+ *
+ * With `deposition` all zeros the result is the bits of soil_stream_power_n with stop == NULL at the same `iters`: D
+ * is 1 + F, (1.0 + 0.0) * b is b and b + 0 * Qup is b — for a finite Qup, and but for b == -0.0, which comes out as
+ * +0.0.  n == 1.0 runs soil_stream_power_deposit's iterations and nothing else and gives its bits: its start is
+ * x^0 = b, not the solve.
+ *
+ * THE ITERATION HAS A DOMAIN.  No damping is added; the arithmetic above is the definition.  Measured on conditioned
+ * noise terrains of 256^2 to 4096^2 cells with a deposition plane G (cell area) / A (DESIGN.md 3.5 has the map): with
+ * K A^m dt / L up to order 1 and G <= 1 it contracts for n up to 3 and stops at the float32 floor of Qs (about 1e-9 of
+ * the height range) after 12 to 35 iterations; with G = 2 it is slow at n = 1.5 and on some terrains diverges for
+ * n >= 2.  With K A^m dt / L of order 100 it still contracts for G <= 1, but for n >= 2 it stalls across level runs as
+ * soil_stream_power_n does, and it diverges for G = 2 at every n: the changes grow from iteration to iteration while
+ * every value stays finite.  Outside the domain the residual grows with `iters` instead of falling, nothing else says
+ * so, and the caller must read it.
+ *
+ * Outputs: `out`, `out64`, `flux` and `residual` are soil_stream_power_deposit's, word for word: x^iters; one more q
+ * pass and accumulation from the returned iterate; the integer maximum of |x^iters - x^(iters-1)| per model.
+ *
+ * Stream order, cached scratch (shared with soil_stream_power_deposit: one stream for both, or order them yourself)
+ * and the batch form are soil_stream_power_deposit's.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): what soil_stream_power_deposit refuses (a null `deposition`, iters < 1 and its aliasing rules
+ * among them) and an n that is not finite, n < 1 or n > 16.  Otherwise, without a device: SOIL_ERR_NO_DEVICE. */
+int soil_stream_power_deposit_n(float* out, double* out64, float* flux, double* residual, const float* height,
+                                const int32_t* graph, const float* erosivity, const float* deposition,
+                                const float* uplift, int64_t H, int64_t W, int edge, const float scale[2], double dt,
+                                double n, int iters, void* stream);
+int soil_stream_power_deposit_n_batch(float* out, double* out64, float* flux, double* residual, const float* height,
+                                      const int32_t* graph, const float* erosivity, const float* deposition,
+                                      const float* uplift, int64_t B, int64_t H, int64_t W, int edge,
+                                      const float* scales, int64_t n_scales, double dt, double n, int iters,
+                                      void* stream);
+/* What the calling host thread's last soil_stream_power_deposit_n or _batch call did: info[0] kernel launches, info[1]
+ * chunks, info[2] iterations run, info[3] bytes of scratch the call asked for.  All zero before the first call; needs
+ * no device. */
+int soil_stream_power_deposit_n_info(int64_t info[4]);
 
 /* ------------------------------------------------------ hillslope diffusion */
 

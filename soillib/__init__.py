@@ -25,6 +25,8 @@ from soillib_amd.soil import (chi, downstream, downstream_batch, downstream_info
 from soillib_amd.soil import (deposition, stream_power_deposit, stream_power_deposit_batch,  # noqa: F401
                               stream_power_deposit_info)
 from soillib_amd.soil import stream_power_n, stream_power_n_batch, stream_power_n_info  # noqa: F401
+from soillib_amd.soil import (stream_power_deposit_n, stream_power_deposit_n_batch,  # noqa: F401
+                              stream_power_deposit_n_info)
 from soillib_amd.soil import diffuse, diffuse_batch, diffuse_info  # noqa: F401
 from soillib_amd.soil import (flat_distance, flat_distance_batch, flat_distance_info, flat_receivers,  # noqa: F401
                               flat_receivers_batch, resolve_flats, resolve_flats_batch)

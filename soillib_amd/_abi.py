@@ -253,6 +253,12 @@ SIGNATURES = {
     "soil_stream_power_n_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, C.c_double,
                                          C.c_double, cint, vp]),
     "soil_stream_power_n_info": (cint, [C.POINTER(i64)]),
+    # the deposit step at a slope exponent above 1: the deposit step's arguments with n between dt and iters
+    "soil_stream_power_deposit_n": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double,
+                                           C.c_double, cint, vp]),
+    "soil_stream_power_deposit_n_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64,
+                                                 C.c_double, C.c_double, cint, vp]),
+    "soil_stream_power_deposit_n_info": (cint, [C.POINTER(i64)]),
     # hillslope diffusion: out / out64 (one may be NULL), height, diffusivity / uplift / fixed (each may be NULL);
     # host scale pairs, kappa, dt, border, first_axis
     "soil_diffuse": (cint, [vp, vp, vp, vp, vp, vp, i64, i64, F3, C.c_double, C.c_double, cint, cint, vp]),

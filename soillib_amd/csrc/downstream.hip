@@ -9,7 +9,9 @@
 // solver.  At the end of the file, the stream-power step with a deposition term (soil_stream_power_deposit /
 // soil_stream_power_deposit_batch): the same rounds inside a fixed-point iteration with graph.hip's accumulation; and
 // the step with a slope exponent above 1 (soil_stream_power_n / soil_stream_power_n_batch): the same rounds inside a
-// Newton iteration, whose linearisation about an iterate is an affine recurrence again.
+// Newton iteration, whose linearisation about an iterate is an affine recurrence again; and the two in one step
+// (soil_stream_power_deposit_n / soil_stream_power_deposit_n_batch): the deposit step's driver with an init pass that
+// writes both sets of coefficients.
 //
 // The composition of affine maps is associative, so this is the pointer doubling of flow_paths.hip with other
 // records: where that file adds three counters, a round here composes x -> A + B x with the map of the cell the
@@ -486,48 +488,14 @@ static int solve_pass(int64_t& launches, int64_t models, int64_t H, int64_t W, c
 }
 
 template <int K>
-static void dep_launch_q(const DepWork& w, const DepPlanes& in, int64_t models, int64_t H, int64_t W, bool first,
-                         hipStream_t st) {
+static void dep_launch_q(DepInfo& info, const DepWork& w, const DepPlanes& in, int64_t models, int64_t H, int64_t W,
+                         bool first, hipStream_t st) {
   const bool vec = ptr_vec_init(W, in.graph, in.height, in.uplift, w.x, w.q, w.qs);
   dim3 grid = grid_rows(H, vec ? W / 4 : W, kPBlock);
   grid.z = static_cast<unsigned>(models);
   if (first) launch_vec(vec, k_dep_q<K, true, true>, k_dep_q<K, false, true>, grid, st, w, in, H, W);
   else launch_vec(vec, k_dep_q<K, true, false>, k_dep_q<K, false, false>, grid, st, w, in, H, W);
-  t_dep_info.launches += 1;
-}
-
-// One chunk of `models` models: x^0, then `iters` times q, Qs and a solve pass from them, then the flux of the
-// returned iterate.  `in`, `o` and `w` are the chunk's own.
-template <int K>
-static int dep_chunk(StepOut o, const DepPlanes& in, const DepWork& w, int iters, int64_t models, int64_t H, int64_t W,
-                     int edge, const PathScales& scales, char* scratch, RakeStats& rake, hipStream_t st) {
-  t_dep_info.chunks += 1;
-  dep_launch_q<K>(w, in, models, H, W, true, st);
-  SOIL_LAUNCH_CHECK();
-  auto init = [&](const PtrChunk& c) {
-    const bool vec = ptr_vec_init(W, in.graph, in.height, in.erosivity, in.uplift, in.deposition, w.qs, w.q);
-    launch_vec(vec, k_dep_init<K, true>, k_dep_init<K, false>, ptr_init_grid(c, H, W, vec), st, c.rec[0],
-               static_cast<double*>(c.extra[0]), in, w.qs, w.q, H, W, scales, c.flags);
-    return vec;
-  };
-  for (int k = 1; k <= iters; ++k) {
-    if (k > 1) {
-      dep_launch_q<K>(w, in, models, H, W, false, st);
-      SOIL_LAUNCH_CHECK();
-      if (int rc = rake_accumulate(w.qs, in.graph, w.q, models, H, W, edge, st, WS_DEPOSIT_RAKE, &rake); rc != SOIL_OK)
-        return rc;
-    }
-    if (int rc = solve_pass(t_dep_info.launches, models, H, W, scratch, st, init, w.x, k == iters ? o : StepOut{});
-        rc != SOIL_OK)
-      return rc;
-  }
-  if (o.flux) {
-    dep_launch_q<K>(w, in, models, H, W, false, st);
-    SOIL_LAUNCH_CHECK();
-    if (int rc = rake_accumulate(o.flux, in.graph, w.q, models, H, W, edge, st, WS_DEPOSIT_RAKE, &rake); rc != SOIL_OK)
-      return rc;
-  }
-  return SOIL_OK;
+  info.launches += 1;
 }
 
 // Neither the flux (4 bytes a cell) nor the residual (8 bytes a model) shares a byte with one of `planes` (4 bytes a
@@ -543,14 +511,18 @@ static int check_side_outputs_apart(const std::string& msg, const StepOut& o, in
   return SOIL_OK;
 }
 
-// What the two deposit entries refuse before any device work: soil_stream_power's refusals and their own
-static int check_deposit(const char* what, const StepOut& o, const DepPlanes& in, int iters, const float* scales,
-                         int64_t B, int64_t H, int64_t W, int edge, int64_t n_scales) {
+// What the deposit entries refuse before any device work: soil_stream_power's refusals and their own.  `n`: the
+// slope exponent, 1.0 from the entries that take none.
+static int check_deposit(const char* what, const StepOut& o, const DepPlanes& in, double n, int iters,
+                         const float* scales, int64_t B, int64_t H, int64_t W, int edge, int64_t n_scales) {
   const std::string w(what);
   const DownPlanes power{in.graph, nullptr, in.height, in.erosivity, in.uplift, in.dt};
   if (int rc = check_downstream(what, kPower, o.out, o.out64, power, scales, B, H, W, edge, n_scales); rc != SOIL_OK)
     return rc;
   SOIL_REQUIRE(in.deposition, w + ": null deposition");
+  SOIL_REQUIRE(std::isfinite(n) && n >= 1.0 && n <= 16.0,
+               w + ": n must be a finite slope exponent in 1 .. 16 (n < 1 makes the per-cell equation concave: it needs "
+                   "a safeguarded solve per cell, which no affine map expresses)");
   SOIL_REQUIRE(iters >= 1, w + ": iters must be >= 1");
   const size_t cells = plane_cells(B, H * W);
   // (out and out64 are apart: check_downstream saw to it)
@@ -578,32 +550,6 @@ static int iter_setup(IterSetup& s, WorkspaceSlot slot, const size_t (&side)[3],
   if (residual) SOIL_HIP(hipMemsetAsync(residual, 0, sizeof(double) * static_cast<size_t>(B), st));
   s.bytes = static_cast<int64_t>(total + blk.b_scales + blk.b_chunk);
   return SOIL_OK;
-}
-
-// A call, under the entry's name: the chunks of ptr_run through slot WS_DEPOSIT, the chunk's planes in
-// WS_DEPOSIT_PLANES beside them
-static int deposit_run(const char* what, StepOut o, const DepPlanes& in, int iters, int64_t B, int64_t H, int64_t W,
-                       int edge, const float* scales, int64_t n_scales, void* stream) {
-  if (int rc = check_deposit(what, o, in, iters, scales, B, H, W, edge, n_scales); rc != SOIL_OK) return rc;
-  SOIL_DEVICE();
-  const hipStream_t st = as_stream(stream);
-  t_dep_info = DepInfo{0, 0, iters, 0};
-  IterSetup s;
-  if (int rc = iter_setup(s, WS_DEPOSIT_PLANES, {8, 4, 4}, o.residual, B, H, W, scales, n_scales, st); rc != SOIL_OK)
-    return rc;
-  const DepWork w{reinterpret_cast<double*>(s.plane[0]), reinterpret_cast<float*>(s.plane[1]),
-                  reinterpret_cast<float*>(s.plane[2])};
-  RakeStats rake{0, 0};
-  PtrInfo pinfo{0, 0, 0, 0};
-  auto go = edge == SOIL_D4 ? dep_chunk<4> : dep_chunk<8>;
-  const int rc = ptr_run(WS_DEPOSIT, pinfo, B, H, W, sizeof(double), scales, n_scales, PathScale{1.0, 1.0, 1.0}, st,
-                         [&](int64_t b0, int64_t nb, const PathScales& sc, char* scratch) {
-                           const int64_t off = b0 * H * W;
-                           return go(o.at(off, b0), in.at(off), w, iters, nb, H, W, edge, sc, scratch, rake, st);
-                         });
-  t_dep_info.launches += rake.launches;
-  t_dep_info.bytes = s.bytes + rake.bytes;
-  return rc;
 }
 
 // ---- slope exponents above 1: Newton steps on the whole triangular system, each one solve of the rounds above ---
@@ -699,6 +645,103 @@ __global__ void __launch_bounds__(kPBlock)
   }
 }
 
+// The grid of an init pass on bands of kPnBand rows: ptr_init_grid's, grid.y the shorter bands
+static dim3 pn_init_grid(const PtrChunk& c, int64_t H, int64_t W, bool vec) {
+  const dim3 grid = ptr_init_grid(c, H, W, vec);
+  const int64_t bands = (H + kPnBand - 1) / kPnBand;
+  return dim3(grid.x, static_cast<unsigned>(bands < 65535 ? bands : 65535), grid.z);
+}
+
+// The planes of soil_stream_power_deposit_n: the deposit step's and the slope exponent, n1 = n - 1 made once on the host
+struct DnPlanes {
+  DepPlanes dep;
+  double n, n1;
+  DnPlanes at(int64_t off) const { return {dep.at(off), n, n1}; }
+};
+
+// The record of one cell of the deposit step at a slope exponent (soil_stream_power_deposit_n), and its B:
+// soil_hip.h's operations in its order, each rounded once.  pn_init_cell's slope, power, F and c; dep_init_cell's g,
+// Qup and the self-implicit (1 + g) and + g.  There is no stop plane, as in the deposit step.
+template <int K>
+__device__ __forceinline__ void dn_init_cell(uint4* __restrict__ rec, double* __restrict__ bcoef, int64_t n,
+                                             int32_t gr, float h, float e, float u, bool has_u, float dep, float qs,
+                                             float q, double xi, const double* __restrict__ xit, int64_t x, int64_t y,
+                                             int64_t H, int64_t W, uint32_t first, const PathScale& s,
+                                             const DnPlanes& in) {
+  const int kind = edge_kind<K>(gr, x, y, H, W);
+  double A = static_cast<double>(h), B = 0.0;  // a terminal: the height of the base level
+  uint32_t ptr = (first + static_cast<uint32_t>(n)) | kFinal;
+  if (kind >= 0) {
+    ptr = first + static_cast<uint32_t>(gr);
+    const double dt = in.dep.dt;
+    const double L = kind == 0 ? s.sx : (kind == 1 ? s.sy : s.dd);
+    const double Qup = __dsub_rn(static_cast<double>(qs), static_cast<double>(q));
+    const double d = __dsub_rn(xi, xit[gr]);
+    const double S = d <= 0.0 ? 0.0 : __ddiv_rn(d, L);  // (a NaN d is not <= 0: it stays a NaN)
+    const double P = in.n == 2.0 ? S : sp_pow(S, in.n1);
+    const double kd = __dmul_rn(static_cast<double>(e), dt);
+    const double F = __dmul_rn(__ddiv_rn(__dmul_rn(in.n, kd), L), P);
+    const double c = __dmul_rn(__dmul_rn(kd, in.n1), __dmul_rn(P, S));
+    const double g = static_cast<double>(dep);
+    const double b = dep_lifted(h, u, has_u, dt);
+    const double D = __dadd_rn(__dadd_rn(1.0, F), g);
+    A = __ddiv_rn(__dadd_rn(__dadd_rn(__dmul_rn(__dadd_rn(1.0, g), b), __dmul_rn(g, Qup)), c), D);
+    B = __ddiv_rn(F, D);
+  }
+  rec[n] = down_rec(ptr, kind < 0 ? 0u : 1u, A);
+  bcoef[n] = B;
+}
+
+// The init pass of the deposit step at a slope exponent: k_dep_init's seven planes and k_pn_init's iterate with the
+// gather of the receiver's value, on k_pn_init's bands of kPnBand rows for the reason given there.
+template <int K, bool VEC>
+__global__ void __launch_bounds__(kPBlock)
+    k_dn_init(uint4* __restrict__ rec, double* __restrict__ bcoef, DnPlanes in, const float* __restrict__ qs,
+              const float* __restrict__ q, const double* __restrict__ xit, int64_t H, int64_t W, PathScales scales,
+              int* __restrict__ flags) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < kPathFlags)
+    flags[threadIdx.x] = threadIdx.x == 0 ? 1 : 0;
+  const int64_t y = (static_cast<int64_t>(blockIdx.x) * kPBlock + threadIdx.x) * (VEC ? 4 : 1);
+  if (y >= W) return;
+  const int64_t first64 = static_cast<int64_t>(blockIdx.z) * H * W;
+  const uint32_t first = static_cast<uint32_t>(first64);
+  const PathScale s = scales.per_model ? scales.per_model[blockIdx.z] : scales.one;
+  rec += first64, bcoef += first64, qs += first64, q += first64, xit += first64;
+  const int32_t* const graph = in.dep.graph + first64;
+  const float* const height = in.dep.height + first64;
+  const float* const erosivity = in.dep.erosivity + first64;
+  const float* const deposition = in.dep.deposition + first64;
+  const float* const uplift = in.dep.uplift ? in.dep.uplift + first64 : nullptr;
+  const bool has_u = uplift != nullptr;
+  for (int64_t band = blockIdx.y; band * kPnBand < H; band += gridDim.y) {
+    for (int64_t x = band * kPnBand, end = x + kPnBand < H ? x + kPnBand : H; x < end; ++x) {
+      const int64_t n = x * W + y;
+      if constexpr (VEC) {
+        const int4 g = *reinterpret_cast<const int4*>(graph + n);
+        const float4 h = *reinterpret_cast<const float4*>(height + n);
+        const float4 e = *reinterpret_cast<const float4*>(erosivity + n);
+        const float4 u = uplift ? *reinterpret_cast<const float4*>(uplift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 dp = *reinterpret_cast<const float4*>(deposition + n);
+        const float4 s4 = *reinterpret_cast<const float4*>(qs + n);
+        const float4 q4 = *reinterpret_cast<const float4*>(q + n);
+        const double2 x01 = *reinterpret_cast<const double2*>(xit + n);
+        const double2 x23 = *reinterpret_cast<const double2*>(xit + n + 2);
+        dn_init_cell<K>(rec, bcoef, n + 0, g.x, h.x, e.x, u.x, has_u, dp.x, s4.x, q4.x, x01.x, xit, x, y + 0, H, W,
+                        first, s, in);
+        dn_init_cell<K>(rec, bcoef, n + 1, g.y, h.y, e.y, u.y, has_u, dp.y, s4.y, q4.y, x01.y, xit, x, y + 1, H, W,
+                        first, s, in);
+        dn_init_cell<K>(rec, bcoef, n + 2, g.z, h.z, e.z, u.z, has_u, dp.z, s4.z, q4.z, x23.x, xit, x, y + 2, H, W,
+                        first, s, in);
+        dn_init_cell<K>(rec, bcoef, n + 3, g.w, h.w, e.w, u.w, has_u, dp.w, s4.w, q4.w, x23.y, xit, x, y + 3, H, W,
+                        first, s, in);
+      } else {
+        dn_init_cell<K>(rec, bcoef, n, graph[n], height[n], erosivity[n], uplift ? uplift[n] : 0.0f, has_u,
+                        deposition[n], qs[n], q[n], xit[n], xit, x, y, H, W, first, s, in);
+      }
+    }
+  }
+}
+
 static thread_local DepInfo t_pn_info{0, 0, 0, 0};  // soil_stream_power_n_info
 
 // One chunk of `models` models: the start (soil_stream_power's init), then `iters` times k_pn_init, each a solve
@@ -716,10 +759,7 @@ static int pn_chunk(StepOut o, const PnPlanes& in, double* x, int iters, int64_t
     return vec;
   };
   auto init = [&](const PtrChunk& c) {
-    const dim3 grid = ptr_init_grid(c, H, W, vec);
-    const int64_t bands = (H + kPnBand - 1) / kPnBand;
-    launch_vec(vec, k_pn_init<K, true>, k_pn_init<K, false>,
-               dim3(grid.x, static_cast<unsigned>(bands < 65535 ? bands : 65535), grid.z), st, c.rec[0],
+    launch_vec(vec, k_pn_init<K, true>, k_pn_init<K, false>, pn_init_grid(c, H, W, vec), st, c.rec[0],
                static_cast<double*>(c.extra[0]), in, x, H, W, scales, c.flags);
     return vec;
   };
@@ -782,6 +822,96 @@ static int power_n_run(const char* what, StepOut o, const PnPlanes& in, int iter
   return rc;
 }
 
+// ---- the deposit driver: soil_stream_power_deposit and, with a slope exponent, soil_stream_power_deposit_n ----
+//
+// Below the init passes of both sections, which a chunk launches: k_dep_init at n == 1, k_dn_init at any other n.
+
+// One chunk of `models` models: x^0, then `iters` times q, Qs and a solve pass from them, then the flux of the
+// returned iterate.  `in`, `o` and `w` are the chunk's own.  in.n == 1: x^0 = b from the first q pass, whose zero
+// planes stand in for the first iteration's q and Qs, and k_dep_init.  Any other n (soil_stream_power_deposit_n):
+// x^0 is soil_stream_power's solve, every iteration has its q pass and accumulation, and the init pass is k_dn_init.
+template <int K>
+static int dep_chunk(DepInfo& info, StepOut o, const DnPlanes& in, const DepWork& w, int iters, int64_t models,
+                     int64_t H, int64_t W, int edge, const PathScales& scales, char* scratch, RakeStats& rake,
+                     hipStream_t st) {
+  info.chunks += 1;
+  const DepPlanes& dep = in.dep;
+  const bool newton = in.n != 1.0;
+  const bool vec = ptr_vec_init(W, dep.graph, dep.height, dep.erosivity, dep.uplift, dep.deposition, w.qs, w.q, w.x);
+  auto init = [&](const PtrChunk& c) {
+    launch_vec(vec, k_dep_init<K, true>, k_dep_init<K, false>, ptr_init_grid(c, H, W, vec), st, c.rec[0],
+               static_cast<double*>(c.extra[0]), dep, w.qs, w.q, H, W, scales, c.flags);
+    return vec;
+  };
+  auto init_n = [&](const PtrChunk& c) {
+    launch_vec(vec, k_dn_init<K, true>, k_dn_init<K, false>, pn_init_grid(c, H, W, vec), st, c.rec[0],
+               static_cast<double*>(c.extra[0]), in, w.qs, w.q, w.x, H, W, scales, c.flags);
+    return vec;
+  };
+  if (newton) {
+    const DownPlanes power{dep.graph, nullptr, dep.height, dep.erosivity, dep.uplift, dep.dt};
+    auto start = [&](const PtrChunk& c) {
+      launch_vec(vec, k_down_init<K, true, kPower, true>, k_down_init<K, false, kPower, true>,
+                 ptr_init_grid(c, H, W, vec), st, c.rec[0], static_cast<double*>(c.extra[0]), power, H, W, scales,
+                 c.flags);
+      return vec;
+    };
+    if (int rc = solve_pass(info.launches, models, H, W, scratch, st, start, w.x, StepOut{}); rc != SOIL_OK) return rc;
+  } else {
+    dep_launch_q<K>(info, w, dep, models, H, W, true, st);
+    SOIL_LAUNCH_CHECK();
+  }
+  for (int k = 1; k <= iters; ++k) {
+    if (k > 1 || newton) {
+      dep_launch_q<K>(info, w, dep, models, H, W, false, st);
+      SOIL_LAUNCH_CHECK();
+      if (int rc = rake_accumulate(w.qs, dep.graph, w.q, models, H, W, edge, st, WS_DEPOSIT_RAKE, &rake); rc != SOIL_OK)
+        return rc;
+    }
+    const StepOut ok = k == iters ? o : StepOut{};
+    if (int rc = newton ? solve_pass(info.launches, models, H, W, scratch, st, init_n, w.x, ok)
+                        : solve_pass(info.launches, models, H, W, scratch, st, init, w.x, ok);
+        rc != SOIL_OK)
+      return rc;
+  }
+  if (o.flux) {
+    dep_launch_q<K>(info, w, dep, models, H, W, false, st);
+    SOIL_LAUNCH_CHECK();
+    if (int rc = rake_accumulate(o.flux, dep.graph, w.q, models, H, W, edge, st, WS_DEPOSIT_RAKE, &rake); rc != SOIL_OK)
+      return rc;
+  }
+  return SOIL_OK;
+}
+
+static thread_local DepInfo t_dn_info{0, 0, 0, 0};  // soil_stream_power_deposit_n_info
+
+// A call, under the entry's name: the chunks of ptr_run through slot WS_DEPOSIT, the chunk's planes in
+// WS_DEPOSIT_PLANES beside them.  `info`: the record of the entry's family; the deposit step at a slope exponent
+// shares the slots, as a thread's calls of one entry do.
+static int deposit_run(const char* what, DepInfo& info, StepOut o, const DnPlanes& in, int iters, int64_t B, int64_t H,
+                       int64_t W, int edge, const float* scales, int64_t n_scales, void* stream) {
+  if (int rc = check_deposit(what, o, in.dep, in.n, iters, scales, B, H, W, edge, n_scales); rc != SOIL_OK) return rc;
+  SOIL_DEVICE();
+  const hipStream_t st = as_stream(stream);
+  info = DepInfo{0, 0, iters, 0};
+  IterSetup s;
+  if (int rc = iter_setup(s, WS_DEPOSIT_PLANES, {8, 4, 4}, o.residual, B, H, W, scales, n_scales, st); rc != SOIL_OK)
+    return rc;
+  const DepWork w{reinterpret_cast<double*>(s.plane[0]), reinterpret_cast<float*>(s.plane[1]),
+                  reinterpret_cast<float*>(s.plane[2])};
+  RakeStats rake{0, 0};
+  PtrInfo pinfo{0, 0, 0, 0};
+  auto go = edge == SOIL_D4 ? dep_chunk<4> : dep_chunk<8>;
+  const int rc = ptr_run(WS_DEPOSIT, pinfo, B, H, W, sizeof(double), scales, n_scales, PathScale{1.0, 1.0, 1.0}, st,
+                         [&](int64_t b0, int64_t nb, const PathScales& sc, char* scratch) {
+                           const int64_t off = b0 * H * W;
+                           return go(info, o.at(off, b0), in.at(off), w, iters, nb, H, W, edge, sc, scratch, rake, st);
+                         });
+  info.launches += rake.launches;
+  info.bytes = s.bytes + rake.bytes;
+  return rc;
+}
+
 }  // namespace soil
 
 using namespace soil;
@@ -821,22 +951,48 @@ int soil_stream_power_deposit(float* out, double* out64, float* flux, double* re
                               const int32_t* graph, const float* erosivity, const float* deposition,
                               const float* uplift, int64_t H, int64_t W, int edge, const float scale[2], double dt,
                               int iters, void* stream) {
-  return deposit_run("stream_power_deposit", StepOut{out, out64, flux, residual},
-                     DepPlanes{graph, height, erosivity, uplift, deposition, dt}, iters, 1, H, W, edge, scale, 1, stream);
+  return deposit_run("stream_power_deposit", t_dep_info, StepOut{out, out64, flux, residual},
+                     DnPlanes{{graph, height, erosivity, uplift, deposition, dt}, 1.0, 0.0}, iters, 1, H, W, edge, scale,
+                     1, stream);
 }
 
 int soil_stream_power_deposit_batch(float* out, double* out64, float* flux, double* residual, const float* height,
                                     const int32_t* graph, const float* erosivity, const float* deposition,
                                     const float* uplift, int64_t B, int64_t H, int64_t W, int edge,
                                     const float* scales, int64_t n_scales, double dt, int iters, void* stream) {
-  return deposit_run("stream_power_deposit_batch", StepOut{out, out64, flux, residual},
-                     DepPlanes{graph, height, erosivity, uplift, deposition, dt}, iters, B, H, W, edge, scales, n_scales,
-                     stream);
+  return deposit_run("stream_power_deposit_batch", t_dep_info, StepOut{out, out64, flux, residual},
+                     DnPlanes{{graph, height, erosivity, uplift, deposition, dt}, 1.0, 0.0}, iters, B, H, W, edge, scales,
+                     n_scales, stream);
 }
 
 int soil_stream_power_deposit_info(int64_t info[4]) {
   SOIL_REQUIRE(info, "stream_power_deposit_info: null info");
   info[0] = t_dep_info.launches, info[1] = t_dep_info.chunks, info[2] = t_dep_info.iters, info[3] = t_dep_info.bytes;
+  return SOIL_OK;
+}
+
+int soil_stream_power_deposit_n(float* out, double* out64, float* flux, double* residual, const float* height,
+                                const int32_t* graph, const float* erosivity, const float* deposition,
+                                const float* uplift, int64_t H, int64_t W, int edge, const float scale[2], double dt,
+                                double n, int iters, void* stream) {
+  return deposit_run("stream_power_deposit_n", t_dn_info, StepOut{out, out64, flux, residual},
+                     DnPlanes{{graph, height, erosivity, uplift, deposition, dt}, n, n - 1.0}, iters, 1, H, W, edge,
+                     scale, 1, stream);
+}
+
+int soil_stream_power_deposit_n_batch(float* out, double* out64, float* flux, double* residual, const float* height,
+                                      const int32_t* graph, const float* erosivity, const float* deposition,
+                                      const float* uplift, int64_t B, int64_t H, int64_t W, int edge,
+                                      const float* scales, int64_t n_scales, double dt, double n, int iters,
+                                      void* stream) {
+  return deposit_run("stream_power_deposit_n_batch", t_dn_info, StepOut{out, out64, flux, residual},
+                     DnPlanes{{graph, height, erosivity, uplift, deposition, dt}, n, n - 1.0}, iters, B, H, W, edge,
+                     scales, n_scales, stream);
+}
+
+int soil_stream_power_deposit_n_info(int64_t info[4]) {
+  SOIL_REQUIRE(info, "stream_power_deposit_n_info: null info");
+  info[0] = t_dn_info.launches, info[1] = t_dn_info.chunks, info[2] = t_dn_info.iters, info[3] = t_dn_info.bytes;
   return SOIL_OK;
 }
 

@@ -844,6 +844,57 @@ class ErosionBatch:
         return soil.stream_power_deposit_batch(filled, graph, soil.erosivity(area, K, m), soil.deposition(area, G, cell),
                                                e, scale, dt, uplift, int(iters), False, flux, residual)
 
+    def stream_power_deposit_n(self, dt, K, m=0.5, G=1.0, n=2.0, iters=None, kind="steepest", edge=None, T=None,
+                               offset=0, uplift=None, flux=False, residual=False):
+        """stream_power_deposit() at a slope exponent `n` in 1 .. 16, dh/dt = u - K A^m S^n + (G / A) Qs: the same
+        chain, conditioned() -> drainage(graph=g) -> soil.erosivity(area, K, m) and soil.deposition(area, G, cell) ->
+        soil.stream_power_deposit_n_batch with `iters` iterations (None: its default) and the batch's scale(s).
+        Returns what stream_power_deposit() returns; the batch's own planes are not touched.  The iteration has a
+        domain (soil.stream_power_deposit_n): ask for the residual where K dt / L is large and G is above 1.  A bad
+        argument raises ValueError before any device work.  Synchronises the stream (the fill does)."""
+        from . import soil
+        who = "ErosionBatch.stream_power_deposit_n"
+        _check.number(who, "dt", dt)
+        _check.number(who, "K", K)
+        _check.number(who, "m", m, lo=None)
+        _check.number(who, "G", G)
+        n = _check.exponent(who, n)
+        iters = _check.count(who, "iters", soil.DEPOSIT_N_ITERS if iters is None else iters)
+        e, scale = self._routing("stream_power_deposit_n", kind, edge, T, offset, uplift)
+        filled, graph = self.conditioned(kind, e, T, offset)
+        area = self.drainage(graph=graph, edge=e)
+        pairs = scale if self.scales is not None else [scale] * self.B  # (a cell's area: stream_power_deposit's)
+        cell = silt.tensor.from_numpy(np.array([s[0] * s[1] for s in pairs], np.float32).reshape(self.B, 1, 1)).gpu()
+        return soil.stream_power_deposit_n_batch(filled, graph, soil.erosivity(area, K, m),
+                                                 soil.deposition(area, G, cell), e, scale, dt, n, uplift, int(iters),
+                                                 False, flux, residual)
+
+    def evolve_deposit(self, dt, K, G, n, m=0.5, kappa=None, critical_slope=None, uplift=None, iters=None,
+                       kind="steepest", edge=None, T=None, offset=0, first_axis=0):
+        """The landscape-evolution step with every term the library has: stream_power_deposit_n(dt, K, m, G, n, iters,
+        ...), then with `critical_slope` (as in slope_limited()) the collapse to the threshold, soil.slope_limit_batch
+        with the step's `edge`, then soil.diffuse_batch over the same `dt` with the diffusivity `kappa` and
+        border="fixed", as in evolve().  The uplift is applied once, in the first step.  Returns the (B, H, W) float32
+        heights; the batch's own planes are not touched.  A bad argument raises ValueError before any device work.
+        Synchronises the stream (the fill does)."""
+        from . import soil
+        who = "ErosionBatch.evolve_deposit"
+        self._check_diffuse("evolve_deposit", dt, kappa, None, None, None, "fixed", first_axis)
+        e = self._edge("evolve_deposit", edge)
+        if critical_slope is not None:
+            critical_slope = self._critical_slope("evolve_deposit", critical_slope)
+        _check.number(who, "K", K)
+        _check.number(who, "m", m, lo=None)
+        _check.number(who, "G", G)
+        _check.exponent(who, n)
+        if iters is not None:
+            _check.count(who, "iters", iters)
+        _, scale = self._routing("evolve_deposit", kind, edge, T, offset, uplift)
+        carved = self.stream_power_deposit_n(dt, K, m, G, n, iters, kind, edge, T, offset, uplift)
+        if critical_slope is not None:
+            carved = soil.slope_limit_batch(carved, scale, critical_slope, e)
+        return soil.diffuse_batch(carved, scale, dt, kappa, border="fixed", first_axis=first_axis)
+
     def _check_diffuse(self, who, dt, kappa, diffusivity, uplift, fixed, border, first_axis):
         """The arguments of diffuse() and of the diffusion half of evolve(), or ValueError."""
         full = "ErosionBatch.%s" % who
@@ -874,9 +925,10 @@ class ErosionBatch:
         what the stream-power step left them.  The uplift is applied once, in the stream-power step.  With `G` (a
         finite number >= 0) the first half is stream_power_deposit(dt, K, m, G, iters, ...) instead: the eroded
         material is deposited on its way down.  With `n` != 1 (a slope exponent in 1 .. 16) the first half is
-        stream_power(..., n=n, iters=iters); the deposit step stays at n = 1, so `G` together with n != 1 raises
-        ValueError.  Returns the (B, H, W) float32 heights; the batch's own planes are not touched.  A bad argument
-        raises ValueError before any device work.  Synchronises the stream (the fill does)."""
+        stream_power(..., n=n, iters=iters); `G` together with n != 1 raises ValueError here: that step is
+        evolve_deposit(), on stream_power_deposit_n().  Returns the (B, H, W) float32 heights; the batch's own planes
+        are not touched.  A bad argument raises ValueError before any device work.  Synchronises the stream (the fill
+        does)."""
         from . import soil
         carved, scale = self._carved("evolve", dt, K, m, kappa, uplift, kind, edge, T, offset, first_axis, G, iters, n)
         return soil.diffuse_batch(carved, scale, dt, kappa, border="fixed", first_axis=first_axis)

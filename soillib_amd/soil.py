@@ -502,9 +502,15 @@ def chi(graph, area, edge_, scale, theta=0.45, A0=1.0, stop=None):
 # ---- erosion-deposition (soil_hip.h: "flow graphs: erosion-deposition"): the stream-power step with a deposition
 # term fed by the upstream sum of what the step removes, a fixed number of iterations.  Stream-ordered.
 
+# The default `iters` of stream_power_deposit_n: the count at which n <= 2 with G <= 1 has converged on the bench
+# terrains at every size (the table of "Erosion-deposition at slope exponents above 1")
+DEPOSIT_N_ITERS = 28
+
+
 def _stream_power_deposit(who, dims, height, graph, erosivity, deposition, edge_, scale, dt, uplift, iters, double,
-                          flux, residual):
-    """soil_stream_power_deposit and its _batch form.  Every check comes before any device work."""
+                          flux, residual, n=None):
+    """soil_stream_power_deposit and its _batch form; with `n` soil_stream_power_deposit_n and its _batch form.  Every
+    check comes before any device work."""
     shape = _shape(dims, graph, "%s: graph" % who)
     e = _check.edge(who, edge_)
     _int_plane(graph, shape, "%s: graph" % who)
@@ -514,14 +520,16 @@ def _stream_power_deposit(who, dims, height, graph, erosivity, deposition, edge_
     pairs, tail = _scales(who, dims, scale, shape[0])
     _positive(who, pairs, scale)
     dt = _check.number(who, "dt", dt)
+    exponent = () if n is None else (_check.exponent(who, n),)
     iters = _check.count(who, "iters", iters)
     g_ptr = _gpu(graph, silt.int32, "graph")
     h_ptr, k_ptr, d_ptr, u_ptr = (_opt_f(t, name) for name, t, _ in planes)
     out, outs = _out_pair(shape, double)
     f = silt.tensor(silt.float32, silt.shape(*shape), silt.gpu) if flux else None
     r = silt.tensor(silt.float64, silt.shape(1 if dims == 2 else shape[0]), silt.gpu) if residual else None
-    _call("soil_stream_power_deposit" + ("" if dims == 2 else "_batch"), *outs, None if f is None else f.c_ptr,
-          None if r is None else r.c_ptr, h_ptr, g_ptr, k_ptr, d_ptr, u_ptr, *shape, e, *tail, dt, iters, _abi.stream())
+    _call("soil_stream_power_deposit" + ("" if n is None else "_n") + ("" if dims == 2 else "_batch"), *outs,
+          None if f is None else f.c_ptr, None if r is None else r.c_ptr, h_ptr, g_ptr, k_ptr, d_ptr, u_ptr, *shape, e,
+          *tail, dt, *exponent, iters, _abi.stream())
     extras = tuple(t for t in (f, r) if t is not None)
     return (out,) + extras if extras else out
 
@@ -529,7 +537,8 @@ def _stream_power_deposit(who, dims, height, graph, erosivity, deposition, edge_
 def stream_power_deposit(height, graph, erosivity, deposition, edge_, scale, dt, uplift=None, iters=8, double=False,
                          flux=False, residual=False):
     """soil_stream_power_deposit: one implicit step of stream-power incision with sediment deposition (the
-    erosion-deposition model; slope exponent 1 — the deposit step has no counterpart of stream_power_n yet) along `graph`: stream_power's step plus (G / A) Qs, Qs the net material
+    erosion-deposition model; slope exponent 1 — any other exponent in 1 .. 16: stream_power_deposit_n) along
+    `graph`: stream_power's step plus (G / A) Qs, Qs the net material
     removed upstream, by `iters` fixed-point iterations of an upstream sum and a downstream solve.  `erosivity` is
     K A^m (soil.erosivity), `deposition` G cell / A (soil.deposition), `uplift` a float32 plane or None.  Returns the
     new heights, float32 (float64 with `double`); with `flux` and / or `residual` a tuple (heights, flux, residual) of
@@ -568,6 +577,40 @@ def stream_power_deposit_info():
     """What this thread's last stream_power_deposit / _batch call did (soil_stream_power_deposit_info): a dict with the
     number of kernel `launches`, of `chunks`, the `iters` run and the `scratch_bytes` it asked for."""
     return _call_info("soil_stream_power_deposit_info", ("launches", "chunks", "iters", "scratch_bytes"))
+
+
+# The deposit step at a slope exponent above 1 (soil_hip.h: "flow graphs: erosion-deposition at slope exponents above
+# 1"): each iteration renews the Newton tangent of stream_power_n and the upstream sum of the deposit step together.
+
+def stream_power_deposit_n(height, graph, erosivity, deposition, edge_, scale, dt, n, uplift=None,
+                           iters=DEPOSIT_N_ITERS, double=False, flux=False, residual=False):
+    """soil_stream_power_deposit_n: one implicit step of dh/dt = u - K A^m S^n + (G / A) Qs along `graph` with a slope
+    exponent `n` in 1 .. 16: `iters` iterations, each the deposit step's upstream sum of what the iterate before
+    removed and one solve of stream_power's rounds with the coefficients of stream_power_n's linearisation about that
+    iterate, started from stream_power's own result.  The planes and the returned values are stream_power_deposit's:
+    the heights, or with `flux` and / or `residual` a tuple (heights, flux, residual) of those asked for.  The
+    iteration has a domain: for K dt / L up to order 1 and G <= 1 it contracts for n up to 3, with
+    G = 2 it can diverge for n >= 2; under a K dt / L of order 100 it stalls across lakes for n >= 2 and diverges for
+    G = 2, while every value stays finite — so read the residual.  The default of `iters` is the count at which
+    n <= 2 with G <= 1 has reached the float32 floor of the upstream sum on the bench terrains at every size.  A zero
+    deposition plane gives stream_power_n's bits, n == 1 stream_power_deposit's; n < 1 is refused.  `height` is left
+    as it is."""
+    return _stream_power_deposit("stream_power_deposit_n", 2, height, graph, erosivity, deposition, edge_, scale, dt,
+                                 uplift, iters, double, flux, residual, n)
+
+
+def stream_power_deposit_n_batch(height, graph, erosivity, deposition, edge_, scale, dt, n, uplift=None,
+                                 iters=DEPOSIT_N_ITERS, double=False, flux=False, residual=False):
+    """`stream_power_deposit_n` of each of the B models of (B, H, W) planes (soil_stream_power_deposit_n_batch);
+    `scale` is one pair or B pairs; the residual tensor has B entries."""
+    return _stream_power_deposit("stream_power_deposit_n_batch", 3, height, graph, erosivity, deposition, edge_, scale,
+                                 dt, uplift, iters, double, flux, residual, n)
+
+
+def stream_power_deposit_n_info():
+    """What this thread's last stream_power_deposit_n / _batch call did (soil_stream_power_deposit_n_info): a dict
+    with the number of kernel `launches`, of `chunks`, the `iters` run and the `scratch_bytes` it asked for."""
+    return _call_info("soil_stream_power_deposit_n_info", ("launches", "chunks", "iters", "scratch_bytes"))
 
 
 # ---- slope exponents above 1 (soil_hip.h: "flow graphs: slope exponents above 1"): the stream-power step as Newton
