@@ -1067,6 +1067,67 @@ int soil_stream_power_batch(float* out, double* out64, const float* height, cons
  * forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
 int soil_downstream_info(int64_t info[4]);
 
+/* --------------------------------------------- flow graphs: upstream extrema */
+
+/* A minimum or a maximum carried UP a receiver graph: for every cell the least (the greatest) of `value` over all the
+ * cells that drain through it, and which cell holds it.  With the heights as `value` and the graph that depression
+ * filling and flat routing give, the minimum is the breached (carved) surface — every cell lowered to the lowest
+ * height of anything that drains through it, never above the DEM and never rising along the graph (`carve` in
+ * fastscape, Cordonnier et al. 2019; "breach" in Lindsay's tools) —; the maximum of soil_flow_paths' length is the
+ * longest flow path into a cell, the maximum of the heights the catchment's highest point.  The reference has no such
+ * call; the definition is this library's.
+ *
+ * Grid (H, W), cell n = x * W + y, `edge` D4 or D8, `graph` any int32 plane.  Edge rule, `stop` and terminals are
+ * word for word those of soil_flow_paths above: cell n has an edge to r = graph[n] iff r is the index of one of its K
+ * neighbours inside the model, anything else (INT32_MIN included) is no edge, and a cell with stop[n] != 0 has no
+ * outgoing edge whatever its graph entry: it collects its catchment and passes nothing on.  `stop` may be NULL.
+ *
+ * Reach.  u reaches n iff n is u or lies on the walk from u along edges.  Cycles are allowed: a cell on a cycle is
+ * reached by every cell of the cycle and by everything that drains into it.  No cell is special-cased, and nothing is
+ * -1 or NaN because of a cycle.
+ *
+ * Order.  Values are compared by the integer key of csrc/erosion_quantiles.hip key_of, never as floats:
+ *     -inf < ... < -0 < +0 < ... < +inf < NaN
+ * with denormals kept as they are and every NaN, whatever its sign and payload, one key.
+ *
+ * op 0, min.  out[n] = the least value[u] over all u that reach n, its own bits.  A NaN is ignored wherever a number
+ * reaches the cell; out[n] is NaN — the quiet NaN 0x7fc00000 whatever the payloads were — only where every value
+ * that reaches n is NaN.
+ * op 1, max.  out = -min(-value) under the same rule, negation being the exact flip of the sign bit: a NaN is again
+ * ignored (and written as 0x7fc00000 where nothing else reaches the cell), and +0 wins over -0.
+ * `arg` (int32): the index within the model of the cell that attains out[n]; among cells of equal key the smallest
+ * index, for min and for max alike; -1 where out[n] is NaN.
+ * Either of `out` and `arg` may be NULL, not both.
+ *
+ * The result is one definite bit pattern, fixed by the graph and the planes alone: min is idempotent and order-free,
+ * so path, chunking, launch shape and run do not show.  ceil(log2(H * W)) pointer-doubling rounds over 4-byte
+ * pointers and one plane of packed (key << 32 | index) words lowered by 64-bit atomic minima (csrc/upstream.hip, with
+ * the proof of the round rule).
+ *
+ * Both entries are stream-ordered and do not synchronise (a call that finds its cached scratch too small
+ * synchronises the device before replacing it, as everywhere); a host thread's calls on one device share one cached
+ * scratch block of their own: issue them on ONE stream, or order the streams yourself.
+ *
+ * Batch form: the conventions of soil_flow_paths_batch.  Model-major planes; graph and `arg` entries are indices
+ * WITHIN their model; nothing reaches another model; model b's slice of each output is bit for bit what the single
+ * call gives for model b's slices alone.  Chunks of whole models by soil_flow_paths_batch's rule (as many as would
+ * keep 16-byte records on 32-bit offsets, at most 65535, SOIL_FLOW_BATCH_CELLS lowers the cells of a chunk; a single
+ * model above that is a chunk of its own on 64-bit offsets), and per chunk one init launch, the rounds of ONE model
+ * and one final launch, whatever B is.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): null `graph` or `value`, both outputs null, an output that aliases an input plane (or the other
+ * output), B, H or W < 1, H * W > INT32_MAX, an invalid `edge`, `op` not 0 or 1.  Otherwise, without a device:
+ * SOIL_ERR_NO_DEVICE. */
+int soil_upstream_extreme(float* out, int32_t* arg, const int32_t* graph, const float* value, const int32_t* stop,
+                          int64_t H, int64_t W, int edge, int op, void* stream);
+int soil_upstream_extreme_batch(float* out, int32_t* arg, const int32_t* graph, const float* value,
+                                const int32_t* stop, int64_t B, int64_t H, int64_t W, int edge, int op, void* stream);
+/* What the calling host thread's last call of one of the two entries above did, as soil_flow_paths_info: info[0]
+ * chunks, info[1] chunks whose init pass took the 16-byte form, info[2] chunks on 64-bit offsets (SOIL_PATHS_IDX64=1
+ * forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
+int soil_upstream_extreme_info(int64_t info[4]);
+
 /* ----------------------------------------- flow graphs: erosion-deposition */
 
 /* The stream-power step with sediment deposition: the erosion-deposition (xi-q) model of Davy & Lague in the implicit

@@ -32,6 +32,9 @@ from soillib_amd.soil import (flat_distance, flat_distance_batch, flat_distance_
                               flat_receivers_batch, resolve_flats, resolve_flats_batch)
 from soillib_amd.soil import slope_limit, slope_limit_batch, slope_limit_info  # noqa: F401
 from soillib_amd.soil import condition, condition_batch, fill_depressions_batch, fill_info  # noqa: F401
+from soillib_amd.soil import (breach, breach_batch, condition_breached, condition_breached_batch,  # noqa: F401
+                              upstream_info, upstream_length, upstream_length_batch, upstream_max,
+                              upstream_max_batch, upstream_min, upstream_min_batch)
 from soillib_amd.io import geotiff, geotiff_meta, mesh, tiff  # noqa: F401  (python/source/io.cpp:20-110)
 from soillib_amd.legacy import (buffer, clamp, data_t, erode, index, map_t, multiply, param_t,  # noqa: F401
                                 resize)

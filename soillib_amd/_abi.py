@@ -241,6 +241,10 @@ SIGNATURES = {
     "soil_stream_power": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double, vp]),
     "soil_stream_power_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, cint, F3, i64, C.c_double, vp]),
     "soil_downstream_info": (cint, [C.POINTER(i64)]),
+    # upstream minima / maxima: out / arg (one may be NULL), graph, value, stop (may be NULL); op 0 min, 1 max
+    "soil_upstream_extreme": (cint, [vp, vp, vp, vp, vp, i64, i64, cint, cint, vp]),
+    "soil_upstream_extreme_batch": (cint, [vp, vp, vp, vp, vp, i64, i64, i64, cint, cint, vp]),
+    "soil_upstream_extreme_info": (cint, [C.POINTER(i64)]),
     # the stream-power step with deposition: out / out64, flux / residual (may be NULL), height, graph, erosivity,
     # deposition, uplift (may be NULL); host scale pairs, dt, iters
     "soil_stream_power_deposit": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double, cint, vp]),

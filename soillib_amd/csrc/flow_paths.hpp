@@ -1,6 +1,7 @@
 // flow_paths.hpp — the pointer-doubling engine along a receiver graph, once: flow_paths.hip (terminal, steps, length)
 // and downstream.hip (the linear recurrence x[n] = a L + b x[r(n)]) run it over 16-byte records whose first word is
-// the pointer with kFinal in bit 31.  Here are
+// the pointer with kFinal in bit 31; upstream.hip (minima and maxima UP the graph) runs it over 4-byte records, the
+// pointer alone, beside one plane of 8 bytes a cell (PtrSizes).  Here are
 //
 //   device  rec_at, the edge rule (edge_kind), the append to a work-group's list (path_append) and the bodies of the
 //           dense and the listed round (ptr_round, ptr_list) over a per-cell operation `bool cell(IDX n)`: "one round
@@ -177,14 +178,25 @@ inline int64_t ptr_chunk_models(int64_t cells_per_model) {
   return chunk_models(static_cast<int64_t>((1ull << 32) / sizeof(uint4)) - 1, cells_per_model, kPathsMaxGridZ);
 }
 
-// The scratch of a chunk of `elem` cells, in this order: two record buffers, two planes of `extra` bytes a cell
+// What a file keeps per cell: two record buffers of `rec` bytes a cell (16 unless the file says otherwise; the chunk
+// rule and the choice of the offsets stay those of 16-byte records either way, so that every file cuts a batch alike)
+// and `planes` planes of `extra` bytes a cell (0: none).  A bare byte count is downstream.hip's B: two planes.
+struct PtrSizes {
+  size_t extra, rec;
+  int planes;
+  PtrSizes(size_t extra_bytes, size_t rec_bytes = sizeof(uint4), int n_planes = 2)
+      : extra(extra_bytes), rec(rec_bytes), planes(n_planes) {}
+};
+
+// The scratch of a chunk of `elem` cells, in this order: two record buffers, the planes of `extra` bytes a cell
 // (0: none; downstream.hip's B), two lists of `groups` segments, their fills, the control words.
 struct PtrLayout {
   unsigned groups;
   size_t seg, b_rec, b_extra, b_list, b_fill;
-  size_t bytes() const { return 2 * b_rec + 2 * b_extra + 2 * b_list + 2 * b_fill + 256; }
+  int planes;
+  size_t bytes() const { return 2 * b_rec + planes * b_extra + 2 * b_list + 2 * b_fill + 256; }
 };
-inline PtrLayout ptr_layout(int64_t elem, size_t extra) {
+inline PtrLayout ptr_layout(int64_t elem, PtrSizes sizes) {
   static const unsigned groups_env = [] {
     const char* e = std::getenv("SOIL_PATHS_GROUPS");
     return e && std::atoi(e) > 0 ? static_cast<unsigned>(std::atoi(e)) : 256u * 32u;
@@ -193,8 +205,9 @@ inline PtrLayout ptr_layout(int64_t elem, size_t extra) {
   L.groups = std::min(blocks_for(elem, kPBlock), groups_env);
   // a work-group's segment of the lists: its share of the cells, in whole work-groups' worth of entries
   L.seg = ((static_cast<size_t>(elem) + L.groups - 1) / L.groups + 255) / 256 * 256;
-  L.b_rec = align256(sizeof(uint4) * static_cast<size_t>(elem));
-  L.b_extra = align256(extra * static_cast<size_t>(elem));
+  L.b_rec = align256(sizes.rec * static_cast<size_t>(elem));
+  L.b_extra = align256(sizes.extra * static_cast<size_t>(elem));
+  L.planes = sizes.planes;
   L.b_list = align256(sizeof(uint32_t) * L.seg * L.groups);
   L.b_fill = align256(sizeof(uint32_t) * L.groups);
   return L;
@@ -202,7 +215,7 @@ inline PtrLayout ptr_layout(int64_t elem, size_t extra) {
 
 // One chunk at work: its buffers carved out of the call's block, its launch shapes and its round plan
 struct PtrChunk {
-  uint4* rec[2];
+  uint4* rec[2];   // (records of PtrSizes::rec bytes: a file with other records than uint4 casts)
   void* extra[2];  // null without the plane
   uint32_t* list[2];
   uint32_t* fill[2];
@@ -261,14 +274,16 @@ void ptr_launch_round(const PtrChunk& c, const PtrRound& q, hipStream_t st, List
 //   round(chunk, PtrRound)    launches the file's dense or listed round, 32- or 64-bit by chunk.idx32
 //   final(chunk, grid, rec)   launches the file's final pass over `rec`
 template <typename Init, typename Round, typename Final>
-int ptr_chunk(PtrInfo& info, int64_t models, int64_t H, int64_t W, size_t extra, char* scratch, Init init,
+int ptr_chunk(PtrInfo& info, int64_t models, int64_t H, int64_t W, PtrSizes sizes, char* scratch, Init init,
               Round round, Final fin) {
   const int64_t hw = H * W, elem = models * hw;
-  const PtrLayout L = ptr_layout(elem, extra);
+  const size_t extra = sizes.extra;
+  const PtrLayout L = ptr_layout(elem, sizes);
   PtrChunk c;
   char* p = scratch;
   c.rec[0] = reinterpret_cast<uint4*>(p), c.rec[1] = reinterpret_cast<uint4*>(p + L.b_rec), p += 2 * L.b_rec;
-  c.extra[0] = extra ? p : nullptr, c.extra[1] = extra ? p + L.b_extra : nullptr, p += 2 * L.b_extra;
+  c.extra[0] = extra ? p : nullptr, c.extra[1] = extra && L.planes > 1 ? p + L.b_extra : nullptr;
+  p += L.planes * L.b_extra;
   c.list[0] = reinterpret_cast<uint32_t*>(p), c.list[1] = reinterpret_cast<uint32_t*>(p + L.b_list), p += 2 * L.b_list;
   c.fill[0] = reinterpret_cast<uint32_t*>(p), c.fill[1] = reinterpret_cast<uint32_t*>(p + L.b_fill), p += 2 * L.b_fill;
   c.flags = reinterpret_cast<int*>(p);
@@ -317,16 +332,16 @@ struct PtrBlock {
   int64_t per, cells;
   size_t b_scales, b_chunk;
 };
-inline PtrBlock ptr_block(int64_t B, int64_t hw, size_t extra, const float* scales, int64_t n_scales) {
+inline PtrBlock ptr_block(int64_t B, int64_t hw, PtrSizes sizes, const float* scales, int64_t n_scales) {
   const int64_t per = ptr_chunk_models(hw), cells = (B < per ? B : per) * hw;
   const bool per_model = scales && n_scales > 1;
   return PtrBlock{per, cells, per_model ? align256(sizeof(PathScale) * static_cast<size_t>(B)) : 0,
-                  ptr_layout(cells, extra).bytes()};
+                  ptr_layout(cells, sizes).bytes()};
 }
 template <typename Chunk>
-int ptr_run(WorkspaceSlot slot, PtrInfo& info, int64_t B, int64_t H, int64_t W, size_t extra, const float* scales,
+int ptr_run(WorkspaceSlot slot, PtrInfo& info, int64_t B, int64_t H, int64_t W, PtrSizes sizes, const float* scales,
             int64_t n_scales, PathScale none, hipStream_t st, Chunk chunk) {
-  const auto [per, cells, b_scales, b_chunk] = ptr_block(B, H * W, extra, scales, n_scales);
+  const auto [per, cells, b_scales, b_chunk] = ptr_block(B, H * W, sizes, scales, n_scales);
   info = PtrInfo{0, 0, 0, 0};
   const bool per_model = b_scales != 0;
   void* base = nullptr;

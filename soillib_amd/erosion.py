@@ -1020,6 +1020,57 @@ class ErosionBatch:
             graph = soil.random_weighted_batch(filled, e, self.seeds, int(offset), float(T))
         return filled, soil.resolve_flats_batch(filled, e, graph)
 
+    # ---- upstream extrema and breaching (soil_hip.h: "flow graphs: upstream extrema") ----
+
+    def _upstream(self, who, batch_call, value, graph, stop, edge, arg):
+        e = self._edge(who, edge)
+        self._flow_tensor(who, "value", value, silt.float32)
+        self._optional(who, silt.int32, graph=graph, stop=stop)
+        if graph is None:
+            graph = self.flow(edge=e)
+        return batch_call(graph, value, e, stop, arg)
+
+    def upstream_min(self, value, graph=None, stop=None, edge=None, arg=False):
+        """For every cell of every model the least of `value`, a (B, H, W) float32 tensor, over all the cells that
+        drain through it along `graph` (default: flow()), the cell itself included (soil_upstream_extreme_batch): a
+        (B, H, W) float32 silt GPU tensor, with `arg` the pair (out, arg), arg the int32 index within its model of the
+        cell that holds the value (the smallest among equals, -1 where out is NaN).  NaN is ignored wherever a number
+        reaches the cell; cycles are allowed.  `stop` and `edge` as in basins().  A tensor of the wrong shape or dtype
+        or a bad edge raises ValueError before any device work.  Nothing synchronises."""
+        from . import soil
+        return self._upstream("upstream_min", soil.upstream_min_batch, value, graph, stop, edge, arg)
+
+    def upstream_max(self, value, graph=None, stop=None, edge=None, arg=False):
+        """The greatest of `value` over all the cells that drain through each cell: -upstream_min(-value), as
+        soil.upstream_max_batch states it."""
+        from . import soil
+        return self._upstream("upstream_max", soil.upstream_max_batch, value, graph, stop, edge, arg)
+
+    def breached(self, kind="steepest", edge=None, T=None, offset=0):
+        """(surface, graph): the graph of conditioned() and every model's ORIGINAL `height` carved along it
+        (soil.breach_batch) — each cell lowered to the lowest height of anything that drains through it.  The surface
+        never stands above `height` and never rises along the graph, where filled() raises every lake to its rim.
+        soil.stream_power_batch(surface, graph, ...) on this pair is the step that adds no mass: the solver methods
+        of the batch run on the filled surface and turn every lake into land at each step.  `kind`, `edge`, `T`,
+        `offset` as in conditioned().  Synchronises the stream (the fill does)."""
+        from . import soil
+        e = self._edge("breached", edge)
+        _, graph = self.conditioned(kind, e, T, offset)
+        return soil.breach_batch(self.height, graph, e), graph
+
+    def upstream_length(self, graph=None, stop=None, edge=None):
+        """The length of the longest way down to each cell along `graph` (default: flow()), a (B, H, W) float32 silt
+        GPU tensor (soil.upstream_length_batch): the greatest flow_length() in the cell's catchment less the cell's
+        own, with the batch's scale(s) as flow_length() takes them.  NaN for a cell on a cycle or draining into one.
+        `stop` and `edge` as in basins()."""
+        from . import soil
+        e = self._edge("upstream_length", edge)
+        self._optional("upstream_length", silt.int32, graph=graph, stop=stop)
+        scale = self._path_scale("upstream_length")
+        if graph is None:
+            graph = self.flow(edge=e)
+        return soil.upstream_length_batch(graph, e, scale, stop)
+
     def _copy(self, name, b, model, into_batch):
         """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""
         t, single = getattr(self, name), getattr(model, name)

@@ -675,6 +675,110 @@ def downstream_info():
     return _call_info("soil_downstream_info")
 
 
+# ---- upstream extrema (soil_hip.h: "flow graphs: upstream extrema"): the least or the greatest of a plane over
+# everything that drains through a cell, in the integer key order of the floats; breaching is the minimum of the
+# heights.  Stream-ordered.
+
+def _upstream(who, dims, graph, value, edge_, stop, arg, op, name="value"):
+    """soil_upstream_extreme on (H, W) planes, soil_upstream_extreme_batch on (B, H, W); `name`: what the caller calls
+    the value plane, for the messages.  Every check comes before any device work."""
+    shape = _shape(dims, graph, "%s: graph" % who)
+    e = _check.edge(who, edge_)
+    _int_plane(graph, shape, "%s: graph" % who)
+    _float_plane(value, shape, "%s: %s" % (who, name))
+    if stop is not None:
+        _int_plane(stop, shape, "%s: stop" % who)
+    g_ptr, v_ptr, s_ptr = _gpu(graph, silt.int32, "graph"), _f(value, name), _opt_i(stop, "stop")
+    out = silt.tensor(silt.float32, silt.shape(*shape), silt.gpu)
+    where = silt.tensor(silt.int32, silt.shape(*shape), silt.gpu) if arg else None
+    _call("soil_upstream_extreme" + ("" if dims == 2 else "_batch"), out.c_ptr, None if where is None else where.c_ptr,
+          g_ptr, v_ptr, s_ptr, *shape, e, op, _abi.stream())
+    return (out, where) if arg else out
+
+
+def upstream_min(graph, value, edge_, stop=None, arg=False):
+    """soil_upstream_extreme, op min: for every cell of a (H, W) receiver graph the least `value` (a float32 plane) over
+    all the cells that reach it — the cell itself and everything whose walk along the edges passes through it; cycles
+    are allowed.  The order is the integer key order -inf < .. < -0 < +0 < .. < +inf < NaN: a NaN is ignored wherever a
+    number reaches the cell, and the result is NaN (0x7fc00000) only where nothing else does.  `stop`: an optional
+    int32 plane; a non-zero cell collects its catchment and passes nothing on.  With `arg` returns (out, arg), arg the
+    int32 index of the cell that attains the value, the smallest among equals, -1 where out is NaN.  One definite bit
+    pattern."""
+    return _upstream("upstream_min", 2, graph, value, edge_, stop, arg, 0)
+
+
+def upstream_max(graph, value, edge_, stop=None, arg=False):
+    """soil_upstream_extreme, op max: -upstream_min(-value), the negations exact.  NaN is ignored as there, +0 wins
+    over -0, and `arg` is again the smallest index among equals."""
+    return _upstream("upstream_max", 2, graph, value, edge_, stop, arg, 1)
+
+
+def upstream_min_batch(graph, value, edge_, stop=None, arg=False):
+    """`upstream_min` of each of the B models of (B, H, W) planes (soil_upstream_extreme_batch); entries of `graph`
+    and of arg are indices within their model."""
+    return _upstream("upstream_min_batch", 3, graph, value, edge_, stop, arg, 0)
+
+
+def upstream_max_batch(graph, value, edge_, stop=None, arg=False):
+    """`upstream_max` of each of the B models of (B, H, W) planes."""
+    return _upstream("upstream_max_batch", 3, graph, value, edge_, stop, arg, 1)
+
+
+def upstream_info():
+    """What this thread's last upstream_min / upstream_max call (or _batch form) did (soil_upstream_extreme_info): a
+    dict with the number of `chunks`, of chunks whose init pass took the 16-byte form (`vec_chunks`), of chunks on
+    64-bit offsets (`idx64_chunks`) and the `rounds` per chunk."""
+    return _call_info("soil_upstream_extreme_info")
+
+
+def _minus(a, b):
+    """a - b of two float32 GPU tensors as a new tensor: an exact negation and one fp32 addition (silt.multiply,
+    silt.add)."""
+    out = silt.clone(b)
+    silt.multiply(out, -1.0)
+    silt.add(out, a)
+    return out
+
+
+def _breach(who, dims, height, graph, edge_, cut):
+    breached = _upstream(who, dims, graph, height, edge_, None, False, 0, name="height")
+    return (breached, _minus(height, breached)) if cut else breached
+
+
+def breach(height, graph, edge_, cut=False):
+    """The DEM `height` carved along `graph`: upstream_min(graph, height, edge_), every cell lowered to the lowest
+    height of anything that drains through it.  The surface never stands above `height` and never rises along an edge
+    of `graph`.  With `cut` returns (breached, height - breached), the depth carved: one fp32 subtraction, NaN where
+    the height is NaN."""
+    return _breach("breach", 2, height, graph, edge_, cut)
+
+
+def breach_batch(height, graph, edge_, cut=False):
+    """`breach` of each of the B models of (B, H, W) planes."""
+    return _breach("breach_batch", 3, height, graph, edge_, cut)
+
+
+def _upstream_length(who, dims, graph, edge_, scale, stop):
+    length = _flow_paths(who, dims, graph, edge_, scale, stop, (False, False, True))[2]
+    out = _upstream(who, dims, graph, length, edge_, stop, False, 1)
+    silt.multiply(length, -1.0)
+    silt.add(out, length)
+    return out
+
+
+def upstream_length(graph, edge_, scale, stop=None):
+    """The length of the longest way down to every cell: upstream_max(graph, L) + (-1 * L) with L = flow_length(graph,
+    edge_, scale, stop) — the greatest distance to the outlet in the cell's catchment less the cell's own, an exact
+    negation and one fp32 addition.  0 on a cell nothing drains into; NaN where L is NaN (a cell on a cycle or
+    draining into one)."""
+    return _upstream_length("upstream_length", 2, graph, edge_, scale, stop)
+
+
+def upstream_length_batch(graph, edge_, scale, stop=None):
+    """`upstream_length` of each of the B models; `scale` is one pair or B pairs."""
+    return _upstream_length("upstream_length_batch", 3, graph, edge_, scale, stop)
+
+
 # ---- hillslope diffusion (soil_hip.h: "hillslope diffusion"): one implicit step of dh/dt = div(kappa grad h) + u, a
 # tridiagonal solve per grid line along one axis, then along the other.  Stream-ordered.
 
@@ -898,6 +1002,27 @@ def condition_batch(height, edge_=None, graph=None):
         _int_plane(graph, shape, "condition_batch: graph")
     filled = fill_depressions_batch(height, e)
     return filled, resolve_flats_batch(filled, e, graph)
+
+
+def condition_breached(height, edge_=None):
+    """A (H, W) DEM made ready for routing by carving instead of filling: (breached, graph) with graph that of
+    condition(height, edge) and breached = breach(height, graph, edge), the ORIGINAL heights lowered along it.  No cell
+    is raised: a lake drains through a cut in its rim, not over a surface that was added."""
+    e = _check.edge("condition_breached", d8 if edge_ is None else edge_)
+    _float_plane(height, _hw2(height, "condition_breached: height"), "condition_breached: height")
+    _, graph = condition(height, e)
+    return _breach("condition_breached", 2, height, graph, e, False), graph
+
+
+def condition_breached_batch(height, edge_=None, graph=None):
+    """`condition_breached` of each of the B models of a (B, H, W) tensor; `graph` as in condition_batch."""
+    e = _check.edge("condition_breached_batch", d8 if edge_ is None else edge_)
+    shape = _bhw(height, "condition_breached_batch: height")
+    _float_plane(height, shape, "condition_breached_batch: height")
+    if graph is not None:
+        _int_plane(graph, shape, "condition_breached_batch: graph")
+    _, routed = condition_batch(height, e, graph)
+    return _breach("condition_breached_batch", 3, height, routed, e, False), routed
 
 
 def multiflow(height, source, K, T, edge_=None, seed=0, first=0, stride=1, out=None):
