@@ -1128,6 +1128,83 @@ int soil_upstream_extreme_batch(float* out, int32_t* arg, const int32_t* graph, 
  * forces them), info[3] rounds per chunk.  All zero before the first call; needs no device. */
 int soil_upstream_extreme_info(int64_t info[4]);
 
+/* ------------------------------------------------ flow graphs: stream order */
+
+/* The channel network of a receiver graph: which cells are channels, the Strahler order of each, how many channel
+ * cells drain straight into it, where the links (junction to junction) and the Strahler streams (order change to order
+ * change) end, and the graph restricted to the channels.  Per-segment steepness, Horton ratios, order-based channel
+ * masks and the `stop` planes of soil_flow_paths start from these.  The reference has no such call; the definition is
+ * this library's.
+ *
+ * Grid (H, W), cell n = x * W + y, `edge` D4 or D8, `graph` any int32 plane.  The edge rule and `stop` are word for
+ * word those of soil_flow_paths above: cell n has an edge to r = graph[n] iff r is the index of one of its K
+ * neighbours inside the model, anything else (INT32_MIN included) is no edge, with D4 a diagonal entry is no edge, and
+ * a cell with stop[n] != 0 has no outgoing edge whatever its graph entry.  `stop` may be NULL.
+ *
+ * Channel cells.  Cell n is a channel cell iff  (channel == NULL || channel[n] != 0)  and
+ * (area == NULL || area[n] >= threshold),  a float32 comparison: a NaN area fails, +inf passes any threshold, -inf
+ * only threshold -inf.  Both planes are optional; with neither every cell is a channel cell.  `threshold` is not read
+ * without `area`.
+ *
+ * The channel graph.  The edge n -> r exists iff the edge rule gives it, stop[n] == 0, and n and r are BOTH channel
+ * cells.  A non-channel cell is isolated; a stream that leaves the channels and enters them again is cut in two.
+ * donors[n] is the number of channel-graph edges into n: 0 .. K, and 0 off the channels.
+ *
+ * Order, by levels.  Cycles are allowed and no cell is special-cased.
+ *     M_1     = the channel cells
+ *     J_k     = the cells of M_1 with at least two donors in M_k
+ *     M_{k+1} = every cell that some cell of J_k reaches along the channel graph, that cell included
+ *     order[n] = the largest k with n in M_k, and 0 off the channels.
+ * (M_1 contains M_2 contains ...: by induction J_{k+1} lies in J_k.)  On a forest this is the Strahler number S: a
+ * head (no donor) has S = 1; a cell has the greatest S among its donors, plus one where two or more donors share it.
+ * Proof, by induction on k along the forest from the heads down, of  n in M_k iff S(n) >= k:  S(u) >= k + 1 iff two
+ * donors have S >= k (they share the maximum k, or the maximum is above k anyway — then one donor has S >= k + 1) or
+ * one donor has S >= k + 1; that is, iff two donors are in M_k (u in J_k) or one donor is in M_{k+1} (u is reached
+ * from J_k through it) — the definition of M_{k+1}.  On a cycle the value is whatever the levels give: an isolated
+ * cycle has order 1, and a cycle that a tree of order k drains into has order k + 1 at least all round — the cell where
+ * the tree enters has two donors in M_k, the tree's foot and its own predecessor on the cycle.
+ *
+ * Foot planes (int32, 0 / 1), both 0 off the channels:
+ *     link_foot[n]  = 1 iff n is a channel cell and has no channel-graph edge, or its receiver has donors >= 2:
+ *                     a link ends just above a junction, or at an outlet of the channel graph.
+ *     order_foot[n] = 1 iff n is a channel cell and has no channel-graph edge, or order[receiver] > order[n].
+ * channel_graph[n] = graph[n] where the channel-graph edge n -> graph[n] exists, -1 elsewhere: the graph that
+ * soil_accumulate, soil_flow_paths and the other calls take to stay inside the network.  soil_flow_paths on it with
+ * a foot plane as `stop` gives every channel cell the foot of its link (its Strahler stream) and the way there; a
+ * non-channel cell is its own terminal at distance 0.
+ *
+ * Every output may be NULL, not all of them.  The results are integers fixed by the definition: one bit pattern
+ * under any schedule, chunking and launch shape.
+ *
+ * How (csrc/stream_order.hip, with the invariant and its proof): per level one gather pass that raises the cells of
+ * J_k and one max-closure of ceil(log2(H * W)) pointer-doubling rounds with 32-bit atomic maxima, until a gather pass
+ * raises nothing; the host looks at one pinned word per level, so BOTH ENTRIES SYNCHRONISE THE STREAM, once per
+ * level (the fill does the same).  The levels are at most floor(log2(H * W)) + 1.  A host thread's calls on one
+ * device share one cached scratch block of their own.
+ *
+ * Batch form: the conventions of soil_flow_paths_batch.  Model-major planes; graph and channel_graph entries are
+ * indices WITHIN their model; `threshold` is one number for the batch; model b's slice of each output is bit for bit
+ * what the single call gives for model b's slices alone.  Chunks of whole models by soil_flow_paths_batch's rule;
+ * the models of a chunk iterate together, as many levels as the model that needs most.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): null `graph`, no output asked for, an output that aliases an input plane or another output, B, H
+ * or W < 1, H * W > INT32_MAX, an invalid `edge`, a NaN `threshold` with `area` given.  Otherwise, without a device:
+ * SOIL_ERR_NO_DEVICE. */
+int soil_stream_order(int32_t* order, int32_t* donors, int32_t* link_foot, int32_t* order_foot, int32_t* channel_graph,
+                      const int32_t* graph, const int32_t* channel, const float* area, float threshold,
+                      const int32_t* stop, int64_t H, int64_t W, int edge, void* stream);
+int soil_stream_order_batch(int32_t* order, int32_t* donors, int32_t* link_foot, int32_t* order_foot,
+                            int32_t* channel_graph, const int32_t* graph, const int32_t* channel, const float* area,
+                            float threshold, const int32_t* stop, int64_t B, int64_t H, int64_t W, int edge,
+                            void* stream);
+/* What the calling host thread's last call of one of the two entries above did: info[0 .. 3] as
+ * soil_upstream_extreme_info (chunks, chunks whose init pass took the 16-byte form, chunks on 64-bit offsets, rounds
+ * per closure), info[4] the levels run: the gather passes, which is the greatest order found (1 where there is no
+ * channel cell), the most over the models of the call; the closures run per chunk are one fewer, the last gather pass
+ * having raised nothing.  All zero before the first call; needs no device. */
+int soil_stream_order_info(int64_t info[5]);
+
 /* ----------------------------------------- flow graphs: erosion-deposition */
 
 /* The stream-power step with sediment deposition: the erosion-deposition (xi-q) model of Davy & Lague in the implicit

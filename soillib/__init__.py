@@ -35,6 +35,8 @@ from soillib_amd.soil import condition, condition_batch, fill_depressions_batch,
 from soillib_amd.soil import (breach, breach_batch, condition_breached, condition_breached_batch,  # noqa: F401
                               upstream_info, upstream_length, upstream_length_batch, upstream_max,
                               upstream_max_batch, upstream_min, upstream_min_batch)
+from soillib_amd.soil import (stream_magnitude, stream_magnitude_batch, stream_order,  # noqa: F401
+                              stream_order_batch, stream_order_info, stream_segments, stream_segments_batch)
 from soillib_amd.io import geotiff, geotiff_meta, mesh, tiff  # noqa: F401  (python/source/io.cpp:20-110)
 from soillib_amd.legacy import (buffer, clamp, data_t, erode, index, map_t, multiply, param_t,  # noqa: F401
                                 resize)

@@ -245,6 +245,11 @@ SIGNATURES = {
     "soil_upstream_extreme": (cint, [vp, vp, vp, vp, vp, i64, i64, cint, cint, vp]),
     "soil_upstream_extreme_batch": (cint, [vp, vp, vp, vp, vp, i64, i64, i64, cint, cint, vp]),
     "soil_upstream_extreme_info": (cint, [C.POINTER(i64)]),
+    # stream order: order / donors / link_foot / order_foot / channel_graph (each may be NULL, not all), graph, channel,
+    # area (may be NULL), threshold, stop (may be NULL)
+    "soil_stream_order": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, i64, i64, cint, vp]),
+    "soil_stream_order_batch": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, i64, i64, i64, cint, vp]),
+    "soil_stream_order_info": (cint, [C.POINTER(i64)]),
     # the stream-power step with deposition: out / out64, flux / residual (may be NULL), height, graph, erosivity,
     # deposition, uplift (may be NULL); host scale pairs, dt, iters
     "soil_stream_power_deposit": (cint, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, cint, F3, C.c_double, cint, vp]),

@@ -7,8 +7,10 @@
 //           dense and the listed round (ptr_round, ptr_list) over a per-cell operation `bool cell(IDX n)`: "one round
 //           for cell n, in -> out; true where it wrote a new record".  Each file's __global__ round kernels are one
 //           statement: the body over a lambda around its path_cell / down_cell.
-//   host    models per chunk, the layout and carving of a chunk's scratch, the round plan, the chunk (init, rounds,
-//           final) and the loop over the chunks of a call (ptr_chunk, ptr_run), the call's info record.  Each file
+//   host    models per chunk, the layout and carving of a chunk's scratch (ptr_carve), the round plan (ptr_rounds), the
+//           chunk (init, rounds, final) and the loop over the chunks of a call (ptr_chunk, ptr_run), the call's info
+//           record.  stream_order.hip runs the rounds once per level between passes of its own: it takes ptr_carve,
+//           ptr_rounds and ptr_run and leaves ptr_chunk.  Each file
 //           hands in its launches as callables and keeps its workspace slot and info instance.  The shape refusals,
 //           the chunk-size rule and the knobs read per call are flow_host.hpp's.
 //
@@ -269,13 +271,9 @@ void ptr_launch_round(const PtrChunk& c, const PtrRound& q, hipStream_t st, List
                                                                 q.fill_out, c.seg);
 }
 
-// One chunk of `models` models of (H, W), stream-ordered: init, the rounds of ONE model, final.
-//   init(chunk) -> bool       launches the file's init on rec[0] (extra[0], flags); whether it took the vector form
-//   round(chunk, PtrRound)    launches the file's dense or listed round, 32- or 64-bit by chunk.idx32
-//   final(chunk, grid, rec)   launches the file's final pass over `rec`
-template <typename Init, typename Round, typename Final>
-int ptr_chunk(PtrInfo& info, int64_t models, int64_t H, int64_t W, PtrSizes sizes, char* scratch, Init init,
-              Round round, Final fin) {
+// The buffers of one chunk of `models` models of (H, W) carved out of `scratch` in ptr_layout's order, its launch
+// shapes and its round count; a file with more than two planes finds plane k at extra[0] + k * ptr_layout().b_extra
+inline PtrChunk ptr_carve(int64_t models, int64_t H, int64_t W, PtrSizes sizes, char* scratch) {
   const int64_t hw = H * W, elem = models * hw;
   const size_t extra = sizes.extra;
   const PtrLayout L = ptr_layout(elem, sizes);
@@ -288,23 +286,20 @@ int ptr_chunk(PtrInfo& info, int64_t models, int64_t H, int64_t W, PtrSizes size
   c.fill[0] = reinterpret_cast<uint32_t*>(p), c.fill[1] = reinterpret_cast<uint32_t*>(p + L.b_fill), p += 2 * L.b_fill;
   c.flags = reinterpret_cast<int*>(p);
   c.groups = L.groups, c.seg = static_cast<uint32_t>(L.seg), c.elem = elem, c.z = static_cast<unsigned>(models);
-
-  // Rounds from `list_from` on run over the lists; the dense round in front of them makes the first lists.
-  // SOIL_PATHS_LIST_FROM: that round (0, or beyond the last round: dense rounds throughout), read per call.
-  const char* const e = std::getenv("SOIL_PATHS_LIST_FROM");
-  const int list_from_env = e ? std::atoi(e) : 1;
   c.rounds = ceil_log2(hw);
-  const int list_from = (list_from_env >= 1 && list_from_env < c.rounds) ? list_from_env : c.rounds;
   // (64-bit offsets: the form a single model of 2^28 cells or more takes, or SOIL_PATHS_IDX64)
   c.idx32 = static_cast<uint64_t>(elem) * sizeof(uint4) < (1ull << 32) && !force_idx64();
+  return c;
+}
 
-  const bool vec = init(c);
-  SOIL_LAUNCH_CHECK();
-  info.chunks += 1;
-  info.vec_chunks += vec ? 1 : 0;
-  info.idx64_chunks += c.idx32 ? 0 : 1;
-  info.rounds = c.rounds;
-
+// The rounds of a chunk from records rec[0] (and flags {1, 0, 0}) on: rounds from `list_from` on run over the lists;
+// the dense round in front of them makes the first lists.  SOIL_PATHS_LIST_FROM: that round (0, or beyond the last
+// round: dense rounds throughout), read per call.
+template <typename Round>
+void ptr_rounds(const PtrChunk& c, Round round) {
+  const char* const e = std::getenv("SOIL_PATHS_LIST_FROM");
+  const int list_from_env = e ? std::atoi(e) : 1;
+  const int list_from = (list_from_env >= 1 && list_from_env < c.rounds) ? list_from_env : c.rounds;
   for (int r = 0; r < c.rounds; ++r) {
     uint32_t* const fo = c.fill[(r + 1) & 1];
     if (r >= list_from)
@@ -313,12 +308,33 @@ int ptr_chunk(PtrInfo& info, int64_t models, int64_t H, int64_t W, PtrSizes size
       round(c, PtrRound{r, nullptr, nullptr, list_from < c.rounds && r + 1 == list_from ? c.list[(r + 1) & 1] : nullptr,
                         fo});
   }
-  SOIL_LAUNCH_CHECK();
+}
 
+// The grid of a final pass: a few thousand work-groups in all stride over the cells; a batch of many small models
+// has one per model
+inline dim3 ptr_final_grid(const PtrChunk& c, int64_t hw) {
   const int64_t per_model = (hw + kPBlock - 1) / kPBlock;
-  // (a few thousand work-groups in all stride over the cells; a batch of many small models has one per model)
-  const int64_t want = (8192 + models - 1) / models;
-  fin(c, dim3(static_cast<unsigned>(per_model < want ? per_model : want), 1, c.z), c.rec[c.rounds & 1]);
+  const int64_t want = (8192 + static_cast<int64_t>(c.z) - 1) / static_cast<int64_t>(c.z);
+  return dim3(static_cast<unsigned>(per_model < want ? per_model : want), 1, c.z);
+}
+
+// One chunk of `models` models of (H, W), stream-ordered: init, the rounds of ONE model, final.
+//   init(chunk) -> bool       launches the file's init on rec[0] (extra[0], flags); whether it took the vector form
+//   round(chunk, PtrRound)    launches the file's dense or listed round, 32- or 64-bit by chunk.idx32
+//   final(chunk, grid, rec)   launches the file's final pass over `rec`
+template <typename Init, typename Round, typename Final>
+int ptr_chunk(PtrInfo& info, int64_t models, int64_t H, int64_t W, PtrSizes sizes, char* scratch, Init init,
+              Round round, Final fin) {
+  const PtrChunk c = ptr_carve(models, H, W, sizes, scratch);
+  const bool vec = init(c);
+  SOIL_LAUNCH_CHECK();
+  info.chunks += 1;
+  info.vec_chunks += vec ? 1 : 0;
+  info.idx64_chunks += c.idx32 ? 0 : 1;
+  info.rounds = c.rounds;
+  ptr_rounds(c, round);
+  SOIL_LAUNCH_CHECK();
+  fin(c, ptr_final_grid(c, H * W), c.rec[c.rounds & 1]);
   SOIL_LAUNCH_CHECK();
   return SOIL_OK;
 }

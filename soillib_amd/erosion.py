@@ -1071,6 +1071,41 @@ class ErosionBatch:
             graph = self.flow(edge=e)
         return soil.upstream_length_batch(graph, e, scale, stop)
 
+    # ---- stream order and channel segments (soil_hip.h: "flow graphs: stream order") ----
+
+    def _network(self, who, threshold, kind, edge, graph, area):
+        """The (graph, area, edge) a channel network is cut from: those given, or conditioned() -> drainage() as the
+        solver methods route."""
+        _check.number("ErosionBatch.%s" % who, "threshold", threshold, lo=None)
+        _check.kind("ErosionBatch.%s" % who, kind, ("steepest", "random_weighted"))
+        e = self._edge(who, edge)
+        self._optional(who, silt.int32, graph=graph)
+        self._optional(who, silt.float32, area=area)
+        if graph is None:
+            _, graph = self.conditioned(kind, e)
+        if area is None:
+            area = self.drainage(graph=graph, edge=e)
+        return graph, area, e
+
+    def stream_order(self, threshold, kind="steepest", edge=None, graph=None, area=None, donors=False):
+        """The Strahler order of every cell of every model, a (B, H, W) int32 silt GPU tensor, 0 off the channels
+        (soil.stream_order_batch): the channels are the cells whose drainage area is >= `threshold`.  `graph=None`:
+        the graph of conditioned(kind, edge); `area=None`: drainage() along the graph, the count of upstream cells.
+        With `donors` returns (order, donors).  The batch's own planes are not touched.  A tensor of the wrong shape
+        or dtype, a bad kind, edge or threshold raises ValueError before any device work.  Synchronises the stream."""
+        from . import soil
+        g, a, e = self._network("stream_order", threshold, kind, edge, graph, area)
+        return soil.stream_order_batch(g, e, None, a, float(threshold), None, donors)
+
+    def stream_segments(self, threshold, kind="steepest", edge=None, graph=None, area=None, by="link"):
+        """(order, segment, steps, length) of every model's channel network (soil.stream_segments_batch), the
+        channels, `graph` and `area` as in stream_order(), lengths with the batch's scale(s); `by` is "link" or
+        "order".  A non-channel cell is its own segment at distance 0 with order 0."""
+        from . import soil
+        scale = self._path_scale("stream_segments")
+        g, a, e = self._network("stream_segments", threshold, kind, edge, graph, area)
+        return soil.stream_segments_batch(g, e, None, a, float(threshold), None, scale, by)
+
     def _copy(self, name, b, model, into_batch):
         """Plane `name` of model b of the batch from (into_batch) or to ErosionModel `model`, on the stream."""
         t, single = getattr(self, name), getattr(model, name)

@@ -779,6 +779,120 @@ def upstream_length_batch(graph, edge_, scale, stop=None):
     return _upstream_length("upstream_length_batch", 3, graph, edge_, scale, stop)
 
 
+# ---- stream order and channel segments (soil_hip.h: "flow graphs: stream order"): the channel network of a receiver
+# graph — which cells are channels, their Strahler order, their donors, where links and Strahler streams end, and the
+# graph restricted to the channels.  One host look per level: the calls synchronise the stream.
+
+_SO_OUTPUTS = ("order", "donors", "link_foot", "order_foot", "channel_graph")
+
+
+def _stream_order(who, dims, graph, edge_, channel, area, threshold, stop, want):
+    """soil_stream_order on (H, W) planes, soil_stream_order_batch on (B, H, W); `want`: the names of the outputs to
+    make, returned as a dict.  Every check comes before any device work."""
+    shape = _shape(dims, graph, "%s: graph" % who)
+    e = _check.edge(who, edge_)
+    _int_plane(graph, shape, "%s: graph" % who)
+    if channel is not None:
+        _int_plane(channel, shape, "%s: channel" % who)
+    if area is not None:
+        _float_plane(area, shape, "%s: area" % who)
+        if threshold is None:
+            raise ValueError("%s: area needs a threshold" % who)
+    elif threshold is not None:
+        raise ValueError("%s: threshold needs an area" % who)
+    if stop is not None:
+        _int_plane(stop, shape, "%s: stop" % who)
+    th = 0.0 if threshold is None else float(threshold)
+    if th != th:
+        raise ValueError("%s: threshold is NaN" % who)
+    g_ptr, c_ptr, a_ptr, s_ptr = (_gpu(graph, silt.int32, "graph"), _opt_i(channel, "channel"), _opt_f(area, "area"),
+                                  _opt_i(stop, "stop"))
+    outs = {k: silt.tensor(silt.int32, silt.shape(*shape), silt.gpu) for k in _SO_OUTPUTS if k in want}
+    _call("soil_stream_order" + ("" if dims == 2 else "_batch"),
+          *[outs[k].c_ptr if k in outs else None for k in _SO_OUTPUTS], g_ptr, c_ptr, a_ptr, th, s_ptr, *shape, e,
+          _abi.stream())
+    return outs
+
+
+def _order(who, dims, graph, edge_, channel, area, threshold, stop, donors):
+    o = _stream_order(who, dims, graph, edge_, channel, area, threshold, stop, ("order", "donors") if donors else ("order",))
+    return (o["order"], o["donors"]) if donors else o["order"]
+
+
+def stream_order(graph, edge_, channel=None, area=None, threshold=None, stop=None, donors=False):
+    """soil_stream_order: the Strahler order of every cell of a (H, W) receiver graph, int32, 0 off the channels.  A
+    cell is a channel cell iff `channel` (an optional int32 mask) is non-zero there and `area` (an optional float32
+    plane, with `threshold`) is >= threshold — a float comparison, a NaN area fails; with neither, every cell is one.
+    The channel graph keeps the edges of `graph` (the edge rule and `stop` of flow_paths) between channel cells.  A
+    head has order 1; a cell has the greatest order among its donors, plus one where two or more share it.  Cycles
+    are allowed: the order is defined by levels (soil_hip.h) and nothing is special-cased.  With `donors` returns
+    (order, donors), the number of channel-graph edges into each cell.  Synchronises the stream once per level."""
+    return _order("stream_order", 2, graph, edge_, channel, area, threshold, stop, donors)
+
+
+def stream_order_batch(graph, edge_, channel=None, area=None, threshold=None, stop=None, donors=False):
+    """`stream_order` of each of the B models of (B, H, W) planes (soil_stream_order_batch); entries of `graph` are
+    indices within their model, `threshold` is one number for all models."""
+    return _order("stream_order_batch", 3, graph, edge_, channel, area, threshold, stop, donors)
+
+
+def stream_order_info():
+    """What this thread's last stream_order / stream_segments / stream_magnitude call (or _batch form) did
+    (soil_stream_order_info): `chunks`, `vec_chunks`, `idx64_chunks` and `rounds` as upstream_info(), and `levels`,
+    the seed passes run: the greatest order found (1 where there is no channel), the most over a batch's models."""
+    info = (C.c_int64 * 5)()
+    _call("soil_stream_order_info", info)
+    return dict(zip(("chunks", "vec_chunks", "idx64_chunks", "rounds", "levels"), (int(v) for v in info)))
+
+
+def _stream_segments(who, dims, graph, edge_, channel, area, threshold, stop, scale, by):
+    if by not in ("link", "order"):
+        raise ValueError("%s: by must be 'link' or 'order', got %r" % (who, by))
+    foot = by + "_foot"
+    o = _stream_order(who, dims, graph, edge_, channel, area, threshold, stop, ("order", foot, "channel_graph"))
+    segment, steps, length = _flow_paths(who, dims, o["channel_graph"], edge_, scale, o[foot],
+                                         (True, True, scale is not None))
+    return o["order"], segment, steps, length
+
+
+def stream_segments(graph, edge_, channel=None, area=None, threshold=None, stop=None, scale=None, by="link"):
+    """(order, segment, steps, length) of the channel network of `graph` (inputs as stream_order): segment[n] is the
+    index of the foot cell of n's link (`by="link"`: a link ends just above a junction — a cell with two or more
+    donors — or at an outlet of the channel graph) or of n's Strahler stream (`by="order"`: it ends where the order
+    rises or at an outlet); steps and length are the way to that foot along the channels, length with the (sx, sy) of
+    `scale` (None: no length, the last item is None).  One soil_stream_order call for the restricted graph and the
+    foot plane, then flow_paths(channel_graph, edge_, scale, stop=foot).  A non-channel cell is its own foot at
+    distance 0: segment[n] == n, steps 0, length 0 — its order == 0 tells it apart.  Cells on a cycle of the channel
+    graph, or draining into one, get -1 / -1 / NaN as in flow_paths."""
+    return _stream_segments("stream_segments", 2, graph, edge_, channel, area, threshold, stop, scale, by)
+
+
+def stream_segments_batch(graph, edge_, channel=None, area=None, threshold=None, stop=None, scale=None, by="link"):
+    """`stream_segments` of each of the B models of (B, H, W) planes; `scale` is one pair or B pairs; segment entries
+    are indices within their model."""
+    return _stream_segments("stream_segments_batch", 3, graph, edge_, channel, area, threshold, stop, scale, by)
+
+
+def _stream_magnitude(who, dims, graph, edge_, channel, area, threshold, stop):
+    o = _stream_order(who, dims, graph, edge_, channel, area, threshold, stop, ("order", "donors", "channel_graph"))
+    with _on_stream():
+        heads = ((o["donors"].view_torch() == 0) & (o["order"].view_torch() > 0)).float()
+    heads = silt.tensor.from_torch(heads.contiguous())
+    return (accumulate if dims == 2 else accumulate_batch)(o["channel_graph"], heads, edge_)
+
+
+def stream_magnitude(graph, edge_, channel=None, area=None, threshold=None, stop=None):
+    """The Shreve magnitude of every cell (inputs as stream_order): the number of channel heads — channel cells with
+    no donor — that drain through it along the channel graph, float32: accumulate(channel_graph, heads).  0 off the
+    channels; on and below a cycle it is whatever accumulate gives there."""
+    return _stream_magnitude("stream_magnitude", 2, graph, edge_, channel, area, threshold, stop)
+
+
+def stream_magnitude_batch(graph, edge_, channel=None, area=None, threshold=None, stop=None):
+    """`stream_magnitude` of each of the B models of (B, H, W) planes."""
+    return _stream_magnitude("stream_magnitude_batch", 3, graph, edge_, channel, area, threshold, stop)
+
+
 # ---- hillslope diffusion (soil_hip.h: "hillslope diffusion"): one implicit step of dh/dt = div(kappa grad h) + u, a
 # tridiagonal solve per grid line along one axis, then along the other.  Stream-ordered.
 

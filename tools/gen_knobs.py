@@ -96,6 +96,7 @@ KNOBS = {
     "SOIL_RAKE_LIST_FROM": ("graph", "first rake-compress round that runs over the lists of pending cells [2; 0: dense rounds throughout]"),
     "SOIL_FLOW_BATCH_CELLS": ("graph", "cap on the cells of a chunk of soil_accumulate_batch, of soil_flow_paths_batch, of soil_downstream_batch / soil_stream_power_batch and of soil_diffuse_batch — whole models, at least one — below the default, the most that keep the rounds' 32-bit offsets [2^32 / (4 K) - 1; flow paths, downstream sums and diffusion: 2^28 - 1], read per call; the tests reach the chunking with tiny shapes through it"),
     "SOIL_PATHS_LIST_FROM": ("graph", "first pointer-doubling round of soil_flow_paths(_batch) and of soil_downstream / soil_stream_power (_batch) that runs over the lists of unresolved cells [1; 0: dense rounds throughout], read per call"),
+    "SOIL_STREAM_ORDER_NARROW": ("graph", "0: the closures of soil_stream_order(_batch) from level 2 on keep every channel cell in the work set instead of the cells of that level alone (csrc/stream_order.hip, Narrowing); the A/B of DESIGN.md 3.5, the result does not depend on it; read per call"),
     "SOIL_PATHS_IDX64": ("graph", "1: the rounds of soil_flow_paths(_batch) and of soil_downstream / soil_stream_power (_batch) on 64-bit offsets whatever the size (the form a model of 2^28 cells or more takes; the tests reach it at small shapes through it), and the sweeps of soil_diffuse(_batch) likewise (there the form of a model of 2^29 cells or more), read per call"),
     "SOIL_PATHS_GROUPS": ("graph", "work-groups of a pointer-doubling round of soil_flow_paths(_batch) and of soil_downstream / soil_stream_power (_batch) [8192]"),
     "SOIL_FLOW_LANES": ("graph", "1: soil_multiflow's realisations one after the other instead of two in flight [2]"),
