@@ -1614,6 +1614,75 @@ int soil_slope_limit_batch(float* out, float* excess, const float* height, const
  * first call; needs no device. */
 int soil_slope_limit_info(int64_t info[4]);
 
+/* ---- flow graphs: exact multiple-flow accumulation (not in the reference, whose multiple-flow product is the
+ * Monte-Carlo mean of example/dem_multiflow.py: K random_weighted graphs, accumulated and averaged; soil_multiflow) ----
+ *
+ * Every cell of a random_weighted graph draws its receiver independently and every edge goes strictly downhill, so the
+ * expectation of the accumulation is the solution of the sparse triangular system
+ *        a[n] = source[n] + sum over donors d of w(d -> n) a[d],
+ * w(d -> n) the Gibbs share random_weighted gives neighbour n of d.  soil_mfd_weights writes the shares,
+ * soil_mfd_accumulate solves the system (csrc/mfd.hip: 64 x 64 tiles of doubles relaxed in LDS, launches repeated
+ * until no tile moved; SOIL_MFD_PER_CHECK launches per look at the "changed" word).  With kind power the same system
+ * is the deterministic multiple-flow (MFD) accumulation of Freeman, Quinn and Holmgren.
+ *
+ * Grid (H, W), cell n = x * W + y, `edge` D4 or D8 (K = 4 or 8) with the neighbour table above, as in the graph calls.
+ *
+ * Raw weight of cell n towards neighbour k.  diff = h[n] (-) h[k], one fp32 subtraction.  P_k = 0 where the neighbour
+ * is off the grid or diff <= 0.  A NaN diff is not <= 0: the weight is NaN, for both kinds.  Otherwise
+ *   - kind SOIL_MFD_GIBBS, param the temperature T: P_k = rw_exp2(diff, c_k) with the constants rw_const((float)T)
+ *     (csrc/soil_math.hpp) — the weight function and the constants of soil_random_weighted, the same inline functions;
+ *     soil_selftest_math op 12.  T obeys the rule of soil_random_weighted: as a float it is 0 or a normal positive
+ *     number.  T = 0 makes every cell a terminal, as random_weighted does.  No scale is read.
+ *   - kind SOIL_MFD_POWER, param the exponent p, finite, 0 <= p <= 16: P_k = (float) sp_pow((double)diff / L_k, p), one
+ *     fp64 division, the inline pow of csrc/soil_math.hpp (soil_selftest_math64 op 0), one rounding to fp32.  L_k is
+ *     the fp64 step length of soil_flow_paths: sx = (double)scale[0] for a row step (dx != 0, dy == 0), sy =
+ *     (double)scale[1] for a column step, sqrt(sx sx + sy sy) for a diagonal one.  (pow(NaN, 0) is 1; the NaN diff is
+ *     tested for itself, or two NaN cells would feed each other.)
+ * Partition sum.  Z = ((P_0 + P_1) + ...) in fp32, in table order, as random_weighted sums it.
+ * Sending.  A cell sends iff Z is finite and > 0 — exactly the cells where random_weighted can pick a receiver.  Its
+ * share towards k is w_k = P_k / Z, one IEEE fp32 division.  Every other cell is a terminal with all shares 0.
+ * Flats (`dist`, may be NULL: int32, as soil_flat_distance makes it).  A cell that does not send, with Z == 0 and
+ * dist[n] > 0, sends share 1.0 to the first neighbour in table order that lies in the grid, has h[k] == h[n] and
+ * dist[k] == dist[n] - 1: the rule of soil_flat_receivers.  Every edge strictly lowers the pair (height, dist), so the
+ * graph of the non-zero shares is acyclic for any content of `dist`.
+ *
+ * soil_mfd_weights: weights[k * H * W + n] = w_k of cell n, planar (K, H, W) float32; batch (B, K, H, W).
+ * Stream-ordered, nothing synchronises.
+ *
+ * Accumulation, in fp64.  s = (double)source[n] (`source` NULL: 1).  For k in table order: where neighbour k is in the
+ * grid and its share w towards n is non-zero, s = s + a[k] * (double)w — one rounded product and one rounded sum, no
+ * contraction.  A zero share is skipped, so an infinite a[k] never makes inf * 0.  a[n] = s, a NaN stored as the
+ * canonical quiet NaN.  On a DAG this is one fixed expression of the donors' final values a cell: the result does not
+ * depend on the schedule.  out64 (may be NULL) = a; out (may be NULL) = a rounded once to float; at least one is given.
+ * Terminals keep what arrived: with a unit source their values sum to H * W, up to rounding.
+ *
+ * soil_mfd_accumulate(_batch) synchronise the stream before they return, as soil_slope_limit does.  Batch form:
+ * model-major planes, `scales` one pair or B pairs (host; read by kind power only), model b's slice bit for bit what the
+ * single call gives for it alone (a model's first cell is addressed in int64).  The models relax side by side under
+ * one "changed" word; the batch is never cut into chunks, B above 65535 included.  The launches of a call never exceed
+ * tiles * 272 + 2 plus the launches of one look (csrc/mfd.hip derives it from the longest chain of donors); reaching
+ * that is an internal error (SOIL_ERR_HIP), never a property of the input.
+ *
+ * Refused with SOIL_ERR_INVALID_ARGUMENT before any device work, with or without a device, the entry's name in
+ * soil_last_error(): a null `height` (or `weights`); both outputs null; B, H or W < 1; H * W > INT32_MAX; n_scales not 1
+ * or B; an invalid `edge` or `kind`; a T that soil_random_weighted refuses, a p that is not in 0 .. 16; kind power with
+ * a null scale or one that is not positive and finite; an output that shares a byte with `height`, `source`, `dist`
+ * or the other output.  Otherwise, without a device: SOIL_ERR_NO_DEVICE. */
+typedef enum soil_mfd_kind { SOIL_MFD_GIBBS = 0, SOIL_MFD_POWER = 1 } soil_mfd_kind;
+int soil_mfd_weights(float* weights, const float* height, const int32_t* dist, int kind, double param, int64_t H,
+                     int64_t W, const float scale[2], int edge, void* stream);
+int soil_mfd_weights_batch(float* weights, const float* height, const int32_t* dist, int kind, double param, int64_t B,
+                           int64_t H, int64_t W, const float* scales, int64_t n_scales, int edge, void* stream);
+int soil_mfd_accumulate(float* out, double* out64, const float* height, const float* source, const int32_t* dist,
+                        int kind, double param, int64_t H, int64_t W, const float scale[2], int edge, void* stream);
+int soil_mfd_accumulate_batch(float* out, double* out64, const float* height, const float* source, const int32_t* dist,
+                              int kind, double param, int64_t B, int64_t H, int64_t W, const float* scales,
+                              int64_t n_scales, int edge, void* stream);
+/* What the calling host thread's last call of soil_mfd_accumulate or soil_mfd_accumulate_batch did: info[0] relaxation
+ * launches, info[1] tiles of a model, info[2] models, info[3] looks at the "changed" word.  All zero before the first
+ * call; needs no device. */
+int soil_mfd_info(int64_t info[4]);
+
 /* ---------------------------------------------------------------- stencils */
 
 /* soil::gradient — grad.hpp:11, grad.cu:89-97 (__gradient :22-87), model.cpp:193-195.  out (H,W,2). */

@@ -31,6 +31,8 @@ from soillib_amd.soil import diffuse, diffuse_batch, diffuse_info  # noqa: F401
 from soillib_amd.soil import (flat_distance, flat_distance_batch, flat_distance_info, flat_receivers,  # noqa: F401
                               flat_receivers_batch, resolve_flats, resolve_flats_batch)
 from soillib_amd.soil import slope_limit, slope_limit_batch, slope_limit_info  # noqa: F401
+from soillib_amd.soil import (mfd_accumulate, mfd_accumulate_batch, mfd_info, mfd_weights,  # noqa: F401
+                              mfd_weights_batch)
 from soillib_amd.soil import condition, condition_batch, fill_depressions_batch, fill_info  # noqa: F401
 from soillib_amd.soil import (breach, breach_batch, condition_breached, condition_breached_batch,  # noqa: F401
                               upstream_info, upstream_length, upstream_length_batch, upstream_max,

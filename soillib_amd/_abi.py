@@ -20,6 +20,7 @@ SOIL_ERR_IO = -5
 SOIL_ERR_COMM = -6
 
 D4, D8 = 0, 1
+MFD_GIBBS, MFD_POWER = 0, 1
 SOIL_CELLS_KEEP_FLUX = 1
 SOIL_FLUX_OVERWRITE = 1
 SOIL_STEP_FLUX_IN_DIRTY, SOIL_STEP_FLUX_OUT_DIRTY = 1, 2
@@ -283,6 +284,11 @@ SIGNATURES = {
     "soil_slope_limit": (cint, [vp, vp, vp, vp, C.c_double, i64, i64, F3, cint, vp]),
     "soil_slope_limit_batch": (cint, [vp, vp, vp, vp, C.c_double, i64, i64, i64, F3, i64, cint, vp]),
     "soil_slope_limit_info": (cint, [C.POINTER(i64)]),
+    "soil_mfd_weights": (cint, [vp, vp, vp, cint, C.c_double, i64, i64, F3, cint, vp]),
+    "soil_mfd_weights_batch": (cint, [vp, vp, vp, cint, C.c_double, i64, i64, i64, F3, i64, cint, vp]),
+    "soil_mfd_accumulate": (cint, [vp, vp, vp, vp, vp, cint, C.c_double, i64, i64, F3, cint, vp]),
+    "soil_mfd_accumulate_batch": (cint, [vp, vp, vp, vp, vp, cint, C.c_double, i64, i64, i64, F3, i64, cint, vp]),
+    "soil_mfd_info": (cint, [C.POINTER(i64)]),
     "soil_workspace_release": (cint, []),
     "soil_gradient": (cint, [vp, vp, i64, i64, F3, vp]),
     "soil_negslope": (cint, [vp, vp, i64, i64, F3, vp]),

@@ -18,7 +18,7 @@ OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libsoil_hip.so")
 
 SOURCES = ["runtime.hip", "erosion_cells.hip", "erosion_particles.hip", "erosion_particles_tiled.hip", "erosion_step.hip", "erosion_batch.hip", "erosion_resize.hip", "erosion_stats.hip", "erosion_quantiles.hip", "slab_runner.hip", "graph.hip", "flow_paths.hip", "downstream.hip", "upstream.hip", "stream_order.hip", "diffuse.hip",
-           "stencil.hip", "path.hip", "noise.hip", "io_tiff.hip", "conditioning.hip", "flats.hip", "slope_limit.hip"]
+           "stencil.hip", "path.hip", "noise.hip", "io_tiff.hip", "conditioning.hip", "flats.hip", "slope_limit.hip", "mfd.hip"]
 
 # -ffp-contract=off / no fast-math: the numerical contract
 # needs every fp32 operation evaluated as written.  -munsafe-fp-atomics selects

@@ -77,6 +77,7 @@ enum WorkspaceSlot {
   WS_SLOPE_LIMIT = 24,   // slope_limit.hip: soil_slope_limit(_batch): scale records, the tiles' marks
   WS_UPSTREAM = 25,      // upstream.hip: soil_upstream_extreme(_batch): the two pointer buffers, the packed plane, lists
   WS_STREAM_ORDER = 26,  // stream_order.hip: soil_stream_order(_batch): the two pointer buffers, P, L, D, lists
+  WS_MFD = 27,           // mfd.hip: soil_mfd_weights / soil_mfd_accumulate (_batch): scale records, marks, shares, iterate
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();

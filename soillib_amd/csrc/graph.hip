@@ -260,15 +260,7 @@ void launch_steepest4(int32_t* out, const float* height, int64_t H, int64_t W, h
 // for -0, zero), Z is inf or 0 and every receiver -1.  A subnormal T overflows the constants where the reference's
 // dE / T may stay finite, a negative T puts the weights where v_exp_f32 and the reference's __expf flush
 // differently, and NaN / inf are no temperature: the entry points refuse all of these (rw_temperature_ok).
-struct RwConst {  // log2(e) / (|shift_k| T) for the straight and the diagonal neighbours
-  float straight, diagonal;
-};
-inline bool rw_temperature_ok(float T) { return T == 0.0f || (T >= FLT_MIN && T <= FLT_MAX); }
-inline RwConst rw_const(float T) {
-  const double log2e = 1.4426950408889634;
-  return RwConst{static_cast<float>(log2e / static_cast<double>(T)),
-                 static_cast<float>(log2e / (static_cast<double>(kSqrt2) * static_cast<double>(T)))};
-}
+// RwConst, rw_temperature_ok and rw_const live in soil_math.hpp beside rw_exp2: mfd.hip takes the same weights.
 // cumulative weights of a cell (:126-143): `hn[k]`, `ok[k]`: neighbour k's height, and whether it
 // lies in the grid.  A neighbour outside leaves CDF[k] at the running sum; it is never looked at.
 template <int K>

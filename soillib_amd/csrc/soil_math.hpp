@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cfloat>
+
 #define SOIL_HD __host__ __device__ __forceinline__
 
 namespace soil {
@@ -222,6 +224,17 @@ __device__ __forceinline__ float att_exp(float x) { return __builtin_amdgcn_exp2
 // v_exp_f32, with c = log2(e) / (|shift| T) made on the host.  soil_selftest_math op 12 is this function, so the
 // tests' restatement of the kernel takes its weights from the very expression the kernel evaluates.
 __device__ __forceinline__ float rw_exp2(float diff, float c) { return __builtin_amdgcn_exp2f(diff * c); }
+// The constants of that weight, made on the host (graph.hip states which temperatures the entries take and why), and
+// shared by random_weighted and the exact multiple-flow weights (mfd.hip): one definition, one set of bits.
+struct RwConst {  // log2(e) / (|shift_k| T) for the straight and the diagonal neighbours
+  float straight, diagonal;
+};
+inline bool rw_temperature_ok(float T) { return T == 0.0f || (T >= FLT_MIN && T <= FLT_MAX); }
+inline RwConst rw_const(float T) {
+  const double log2e = 1.4426950408889634;
+  return RwConst{static_cast<float>(log2e / static_cast<double>(T)),
+                 static_cast<float>(log2e / (static_cast<double>(kSqrt2) * static_cast<double>(T)))};
+}
 
 // The slope power of soil_stream_power_n (downstream.hip: pn_init_cell): S^e in fp64 through the device library's pow,
 // which is deterministic but not correctly rounded.  soil_selftest_math64 op 0 is this function, so the tests'

@@ -731,6 +731,32 @@ class ErosionBatch:
             silt.set(source, 1.0)
         return soil.accumulate_batch(graph, source, e, decay)
 
+    def drainage_mfd(self, T=None, p=None, source=None, edge=None, conditioned=True):
+        """What drains through each cell of each model under multiple flow directions, exactly
+        (soil.mfd_accumulate_batch): a (B, H, W) float32 silt GPU tensor.  Exactly one of `T` and `p` is given: with
+        `T` the limit of the mean of drainage() over random_weighted graphs at that temperature, with `p` the
+        multiple-flow accumulation with shares proportional to (drop / length) ** p and the batch's scale(s).  `source`
+        defaults to ones.  With `conditioned` it runs on filled() with soil.flat_distance_batch routing the flats and
+        filled lakes, so that every cell drains off the grid; otherwise on the raw heights, where every pit is a
+        terminal.  The batch's planes are not touched.  A wrong argument raises ValueError before any device work.
+        Synchronises the stream."""
+        from . import soil
+        who = "ErosionBatch.drainage_mfd"
+        e = self._edge("drainage_mfd", edge)
+        if (T is None) == (p is None):
+            raise ValueError("%s: exactly one of T and p must be given" % who)
+        self._optional("drainage_mfd", silt.float32, source=source)
+        scale = None if p is None else self._path_scale("drainage_mfd")
+        if T is not None and (isinstance(T, bool) or not isinstance(T, numbers.Real) or not soil.valid_temperature(T)):
+            raise ValueError("%s: T must be 0 or a normal positive float32, got %r" % (who, T))
+        if p is not None and (_check.number(who, "p", p) > 16):
+            raise ValueError("%s: p must be a finite number in 0 .. 16, got %r" % (who, p))
+        height, dist = self.height, None
+        if conditioned:
+            height = soil.fill_depressions_batch(self.height, e)
+            dist = soil.flat_distance_batch(height, e)
+        return soil.mfd_accumulate_batch(height, source, e, T=T, p=p, scale=scale, dist=dist)
+
     def flow_slope(self, graph=None):
         """The slope of each model's `height` along `graph` (default: flow()), a (B, H, W) float32 silt GPU tensor
         (soil_slope_batch), with the batch's one scale or model b's own (x, y) of `scales`.  A graph of the wrong

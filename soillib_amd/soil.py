@@ -1070,6 +1070,91 @@ def slope_limit_info():
     return _call_info("soil_slope_limit_info", ("launches", "tiles", "models", "looks"))
 
 
+# ---- exact multiple-flow accumulation (soil_hip.h: soil_mfd_weights, soil_mfd_accumulate): what the mean of
+# multiflow's K random_weighted accumulations tends to, in one call; with `p` the MFD of Freeman, Quinn and Holmgren.
+
+def _mfd_args(who, dims, height, edge_, T, p, scale, dist):
+    """What both mfd calls check, before any device work: (shape, edge, kind, param, C scale arguments)."""
+    shape = _shape(dims, height, "%s: height" % who)
+    _float_plane(height, shape, "%s: height" % who)
+    e = _check.edge(who, edge_)
+    if (T is None) == (p is None):
+        raise ValueError("%s: exactly one of T and p must be given" % who)
+    if dist is not None:
+        _int_plane(dist, shape, "%s: dist" % who)
+    if T is not None:
+        _check.number(who, "T", T, lo=None)
+        if not valid_temperature(T):
+            raise ValueError("%s: T must be 0 or a normal positive float32, got %r" % (who, T))
+        pairs, tail = _scales(who, dims, scale, shape[0], none_ok=True)
+        return shape, e, _abi.MFD_GIBBS, float(T), tail
+    param = _check.number(who, "p", p)
+    if param > 16:
+        raise ValueError("%s: p must be a finite number in 0 .. 16, got %r" % (who, p))
+    pairs, tail = _scales(who, dims, scale, shape[0])
+    _positive(who, pairs, scale)
+    return shape, e, _abi.MFD_POWER, param, tail
+
+
+def _mfd_weights(who, dims, height, edge_, T, p, scale, dist):
+    shape, e, kind, param, tail = _mfd_args(who, dims, height, edge_, T, p, scale, dist)
+    h_ptr, d_ptr = _f(height, "height"), _opt_i(dist, "dist")
+    K = 8 if e == d8 else 4
+    out = silt.tensor(silt.float32, silt.shape(*(shape[:-2] + (K,) + shape[-2:])), silt.gpu)
+    _call("soil_mfd_weights" + ("" if dims == 2 else "_batch"), out.c_ptr, h_ptr, d_ptr, kind, param, *shape, *tail, e,
+          _abi.stream())
+    return out
+
+
+def _mfd_accumulate(who, dims, height, source, edge_, T, p, scale, dist, double):
+    shape, e, kind, param, tail = _mfd_args(who, dims, height, edge_, T, p, scale, dist)
+    if source is not None:
+        _float_plane(source, shape, "%s: source" % who)
+    h_ptr, s_ptr, d_ptr = _f(height, "height"), _opt_f(source, "source"), _opt_i(dist, "dist")
+    out, ptrs = _out_pair(shape, double)
+    _call("soil_mfd_accumulate" + ("" if dims == 2 else "_batch"), *ptrs, h_ptr, s_ptr, d_ptr, kind, param, *shape,
+          *tail, e, _abi.stream())
+    return out
+
+
+def mfd_weights(height, edge_, T=None, p=None, scale=None, dist=None):
+    """soil_mfd_weights: the K (4 or 8) outgoing multiple-flow shares of every cell of a (H, W) float32 DEM, a
+    (K, H, W) float32 tensor in the neighbour table's order.  Exactly one of `T` and `p` is given.  `T`: the Gibbs
+    shares random_weighted draws by at that temperature (soil.valid_temperature).  `p`: shares proportional to
+    (drop / length) ** p, 0 <= p <= 16, with the spacings (sx, sy) of `scale`.  A cell whose partition sum is not
+    finite and positive is a terminal: all shares 0.  `dist` (int32, soil.flat_distance): a flat cell with dist > 0
+    sends share 1 to the neighbour flat_receivers picks.  Nothing synchronises."""
+    return _mfd_weights("mfd_weights", 2, height, edge_, T, p, scale, dist)
+
+
+def mfd_weights_batch(height, edge_, T=None, p=None, scale=None, dist=None):
+    """`mfd_weights` of each of the B models of a (B, H, W) tensor (soil_mfd_weights_batch): (B, K, H, W); `scale` is
+    one pair or B pairs."""
+    return _mfd_weights("mfd_weights_batch", 3, height, edge_, T, p, scale, dist)
+
+
+def mfd_accumulate(height, source, edge_, T=None, p=None, scale=None, dist=None, double=False):
+    """soil_mfd_accumulate: the exact multiple-flow accumulation of `source` (a float32 plane, or None for ones) over a
+    (H, W) float32 DEM: a[n] = source[n] + the sum over the donors d of share(d -> n) * a[d], the shares those of
+    mfd_weights, the sums in fp64 in the neighbour table's order.  With `T` it is what the mean of multiflow's
+    random_weighted accumulations tends to; with `p` the multiple-flow accumulation of Freeman, Quinn and Holmgren.  One
+    definite bit pattern (soil_hip.h states the arithmetic).  Returns float32 (float64 with `double`); synchronises the
+    stream."""
+    return _mfd_accumulate("mfd_accumulate", 2, height, source, edge_, T, p, scale, dist, double)
+
+
+def mfd_accumulate_batch(height, source, edge_, T=None, p=None, scale=None, dist=None, double=False):
+    """`mfd_accumulate` of each of the B models of (B, H, W) planes, side by side (soil_mfd_accumulate_batch): launches
+    that do not grow with B.  `scale` is one pair or B pairs."""
+    return _mfd_accumulate("mfd_accumulate_batch", 3, height, source, edge_, T, p, scale, dist, double)
+
+
+def mfd_info():
+    """What this thread's last mfd_accumulate / mfd_accumulate_batch call did (soil_mfd_info): a dict with the
+    relaxation `launches`, the `tiles` of a model, the `models` and the `looks` at the "changed" word."""
+    return _call_info("soil_mfd_info", ("launches", "tiles", "models", "looks"))
+
+
 # ---- the fill of a batch, and the conditioned drainage graph: fill -> steepest / random_weighted -> resolve_flats
 
 def fill_depressions_batch(height, edge_=None):

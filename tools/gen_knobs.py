@@ -105,6 +105,7 @@ KNOBS = {
     "SOIL_FILL_VERBOSE": ("graph", "set: launches per level on stderr"),
     "SOIL_FLATS_PER_CHECK": ("graph", "relaxation launches of soil_flat_distance(_batch) between two looks at the 'changed' word [3], read per call"),
     "SOIL_SLOPE_LIMIT_PER_CHECK": ("graph", "relaxation launches of soil_slope_limit(_batch) between two looks at the 'changed' word [3], read per call"),
+    "SOIL_MFD_PER_CHECK": ("graph", "relaxation launches of soil_mfd_accumulate(_batch) between two looks at the 'changed' word [4], read per call"),
     # ---- bench.py
     "SOIL_BENCH_ARITH": ("bench", "default of --particle-arith [exact]"),
     "SOIL_BENCH_GRID": ("bench", "default of --grid (strong scaling on a fixed grid) [0]"),
