@@ -755,7 +755,12 @@ int soil_erode(const soil_erode_model* model, int64_t H, int64_t W, int64_t N, u
  * gather of pre-digested cell terms per step, flux tiles in LDS).  Auto picks
  * tiled for N >= 45000 (grids up to 2^31 cells), staged for N >= 1024, else direct.  All
  * shapes produce the same trajectories and deposits; only the order of the
- * fp32 additions into a cell differs.  For ablation and tests. */
+ * fp32 additions into a cell differs.  For ablation and tests.
+ * In the tiled shape the host follows the device: it reads one pinned word per round and queues the
+ * next rounds, or the finishing launch, by what it finds.  A particle launch in that shape, alone or
+ * inside a step, is ordered on `stream` like every other, but it synchronises with the stream's
+ * progress: it returns when its last launch is queued, which is after the work queued ahead of it
+ * has run.  The direct and the staged shape return with everything in flight. */
 int soil_set_particle_mode(int mode);
 /* Arithmetic of the particle step (the loops of erosion.cu:100-139 / :306-349) in the tiled shape:
  * 0 = exact (default): every `/` of the reference's step a correctly rounded IEEE quotient, sqrt
@@ -842,7 +847,9 @@ int soil_accumulate(float* out, const int32_t* graph, const float* source, const
  *   sum += double(float(accumulate(random_weighted(height, edge, seed, k, T), source) / K))
  * `sum` (H*W doubles) is accumulated into — zero it first.  A rank of an N-GPU run
  * passes k_first = rank, k_stride = N and all-reduces `sum` afterwards: accumulation
- * does not shard (pointer jumps span the grid), the realisations do. */
+ * does not shard (pointer jumps span the grid), the realisations do.
+ * Synchronises the stream before returning, like soil_accumulate: the realisations run on private
+ * lanes that wait for `stream` and are joined back into it first. */
 int soil_multiflow(double* sum, const float* height, const float* source, int64_t H, int64_t W,
                    int edge, uint64_t seed, uint64_t k_first, uint64_t k_stride, uint64_t k_end,
                    uint64_t K, float T, void* stream);

@@ -255,11 +255,40 @@ def P(name, role, data, dtype=None, fills=None):
     return (name, role, data, dtype, fills)
 
 
+def end_session_on_fault(e, what):
+    """A HIP runtime call failed (SOIL_ERR_HIP, a device fault among them): the context is gone, and whatever ran
+    after it on this device would only pile on: end the session here.  Every other status is a failure."""
+    from soillib_amd import _abi
+    if str(e).startswith("libsoil_hip error %d:" % _abi.SOIL_ERR_HIP):
+        import pytest
+        pytest.exit("%s: %s" % (what, e), returncode=3)
+
+
+def judge_outputs(case, arena, after, want, what):
+    """Every output plane of `want` read from the arena's bytes `after` and held to its reference, each the way its
+    entry of `want` says (Case); returns name -> the plane as read.  Shared by run_case and tests/busy_stream.py."""
+    from util import assert_bit_equal
+    got = {}
+    for name, exp in want.items():
+        exp, how = exp if isinstance(exp, tuple) else (exp, "bits")
+        if name == "*":
+            how({n: arena.read(n, after) for n, *_ in case.planes}, exp, what)
+            continue
+        got[name] = arena.read(name, after)
+        label = "%s: %s" % (what, name)
+        if how == "bits":
+            assert_bits(got[name], np.asarray(exp).reshape(got[name].shape), label)
+        elif how == "naneq":
+            assert_bit_equal(got[name], np.asarray(exp).reshape(got[name].shape), label)
+        else:
+            how(got[name], exp, label)
+    return got
+
+
 def run_case(lib, case, placement, want, what=""):
     """The four checks of a row at one placement, under both fills: the guards hold, the pure inputs are unchanged
     (Arena.check), every output is the reference's, and the outputs under fill A and fill B are the same bits."""
     from soillib_amd import _abi
-    from util import assert_bit_equal
     outs = {}
     for fill in FILLS:
         arena = Arena(placement, fill, "device")
@@ -272,28 +301,11 @@ def run_case(lib, case, placement, want, what=""):
             case.call(lib, arena.ptr)
             _abi.check(lib.soil_device_synchronize())
         except _abi.SoilError as e:
-            if str(e).startswith("libsoil_hip error %d:" % _abi.SOIL_ERR_HIP):
-                # a HIP runtime call failed (SOIL_ERR_HIP, a device fault among them): the context is gone, and whatever
-                # ran after it on this device would only pile on: end the session here.  Every other status is a failure
-                import pytest
-                pytest.exit("%s %s fill %s: %s" % (what, placement, fill, e), returncode=3)
+            end_session_on_fault(e, "%s %s fill %s" % (what, placement, fill))
             raise
         after = arena.snapshot()
         arena.check(before, after)
-        got = outs[fill] = {}
-        for name, exp in want.items():
-            exp, how = exp if isinstance(exp, tuple) else (exp, "bits")
-            if name == "*":
-                how({n: arena.read(n, after) for n, *_ in case.planes}, exp, "%s %s fill %s" % (what, placement, fill))
-                continue
-            got[name] = arena.read(name, after)
-            label = "%s %s fill %s: %s" % (what, placement, fill, name)
-            if how == "bits":
-                assert_bits(got[name], np.asarray(exp).reshape(got[name].shape), label)
-            elif how == "naneq":
-                assert_bit_equal(got[name], np.asarray(exp).reshape(got[name].shape), label)
-            else:
-                how(got[name], exp, label)
+        outs[fill] = judge_outputs(case, arena, after, want, "%s %s fill %s" % (what, placement, fill))
     for name, exp in want.items():
         how = exp[1] if isinstance(exp, tuple) else "bits"
         if name != "*" and (not callable(how) or getattr(how, "deterministic", False)):
