@@ -1,0 +1,595 @@
+"""The history of a call as a tested dimension: what the calls before it left in the library's workspace.
+
+csrc/runtime.hip keeps one block per host thread, device and slot (csrc/common.hpp: WorkspaceSlot); a block grows on
+demand, is never shrunk and never cleared, so a call starts on what the previous user of its slot left: tile marks, list
+heads and counts, "changed" words, partial records, pointer buffers, fp64 iterates, records uploaded for another batch.
+The parity files judge one call on allocations of its own.  A kernel that reads a mark, count or partial result it did
+not initialise, that initialises only the extent of the current grid, that sizes something by the block instead of by
+the call, or that keeps a result of the last call of the same shape passes all of them: a first call on freshly mapped
+memory hides the first, a repeat of the identical call hides the last, because the stale values are the right ones.
+
+A history is a list of Steps.  A step is a release of the workspace, a call of a row of the guard-band tables
+(tests/test_gpu_guard_bands.py: all_rows) at one of the row's keys on one image of its arena, or a refused call of that
+row.  All steps run on the null stream, on arena pointers, with the device synchronised between them (Library.run).
+Every step is judged as the guard-band test judges it: the guards and the pure inputs are what they were
+(guard_arena.Arena.check), and on the real image, where a reference is memoised, the outputs are the reference's.  The
+last step is the row under test on its real image; where the entry has a soil_*_info call, the record after it is, field
+by field, the record of the same call made cold (released workspace).  Every predecessor is a legal call: what it leaves
+indexes within blocks and arenas that exist.  Nothing here writes into the workspace from outside.
+
+Images.  "real": the planes as the row builds them.  "decoy": busy_stream.decoy_bytes, the same layout with other valid
+inputs, which tests/test_gpu_on_a_busy_stream.py proves to change the outputs of every row.  The others are the inputs
+of the non-quiescent predecessors (RESTLESS_IMAGES, restless_image): a finished call tends to leave a benign state, lists drained and marks
+clean; these are built so that it does not.
+
+The runner is written against a small interface (release, prepare, run, refuse, info), which SoilLibrary implements on
+the library and tests/test_workspace_history.py on a numpy stand-in with a persistent scratch array.
+
+What the histories prove: a call's bits do not depend on the legal calls before it, at these shapes.  What they do not:
+memory the allocator hands out fresh and happens to zero (not measured here); state reachable only through illegal
+inputs; two host threads; calls on different streams without ordering, which csrc/common.hpp excludes by rule.
+"""
+import contextlib
+import ctypes as C
+import json
+import os
+import re
+
+import numpy as np
+
+import guard_arena as ga
+from guard_arena import IN, INOUT
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+COLD, STALE, SHRINK, REGROW, SIBLINGS, RESTLESS, REFUSAL, SHAPES = (
+    "cold", "stale", "shrink", "regrow", "siblings", "restless", "refusal", "shapes")
+KINDS = (COLD, STALE, SHRINK, REGROW, SIBLINGS, RESTLESS, REFUSAL, SHAPES)
+
+
+class HistoryError(AssertionError):
+    """What the runner reports.  `kind`: "guard" (a guard band or pure input changed), "mismatch" (an output is not the
+    reference), "info" (the record is not the cold call's), "refusal" (a refused call was not refused, or touched a
+    plane); `step`: the index of the step in the history."""
+
+    def __init__(self, kind, step, what, detail):
+        self.kind, self.step = kind, step
+        AssertionError.__init__(self, "%s [%s at step %d]: %s" % (what, kind, step, detail))
+
+
+class Step:
+    """`op`: "release", "call" or "refuse"; `entry`, `key`: a row and one of its keys; `image`: "real", "decoy" or a
+    name of RESTLESS_IMAGES; `mode`: a launch shape of the particle kernels (None: the library's own choice)."""
+
+    def __init__(self, op, entry=None, key=None, image="real", mode=None):
+        assert op in ("release", "call", "refuse")
+        self.op, self.entry, self.key, self.image, self.mode = op, entry, key, image, mode
+
+    def __repr__(self):
+        if self.op == "release":
+            return "release"
+        key = "x".join(str(k) for k in self.key)
+        return "%s%s %s on %s%s" % ("refused " if self.op == "refuse" else "", self.entry, key, self.image,
+                                    " [%s]" % self.mode if self.mode else "")
+
+
+RELEASE = Step("release")
+
+
+def call(entry, key, image="real", mode=None):
+    return Step("call", entry, key, image, mode)
+
+
+def refuse(entry, key):
+    return Step("refuse", entry, key)
+
+
+class Prepared:
+    """One step made ready: `arena` (a built numpy-backend Arena: the layout), `image` (the bytes the call is given),
+    `judge(snapshot)` or None where no reference exists for the image, `handle` (the library's own)."""
+
+    def __init__(self, arena, image, judge, handle=None):
+        self.arena, self.image, self.judge, self.handle = arena, image, judge, handle
+
+
+def run_history(lib, steps, what="", cold_info=None):
+    """Runs `steps` on `lib` and judges every one; the last step is the call under test.  `cold_info`: the info record
+    of the last step's call made cold (None: the entry has none).  Raises HistoryError at the first thing found; the
+    message names the step and what preceded it.  Returns the info record after the last step."""
+    assert steps and steps[-1].op == "call" and steps[-1].image == "real"
+    for i, step in enumerate(steps):
+        told = "%s%s, after [%s]" % (what + ": " if what else "", step, "; ".join(repr(s) for s in steps[:i]) or "nothing")
+        if step.op == "release":
+            lib.release()
+            continue
+        prep = lib.prepare(step)
+        before_info = lib.info(step.entry)
+        if step.op == "refuse":
+            try:
+                after = lib.refuse(prep, step)
+            except AssertionError as e:
+                raise HistoryError("refusal", i, told, str(e))
+            if not ga.bits_equal(after, prep.image):
+                at = int(np.flatnonzero(after != prep.image)[0])
+                raise HistoryError("refusal", i, told, "the refused call changed byte %d of the arena" % at)
+            if lib.info(step.entry) != before_info:
+                raise HistoryError("info", i, told, "the refused call changed the record: %r -> %r" % (before_info, lib.info(step.entry)))
+            continue
+        after = lib.run(prep, step)
+        try:
+            prep.arena.check(prep.image, after)
+        except ga.GuardError as e:
+            raise HistoryError("guard", i, told, str(e))
+        if prep.judge is not None:
+            try:
+                prep.judge(after)
+            except AssertionError as e:
+                raise HistoryError("mismatch", i, told, str(e))
+    info = lib.info(steps[-1].entry)
+    if cold_info is not None and info != cold_info:
+        fields = [j for j in range(len(cold_info)) if info[j] != cold_info[j]]
+        raise HistoryError("info", len(steps) - 1, told, "fields %s of the record differ from the cold call's: %r, cold %r" % (
+            fields, info, cold_info))
+    return info
+
+
+# ------------------------------------------------------------------ the slots (csrc/common.hpp: WorkspaceSlot)
+
+def _both(*names):
+    return [n + b for n in names for b in ("", "_batch")]
+
+
+_PAIRS = ["soil_particles_pair_slab", "soil_particles_pair_slab_ex", "soil_particles_pair_colour", "soil_particles_pair_colour_slab"]
+_SINGLE_LAUNCH = ["soil_transport_fluvial", "soil_transport_debris", "soil_particles_fluvial_slab", "soil_particles_debris_slab"]
+_STEPS = ["soil_erode_step", "soil_erode_step_ex", "soil_erode_step_colour"]
+_BATCH_PARTICLES = ["soil_particles_batch" + s for s in ("", "_colour", "_params", "_models")]
+_BATCH_STEPS = ["soil_erode_step_batch" + s for s in ("", "_colour", "_params", "_models")]
+# batch_models_to_device (csrc/erosion_particles.hip) alone: the cell phase of a sweep or of a batch of models
+_BATCH_RECORDS = ["soil_erode_cells_fused_batch_params", "soil_erode_cells_fused_batch_models"]
+
+# slot -> the entries whose call reaches workspace_get with it, as read from csrc/ (the launch shape decides which of
+# the particle slots a launch takes: every particle entry is listed under each)
+SLOTS = {
+    "WS_ACCUMULATE_0": ["soil_accumulate", "soil_multiflow"],
+    "WS_ACCUMULATE_1": ["soil_multiflow"],
+    "WS_SMALL_LAUNCH": _SINGLE_LAUNCH + _PAIRS + _STEPS + ["soil_erode"],
+    "WS_TILED_FLUVIAL": ["soil_transport_fluvial", "soil_particles_fluvial_slab"] + _PAIRS + _STEPS + ["soil_erode"],
+    "WS_TILED_DEBRIS": ["soil_transport_debris", "soil_particles_debris_slab"] + _PAIRS + _STEPS + ["soil_erode"],
+    "WS_PAIR_GATE": _PAIRS + _STEPS + ["soil_erode"],
+    "WS_MULTIFLOW": ["soil_multiflow"],
+    "WS_CONDITIONING": _both("soil_fill_depressions"),
+    "WS_ERODE": ["soil_erode"],
+    "WS_STEP_RNG": _STEPS,
+    "WS_BATCH": _BATCH_PARTICLES + _BATCH_STEPS + _BATCH_RECORDS,
+    "WS_STATS": ["soil_erode_batch_stats"],
+    "WS_FLOW_BATCH": ["soil_random_weighted_batch", "soil_slope_batch"],
+    "WS_ACCUMULATE_BATCH": ["soil_accumulate_batch"],
+    "WS_FLOW_PATHS": _both("soil_flow_paths"),
+    "WS_FLATS": _both("soil_flat_distance"),
+    "WS_DOWNSTREAM": _both("soil_downstream", "soil_stream_power"),
+    "WS_DIFFUSE": _both("soil_diffuse"),
+    "WS_DEPOSIT": _both("soil_stream_power_deposit", "soil_stream_power_deposit_n"),
+    "WS_DEPOSIT_RAKE": _both("soil_stream_power_deposit", "soil_stream_power_deposit_n"),
+    "WS_DEPOSIT_PLANES": _both("soil_stream_power_deposit", "soil_stream_power_deposit_n"),
+    "WS_POWER_N": _both("soil_stream_power_n"),
+    "WS_POWER_N_ITERATE": _both("soil_stream_power_n"),
+    "WS_SLOPE_LIMIT": _both("soil_slope_limit"),
+    "WS_UPSTREAM": _both("soil_upstream_extreme"),
+    "WS_STREAM_ORDER": _both("soil_stream_order"),
+    "WS_MFD": _both("soil_mfd_weights", "soil_mfd_accumulate"),
+}
+
+# The groups of history 5: every ordered pair of a group runs back to back.  A group is the users of one slot, or of
+# slots that travel together; grid and batch forms of one operation are siblings.  The flow-batch group holds all five
+# flow-batch entries, of which two upload words into WS_FLOW_BATCH: the other three run between them.
+SIBLING_GROUPS = {
+    "WS_FLOW_BATCH": ["soil_direction_batch", "soil_steepest_batch", "soil_random_weighted_batch", "soil_slope_batch",
+                      "soil_accumulate_batch"],
+    "WS_BATCH": SLOTS["WS_BATCH"],
+    "WS_DOWNSTREAM": SLOTS["WS_DOWNSTREAM"],
+    "WS_MFD": SLOTS["WS_MFD"],
+    "WS_CONDITIONING": SLOTS["WS_CONDITIONING"],
+    "WS_FLOW_PATHS": SLOTS["WS_FLOW_PATHS"],
+    "WS_ACCUMULATE": ["soil_accumulate", "soil_multiflow"],                      # the lanes: WS_ACCUMULATE_0 / _1
+    "WS_DEPOSIT": SLOTS["WS_DEPOSIT"],                                           # and the rake, and the planes
+    "WS_POWER_N": SLOTS["WS_POWER_N"],
+    "WS_FLATS": SLOTS["WS_FLATS"],
+    "WS_DIFFUSE": SLOTS["WS_DIFFUSE"],
+    "WS_SLOPE_LIMIT": SLOTS["WS_SLOPE_LIMIT"],
+    "WS_UPSTREAM": SLOTS["WS_UPSTREAM"],
+    "WS_STREAM_ORDER": SLOTS["WS_STREAM_ORDER"],
+    "WS_STEP_RNG": SLOTS["WS_STEP_RNG"],
+}
+
+
+def slot_enumerators():
+    """The enumerators of WorkspaceSlot, parsed from csrc/common.hpp."""
+    text = open(os.path.join(ROOT, "soillib_amd", "csrc", "common.hpp")).read()
+    m = re.search(r"enum\s+WorkspaceSlot\s*\{(.*?)\}\s*;", text, flags=re.S)
+    assert m, "csrc/common.hpp has no enum WorkspaceSlot"
+    body = re.sub(r"//[^\n]*", "", m.group(1))
+    return [n for n in re.findall(r"\b(WS_[A-Z0-9_]+)\s*(?:=\s*\d+\s*)?,?", body)]
+
+
+# ------------------------------------------------------------------ the info records (include/soil_hip.h)
+
+INFO = {}
+for _names, _fn, _n in ((("soil_fill_depressions",), "soil_fill_depressions_info", 16),
+                        (("soil_flow_paths",), "soil_flow_paths_info", 4),
+                        (("soil_downstream", "soil_stream_power"), "soil_downstream_info", 4),
+                        (("soil_upstream_extreme",), "soil_upstream_extreme_info", 4),
+                        (("soil_stream_order",), "soil_stream_order_info", 5),
+                        (("soil_stream_power_deposit",), "soil_stream_power_deposit_info", 4),
+                        (("soil_stream_power_n",), "soil_stream_power_n_info", 4),
+                        (("soil_stream_power_deposit_n",), "soil_stream_power_deposit_n_info", 4),
+                        (("soil_diffuse",), "soil_diffuse_info", 4),
+                        (("soil_flat_distance",), "soil_flat_distance_info", 4),
+                        (("soil_slope_limit",), "soil_slope_limit_info", 4),
+                        (("soil_mfd_accumulate",), "soil_mfd_info", 4)):
+    for _e in _both(*_names):
+        INFO[_e] = (_fn, _n)
+# No field of any record is excluded: the header calls each of them a function of the call alone (launches, chunks,
+# rounds, passes, looks, "bytes of scratch the call asked for": asked for, not held).
+
+
+# ------------------------------------------------------------------ keys
+
+def cells_of(key):
+    return int(np.prod([k for k in key if not isinstance(k, str)], dtype=np.int64))
+
+
+def is_batch(key):
+    return len([k for k in key if not isinstance(k, str)]) == 3
+
+
+def largest(row):
+    return max(row.cases, key=cells_of)         # (the first of equals)
+
+
+def _is_thin(key):
+    return 1 in tuple(k for k in key if not isinstance(k, str))[-2:]
+
+
+def smallest(row):
+    """The smallest key with more than one row and column: (5, 7) or a batch of it; (1, 9) and (9, 1) come after it."""
+    wide = [k for k in row.cases if not _is_thin(k)]
+    return min(wide or row.cases, key=cells_of)
+
+
+def thin(row):
+    """(1, 9) or (9, 1), or a batch of them, where the row has one."""
+    for key in row.cases:
+        dims = tuple(k for k in key if not isinstance(k, str))
+        if dims[-2:] in ((1, 9), (9, 1)) and len(dims) == len(key):
+            return key
+    return None
+
+
+def sibling_key(row):
+    """The one key of history 5: (65, 70), (3, 65, 67) (the staged walker count where there are two), else the largest."""
+    for key in ((65, 70), (3, 65, 67), (3, 65, 67, "N1100")):
+        if key in row.cases:
+            return key
+    return largest(row)
+
+
+# rows without any input plane (tests/test_gpu_on_a_busy_stream.py: DECOY): history 2 uses another key in place of a decoy
+OUTPUTS_ONLY = ("soil_set_f32", "soil_set_i32", "soil_rng_seed", "soil_noise", "soil_noise_window")
+
+
+# ------------------------------------------------------------------ the plans
+
+def plan(kind, rows, entry):
+    """The steps of history `kind` (cold, stale, shrink, regrow, refusal) for row `entry`."""
+    row = rows[entry]
+    big, small = largest(row), smallest(row)
+    one = big == small                      # a row with one key: the decoy stands in for the other size
+    if kind == COLD:
+        return [RELEASE, call(entry, big)]
+    if kind == STALE:
+        if entry in OUTPUTS_ONLY:
+            return [call(entry, small), call(entry, big)]
+        return [call(entry, big, "decoy"), call(entry, big)]
+    if kind == SHRINK:
+        if is_batch(big) and (3, 65, 67) in row.cases and (3, 5, 7) in row.cases:
+            return [call(entry, (3, 65, 67)), call(entry, (3, 5, 7))]
+        if one:
+            return [call(entry, big, "decoy"), call(entry, big)]
+        steps = [call(entry, big), call(entry, small)]
+        if thin(row) is not None and thin(row) != small:
+            steps.append(call(entry, thin(row)))
+        return steps
+    if kind == REGROW:
+        if one:
+            return [RELEASE, call(entry, small, "decoy"), call(entry, small)]
+        return [RELEASE, call(entry, small), call(entry, big), call(entry, small)]
+    if kind == REFUSAL:
+        assert entry not in NO_REFUSAL, entry
+        return [call(entry, big), refuse(entry, big), call(entry, big)]
+    raise ValueError(kind)
+
+
+def sibling_plans(rows):
+    """(group, first, second): every ordered pair of every group of SIBLING_GROUPS."""
+    return [(g, a, b) for g, names in SIBLING_GROUPS.items() for a in names for b in names if a != b]
+
+
+def sibling_plan(rows, first, second):
+    return [call(first, sibling_key(rows[first])), call(second, sibling_key(rows[second]))]
+
+
+# The non-quiescent predecessors of history 6: entry -> the images its predecessor runs on
+# (every entry of the pointer-doubling engine: the header gives the result of "a cell that is not final after the last
+# round", and the ops' own parity files run cyclic graphs; the deposit rows have no stop plane)
+CYCLES = _both("soil_flow_paths", "soil_downstream", "soil_stream_power", "soil_stream_power_n", "soil_stream_power_deposit",
+               "soil_stream_power_deposit_n", "soil_upstream_extreme", "soil_stream_order")
+RELAXATIONS = _both("soil_fill_depressions", "soil_flat_distance", "soil_slope_limit", "soil_mfd_weights", "soil_mfd_accumulate")
+HOSTILE_LAST = ["soil_erode_cells_fused_batch" + s for s in ("", "_colour", "_params", "_models")]
+RESTLESS_IMAGES = dict([(e, ("cycles",)) for e in CYCLES] + [(e, ("nan", "plateau")) for e in RELAXATIONS] +
+                       [(e, ("hostile_last",)) for e in HOSTILE_LAST])
+
+
+def restless_plans():
+    return [(e, image) for e, images in RESTLESS_IMAGES.items() for image in images]
+
+
+def restless_plan(rows, entry, image):
+    key = sibling_key(rows[entry])
+    return [call(entry, key, image), call(entry, key)]
+
+
+# The launch shapes of history 8 (tests/test_gpu_parity.py: particle_mode)
+LAUNCH_SHAPES = ("direct", "staged", "tiled", "tiled-full", "tiled-panels", "tiled-sparse", "tiled-sparse-full")
+PAIR_ROW = "soil_particles_pair_colour"        # every ordered pair of shapes runs on it
+
+
+def shape_plans(rows):
+    """(entry, the predecessor's shape, the shape under test)"""
+    modes = [e for e, r in rows.items() if getattr(r, "modes", False)]
+    plans = [(PAIR_ROW, a, b) for a in LAUNCH_SHAPES for b in LAUNCH_SHAPES if a != b]
+    n = len(LAUNCH_SHAPES)
+    for i, e in enumerate(e for e in modes if e != PAIR_ROW):       # the remaining rows: shape i under test behind shape i + 1 + i / n
+        plans.append((e, LAUNCH_SHAPES[(i + 1 + i // n) % n], LAUNCH_SHAPES[i % n]))
+    return plans
+
+
+def shape_plan(rows, entry, before, under_test):
+    key = rows[entry].cases[0]
+    return [call(entry, key, "decoy", before), call(entry, key, "real", under_test)]
+
+
+# ------------------------------------------------------------------ the images of history 6
+
+def cyclic_graph(shape):
+    """A receiver graph without a terminal: every cell and its neighbour in the row (in the column where W == 1) point
+    at each other, an odd cell out points into the last pair.  Every receiver is a D4 neighbour inside its own model."""
+    dims = tuple(shape)
+    B = dims[0] if len(dims) == 3 else 1
+    H, W = dims[-2:]
+    assert H * W >= 2
+    idx = np.arange(H * W, dtype=np.int64).reshape(H, W)
+    g = np.empty((H, W), np.int64)
+    if W > 1:
+        x = np.arange(W)
+        partner = np.where(x % 2 == 0, x + 1, x - 1)
+        partner[partner >= W] = W - 2
+        g[:] = idx[:, partner]
+    else:
+        y = np.arange(H)
+        partner = np.where(y % 2 == 0, y + 1, y - 1)
+        partner[partner >= H] = H - 2
+        g[:] = idx[partner, :]
+    g = g.astype(np.int32)
+    return np.ascontiguousarray(np.broadcast_to(g, (B, H, W)).reshape(dims))
+
+
+def never_ends(graph):
+    """Reference side: no cell of `graph` is terminal, and every receiver lies in the cell's own model: a walk from any
+    cell goes on for ever, so the engine's lists never empty."""
+    g = np.asarray(graph)
+    n = g.shape[-2] * g.shape[-1]
+    flat = g.reshape(-1, n)
+    own = np.arange(n)[None, :]
+    return bool(((flat >= 0) & (flat < n) & (flat != own)).all())
+
+
+def restless_image(arena, entry, name, oracle=None):
+    """The bytes of image `name` for a built arena of row `entry`: the real image with the named planes replaced."""
+    out = arena.host.copy()
+
+    def put(p, new):
+        new = np.ascontiguousarray(new, p.dtype)
+        assert new.shape == tuple(p.shape), (p.name, new.shape, p.shape)
+        out[p.start:p.start + p.nbytes] = new.reshape(-1).view(np.uint8)
+    hit = 0
+    for p in arena.planes:
+        if name == "cycles":
+            if p.name == "graph":
+                put(p, cyclic_graph(p.shape))
+                hit += 1
+            elif p.name == "stop":                      # nothing stops a walk either
+                put(p, np.zeros(p.shape, np.int32))
+        elif name in ("nan", "plateau") and p.name == "height":
+            put(p, np.full(p.shape, np.nan if name == "nan" else 5.0, np.float32))
+            hit += 1
+        elif name == "hostile_last" and p.data is not None and p.role in (IN, INOUT):
+            import util
+            B, H, W = p.shape[:3]
+            hostile = util.hostile_cell_inputs(oracle, H, W, seed=H * 1000 + W)
+            if p.name in hostile:
+                new = p.data.copy()
+                new[B - 1] = hostile[p.name]
+                put(p, new)
+                hit += 1
+    assert hit, "image %r replaces no plane of %s" % (name, entry)
+    return out
+
+
+# ------------------------------------------------------------------ the library
+
+# Rows without a refusal: the header names none for them (n <= 0 is a no-op that returns SOIL_OK, a null pointer is
+# not checked), and none of them takes a workspace slot.  History 7 runs every other row.
+NO_REFUSAL = ("soil_set_f32", "soil_set_i32", "soil_add_f32", "soil_multiply_f32", "soil_rng_seed")
+# Entries whose listed refusals (tests/golden/refusal_text.json) are all of the temperature T, the argument before the
+# stream: the refused call passes T = -1
+REFUSED_T = ("soil_random_weighted", "soil_random_weighted_batch", "soil_multiflow")
+
+
+def bad_scalar(entry):
+    """The one invalid scalar of the refused call of `entry`, where tests/golden/refusal_text.json lists one that a row
+    can pass: "T" (T = -1), "H" (H = 0: "<entry>: empty grid"), or None: the table lists nothing for the entry, and the
+    refused call passes every plane pointer NULL instead."""
+    if entry in REFUSED_T:
+        return "T"
+    if any(msg.endswith(": empty grid") for _, msg in listed_refusals(entry)):
+        return "H"
+    return None
+
+
+class _Refusing:
+    """`lib` with the invalid scalar of bad_scalar in its place for `entry`: T = -1 before the stream, or H = 0, the
+    first int64 argument of a grid entry and the second (behind B) of a batch entry, by soillib_amd._abi.SIGNATURES."""
+
+    def __init__(self, lib, entry):
+        self._lib, self._entry, self._bad = lib, entry, bad_scalar(entry)
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name != self._entry or self._bad is None:
+            return fn
+        if self._bad == "T":
+            return lambda *args: fn(*(args[:-2] + (-1.0, args[-1])))
+        from soillib_amd import _abi
+        sizes = [i for i, t in enumerate(_abi.SIGNATURES[name][1]) if t is C.c_int64]
+        at = sizes[1 if name.endswith("_batch") else 0]
+        return lambda *args: fn(*(args[:at] + (0,) + args[at + 1:]))
+
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "refusal_text.json")
+_REFUSALS = {}
+
+
+def listed_refusals(entry):
+    """The messages tests/golden/refusal_text.json lists for the C entry `entry` (empty: it lists none)."""
+    if not _REFUSALS:
+        for k, v in json.load(open(GOLDEN)).items():
+            if "rc" in v:
+                _REFUSALS.setdefault(k.split("/")[1], set()).add((v["rc"], v["error"]))
+    return _REFUSALS.get(entry, _REFUSALS.get(entry[len("soil_"):], set()))
+
+
+@contextlib.contextmanager
+def launch_shape(lib, mode):
+    """The particle kernels' launch shape `mode`, as tests/test_gpu_parity.py's particle_mode fixture sets it."""
+    if mode is None:
+        yield
+        return
+    env = {}
+    if mode == "tiled-full":
+        env["SOIL_TILED_SHAPE"] = "3"
+    if mode == "tiled-panels":
+        env["SOIL_TILED_PANELS"] = "1"
+    if mode.startswith("tiled-sparse"):
+        env.update(SOIL_TILED_SPARSE="1", SOIL_TILED_SPARSE_MIN="1", SOIL_TILED_SPARSE_PCT="1")
+    if mode == "tiled-sparse-full":
+        env["SOIL_TILED_SPARSE_PROBE"] = "1"
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    assert lib.soil_set_particle_mode(1 if mode == "direct" else 2 if mode == "staged" else 3) == 0
+    try:
+        yield
+    finally:
+        lib.soil_set_particle_mode(0)
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+class SoilLibrary:
+    """The runner's interface on libsoil_hip: the rows of the guard-band tables through soillib_amd._abi, each image
+    uploaded into an allocation of its own and read back whole."""
+
+    def __init__(self, lib, oracle, rows, want):
+        from soillib_amd import _abi
+        self.lib, self.oracle, self.rows, self.want, self._abi, self._last = lib, oracle, rows, want, _abi, None
+
+    def release(self):
+        self._abi.check(self.lib.soil_workspace_release())
+
+    def prepare(self, step):
+        import busy_stream as bs
+        case = self.rows[step.entry].build(step.key, self.oracle)
+        arena = ga.Arena("aligned", "A", "numpy")
+        for name, role, data, dtype, fills in case.planes:
+            arena.add(name, data, role, dtype=dtype, fills=fills)
+        arena.build()
+        judge = None
+        if step.image == "real":
+            image = arena.host
+            if step.op == "call":
+                if (step.entry, step.key) not in self.want:         # made once, shared with the guard-band tests
+                    self.want[step.entry, step.key] = case.want(self.lib, self.oracle)
+                want = self.want[step.entry, step.key]
+                judge = lambda snap: ga.judge_outputs(case, arena, snap, want, repr(step))          # noqa: E731
+        elif step.image == "decoy":
+            image = bs.decoy_bytes(arena)
+        else:
+            image = restless_image(arena, step.entry, step.image, self.oracle)
+        return Prepared(arena, image, judge, case)
+
+    def _on_device(self, prep, step, ptr_of, lib=None):
+        from soillib_amd import silt
+        dev = self._last = silt.tensor.from_numpy(prep.image.view(np.float32)).gpu()
+        base = dev.ptr
+        try:
+            with launch_shape(self.lib, step.mode):
+                prep.handle.call(lib or self.lib, ptr_of(base))
+        finally:
+            try:
+                self._abi.check(self.lib.soil_device_synchronize())
+            except self._abi.SoilError as e:
+                ga.end_session_on_fault(e, repr(step))
+                raise
+        return dev.cpu().numpy().view(np.uint8).copy()
+
+    def run(self, prep, step):
+        arena = prep.arena
+        try:
+            return self._on_device(prep, step, lambda base: lambda name: None if name is None else base + arena.plane(name).start)
+        except self._abi.SoilError as e:
+            ga.end_session_on_fault(e, repr(step))
+            raise
+
+    def refuse(self, prep, step):
+        """The row's call with one invalid scalar that tests/golden/refusal_text.json lists for the entry (bad_scalar:
+        H = 0 or T = -1) and the real arena pointers: refused with SOIL_ERR_INVALID_ARGUMENT and a message the table
+        lists, and the arena, read back, is what it was.  An entry the table does not list passes every plane pointer
+        NULL: no plane is passed then, and what the history holds is the workspace and the info record."""
+        arena, bad = prep.arena, bad_scalar(step.entry)
+        if bad is None:
+            ptr_of = lambda base: lambda name: None                                             # noqa: E731
+        else:
+            ptr_of = lambda base: lambda name: None if name is None else base + arena.plane(name).start    # noqa: E731
+        try:
+            self._on_device(prep, step, ptr_of, _Refusing(self.lib, step.entry))
+        except ValueError as e:                 # _abi.check: SOIL_ERR_INVALID_ARGUMENT, the text of soil_last_error()
+            msg = str(e)
+        except self._abi.SoilError as e:
+            ga.end_session_on_fault(e, repr(step))
+            raise AssertionError("%s with %s: %s" % (step.entry, bad or "null planes", e))
+        else:
+            raise AssertionError("%s with %s was not refused" % (step.entry, "%s invalid" % bad if bad else "null planes"))
+        listed = listed_refusals(step.entry)
+        assert not listed or (self._abi.SOIL_ERR_INVALID_ARGUMENT, msg) in listed, (
+            "%s: %r is no refusal that tests/golden/refusal_text.json lists" % (step.entry, msg))
+        return self._last.cpu().numpy().view(np.uint8).copy()
+
+    def info(self, entry):
+        if entry not in INFO:
+            return None
+        fn, n = INFO[entry]
+        words = (C.c_int64 * n)()
+        self._abi.check(getattr(self.lib, fn)(words))
+        return tuple(int(w) for w in words)
