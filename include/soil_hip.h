@@ -890,6 +890,14 @@ int soil_fill_depressions_info(int64_t info[16]);
  * soil_workspace_release frees all cached blocks of the current device, of every thread: call it
  * while no other thread is inside the library. */
 int soil_workspace_release(void);
+/* What the library holds for its host threads, process-wide and on every device: info[0] streams, info[1] events,
+ * info[2] pinned host allocations, info[3] cached scratch blocks.  Counted where each is made and freed.  A host thread
+ * owns its blocks, the pinned "changed" words of the relaxations, the pinned staging of the batch uploads, the lanes of
+ * soil_multiflow and the forked streams and the pinned record of the tiled particle launches; all of them go when the
+ * thread ends (behind a hipDeviceSynchronize()), except on the thread that loaded the library, which keeps them until
+ * the process exits.  Not counted: what the caller owns (soil_event_create, the handles of soil_slab.h).  All zero
+ * before the first call that needs one; needs no device.  SOIL_ERR_INVALID_ARGUMENT for a null `info`. */
+int soil_host_objects_info(int64_t info[4]);
 
 /* ------------------------------------------ flow graphs: batches of models */
 

@@ -290,6 +290,7 @@ SIGNATURES = {
     "soil_mfd_accumulate_batch": (cint, [vp, vp, vp, vp, vp, cint, C.c_double, i64, i64, i64, F3, i64, cint, vp]),
     "soil_mfd_info": (cint, [C.POINTER(i64)]),
     "soil_workspace_release": (cint, []),
+    "soil_host_objects_info": (cint, [C.POINTER(i64)]),
     "soil_gradient": (cint, [vp, vp, i64, i64, F3, vp]),
     "soil_negslope": (cint, [vp, vp, i64, i64, F3, vp]),
     "soil_laplacian": (cint, [vp, vp, i64, i64, cint, F3, vp]),

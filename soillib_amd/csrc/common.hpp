@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -81,6 +82,96 @@ enum WorkspaceSlot {
 };
 int workspace_get(WorkspaceSlot slot, size_t bytes, void** out);
 int workspace_release_all();
+
+// ---- what a host thread owns besides its blocks -------------------------------------
+// The streams, events and pinned words that a call keeps from one call of its host thread to the next live in a
+// ThreadOwned<T>: device -> T, thread_local at its user.  When the thread ends, every T is released on its device,
+// behind a hipDeviceSynchronize(): a pinned word is written by kernels on the caller's stream and a lane may hold
+// queued work.  Nothing is released on the thread that loaded the library: its destructors run at process exit, next
+// to the HIP runtime's own teardown.  No destructor takes a lock that a call holds while it waits for the device
+// (WsThreadGuard synchronises under the workspace mutex; the counts below are atomics).
+// Every creation and destruction goes through the helpers, which keep the process-wide counts of
+// soil_host_objects_info (runtime.hip).
+enum HostObject { HOST_STREAM = 0, HOST_EVENT = 1, HOST_PINNED = 2, HOST_BLOCK = 3 };
+void host_object_count(HostObject what, int64_t delta);
+bool on_loader_thread();
+inline hipError_t owned_stream_create(hipStream_t* s) {
+  const hipError_t e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+  if (e == hipSuccess) host_object_count(HOST_STREAM, 1);
+  return e;
+}
+inline hipError_t owned_event_create(hipEvent_t* ev) {
+  const hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+  if (e == hipSuccess) host_object_count(HOST_EVENT, 1);
+  return e;
+}
+inline hipError_t owned_pinned_alloc(void** p, size_t bytes, unsigned flags) {
+  const hipError_t e = hipHostMalloc(p, bytes, flags);
+  if (e == hipSuccess) host_object_count(HOST_PINNED, 1);
+  return e;
+}
+inline hipError_t owned_pinned_free(void* p) {
+  if (!p) return hipSuccess;
+  host_object_count(HOST_PINNED, -1);
+  return hipHostFree(p);
+}
+inline void owned_stream_destroy(hipStream_t& s) {
+  if (!s) return;
+  (void)hipStreamSynchronize(s);
+  (void)hipStreamDestroy(s);
+  host_object_count(HOST_STREAM, -1);
+  s = nullptr;
+}
+inline void owned_event_destroy(hipEvent_t& ev) {
+  if (!ev) return;
+  (void)hipEventDestroy(ev);
+  host_object_count(HOST_EVENT, -1);
+  ev = nullptr;
+}
+
+template <class Fn>
+inline void thread_end_on_device(int device, Fn&& release) {  // `release` on `device`, the thread's device kept
+  if (on_loader_thread()) return;
+  int before = 0;
+  if (hipGetDevice(&before) != hipSuccess) {
+    (void)hipGetLastError();
+    return;
+  }
+  if (hipSetDevice(device) == hipSuccess) {
+    (void)hipDeviceSynchronize();
+    release();
+  }
+  (void)hipSetDevice(before);
+  (void)hipGetLastError();
+}
+
+template <class T>  // T: default-constructible, with release()
+struct ThreadOwned {
+  std::map<int, T> of;  // device -> the thread's objects there
+  T& operator[](int device) { return of[device]; }
+  ~ThreadOwned() {
+    for (auto& kv : of) thread_end_on_device(kv.first, [&] { kv.second.release(); });
+  }
+};
+
+// "something changed in this launch": a pinned, device-mapped int the kernels write straight into
+struct PinnedWord {
+  int *host = nullptr, *dev = nullptr;
+  hipError_t ensure() {
+    if (host) return hipSuccess;
+    void* p = nullptr;
+    hipError_t e = owned_pinned_alloc(&p, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) return e;
+    host = static_cast<int*>(p);
+    e = hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), host, 0);
+    if (e != hipSuccess) release();
+    return e;
+  }
+  void release() {
+    (void)owned_pinned_free(host);
+    host = dev = nullptr;
+  }
+};
 
 // Device counter of particle steps (iterations that pass the loop head and its
 // slab check, i.e. what the oracle counts), accumulated by every particle launch

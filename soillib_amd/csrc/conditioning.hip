@@ -389,15 +389,12 @@ static int fill_impl(float* out, const float* height, bool batch, int64_t B, int
   // "some tile moved in this launch": a pinned, device-mapped word the tiles write straight
   // into (a device-to-host copy is a 25-50 us blit kernel on this stack, per launch)
   // (one per host thread and device; one for all the models of a batch)
-  static thread_local std::map<int, std::pair<int*, int*>> t_flags;
+  static thread_local ThreadOwned<PinnedWord> t_flags;  // (goes with the thread: common.hpp)
   int dev = 0;
   SOIL_HIP(hipGetDevice(&dev));
-  auto& fl = t_flags[dev];
-  if (!fl.first) {
-    SOIL_HIP(hipHostMalloc(reinterpret_cast<void**>(&fl.first), sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    SOIL_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&fl.second), fl.first, 0));
-  }
-  int *const t_flag = fl.first, *const t_flag_dev = fl.second;
+  PinnedWord& fl = t_flags[dev];
+  SOIL_HIP(fl.ensure());
+  int *const t_flag = fl.host, *const t_flag_dev = fl.dev;
   // from here on the call launches: what it does is recorded (a call that failed before this leaves the last record)
   t_fill_info = FillInfo{};
   t_fill_info.levels = static_cast<int64_t>(lv.size()), t_fill_info.models = B;

@@ -768,35 +768,35 @@ int particles_debris(const Launch& L) { return particles_single(DEBRIS, L); }
 // copy queued from it the call before has been made — which lets the host queue one batch ahead of the device, and
 // not further.
 namespace {
-const std::thread::id g_seed_loader = std::this_thread::get_id();
 struct SeedStaging {
   void* host = nullptr;
   size_t bytes = 0;
   hipEvent_t copied = nullptr;
-  ~SeedStaging() {  // a thread's buffer goes with it (not the loading thread's: HIP may be gone by then)
-    if (std::this_thread::get_id() == g_seed_loader) return;
-    if (copied) (void)hipEventSynchronize(copied), (void)hipEventDestroy(copied);
-    if (host) (void)hipHostFree(host);
-    (void)hipGetLastError();
+  void release() {  // a thread's buffer goes with it (ThreadOwned, common.hpp)
+    if (copied) (void)hipEventSynchronize(copied);
+    owned_event_destroy(copied);
+    (void)owned_pinned_free(host);
+    host = nullptr, bytes = 0;
   }
 };
 }  // namespace
 
 // One host-to-device copy: the host arrays of `parts` (pointer, bytes; null: left out) one after the other at dst.
 static int upload_seeds(void* dst, std::initializer_list<std::pair<const void*, size_t>> parts, hipStream_t st) {
-  static thread_local std::map<int, SeedStaging> staging;  // device -> staging
+  static thread_local ThreadOwned<SeedStaging> staging;  // device -> staging
   int dev = 0;
   SOIL_HIP(hipGetDevice(&dev));
   SeedStaging& u = staging[dev];
   size_t bytes = 0;
   for (const auto& [src, n] : parts) bytes += src ? n : 0;
   if (u.copied) SOIL_HIP(hipEventSynchronize(u.copied));
-  else SOIL_HIP(hipEventCreateWithFlags(&u.copied, hipEventDisableTiming));
+  else SOIL_HIP(owned_event_create(&u.copied));
   if (u.bytes < bytes) {
-    if (u.host) SOIL_HIP(hipHostFree(u.host));
+    void* const old = u.host;
     u.host = nullptr;
     u.bytes = 0;
-    SOIL_HIP(hipHostMalloc(&u.host, bytes, hipHostMallocDefault));
+    SOIL_HIP(owned_pinned_free(old));
+    SOIL_HIP(owned_pinned_alloc(&u.host, bytes, hipHostMallocDefault));
     u.bytes = bytes;
   }
   size_t at = 0;

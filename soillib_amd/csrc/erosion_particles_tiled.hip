@@ -2933,13 +2933,19 @@ struct TiledRun {
       TiledHostWord *host = nullptr, *host_dev = nullptr;
       uint32_t seq = 0;  // numbers the launches that fill `host`, across runs
       double ticks_per_second = 1.0e8;
+      void release() {  // the record goes with the thread (ThreadOwned, common.hpp)
+        (void)owned_pinned_free(host);
+        host = host_dev = nullptr;
+      }
     };
-    static thread_local std::map<int, HostSide> t_side;
+    static thread_local ThreadOwned<HostSide> t_side;
     int dev = 0;
     SOIL_HIP(hipGetDevice(&dev));
     HostSide& hs = t_side[dev];
     if (!hs.host) {
-      SOIL_HIP(hipHostMalloc(reinterpret_cast<void**>(&hs.host), sizeof(TiledHostWord), hipHostMallocMapped | hipHostMallocCoherent));
+      void* word = nullptr;
+      SOIL_HIP(owned_pinned_alloc(&word, sizeof(TiledHostWord), hipHostMallocMapped | hipHostMallocCoherent));
+      hs.host = static_cast<TiledHostWord*>(word);
       SOIL_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&hs.host_dev), hs.host, 0));
       hs.host->seq = 0;
       int khz = 0;  // rate of the realtime counter the scans time the rounds with
@@ -3254,17 +3260,21 @@ int launch_pair_tiled(const Launch& L, MigrateBox box_fluvial, MigrateBox box_de
   struct Fork {
     hipStream_t sA = nullptr, sB = nullptr;
     hipEvent_t fork = nullptr, joinA = nullptr, joinB = nullptr;
+    void release() {  // they go with the thread (ThreadOwned, common.hpp)
+      owned_stream_destroy(sA), owned_stream_destroy(sB);
+      owned_event_destroy(fork), owned_event_destroy(joinA), owned_event_destroy(joinB);
+    }
   };
-  static thread_local std::map<int, Fork> t_fork;
+  static thread_local ThreadOwned<Fork> t_fork;
   int dev = 0;
   SOIL_HIP(hipGetDevice(&dev));
   Fork& f = t_fork[dev];
-  if (!f.sA) {
-    SOIL_HIP(hipStreamCreateWithFlags(&f.sA, hipStreamNonBlocking));
-    SOIL_HIP(hipStreamCreateWithFlags(&f.sB, hipStreamNonBlocking));
-    SOIL_HIP(hipEventCreateWithFlags(&f.fork, hipEventDisableTiming));
-    SOIL_HIP(hipEventCreateWithFlags(&f.joinA, hipEventDisableTiming));
-    SOIL_HIP(hipEventCreateWithFlags(&f.joinB, hipEventDisableTiming));
+  if (!f.joinB) {
+    if (!f.sA) SOIL_HIP(owned_stream_create(&f.sA));
+    if (!f.sB) SOIL_HIP(owned_stream_create(&f.sB));
+    if (!f.fork) SOIL_HIP(owned_event_create(&f.fork));
+    if (!f.joinA) SOIL_HIP(owned_event_create(&f.joinA));
+    SOIL_HIP(owned_event_create(&f.joinB));
   }
   const hipStream_t sA = f.sA, sB = f.sB;
   TiledRun<FLUVIAL> A = make_run<FLUVIAL>(L, sA);

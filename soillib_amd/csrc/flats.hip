@@ -279,15 +279,12 @@ static int flat_distance_run(int32_t* dist, const float* height, int64_t B, int6
   unsigned char* const mask = inert + b_marks;
   // "some tile moved in this launch": a pinned, device-mapped word the tiles write straight into (one per host
   // thread and device, as in conditioning.hip)
-  static thread_local std::map<int, std::pair<int*, int*>> t_flags;
+  static thread_local ThreadOwned<PinnedWord> t_flags;  // (goes with the thread: common.hpp)
   int dev = 0;
   SOIL_HIP(hipGetDevice(&dev));
-  auto& fl = t_flags[dev];
-  if (!fl.first) {
-    SOIL_HIP(hipHostMalloc(reinterpret_cast<void**>(&fl.first), sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    SOIL_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&fl.second), fl.first, 0));
-  }
-  int *const flag_host = fl.first, *const flag_dev = fl.second;
+  PinnedWord& fl = t_flags[dev];
+  SOIL_HIP(fl.ensure());
+  int *const flag_host = fl.host, *const flag_dev = fl.dev;
   // The fill's bound (conditioning.hip: fill_level): a value reaches a cell along a shortest path inside the flat, a
   // simple path, and a launch finishes in every tile the stretch of it inside the tile up to the next seam, or
   // 4 kLT cells of it.  The models of a batch run side by side: the bound is one model's.

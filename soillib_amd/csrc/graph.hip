@@ -1295,14 +1295,24 @@ struct FlowLanes {
     if (device == dev) return SOIL_OK;
     SOIL_REQUIRE(device < 0, "multiflow: a host thread's lanes belong to the device of its first call");
     for (int j = 0; j < kAccLanes; ++j) {
-      SOIL_HIP(hipStreamCreateWithFlags(&lane[j], hipStreamNonBlocking));
-      SOIL_HIP(hipEventCreateWithFlags(&done[j], hipEventDisableTiming));
-      SOIL_HIP(hipEventCreateWithFlags(&used[j], hipEventDisableTiming));
+      if (!lane[j]) SOIL_HIP(owned_stream_create(&lane[j]));  // (a call that failed half way made some already)
+      if (!done[j]) SOIL_HIP(owned_event_create(&done[j]));
+      if (!used[j]) SOIL_HIP(owned_event_create(&used[j]));
     }
-    SOIL_HIP(hipEventCreateWithFlags(&start, hipEventDisableTiming));
-    for (int j = 0; j < 2; ++j) SOIL_HIP(hipEventCreateWithFlags(&graphs[j], hipEventDisableTiming));
+    if (!start) SOIL_HIP(owned_event_create(&start));
+    for (int j = 0; j < 2; ++j)
+      if (!graphs[j]) SOIL_HIP(owned_event_create(&graphs[j]));
     device = dev;
     return SOIL_OK;
+  }
+  void release() {
+    for (int j = 0; j < kAccLanes; ++j) owned_stream_destroy(lane[j]), owned_event_destroy(done[j]), owned_event_destroy(used[j]);
+    owned_event_destroy(start);
+    for (int j = 0; j < 2; ++j) owned_event_destroy(graphs[j]);
+    device = -1;
+  }
+  ~FlowLanes() {  // the lanes go with the thread (common.hpp)
+    if (device >= 0) thread_end_on_device(device, [this] { release(); });
   }
 };
 static thread_local FlowLanes t_flow;

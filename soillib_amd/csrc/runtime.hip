@@ -1,5 +1,6 @@
 // runtime.hip — error channel, device/memory/event plumbing and the silt
 // element-wise ops of the C ABI (include/soil_hip.h §runtime).
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -73,6 +74,12 @@ static std::map<WsKey, WsBlock> g_ws;
 // launches).  Not for the thread that loaded the library: its thread_local destructors run at process
 // exit, next to the HIP runtime's own teardown.
 static const std::thread::id g_loader_thread = std::this_thread::get_id();
+bool on_loader_thread() { return std::this_thread::get_id() == g_loader_thread; }
+
+// soil_host_objects_info: what the library holds, process-wide (streams, events, pinned allocations, blocks)
+static std::atomic<int64_t> g_host_objects[4];
+void host_object_count(HostObject what, int64_t delta) { g_host_objects[what].fetch_add(delta, std::memory_order_relaxed); }
+
 struct WsThreadGuard {
   ~WsThreadGuard() {
     const std::thread::id me = std::this_thread::get_id();
@@ -88,6 +95,7 @@ struct WsThreadGuard {
       if (it->second.base && hipSetDevice(std::get<1>(it->first)) == hipSuccess) {
         (void)hipDeviceSynchronize();  // the thread's launches may still be in flight on its streams
         (void)hipFree(it->second.base);
+        host_object_count(HOST_BLOCK, -1);
       }
       it = g_ws.erase(it);
     }
@@ -107,10 +115,12 @@ int workspace_get(WorkspaceSlot slot, size_t bytes, void** out) {
     if (w.base) {
       SOIL_HIP(hipDeviceSynchronize());  // nobody may still be reading the old block
       SOIL_HIP(hipFree(w.base));
+      host_object_count(HOST_BLOCK, -1);
     }
     w.base = nullptr;
     w.bytes = 0;
     SOIL_HIP(hipMalloc(&w.base, bytes));
+    host_object_count(HOST_BLOCK, 1);
     w.bytes = bytes;
   }
   *out = w.base;
@@ -142,6 +152,7 @@ int workspace_release_all() {
       if (it->second.base) {
         SOIL_HIP(hipDeviceSynchronize());
         SOIL_HIP(hipFree(it->second.base));
+        host_object_count(HOST_BLOCK, -1);
       }
       it = g_ws.erase(it);
     } else {
@@ -238,6 +249,12 @@ extern "C" {
 
 int soil_abi_version(void) { return SOIL_HIP_ABI_VERSION; }
 const char* soil_last_error(void) { return g_last_error.c_str(); }
+
+int soil_host_objects_info(int64_t info[4]) {
+  SOIL_REQUIRE(info, "host_objects_info: null record");
+  for (int i = 0; i < 4; ++i) info[i] = g_host_objects[i].load(std::memory_order_relaxed);
+  return SOIL_OK;
+}
 
 int soil_device_count(void) {
   int n = 0;

@@ -291,15 +291,12 @@ static int slope_limit_run(float* out, float* excess, const float* height, const
   unsigned char* const inert = dirty_next + b_marks;
   // "some tile moved in this launch": a pinned, device-mapped word the tiles write straight into (one per host
   // thread and device, as in conditioning.hip and flats.hip)
-  static thread_local std::map<int, std::pair<int*, int*>> t_flags;
+  static thread_local ThreadOwned<PinnedWord> t_flags;  // (goes with the thread: common.hpp)
   int dev = 0;
   SOIL_HIP(hipGetDevice(&dev));
-  auto& fl = t_flags[dev];
-  if (!fl.first) {
-    SOIL_HIP(hipHostMalloc(reinterpret_cast<void**>(&fl.first), sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    SOIL_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&fl.second), fl.first, 0));
-  }
-  int *const flag_host = fl.first, *const flag_dev = fl.second;
+  PinnedWord& fl = t_flags[dev];
+  SOIL_HIP(fl.ensure());
+  int *const flag_host = fl.host, *const flag_dev = fl.dev;
   // the bound of the file's header
   const int64_t max_launches = static_cast<int64_t>(ntiles) * (4 * kST + kST * kST / kSInner) + 2;
   const char* const e = std::getenv("SOIL_SLOPE_LIMIT_PER_CHECK");  // read per call

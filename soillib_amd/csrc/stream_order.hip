@@ -269,15 +269,12 @@ inline PtrSizes so_sizes() { return PtrSizes(sizeof(int32_t), sizeof(uint32_t), 
 // "a cell rose in this seed pass": a pinned, device-mapped word the waves write straight into, one per host thread
 // and device (conditioning.hip, flats.hip)
 static int so_changed_word(int** host, int** dev) {
-  static thread_local std::map<int, std::pair<int*, int*>> t_words;
+  static thread_local ThreadOwned<PinnedWord> t_words;  // (goes with the thread: common.hpp)
   int d = 0;
   SOIL_HIP(hipGetDevice(&d));
-  auto& w = t_words[d];
-  if (!w.first) {
-    SOIL_HIP(hipHostMalloc(reinterpret_cast<void**>(&w.first), sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    SOIL_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&w.second), w.first, 0));
-  }
-  *host = w.first, *dev = w.second;
+  PinnedWord& w = t_words[d];
+  SOIL_HIP(w.ensure());
+  *host = w.host, *dev = w.dev;
   return SOIL_OK;
 }
 

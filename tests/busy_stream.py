@@ -46,7 +46,8 @@ What this cannot see: a race narrower than the backlog that happens to order its
 that shares its hardware queue with s (a lane that does not wait for s is then ordered by accident: only the null
 stream's queue is looked at, a lane's cannot be from outside; with several lanes the others still show); the
 library's internal workspace; two streams of one host thread that share a workspace slot (excluded by
-csrc/common.hpp's own rule).
+csrc/common.hpp's own rule); a second host thread: the protocol sees one caller (tests/two_threads.py and
+tests/test_gpu_two_host_threads.py put a second one beside every row).
 """
 import ctypes as C
 import os

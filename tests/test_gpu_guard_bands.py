@@ -820,7 +820,8 @@ EXEMPT = {
                                       "soil_stream_power_deposit_n_info", "soil_diffuse_info", "soil_flat_distance_info",
                                       "soil_slope_limit_info", "soil_mfd_info", "soil_set_particle_mode",
                                       "soil_set_particle_arith", "soil_get_particle_arith", "soil_set_debris_retire",
-                                      "soil_get_debris_retire", "soil_ghost_rows", "soil_workspace_release"],
+                                      "soil_get_debris_retire", "soil_ghost_rows", "soil_workspace_release",
+                                      "soil_host_objects_info"],
     "host memory": ["soil_normal_host", "soil_noise_host", "soil_tiff_peek", "soil_tiff_tag", "soil_tiff_read", "soil_tiff_write"],
     "counters returned through a host pointer": ["soil_debris_retire_violations", "soil_particle_steps"],
 }

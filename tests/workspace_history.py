@@ -27,7 +27,8 @@ the library and tests/test_workspace_history.py on a numpy stand-in with a persi
 
 What the histories prove: a call's bits do not depend on the legal calls before it, at these shapes.  What they do not:
 memory the allocator hands out fresh and happens to zero (not measured here); state reachable only through illegal
-inputs; two host threads; calls on different streams without ordering, which csrc/common.hpp excludes by rule.
+inputs; two host threads (tests/two_threads.py and tests/test_gpu_two_host_threads.py hold every row to its result beside
+one); calls on different streams without ordering, which csrc/common.hpp excludes by rule.
 """
 import contextlib
 import ctypes as C
